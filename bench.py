@@ -24,7 +24,11 @@ the same 182 845 nodes) -- single GPU only; the default `c3d4` is the configurat
 global_elements/elements-per-GPU (= N) so that it is a whole-job aggregate; `cg_iters_per_s` (PCG only) and
 `assemblies_per_s` (elements/s, geometry + assembly kernels) come from HIP events on the ctx stream.
 
-The JSON line carries, besides the contract's keys:
+A plain run (no --full) does only what the headline needs: set-up, pre-warm, W warm-up steps, K timed steps, the
+outputs of the last timed step if --dump-outputs is given, one JSON line.  Besides the contract's keys that line holds
+the figures the HIP events of the timed steps themselves give (cg_iters_per_s, assemblies_per_s, pcg_us_per_iter, ...).
+
+--full adds everything that takes runs of its own:
   roofline     the dominant kernel of the timed region against the ceiling that binds it.  On the headline workload
                that kernel is k_pcg_persist, whose matrix stream comes from the Infinity Cache: `achieved` = the bytes
                its layout makes it move per launch / launch time, `peak` = what a read-only sweep of the same footprint
@@ -40,12 +44,17 @@ The JSON line carries, besides the contract's keys:
                solve beside the tight PCG (eps 1e-12) that served the branch before round 4.
   cpu_baseline the as-written C/OpenMP port of the reference on the host, in a child process pinned one thread per
                physical core (OMP_PLACES=cores, OMP_PROC_BIND=spread; arrays first-touched by the threads that use them).
+  N > 1        the strong-scaling record, both multi-rank PCG paths timed, the mailbox round trip.
 
-Order of the run (so that an external GPU-utilisation sampler sees one contiguous busy stretch at the end):
+Order of a --full run (so that an external GPU-utilisation sampler sees one contiguous busy stretch at the end):
 mesh -> CPU baseline leg (rank 0, N = 1) -> device set-up -> pre-warm (`--prewarm` seconds of untimed steps) ->
 W warm-up steps -> K timed steps -> ceiling probes -> HBM-bound records -> one JSON line.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--iters ITERS] [--workload c3d4|c3d10] [--no-cpu-baseline]
+--dump-outputs DIR writes what the last timed step handed its caller as float64 .npy files (see dump_outputs); the
+inputs depend on the arguments only, so two builds can be compared output for output.
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--iters ITERS] [--workload c3d4|c3d10|cpe8] [--full]
+                  [--no-cpu-baseline] [--dump-outputs DIR]
 """
 import argparse
 import hashlib
@@ -184,6 +193,42 @@ def pmc_traffic(workload, kernel, layout=None):
 def layout_signature(info):
     """what the host decides about the matrix the kernels stream (femcy_get_pattern_info)"""
     return {k: int(getattr(info, k)) for k in ("n", "nnzb", "stored_blocks", "nslices") if hasattr(info, k)}
+
+
+DUMP_VEC_ENTRIES = 2_000_000        # --dump-outputs: entries per vector over all ranks (16 MB of float64)
+DUMP_K_BLOCK_ROWS = 2048            # block rows of K over all ranks (a few MB of blocks)
+
+
+def dump_outputs(ctx, be, out_dir, pcg_result, rank, nranks):
+    """--dump-outputs: what the last timed step handed its caller, float64 .npy files in `out_dir`:
+        x            the PCG solution (VEC_X)
+        residual     the right-hand side it solved for (VEC_RESIDUAL, Dirichlet rows zeroed)
+        pcg          (iterations, r0, rmax) as femcy_pcg returned them
+        K_blocks     the dm x dm blocks of the assembled K after the Dirichlet treatment, for a seeded sample of block
+        K_block_index  rows (all of them on small meshes), ascending block columns; their (block row, block column)
+    Vectors longer than their share of DUMP_VEC_ENTRIES are sampled at seeded positions that depend on the length only,
+    so that the files stay below 64 MB for every size and rank count.  N > 1: each rank writes its slab as
+    `<name>.rank<r>.npy`."""
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f".rank{rank}" if nranks > 1 else ""
+
+    def save(name, arr):
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), np.ascontiguousarray(arr, dtype=np.float64))
+
+    def sample(count, cap):
+        if count <= cap:
+            return np.arange(count)
+        return np.sort(np.random.default_rng(0).choice(count, cap, replace=False))
+
+    idx = sample(ctx.n, DUMP_VEC_ENTRIES // nranks)
+    save("x", ctx.download(be.VEC_X)[idx])
+    save("residual", ctx.download(be.VEC_RESIDUAL)[idx])
+    save("pcg", np.array(pcg_result, dtype=np.float64))
+    K = ctx.get_K_bsr()
+    rows = sample(K.indptr.size - 1, max(1, DUMP_K_BLOCK_ROWS // nranks))
+    pos = np.concatenate([np.arange(K.indptr[r], K.indptr[r + 1]) for r in rows])
+    save("K_blocks", K.data[pos])
+    save("K_block_index", np.stack([np.repeat(rows, np.diff(K.indptr)[rows]), K.indices[pos]], axis=1))
 
 
 def hbm_copy_probe(torch):
@@ -607,8 +652,8 @@ def rank_problem(env, cells, quadratic, use_comm, element, material_cls):
                 pmulti["enabled"] = bool(ctx.comm_persist_agree())
             pmulti["agreed"] = pmulti["enabled"]
             # the mailbox round trip between the ranks' kernels (xGMI latency + skew), measured by the solver's own
-            # cross-rank reduction in a one-wave kernel per rank; collective, so only if EVERY rank imported
-            if env.agree_min(imported) and hasattr(ctx, "probe_mailbox"):
+            # cross-rank reduction in a one-wave kernel per rank; collective, so only if EVERY rank imported (--full)
+            if args.full and env.agree_min(imported) and hasattr(ctx, "probe_mailbox"):
                 try:
                     with Watchdog(args.comm_timeout, "mailbox probe"):
                         env.barrier()
@@ -686,8 +731,8 @@ def rank_problem(env, cells, quadratic, use_comm, element, material_cls):
             log(f"[bench] rank {rank}: persistent multi-rank PCG not used (took {took}, same {same}): RCCL loop")
 
     # both multi-rank PCG paths, timed back to back (solves of 100 iterations, best of three, maximum over the ranks):
-    # whatever the run ends up using, the record holds the price of the other one too
-    if use_comm and pmulti is not None:
+    # whatever the run ends up using, the record holds the price of the other one too (--full)
+    if args.full and use_comm and pmulti is not None:
         paths = {}
         with Watchdog(4 * args.comm_timeout, "timing of the multi-rank PCG paths"):
             ctx.assemble_K(be.VEC_DOF)
@@ -758,19 +803,19 @@ def main():
                     help="PCG iterations per step (the reference's own solve of this system -- eps = 1e-3 -- takes 891)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak (default, the contract's line): 995 328 elements per GPU; strong: BASELINE's 1 M-element "
-                         "plate cut into N z-slabs.  A weak run on N > 1 GPUs appends a short strong-scaling record "
-                         "(`strong_scaling`) unless --no-strong")
+                         "plate cut into N z-slabs.  A weak --full run on N > 1 GPUs appends a short strong-scaling "
+                         "record (`strong_scaling`) unless --no-strong")
     ap.add_argument("--no-strong", action="store_true", help="N > 1, --scaling weak: skip the appended strong-scaling record")
     ap.add_argument("--workload", choices=("c3d4", "c3d10", "cpe8"), default="c3d4",
                     help="c3d4 = BASELINE configs[2]/[3] (the metric's configuration); c3d10 = configs[4], single GPU; "
                          "cpe8 = configs[1] (2-D: generated plane-strain beam, ~1 M DOF), single GPU")
     ap.add_argument("--sample", type=int, default=16, help="time every k-th SpMV launch with HIP events (1 = all)")
     ap.add_argument("--prewarm", type=float, default=4.0, help="seconds of untimed steps before the warm-up steps")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline leg")
     ap.add_argument("--cpu-baseline", choices=("tuned", "both"), default="tuned",
                     help="tuned = one pinned thread per physical core (default); both = also the unpinned all-threads run")
     ap.add_argument("--hbm-bound", choices=("auto", "off"), default="auto",
-                    help="auto: an N = 1 run of the default workload also measures the HBM-bound configurations "
+                    help="auto: an N = 1 --full run of the default workload also measures the HBM-bound configurations "
                          "(8 M C3D4 on this GPU, 124 k C3D10) and reports them under `hbm_bound`")
     ap.add_argument("--force-comm", action="store_true", help="N=1: still run the RCCL exchange path (1-rank communicator)")
     ap.add_argument("--force-dist", action="store_true", help="N=1: still create the torch.distributed (nccl) group and use its barrier / broadcast / all-reduce (exercises the N>1 host code on one GPU)")
@@ -783,8 +828,15 @@ def main():
     ap.add_argument("--cells", type=str, default=None, help="override nx,ny,nz (debug / small runs)")
     ap.add_argument("--launch-timeout", type=float, default=3600.0, help="self-launched N > 1 job: kill after this many seconds")
     ap.add_argument("--comm-timeout", type=float, default=300.0, help="seconds allowed for communicator set-up / tuning")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: roofline with its ceiling probes, cpu_baseline, "
+                         "direct_branch, hbm_bound; N > 1: strong_scaling, both multi-rank PCG paths, the mailbox probe")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (float64)")
     ap.add_argument("--cpu-leg", type=str, default=None, help=argparse.SUPPRESS)   # internal: the pinned child process
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.cpu_leg:                                            # child of cpu_baseline_subprocess(): host work only
         return cpu_leg_main(args.cpu_leg)
@@ -856,7 +908,8 @@ def main():
     # ------------------------------------------------------------------ CPU baseline leg (rank 0, N = 1 only), FIRST:
     # it is host work (20-40 s); running it before the device leg keeps the GPU-busy part of the command contiguous
     cpu = None
-    if rank == 0 and N == 1 and not args.no_cpu_baseline:
+    want_cpu = args.full and rank == 0 and N == 1 and not args.no_cpu_baseline
+    if want_cpu:
         try:
             cpu = cpu_baseline_subprocess(nx, ny, nz, "C3D10" if quadratic else "C3D4", args.cpu_baseline == "both")
         except Exception as e:   # the checker must never take the GPU number down with it
@@ -910,46 +963,50 @@ def main():
         elapsed = float(t.item())
     tm = ctx.timing()
     ctx.set_option(be.OPT_TIMING, 0)
-    probe = hbm_copy_probe(torch) if (on_gpu and rank == 0) else None
-
-    # ------------------------------------------------------------------ roofline of the dominant kernel
+    if args.dump_outputs:
+        dump_outputs(ctx, be, args.dump_outputs, (it, r0, rmax), rank, N)
     spmv_bytes, iter_bytes = algorithmic_bytes(info, ctx.nn, n)
     spmv_us = tm["spmv_ms"] * 1e3 / max(tm["spmv_launches"], 1)
-    persist = tm["persist_launches"] > 0 and tm["spmv_launches"] == 0
     cg_only = total_iters / (tm["pcg_ms"] * 1e-3) if tm["pcg_ms"] > 0 else 0.0
-    iter_gbs = iter_bytes * total_iters / (tm["pcg_ms"] * 1e-3) / 1e9 if tm["pcg_ms"] > 0 else 0.0
-    if persist:
-        roof = persist_roofline(ctx, be, tm, args, n, iter_bytes, probe, rank)
-        kernel = "k_pcg_persist"
-    else:
-        kernel = "k_spmv"
-        achieved = spmv_bytes / (spmv_us * 1e-6) / 1e9 if spmv_us > 0 else 0.0
-        roof = {"kernel": f"k_spmv<{ctx.dm}> (compute_Ad)", "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS,
-                "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "peak_source": "spec (MI355X_MICROARCH.md)",
-                "frac_of_copy_probe": (achieved / probe) if probe else None,
-                "bytes_per_launch": int(spmv_bytes), "avg_launch_us": spmv_us, "launches_timed": int(tm["spmv_launches"])}
-    if not persist and on_gpu and rank == 0 and not use_comm and hasattr(ctx, "probe_spmv"):
-        # the product launch to launch (200 back-to-back launches, one HIP event pair): see hbm_bound_record
-        try:
-            b2b = min(ctx.probe_spmv(200, os.environ.get("FEMCY_BENCH_STORAGE_ORDER", "1") != "0") for _ in range(3))
-            roof["launch_to_launch_us"] = b2b
-            roof["launch_to_launch_gbs"] = spmv_bytes / (b2b * 1e-6) / 1e9
-            roof["launch_to_launch_frac"] = roof["launch_to_launch_gbs"] / HBM_PEAK_GBS
-        except be.FemcyError as e:
-            log(f"[bench] femcy_probe_spmv failed: {e}")
-    if not persist and on_gpu and rank == 0:
-        rprobe = read_stream_probe(ctx, be, info.stored_blocks * 76)
-        roof["read_stream_probe_gbs"] = rprobe
-        roof["frac_of_read_stream_probe"] = (roof["achieved"] / rprobe) if rprobe else None
-    traffic, traffic_src = pmc_traffic(args.workload, kernel, layout_signature(info)) if not args.cells else (None, "non-standard --cells")
-    roof["traffic"], roof["traffic_source"] = traffic, traffic_src
-    roof["copy_probe_gbs"] = probe
-    roof["pcg_iteration_gbs"] = iter_gbs
-    roof["pcg_iteration_frac_of_hbm_peak"] = iter_gbs / HBM_PEAK_GBS
-    if traffic is not None and roof.get("avg_launch_us", 0) > 0:
-        # the rate of the bytes that actually moved between the L2s and the fabric (HBM + Infinity Cache): PMC counters
-        roof["traffic_gbs"] = traffic / (roof["avg_launch_us"] * 1e-6) / 1e9
-        roof["traffic_over_moved"] = traffic / roof["bytes_per_launch"] if roof.get("bytes_per_launch") else None
+
+    # ------------------------------------------------------------------ roofline of the dominant kernel (--full)
+    roof = probe = None
+    if args.full:
+        probe = hbm_copy_probe(torch) if (on_gpu and rank == 0) else None
+        persist = tm["persist_launches"] > 0 and tm["spmv_launches"] == 0
+        iter_gbs = iter_bytes * total_iters / (tm["pcg_ms"] * 1e-3) / 1e9 if tm["pcg_ms"] > 0 else 0.0
+        if persist:
+            roof = persist_roofline(ctx, be, tm, args, n, iter_bytes, probe, rank)
+            kernel = "k_pcg_persist"
+        else:
+            kernel = "k_spmv"
+            achieved = spmv_bytes / (spmv_us * 1e-6) / 1e9 if spmv_us > 0 else 0.0
+            roof = {"kernel": f"k_spmv<{ctx.dm}> (compute_Ad)", "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "peak_source": "spec (MI355X HBM3E)",
+                    "frac_of_copy_probe": (achieved / probe) if probe else None,
+                    "bytes_per_launch": int(spmv_bytes), "avg_launch_us": spmv_us, "launches_timed": int(tm["spmv_launches"])}
+        if not persist and on_gpu and rank == 0 and not use_comm and hasattr(ctx, "probe_spmv"):
+            # the product launch to launch (200 back-to-back launches, one HIP event pair): see hbm_bound_record
+            try:
+                b2b = min(ctx.probe_spmv(200, os.environ.get("FEMCY_BENCH_STORAGE_ORDER", "1") != "0") for _ in range(3))
+                roof["launch_to_launch_us"] = b2b
+                roof["launch_to_launch_gbs"] = spmv_bytes / (b2b * 1e-6) / 1e9
+                roof["launch_to_launch_frac"] = roof["launch_to_launch_gbs"] / HBM_PEAK_GBS
+            except be.FemcyError as e:
+                log(f"[bench] femcy_probe_spmv failed: {e}")
+        if not persist and on_gpu and rank == 0:
+            rprobe = read_stream_probe(ctx, be, info.stored_blocks * 76)
+            roof["read_stream_probe_gbs"] = rprobe
+            roof["frac_of_read_stream_probe"] = (roof["achieved"] / rprobe) if rprobe else None
+        traffic, traffic_src = pmc_traffic(args.workload, kernel, layout_signature(info)) if not args.cells else (None, "non-standard --cells")
+        roof["traffic"], roof["traffic_source"] = traffic, traffic_src
+        roof["copy_probe_gbs"] = probe
+        roof["pcg_iteration_gbs"] = iter_gbs
+        roof["pcg_iteration_frac_of_hbm_peak"] = iter_gbs / HBM_PEAK_GBS
+        if traffic is not None and roof.get("avg_launch_us", 0) > 0:
+            # the rate of the bytes that actually moved between the L2s and the fabric (HBM + Infinity Cache): PMC counters
+            roof["traffic_gbs"] = traffic / (roof["avg_launch_us"] * 1e-6) / 1e9
+            roof["traffic_over_moved"] = traffic / roof["bytes_per_launch"] if roof.get("bytes_per_launch") else None
 
     asm_ms = (tm["geom_ms"] + tm["assemble_ms"]) / max(tm["assemble_launches"], 1)
     per_gpu = ELEMS_PER_GPU[args.workload]
@@ -993,9 +1050,10 @@ def main():
         "spmv_tflops": (2 * info.nnz / (spmv_us * 1e-6) / 1e12 if spmv_us > 0 else
                         (2 * info.nnz * total_iters / (tm["pcg_ms"] * 1e-3) / 1e12 if tm["pcg_ms"] > 0 else 0.0)),
         "assembly_tflops": kflop_per_elem * 1e3 * ne_global / (asm_ms * 1e-3) / 1e12 if asm_ms > 0 else 0.0,
-        "roofline": roof,
     }
-    if rank == 0 and N == 1 and not args.no_cpu_baseline:
+    if args.full:
+        result["roofline"] = roof
+    if want_cpu:
         result["cpu_baseline"] = cpu
         if isinstance(cpu, dict) and isinstance(cpu.get("host_backend"), dict):     # scalars survive flattening parsers
             for k, v in cpu["host_backend"].items():
@@ -1004,8 +1062,8 @@ def main():
     ctx.close()
 
     # ------------------------------------------------------------------ strong scaling beside the weak-scaling line:
-    # BASELINE's metric names ONE mesh ("1M C3D4 elems") on 1 / 2 / 4 / 8 GPUs
-    if use_comm and not strong and not args.no_strong and not quadratic and \
+    # BASELINE's metric names ONE mesh ("1M C3D4 elems") on 1 / 2 / 4 / 8 GPUs (--full)
+    if args.full and use_comm and not strong and not args.no_strong and not quadratic and \
             (not args.cells or os.environ.get("FEMCY_BENCH_STRONG_CELLS")):
         try:
             rec = strong_scaling_record(env, Element_linear_tetrahedral(), LinearIsotropic)
@@ -1017,8 +1075,8 @@ def main():
             rec = {"error": "failed on another rank"}
         result["strong_scaling"] = rec
 
-    # ------------------------------------------------- the reference's direct branch (deck-sized systems), same invocation
-    if rank == 0 and N == 1 and on_gpu and args.hbm_bound == "auto" and not args.cells and not quadratic \
+    # ------------------------------------------------- the reference's direct branch (deck-sized systems), --full
+    if args.full and rank == 0 and N == 1 and on_gpu and args.hbm_bound == "auto" and not args.cells and not quadratic \
             and not args.force_comm and not args.force_dist:
         recs = []
         for label, gen, ele in (
@@ -1037,8 +1095,8 @@ def main():
                 recs.append({"system": label, "error": repr(e)})
         result["direct_branch"] = recs
 
-    # ------------------------------------------------------------------ the HBM-bound configurations, same invocation
-    if rank == 0 and N == 1 and on_gpu and args.hbm_bound == "auto" and not args.cells and not quadratic \
+    # ------------------------------------------------------------------ the HBM-bound configurations, --full
+    if args.full and rank == 0 and N == 1 and on_gpu and args.hbm_bound == "auto" and not args.cells and not quadratic \
             and not args.force_comm and not args.force_dist:
         recs = []
         for name, gen, ele in (
@@ -1078,8 +1136,8 @@ def cpe8_line(args, be, meshgen, torch, user_values):
     """`--workload cpe8`: the contract's line on the 2-D configuration.  One step = femcy_assemble_K (k_geom<8,2> +
     the CPE8 assembly) + Newton Dirichlet treatment + femcy_pcg(eps = 0, maxit = iters) on the generated plane-strain
     beam at state S1 (prescribed values of the first increment), inputs resident in HBM.  The dominant kernel is
-    k_spmv<2> (2 x 2 blocks, 36 bytes per stored block): its roofline comes from `hbm_bound_record` of the same mesh
-    (launch to launch between one HIP event pair), PMC traffic from profiles/spmv_traffic.json when recorded."""
+    k_spmv<2> (2 x 2 blocks, 36 bytes per stored block): with --full its roofline comes from `hbm_bound_record` of the
+    same mesh (launch to launch between one HIP event pair), PMC traffic from profiles/spmv_traffic.json when recorded."""
     from femcy_amd.element_zoo import Element_quadratic_quadrilateral
     from femcy_amd.material_zoo import LinearIsotropicPlaneStrain
     nx, ny = (int(v) for v in args.cells.split(",")[:2]) if args.cells else CPE8_CELLS
@@ -1122,40 +1180,31 @@ def cpe8_line(args, be, meshgen, torch, user_values):
         t0 = time.perf_counter()
         total = 0
         for _ in range(args.steps):
-            total += step()[0]
+            last = step()
+            total += last[0]
         ctx.sync()
         if on_gpu:
             torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         tm = ctx.timing()
         ctx.set_option(be.OPT_TIMING, 0)
+        if args.dump_outputs:
+            dump_outputs(ctx, be, args.dump_outputs, last, 0, 1)
         spmv_b, iter_b = algorithmic_bytes(info, ctx.nn, ctx.n)
         ne, n, dm = int(ctx.ne), int(ctx.n), int(ctx.dm)
         nnz = int(info.nnz)
-        probe = hbm_copy_probe(torch) if on_gpu else None
+        probe = hbm_copy_probe(torch) if (args.full and on_gpu) else None
         # the dominant kernel of the timed region: since round 5 a 2-D system of up to 8 192 slices takes the persistent
         # kernel (k_pcg_persist<2, 8, 2>: eight slices per wave); otherwise the product of the three-launch loop
         persist = tm["persist_launches"] > 0 and tm["spmv_launches"] == 0
-        roof = persist_roofline(ctx, be, tm, args, n, iter_b, probe, 0) if persist else None
+        roof = persist_roofline(ctx, be, tm, args, n, iter_b, probe, 0) if (args.full and persist) else None
     finally:
         ctx.close()
     name = CPE8_NAME if not args.cells else f"beam CPE8 {nx}x{ny} serendipity quadrilaterals, plane strain, nlgeom"
-    rec = hbm_bound_record(be, name, mesh, ele, mat, user_values, probe)
-    kernel = "k_pcg_persist" if persist else "k_spmv"
-    if roof is None:
-        roof = dict(rec["spmv"])
-    traffic, traffic_src = pmc_traffic("cpe8", kernel, layout_signature(info)) if not args.cells else (None, "non-standard --cells")
-    roof.update(traffic=traffic, traffic_source=traffic_src, copy_probe_gbs=probe,
-                pcg_iteration_gbs=rec["pcg_iteration"]["achieved"], pcg_iteration_frac_of_hbm_peak=rec["pcg_iteration"]["frac"],
-                pcg_iteration_us=rec["pcg_iteration"]["us"], pcg_path=rec["pcg_path"],
-                spmv_launch_to_launch_us=rec["spmv"]["avg_launch_us"], spmv_frac_of_hbm_peak=rec["spmv"]["frac"])
-    if traffic is not None and roof.get("avg_launch_us", 0) > 0:
-        roof["traffic_gbs"] = traffic / (roof["avg_launch_us"] * 1e-6) / 1e9
-        roof["traffic_over_moved"] = traffic / roof["bytes_per_launch"] if roof.get("bytes_per_launch") else None
     asm_ms = (tm["geom_ms"] + tm["assemble_ms"]) / max(tm["assemble_launches"], 1)
     # as-written flops of one CPE8 stiffness (B^T C B at 4 Gauss points, B 3 x 16: 2 * (3*3*16 + 16*3*16) * 4)
     kflop = 2 * (3 * 3 * 16 + 16 * 3 * 16) * 4 / 1e3
-    return {
+    line = {
         "metric": "CG iters/sec + element-stiffness assemblies/sec, 1M C3D4 elems, 1/2/4/8 GPU",
         "value": total / elapsed * (ne / ELEMS_PER_GPU["cpe8"]),
         "unit": f"CG iters/s x (global elements / {ELEMS_PER_GPU['cpe8']})",
@@ -1170,11 +1219,25 @@ def cpe8_line(args, be, meshgen, torch, user_values):
         "assemblies_per_s": ne / (asm_ms * 1e-3) if asm_ms > 0 else 0.0,
         "assembly_ms": asm_ms,
         "pcg_us_per_iter": tm["pcg_ms"] * 1e3 / max(total, 1),
-        "spmv_tflops": 2 * nnz / (rec["spmv"]["avg_launch_us"] * 1e-6) / 1e12 if rec["spmv"].get("avg_launch_us") else 0.0,
         "assembly_tflops": kflop * 1e3 * ne / (asm_ms * 1e-3) / 1e12 if asm_ms > 0 else 0.0,
-        "roofline": roof,
-        "hbm_bound": [rec],
     }
+    if not args.full:
+        return line
+    rec = hbm_bound_record(be, name, mesh, ele, mat, user_values, probe)
+    kernel = "k_pcg_persist" if persist else "k_spmv"
+    if roof is None:
+        roof = dict(rec["spmv"])
+    traffic, traffic_src = pmc_traffic("cpe8", kernel, layout_signature(info)) if not args.cells else (None, "non-standard --cells")
+    roof.update(traffic=traffic, traffic_source=traffic_src, copy_probe_gbs=probe,
+                pcg_iteration_gbs=rec["pcg_iteration"]["achieved"], pcg_iteration_frac_of_hbm_peak=rec["pcg_iteration"]["frac"],
+                pcg_iteration_us=rec["pcg_iteration"]["us"], pcg_path=rec["pcg_path"],
+                spmv_launch_to_launch_us=rec["spmv"]["avg_launch_us"], spmv_frac_of_hbm_peak=rec["spmv"]["frac"])
+    if traffic is not None and roof.get("avg_launch_us", 0) > 0:
+        roof["traffic_gbs"] = traffic / (roof["avg_launch_us"] * 1e-6) / 1e9
+        roof["traffic_over_moved"] = traffic / roof["bytes_per_launch"] if roof.get("bytes_per_launch") else None
+    line.update(spmv_tflops=2 * nnz / (rec["spmv"]["avg_launch_us"] * 1e-6) / 1e12 if rec["spmv"].get("avg_launch_us") else 0.0,
+                roofline=roof, hbm_bound=[rec])
+    return line
 
 
 def persist_roofline(ctx, be, tm, args, n, iter_bytes, probe, rank):

@@ -107,6 +107,14 @@ class MockContext:
     def vec_sub(self, c, a, b):
         self.vec[c] = self.vec[a] - self.vec[b]
 
+    def download(self, vid):
+        return self.vec[vid].copy()
+
+    def get_K_bsr(self):
+        K = self.K.tobsr(blocksize=(self.dm, self.dm))
+        K.sort_indices()
+        return K
+
     def iface_sum(self, vid):
         from dist_reference import iface_sum
         self.vec[vid] = iface_sum(self.part, self.vec[vid])
@@ -176,7 +184,7 @@ def _worker(rank, world, port, out_dir):
     out = os.open(os.path.join(out_dir, f"stdout{rank}.txt"), os.O_WRONLY | os.O_CREAT | os.O_TRUNC)
     os.dup2(out, 1)
     sys.argv = ["bench.py", "--gpus", str(world), "--steps", "1", "--warmup", "1", "--iters", "4", "--cells", "4,2,6",
-                "--no-cpu-baseline", "--prewarm", "0"]
+                "--no-cpu-baseline", "--prewarm", "0", "--full"]
     import bench
     bench.main()
     np.save(os.path.join(out_dir, f"uid{rank}.npy"), np.array([MockContext.uid_calls]))
@@ -240,7 +248,7 @@ def test_bench_self_launches_its_ranks():
 def test_bench_appends_a_strong_scaling_record():
     """a weak-scaling run on N > 1 ranks also cuts ONE mesh into N slabs (BASELINE: "1M C3D4 elems, 1/2/4/8 GPU") and
     reports it under `strong_scaling`; --scaling strong makes that the headline instead"""
-    out = _self_launch({"FEMCY_BENCH_STRONG_CELLS": "4,2,8"})
+    out = _self_launch({"FEMCY_BENCH_STRONG_CELLS": "4,2,8"}, extra_args=("--full",))
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.strip().startswith("{")][0])
     assert d["scaling"] == "weak"
@@ -251,6 +259,25 @@ def test_bench_appends_a_strong_scaling_record():
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.strip().startswith("{")][0])
     assert d["scaling"] == "strong" and "strong_scaling" not in d and d["config"]["elements_per_gpu"] == 6 * 4 * 2 * 6 // 2
+
+
+def test_bench_dumps_the_outputs_of_every_rank(tmp_path):
+    """--dump-outputs on N > 1 ranks: every rank writes its slab's outputs of the last timed step as float64 files,
+    K sampled by block rows; the plain line carries none of the --full records"""
+    out = _self_launch({}, extra_args=("--dump-outputs", str(tmp_path)))
+    assert out.returncode == 0, out.stderr[-3000:]
+    d = json.loads([l for l in out.stdout.splitlines() if l.strip().startswith("{")][0])
+    assert "roofline" not in d and "strong_scaling" not in d
+    assert d["config"]["persistent_pcg_across_ranks"].get("us_per_iteration") is None
+    names = ("x", "residual", "pcg", "K_blocks", "K_block_index")
+    assert sorted(os.listdir(tmp_path)) == sorted(f"{n}.rank{r}.npy" for n in names for r in (0, 1))
+    for r in (0, 1):
+        f = {n: np.load(tmp_path / f"{n}.rank{r}.npy") for n in names}
+        assert all(a.dtype == np.float64 for a in f.values())
+        assert f["pcg"][0] == 4 and f["x"].shape == f["residual"].shape and np.abs(f["x"]).max() > 0
+        assert f["K_blocks"].shape == (f["K_block_index"].shape[0], 3, 3)
+        assert (np.diff(f["K_block_index"][:, 0]) >= 0).all()            # block rows ascending, all of them (small slab)
+        assert len(np.unique(f["K_block_index"][:, 0])) * 3 == f["x"].size
 
 
 def test_bench_self_launch_reports_a_failed_rank():

@@ -13,7 +13,7 @@ pytestmark = pytest.mark.gpu
 
 def test_bench_json_contract():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--iters", "20",
-                          "--cells", "16,4,24"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--cells", "16,4,24", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, out.stdout
@@ -34,11 +34,54 @@ def test_bench_json_contract():
     assert d["value"] > 0 and d["cg_iters_per_s"] > 0 and d["assemblies_per_s"] > 0
 
 
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """a run without --full carries the headline only; --dump-outputs writes what the last timed step computed -- K
+    after the Dirichlet treatment (sampled block rows), the right-hand side and the PCG iterate -- and it is what the
+    oracle computes for the same mesh and state"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from femcy_amd import meshgen
+    from femcy_amd.user_defined import user_dirichletBC_values
+    from oracle import femcy_oracle as orc
+    from oracle.elements import elem_def
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--iters", "20",
+                          "--prewarm", "0", "--cells", "16,4,24", "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, out.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "f64" and d["higher_is_better"]
+    assert not {"roofline", "cpu_baseline", "hbm_bound", "direct_branch", "strong_scaling"} & set(d)
+    files = {f: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert set(files) == {"x.npy", "residual.npy", "pcg.npy", "K_blocks.npy", "K_block_index.npy"}
+    assert all(a.dtype == np.float64 for a in files.values()) and sum(a.nbytes for a in files.values()) < 64 << 20
+
+    m = meshgen.twist_plate(16, 4, 24)
+    u, cons = bench.s1_state(m["nodes"], m["dirichlet_bc_info"], user_dirichletBC_values)
+    topo = orc.Topology(m["nodes"], m["elements"], elem_def("C3D4"))
+    mat = orc.Material("lin3d", m["elastic"])
+    Ko = orc._zero_rows_cols_unit_diag(orc.assemble_K(topo, u, mat.C), cons).tocsr()
+    fo = orc.internal_force(topo, u, mat)[0]
+    fo[cons] = 0.0
+    assert files["x.npy"].shape == files["residual.npy"].shape == (Ko.shape[0],)
+    assert np.abs(files["residual.npy"] - fo).max() <= 1e-11 * np.abs(fo).max()
+    idx, blocks = files["K_block_index.npy"].astype(np.int64), files["K_blocks.npy"]
+    assert blocks.shape == (idx.shape[0], 3, 3) and idx.shape[0] > 2048
+    ref = np.stack([Ko[3 * r:3 * r + 3, 3 * c:3 * c + 3].toarray() for r, c in idx])
+    assert np.abs(blocks - ref).max() <= 1e-12 * abs(Ko).max()
+    it, r0, rmax = files["pcg.npy"]
+    assert it == 20 and r0 > 0
+    xo = orc.pcg_reference(Ko, fo, eps=0.0, maxit=20)[0]
+    assert np.linalg.norm(files["x.npy"] - xo) <= 1e-8 * np.linalg.norm(xo)
+
+
 def test_bench_c3d10_workload_and_forced_comm():
     """the configs[4] workload line and the N = 1 run of the RCCL exchange path (both exchange forms, the neighbour
     one with the overlapped schedule) keep the same contract"""
     base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--iters", "20", "--prewarm", "0",
-            "--no-cpu-baseline"]
+            "--full", "--no-cpu-baseline"]
     for extra, workload in ((["--workload", "c3d10", "--cells", "8,2,12"], "C3D10"),
                             (["--cells", "16,4,24", "--force-comm", "--exchange", "allreduce"], "C3D4"),
                             (["--cells", "16,4,24", "--force-comm", "--exchange", "neighbour"], "C3D4")):
@@ -66,7 +109,7 @@ def test_bench_headline_workload_runs_the_persistent_pcg():
     HIP-event time of the launch, over the stream rate probed in the kernel's own launch shape: a fraction <= 1 -- with
     the algorithmic figure of SURVEY.md 8d (which exceeds the HBM peak) under its own name"""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--iters", "100",
-                          "--prewarm", "0", "--no-cpu-baseline", "--hbm-bound", "off"], capture_output=True, text=True,
+                          "--prewarm", "0", "--full", "--no-cpu-baseline", "--hbm-bound", "off"], capture_output=True, text=True,
                          timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -121,7 +164,7 @@ def test_bench_cpe8_workload_line():
     roofline object prices the dominant kernel of the timed region, `hbm_bound[0]` carries the k_spmv<2> product launch
     to launch, the PCG iteration on both paths and the assembly rate"""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cpe8", "--cells", "600,60", "--steps", "2",
-                          "--warmup", "1", "--iters", "50", "--prewarm", "0", "--no-cpu-baseline"], capture_output=True, text=True,
+                          "--warmup", "1", "--iters", "50", "--prewarm", "0", "--full", "--no-cpu-baseline"], capture_output=True, text=True,
                          timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
