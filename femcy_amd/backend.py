@@ -67,6 +67,7 @@ ASM_GATHER, ASM_ATOMIC, ASM_ROWS, ASM_AUTO, ASM_GATHER_SYM, ASM_GATHER_SYM_ROWSU
 EXPORTS = [
     "femcy_ctx_create", "femcy_ctx_destroy", "femcy_last_error", "femcy_version", "femcy_set_option", "femcy_sync",
     "femcy_set_mesh", "femcy_set_element", "femcy_set_material", "femcy_build_pattern", "femcy_get_pattern_info",
+    "femcy_get_assembly_used",
     "femcy_vec_upload", "femcy_vec_download", "femcy_vec_fill", "femcy_vec_copy", "femcy_vec_scatter",
     "femcy_vec_sub", "femcy_vec_axpy", "femcy_vec_scale", "femcy_vec_norm", "femcy_vec_absmax",
     "femcy_assemble_K", "femcy_internal_force", "femcy_residual_and_K", "femcy_apply_dirichlet_linear", "femcy_apply_dirichlet_newton",
@@ -151,7 +152,7 @@ def _bind(lib, kind):
         "femcy_set_option": [p, cint, i64], "femcy_sync": [p],
         "femcy_set_mesh": [p, i32, i32, p, i32, i32, p], "femcy_set_element": [p, i32, p, p, i32],
         "femcy_set_material": [p, i32, p, p, i32], "femcy_build_pattern": [p],
-        "femcy_get_pattern_info": [p, C.POINTER(PatternInfo)],
+        "femcy_get_pattern_info": [p, C.POINTER(PatternInfo)], "femcy_get_assembly_used": [p, C.POINTER(i32)],
         "femcy_vec_upload": [p, cint, p, i64], "femcy_vec_download": [p, cint, p, i64],
         "femcy_vec_fill": [p, cint, f64], "femcy_vec_copy": [p, cint, cint],
         "femcy_vec_scatter": [p, cint, p, p, i32], "femcy_vec_sub": [p, cint, cint, cint],
@@ -362,6 +363,12 @@ class Context:
     # -------------------------------------------------------------------------------- hot path
     def assemble_K(self, u_vec: int = VEC_DOF):
         self._call("femcy_assemble_K", int(u_vec))
+
+    def assembly_used(self) -> int:
+        """the femcy_assembly mode (ASM_*) the last assemble_K / residual_and_K ran, AUTO resolved."""
+        out = C.c_int32()
+        self._call("femcy_get_assembly_used", C.byref(out))
+        return out.value
 
     def internal_force(self, u_vec: int = VEC_DOF, f_vec: int = VEC_FORCE):
         self._call("femcy_internal_force", int(u_vec), int(f_vec))

@@ -199,7 +199,8 @@ struct Ctx {
     int32_t* d_ne_ptr = nullptr;      // [nn+1] node -> incident elements
     int32_t* d_ne_idx = nullptr;      // [ne*npe] packed e*npe+la
     // pair lists of FEMCY_ASM_PAIRS (pattern.cpp: ensure_pairs, built on first use): per chunk of 16 (or 8) consecutive storage
-    // positions the (row, incident element) pairs in (row, ascending element) order -- code e*npe+la and row inside the chunk
+    // positions the (row, incident element) pairs in (row, ascending element) order -- code e*npe+la and row inside the chunk;
+    // 3-D: in step order, the s-th element of every row of the chunk, padded to whole steps
     std::vector<int32_t> h_node_of, h_ne_ptr, h_ne_idx;
     int32_t* d_pr_ptr = nullptr;      // PairBatch descriptors (32 B) in PROCESSING order
     int32_t* d_pr_unit = nullptr;     // [units + 1] first batch of every wavefront's unit of chunks
@@ -321,6 +322,7 @@ struct Ctx {
 
     // ---- options / timing
     int opt_assembly = FEMCY_ASM_AUTO;
+    int asm_used = -1;                // the mode the last assembly ran, AUTO resolved (femcy_get_assembly_used)
     int opt_tangent = 0;              // FEMCY_OPT_TANGENT
     int opt_poll = 32;
     int opt_timing = 0;               // 0 off, 1 every launch, k > 1: every k-th SpMV launch

@@ -519,9 +519,12 @@ FEMCY_HD void neumann_facet(int32_t npe, int32_t nfn, int32_t nip, const double*
                             const double* __restrict__ ft_normal, const double* __restrict__ ft_weight, double traction,
                             const double* __restrict__ dir_or_null, double* __restrict__ contrib) {
     const int32_t* key = ft_nodes + (int64_t)t * nfn;
-    // facet size from the first sorted local nodes (ELE.globalNormal): edge length, or corner-triangle area
-    double size;
-    {
+    // a quadrilateral facet in 3-D (hexahedron face): every facet point weighted by its surface Jacobian (Nanson's
+    // formula, da = |det J| |J^-T n_nat| w), exact in area and shape for warped faces.  Every other facet keeps the size
+    // of its first sorted local nodes (ELE.globalNormal): edge length, or corner-triangle area
+    const bool nanson = DM == 3 && nfn == 4;
+    double size = 0.0;
+    if (!nanson) {
         const double* p0 = nodes + (int64_t)en[key[0]] * DM;
         const double* p1 = nodes + (int64_t)en[key[1]] * DM;
         if (DM == 2) {
@@ -548,9 +551,20 @@ FEMCY_HD void neumann_facet(int32_t npe, int32_t nfn, int32_t nip, const double*
             for (int i = 0; i < DM; ++i)
                 for (int j = 0; j < DM; ++j) J[i][j] += x[i] * dn[j];
         }
-        det_inv<DM>(J, inv);
+        const double det = det_inv<DM>(J, inv);
         double flux[DM];
-        if (dir_or_null) {
+        if (nanson) {
+            double nrm = 0.0;
+            for (int j = 0; j < DM; ++j) {
+                double v = 0.0;
+                for (int i = 0; i < DM; ++i) v += ft_normal[tip * DM + i] * inv[i][j];
+                flux[j] = v;
+                nrm += v * v;
+            }
+            nrm = sqrt(nrm);
+            const double da = fabs(det) * nrm * ft_weight[tip];
+            for (int d = 0; d < DM; ++d) flux[d] = traction * (dir_or_null ? dir_or_null[d] : flux[d] / (nrm + 1.e-30)) * da;
+        } else if (dir_or_null) {
             for (int d = 0; d < DM; ++d) flux[d] = dir_or_null[d];
         } else {
             double nrm = 0.0;
@@ -563,8 +577,10 @@ FEMCY_HD void neumann_facet(int32_t npe, int32_t nfn, int32_t nip, const double*
             nrm = sqrt(nrm) + 1.e-30;
             for (int d = 0; d < DM; ++d) flux[d] /= nrm;
         }
-        const double axw = size * ft_weight[tip];
-        for (int d = 0; d < DM; ++d) flux[d] = traction * flux[d] * axw;
+        if (!nanson) {
+            const double axw = size * ft_weight[tip];
+            for (int d = 0; d < DM; ++d) flux[d] = traction * flux[d] * axw;
+        }
         for (int32_t fn = 0; fn < nfn; ++fn) {
             const double shape = ft_N[tip * npe + key[fn]];
             for (int d = 0; d < DM; ++d) contrib[(int64_t)fn * DM + d] += flux[d] * shape;

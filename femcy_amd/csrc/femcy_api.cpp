@@ -654,6 +654,13 @@ int femcy_build_pattern(femcy_ctx* ctx) {
     return FEMCY_OK;
 }
 
+int femcy_get_assembly_used(femcy_ctx* ctx, int32_t* mode) {
+    CTX_OR_FAIL(ctx);
+    FEMCY_REQUIRE(mode && c->asm_used >= 0, "no assembly has run on this context");
+    *mode = c->asm_used;
+    return FEMCY_OK;
+}
+
 int femcy_get_pattern_info(femcy_ctx* ctx, femcy_pattern_info* out) {
     CTX_OR_FAIL(ctx);
     FEMCY_REQUIRE(c->have_pattern && out, "pattern not built");
@@ -762,6 +769,7 @@ int femcy_vec_absmax(femcy_ctx* ctx, int vec, double* out) {
 int femcy_assemble_K(femcy_ctx* ctx, int u_vec) {
     CTX_OR_FAIL(ctx);
     READY_OR_FAIL();
+    c->asm_used = -1;                          // femcy_get_assembly_used: nothing ran until the assembly succeeds
     const double* du = nullptr;
     if (u_vec >= 0) {
         VEC_OR_FAIL(u_vec);
@@ -788,6 +796,7 @@ int femcy_internal_force(femcy_ctx* ctx, int u_vec, int f_vec) {
 int femcy_residual_and_K(femcy_ctx* ctx, int u_vec, int f_vec) {
     CTX_OR_FAIL(ctx);
     READY_OR_FAIL();
+    c->asm_used = -1;                          // femcy_get_assembly_used: nothing ran until the assembly succeeds
     VEC_OR_FAIL(u_vec);
     VEC_OR_FAIL(f_vec);
     // ONE element pass for both halves of a Newton residual evaluation: the internal force and the matrix are

@@ -98,6 +98,8 @@ __global__ void __launch_bounds__(256) k_geom(int32_t ne, int32_t nGP, const dou
     // instruction), in chunks of the largest divisor of the record width up to 16
     constexpr int CHK = WG % 16 == 0 ? 16 : WG % 15 == 0 ? 15 : WG % 12 == 0 ? 12 : WG % 8 == 0 ? 8 : WG % 6 == 0 ? 6 : 1;
     constexpr bool WIDE = CHK > 1;
+    // the F / sigma records (WT doubles) go through the same staging area as the gradient chunks
+    static_assert(!WIDE || (STAGE ? WG : CHK) >= WT, "stage_lds is smaller than one F / sigma record");
     __shared__ double stage_lds[STAGE ? 257 * (WG > CHK ? WG : CHK) : (WIDE ? 257 * CHK : 1)];
     const int32_t e0 = blockIdx.x * blockDim.x;
     const int nvalid = min(256, ne - e0);
@@ -1347,6 +1349,10 @@ struct SumMap {
 // requested a batch earlier and whose descriptor two batches earlier (scalar loads): the chain descriptor -> codes ->
 // records is paid once per wave.  The write-out leaves the tile zeroed (each LDS word is read and cleared by one lane).
 constexpr int PAIR_ROW_SHIFT = 27;  // pair word: row inside the chunk << 27 | element * npe + local node (ensure_pairs)
+// 3-D lists (C3D8) are in STEP order: the s-th incident element of every row of the chunk, then the (s+1)-th, with a
+// padding word (INT32_MIN: a negative row) where a row has fewer elements.  The PPW = 8 pairs of one step then
+// belong to distinct rows, so no two lanes of one ds_add_f64 address the same LDS word and the bits of K are fixed by
+// the list order alone (not by how the hardware orders same-address adds inside one instruction).
 struct PairBatch {
     int32_t chunk, p0, nb, L;       // chunk id (slice * (64 / RPW) + part), first pair, pairs (<= 64), slice width in blocks
     int64_t off;                    // slice_off of the chunk's slice
@@ -1410,9 +1416,9 @@ __global__ void __launch_bounds__(256) k_assemble_pairs(int32_t nunits, int32_t 
     };
     auto compute = [&](int d, int st, int32_t nb, int Lp) {
         const int pi = st * PPW + q;
-        const bool ok = lane_ok && pi < nb;
-        const int la = C[d] % NPE;
         const int rl = R[d];
+        const bool ok = lane_ok && pi < nb && (DM == 2 || rl >= 0);   // 3-D lists: a padding word adds nothing
+        const int la = C[d] % NPE;
         double S[DD];
 #pragma unroll
         for (int k = 0; k < DD; ++k) S[k] = 0.0;
@@ -1802,6 +1808,7 @@ int launch_geom(Ctx* c, const double* d_u, unsigned what) {
     FEMCY_DISPATCH_ELEMENT(8, 2, GEOM_CALL)
     FEMCY_DISPATCH_ELEMENT(4, 3, GEOM_CALL)
     FEMCY_DISPATCH_ELEMENT(10, 3, GEOM_CALL)
+    FEMCY_DISPATCH_ELEMENT(8, 3, GEOM_CALL)
 #undef GEOM_CALL
     timing_end(c, th);
     if (!launched) {
@@ -1813,9 +1820,11 @@ int launch_geom(Ctx* c, const double* d_u, unsigned what) {
 }
 
 // FEMCY_ASM_PAIRS: instantiated element families, LDS of a workgroup (four chunk tiles [dm^2][rows per wave][Lmax | 1])
+static bool pairs_hex(const Ctx* c) { return c->dm == 3 && c->npe == 8 && c->nGP == 8; }
 static bool pairs_instantiated(const Ctx* c) {
-    return c->dm == 2 && ((c->npe == 8 && c->nGP == 4) || (c->npe == 6 && c->nGP == 3) || (c->npe == 4 && c->nGP == 4) ||
-                          (c->npe == 3 && c->nGP == 1));
+    return pairs_hex(c) ||
+           (c->dm == 2 && ((c->npe == 8 && c->nGP == 4) || (c->npe == 6 && c->nGP == 3) || (c->npe == 4 && c->nGP == 4) ||
+                           (c->npe == 3 && c->nGP == 1)));
 }
 static bool pairs_fits(const Ctx* c) { return (int64_t)c->ne * c->npe < ((int64_t)1 << 27); }   // the packed pair word
 static int pairs_rpw(const Ctx* c) { return ((c->tune_pairs >> 1) & 3) == 1 ? 8 : 16; }
@@ -1849,8 +1858,10 @@ int launch_assemble(Ctx* c) {
             if (lds4 + 512 <= (size_t)c->small_max_lds) mode = FEMCY_ASM_ROWS4;
         }
         // round 6: the 2-D quadratic families (many short rows) -- 16 rows per wave, pair lists in storage order
-        if (c->dm == 2 && c->npe > 4 && pairs_instantiated(c) && pairs_fits(c) && pairs_lds(c) + 512 <= (size_t)c->small_max_lds)
-            mode = FEMCY_ASM_PAIRS;
+        // C3D8 (27 blocks and 8 incident elements per interior row, a 1.5 KiB record per element): the same kernel with
+        // 3 x 3 blocks, 8 pairs per step, lists in step order (ensure_pairs)
+        if ((c->dm == 2 && c->npe > 4) || pairs_hex(c))
+            if (pairs_instantiated(c) && pairs_fits(c) && pairs_lds(c) + 512 <= (size_t)c->small_max_lds) mode = FEMCY_ASM_PAIRS;
     }
     if (c->opt_tangent == 1) {
         FEMCY_REQUIRE(c->mat_kind != FEMCY_MAT_PSTRESS, "the consistent tangent is not available for plane stress");
@@ -1880,6 +1891,7 @@ int launch_assemble(Ctx* c) {
         }
         timing_end(c, th);
         FEMCY_HIP(hipGetLastError());
+        c->asm_used = skip ? FEMCY_ASM_GATHER_SYM_ROWSUM : FEMCY_ASM_GATHER_SYM;   // the gather form of the consistent tangent
         return FEMCY_OK;
     }
     if (mode == FEMCY_ASM_ROWS3) {
@@ -1987,7 +1999,7 @@ int launch_assemble(Ctx* c) {
 #undef FEMCY_ROWS4
     } else if (mode == FEMCY_ASM_ROWS2 || mode == FEMCY_ASM_ROWS3) {
     } else if (mode == FEMCY_ASM_PAIRS) {
-        FEMCY_REQUIRE(pairs_instantiated(c), "PAIRS assembly is instantiated for the 2-D families (npe %d, nGP %d, dm %d)",
+        FEMCY_REQUIRE(pairs_instantiated(c), "PAIRS assembly is instantiated for the 2-D families and C3D8 (npe %d, nGP %d, dm %d)",
                       c->npe, c->nGP, c->dm);
         FEMCY_REQUIRE(pairs_fits(c), "PAIRS assembly packs (row, element, local node) into 32 bits: ne * npe must stay below 2^27");
         // FEMCY_TUNE_PAIRS: bit 0 = XCD-contiguous ranges of the processing order, bits 1-2 = rows per wave (0: 16, 1: 8),
@@ -2002,34 +2014,34 @@ int launch_assemble(Ctx* c) {
                       "blocks), the device allows %d", lds, c->max_row_blocks, c->small_max_lds);
         int rc = ensure_pairs(c, rpw, (tp & 32) != 0, cpw);
         if (rc) return rc;
-        const SumMap<4> T = sum_map<2>(c);
         const int32_t nchunks = c->nslices * (SLICE / rpw);
         const int32_t nunits = (nchunks + cpw - 1) / cpw;
         const int grid = ((nunits + 3) / 4 + 7) / 8 * 8;
-#define FEMCY_PAIRS_K(NPE_, NGP_, RPW_, DEPTH_, X_)                                                                    \
+#define FEMCY_PAIRS_K(NPE_, NGP_, DM_, RPW_, DEPTH_, X_)                                                               \
     do {                                                                                                               \
         if (lds > 48 * 1024)                                                                                           \
-            FEMCY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_assemble_pairs<NPE_, NGP_, 2, RPW_, DEPTH_, X_>), \
+            FEMCY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_assemble_pairs<NPE_, NGP_, DM_, RPW_, DEPTH_, X_>), \
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                      \
-        hipLaunchKernelGGL((k_assemble_pairs<NPE_, NGP_, 2, RPW_, DEPTH_, X_>), dim3(grid), dim3(bs), lds, c->stream,  \
+        hipLaunchKernelGGL((k_assemble_pairs<NPE_, NGP_, DM_, RPW_, DEPTH_, X_>), dim3(grid), dim3(bs), lds, c->stream, \
                            nunits, c->max_row_blocks, c->d_pr_unit, (const PairBatch*)c->d_pr_ptr, c->d_pr_code,            \
-                           c->d_slotj, c->d_dsdx, c->d_vol, T, c->d_Kvals);                                      \
+                           c->d_slotj, c->d_dsdx, c->d_vol, sum_map<DM_>(c), c->d_Kvals);                            \
     } while (0)
-#define FEMCY_PAIRS_D(NPE_, NGP_, RPW_, X_)                                                                            \
+#define FEMCY_PAIRS_D(NPE_, NGP_, DM_, RPW_, X_)                                                                       \
     do {                                                                                                               \
-        if (depth == 2) FEMCY_PAIRS_K(NPE_, NGP_, RPW_, 2, X_);                                                        \
-        else if (depth == 3) FEMCY_PAIRS_K(NPE_, NGP_, RPW_, 3, X_);                                                   \
-        else FEMCY_PAIRS_K(NPE_, NGP_, RPW_, 4, X_);                                                                   \
+        if (depth == 2) FEMCY_PAIRS_K(NPE_, NGP_, DM_, RPW_, 2, X_);                                                   \
+        else if (depth == 3) FEMCY_PAIRS_K(NPE_, NGP_, DM_, RPW_, 3, X_);                                              \
+        else FEMCY_PAIRS_K(NPE_, NGP_, DM_, RPW_, 4, X_);                                                              \
     } while (0)
-#define FEMCY_PAIRS(NPE_, NGP_)                                                                                        \
+#define FEMCY_PAIRS(NPE_, NGP_, DM_)                                                                                   \
     do {                                                                                                               \
-        if (rpw == 16) { if (xcdc) FEMCY_PAIRS_D(NPE_, NGP_, 16, true); else FEMCY_PAIRS_D(NPE_, NGP_, 16, false); }   \
-        else           { if (xcdc) FEMCY_PAIRS_D(NPE_, NGP_, 8, true); else FEMCY_PAIRS_D(NPE_, NGP_, 8, false); }     \
+        if (rpw == 16) { if (xcdc) FEMCY_PAIRS_D(NPE_, NGP_, DM_, 16, true); else FEMCY_PAIRS_D(NPE_, NGP_, DM_, 16, false); } \
+        else           { if (xcdc) FEMCY_PAIRS_D(NPE_, NGP_, DM_, 8, true); else FEMCY_PAIRS_D(NPE_, NGP_, DM_, 8, false); }   \
     } while (0)
-        if (c->npe == 8) FEMCY_PAIRS(8, 4);
-        else if (c->npe == 6) FEMCY_PAIRS(6, 3);
-        else if (c->npe == 4) FEMCY_PAIRS(4, 4);
-        else FEMCY_PAIRS(3, 1);
+        if (pairs_hex(c)) FEMCY_PAIRS(8, 8, 3);
+        else if (c->npe == 8) FEMCY_PAIRS(8, 4, 2);
+        else if (c->npe == 6) FEMCY_PAIRS(6, 3, 2);
+        else if (c->npe == 4) FEMCY_PAIRS(4, 4, 2);
+        else FEMCY_PAIRS(3, 1, 2);
 #undef FEMCY_PAIRS_K
 #undef FEMCY_PAIRS_D
 #undef FEMCY_PAIRS
@@ -2088,6 +2100,7 @@ int launch_assemble(Ctx* c) {
     }
     timing_end(c, th);
     FEMCY_HIP(hipGetLastError());
+    c->asm_used = mode;
     return FEMCY_OK;
 }
 

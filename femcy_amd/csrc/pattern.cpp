@@ -274,25 +274,41 @@ static void spatial_order(const Ctx* c, const std::vector<int32_t>& node_of, int
 // a slice) and walks the (row, incident element) pairs of its rows, NPE lanes per pair.  The list is in storage order, so
 // the kernel's chain is pr_ptr (scalar) -> codes (one coalesced load) -> records, instead of node_of -> ne_ptr -> ne_idx
 // -> records.  Order inside a chunk: by row, then ascending element = the summation order of every stored block.
+// 3-D (C3D8): step order instead -- the s-th incident element of rows 0 .. RPW-1, then the (s+1)-th, a padding word
+// (INT32_MIN) where a row has no s-th element -- so that the 8 pairs of one kernel step are 8 distinct rows (RPW is 8 or
+// 16) and no LDS word receives two adds from one instruction.  Every block still sums its elements in ascending order.
 int ensure_pairs(Ctx* c, int RPW, bool spatial, int cpw) {
     const int64_t key = ((c->pattern_serial * 64 + RPW) * 2 + (spatial ? 1 : 0)) * 64 + cpw;
     if (c->pairs_serial == key) return FEMCY_OK;
     const int64_t npos = (int64_t)c->nslices * SLICE;
     const int64_t nchunks = npos / RPW;
     const int dm = c->dm;
+    const bool steps = dm == 3;
+    auto nelem = [&](int64_t ch, int r) {
+        const int32_t a = c->h_node_of[(size_t)ch * RPW + r];
+        return a >= 0 ? c->h_ne_ptr[a + 1] - c->h_ne_ptr[a] : 0;
+    };
     std::vector<int32_t> ptr((size_t)nchunks + 1, 0);
     for (int64_t ch = 0; ch < nchunks; ++ch) {
-        int32_t cnt = 0;
+        int32_t cnt = 0, mx = 0;
         for (int r = 0; r < RPW; ++r) {
-            const int32_t a = c->h_node_of[(size_t)ch * RPW + r];
-            if (a >= 0) cnt += c->h_ne_ptr[a + 1] - c->h_ne_ptr[a];
+            cnt += nelem(ch, r);
+            mx = std::max(mx, nelem(ch, r));
         }
-        ptr[ch + 1] = ptr[ch] + cnt;
+        ptr[ch + 1] = ptr[ch] + (steps ? mx * RPW : cnt);
     }
     std::vector<int32_t> code((size_t)ptr[nchunks] + 64, 0);    // + 64 zeros: the list of an empty chunk is read, not used
     parallel_for(nchunks, [&](int64_t lo, int64_t hi, int) {
         for (int64_t ch = lo; ch < hi; ++ch) {
             int32_t w = ptr[ch];
+            if (steps) {
+                for (int32_t st = 0; w < ptr[ch + 1]; ++st)
+                    for (int r = 0; r < RPW; ++r) {
+                        const int32_t a = c->h_node_of[(size_t)ch * RPW + r];
+                        code[w++] = st < nelem(ch, r) ? c->h_ne_idx[c->h_ne_ptr[a] + st] | (r << 27) : INT32_MIN;
+                    }
+                continue;
+            }
             for (int r = 0; r < RPW; ++r) {
                 const int32_t a = c->h_node_of[(size_t)ch * RPW + r];
                 if (a < 0) continue;

@@ -73,6 +73,7 @@ struct femcy_ctx {
     double C[36] = {0}, params[4] = {0, 0, 0, 0}, cubic[3] = {0, 0, 0};
     int32_t mat_kind = -1;
     bool C_is_cubic = false, have_mesh = false, have_element = false, have_material = false, have_pattern = false;
+    bool asm_ran = false;                 // femcy_get_assembly_used
     // block-CSR matrix: row a = blocks rowptr[a] .. rowptr[a+1], diagonal first, then ascending columns
     std::vector<int64_t> rowptr;
     std::vector<int32_t> col;
@@ -252,12 +253,14 @@ void assemble(femcy_ctx* c) {
     }
 }
 int assemble_K(femcy_ctx* c) {
+    c->asm_ran = false;
     if (c->opt_tangent == 1 && c->mat_kind == FEMCY_MAT_PSTRESS) {
         set_error("the consistent tangent is not available for plane stress");
         return FEMCY_EINVAL;
     }
     const double t = c->opt_timing ? now_ms() : 0.0;
     if (c->dm == 3) assemble<3>(c); else assemble<2>(c);
+    c->asm_ran = true;
     if (c->opt_timing) {
         c->timing.assemble_ms += now_ms() - t;
         c->timing.assemble_launches++;
@@ -572,6 +575,14 @@ int femcy_build_pattern(femcy_ctx* ctx) {
         }
     c->have_pattern = true;
     c->have_band_order = false;
+    return FEMCY_OK;
+}
+
+// one assembly here: a serial scatter element by element in ascending element order
+int femcy_get_assembly_used(femcy_ctx* ctx, int32_t* mode) {
+    CTX_OR_FAIL(ctx);
+    REQUIRE(mode && c->asm_ran, "no assembly has run on this context");
+    *mode = FEMCY_ASM_ATOMIC;
     return FEMCY_OK;
 }
 

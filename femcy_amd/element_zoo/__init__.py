@@ -10,4 +10,6 @@ for _order in ("linear", "quadratic"):
         _name = f"Element_{_order}_{_shape}"
         globals()[_name] = getattr(import_module(f"{__name__}.{_name.lower()}"), _name)
         __all__.append(_name)
+from .element_linear_hexahedral import Element_linear_hexahedral   # noqa: E402  (no quadratic hexahedron)
+__all__.append("Element_linear_hexahedral")
 del _order, _shape, _name

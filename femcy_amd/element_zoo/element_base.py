@@ -96,11 +96,15 @@ class ElementBase(abc.ABC):
 
     def globalNormal(self, nodes: np.ndarray, facet: list, integPointId=0):
         """outward unit normal n_g = n_nat (dx/dxi)^-1 (normalised with +1e-30) and
-        (facet size) x (facet point weight) for one facet integration point."""
+        (facet size) x (facet point weight) for one facet integration point.  A 3-D facet of four nodes (hexahedron
+        face) takes the surface Jacobian instead of a size: |det J| |n_nat J^-1| x weight (Nanson's formula)."""
         key = tuple(sorted(facet))
         nat = np.asarray(self.facet_natural_coos[key][integPointId], dtype=np.float64)
         jac = np.asarray(nodes).T @ self.dshape_dnat_pyscope(nat)
         n = np.asarray(self.facet_natural_normals[key][integPointId]) @ np.linalg.inv(jac)
+        if self.dm == 3 and len(key) == 4:
+            nrm = np.linalg.norm(n)
+            return n / (nrm + 1.e-30), abs(np.linalg.det(jac)) * nrm * self.facet_point_weights[key][integPointId]
         n = n / (np.linalg.norm(n) + 1.e-30)
         p = np.asarray(nodes)
         if self.dm == 2:
@@ -110,8 +114,22 @@ class ElementBase(abc.ABC):
         return n, size * self.facet_point_weights[key][integPointId]
 
     def getMesh(self, elements: np.ndarray):
-        """triangles for drawing, face -> elements map, and the outer surface (vectorised)."""
+        """triangles for drawing, face -> elements map, and the outer surface (vectorised).  Elements with
+        quadrilateral faces (`_quad_faces`, node cycles) find the outer surface on the faces themselves, keyed by their
+        sorted nodes, so that it does not depend on how neighbours would split a shared face; `mesh` and the map are then
+        keyed by faces, and the outer faces are split into two triangles each."""
         el = np.asarray(elements)
+        if getattr(self, "_quad_faces", None):
+            quads = np.concatenate([el[:, list(f)] for f in self._quad_faces], axis=0)
+            owner = np.tile(np.arange(el.shape[0]), len(self._quad_faces))
+            keys = np.sort(quads, axis=1)
+            mesh, inv, cnt = np.unique(keys, axis=0, return_inverse=True, return_counts=True)
+            face2ele: Dict[Tuple[int, ...], set] = {}
+            for f, e in zip(map(tuple, keys.tolist()), owner.tolist()):
+                face2ele.setdefault(f, set()).add(e)
+            outer = quads[cnt[inv.ravel()] == 1]
+            surfaces = np.concatenate([outer[:, [0, 1, 2]], outer[:, [0, 2, 3]]], axis=0)
+            return mesh, face2ele, surfaces
         tris = np.sort(np.concatenate([el[:, list(t)] for t in self._tri_split], axis=0), axis=1)
         owner = np.tile(np.arange(el.shape[0]), len(self._tri_split))
         face2ele: Dict[Tuple[int, ...], set] = {}

@@ -42,8 +42,9 @@ def _kuhn_local():
     return np.array(tets, dtype=np.int64)
 
 
-def plate_grid(nx: int, ny: int, nz: int, box: Tuple[float, float, float] = BOX):
-    """nodes f64[(nx+1)(ny+1)(nz+1), 3] (x fastest, then y, then z) and tets i32[6*nx*ny*nz, 4]."""
+def _plate_cells(nx: int, ny: int, nz: int, box: Tuple[float, float, float] = BOX):
+    """nodes of the plate grid, the origin node of every cell (x fastest) and the node offsets of the 8 cell corners
+    (corner c = bit0 x, bit1 y, bit2 z)."""
     xs = np.linspace(0.0, box[0], nx + 1)
     ys = np.linspace(0.0, box[1], ny + 1)
     zs = np.linspace(0.0, box[2], nz + 1)
@@ -54,6 +55,12 @@ def plate_grid(nx: int, ny: int, nz: int, box: Tuple[float, float, float] = BOX)
     idt = np.int32 if nodes.shape[0] < 2 ** 31 else np.int64
     base = (ix * sx + iy * sy + iz * sz).ravel().astype(idt)           # cell origin node, cells x-fastest
     corner_off = np.array([(c & 1) * sx + ((c >> 1) & 1) * sy + ((c >> 2) & 1) * sz for c in range(8)], dtype=idt)
+    return nodes, base, corner_off
+
+
+def plate_grid(nx: int, ny: int, nz: int, box: Tuple[float, float, float] = BOX):
+    """nodes f64[(nx+1)(ny+1)(nz+1), 3] (x fastest, then y, then z) and tets i32[6*nx*ny*nz, 4]."""
+    nodes, base, corner_off = _plate_cells(nx, ny, nz, box)
     local = _kuhn_local()                                              # [6,4] corner ids
     tets = base[:, None, None] + corner_off[local][None, :, :]         # [ncell,6,4]
     return nodes, tets.reshape(-1, 4).astype(np.int32, copy=False)
@@ -116,6 +123,38 @@ def twist_plate(nx: int, ny: int, nz: int, quadratic: bool = False, renumber: bo
     dirichlet = ([{"node_set": clamp, "dof": d, "val": 0.0, "user": False} for d in range(3)] +
                  [{"node_set": twist, "dof": d, "val": 0.0, "user": True} for d in range(3)])
     return {"nodes": nodes, "elements": el, "etype": etype, "node_sets": {"Set-10": clamp, "fit_right_z": twist},
+            "dirichlet_bc_info": dirichlet, "neumann_bc_info": [],
+            "elastic": (2.0e11, 0.3), "geometric_nonlinear": True,
+            "time_incs": {"ini_inc": 0.05, "max_time": 1.0, "min_inc": 1e-5, "max_inc": 0.05},
+            "cells": (nx, ny, nz)}
+
+
+# Abaqus C3D8 node order (face zeta = -1 counter-clockwise, then the face above) as cell corner ids
+_HEX_CORNERS = [0, 1, 3, 2, 4, 5, 7, 6]
+
+
+def plate_hex(nx: int, ny: int, nz: int, perturb: float = 0.0, seed: int = 0,
+              box: Tuple[float, float, float] = BOX):
+    """nodes of `plate_grid` and its cells as C3D8 hexahedra i32[nx*ny*nz, 8].  perturb > 0 moves every node off the
+    box faces by a seeded uniform offset of up to perturb x the smallest cell size per coordinate (distorted meshes;
+    perturb < 0.5 keeps every Jacobian positive)."""
+    nodes, base, corner_off = _plate_cells(nx, ny, nz, box)
+    hexes = (base[:, None] + corner_off[_HEX_CORNERS][None, :]).astype(np.int32, copy=False)
+    if perturb:
+        h = min(box[0] / nx, box[1] / ny, box[2] / nz)
+        inner = np.all((nodes > 1e-9 * max(box)) & (nodes < np.asarray(box) * (1 - 1e-12)), axis=1)
+        rng = np.random.default_rng(seed)
+        nodes = nodes.copy()
+        nodes[inner] += rng.uniform(-perturb * h, perturb * h, size=(int(inner.sum()), 3))
+    return nodes, hexes
+
+
+def twist_plate_hex(nx: int, ny: int, nz: int, perturb: float = 0.0, seed: int = 0) -> Dict:
+    """the twist-plate model on C3D8 hexahedra (the cells of `plate_grid`, not split).  192 x 24 x 216 cells:
+    995 328 hexahedra, the element count of the k = 12 C3D4 plate, 1 050 625 nodes."""
+    nodes, el = plate_hex(nx, ny, nz, perturb, seed)
+    dirichlet, node_sets = twist_plate_bcs(nodes)
+    return {"nodes": nodes, "elements": el, "etype": "C3D8", "node_sets": node_sets,
             "dirichlet_bc_info": dirichlet, "neumann_bc_info": [],
             "elastic": (2.0e11, 0.3), "geometric_nonlinear": True,
             "time_incs": {"ini_inc": 0.05, "max_time": 1.0, "min_inc": 1e-5, "max_inc": 0.05},

@@ -6,7 +6,8 @@ face_sets, dirichlet_bc_info, neumann_bc_info, materials, geometric_nonlinear, t
 
 Reference behaviours that are kept on purpose:
   * only the first `*Node` block is read; node labels are renumbered 0.. in file order (:353-368);
-  * the element type is found by substring test in a fixed list order, so CPS6M -> CPS6 (:66-75);
+  * the element type is found by substring test in a fixed list order, so CPS6M -> CPS6 (:66-75), and C3D8R /
+    C3D8I read as C3D8 with full 2 x 2 x 2 integration (no hourglass control, no incompatible modes);
   * only `*Nset`/`*Elset` keyword lines that contain "instance" are kept; `generate` expands
     start,stop,step inclusively (:142-163);
   * `*Surface` data lines `elset, S<k>` map through ELE.inp_surface_num[k-1]; a face set is a
@@ -27,7 +28,7 @@ import numpy as np
 
 from ..element_zoo import (Element_linear_triangular, Element_linear_quadrilateral,
                            Element_quadratic_triangular, Element_quadratic_quadrilateral,
-                           Element_linear_tetrahedral, Element_quadratic_tetrahedral)
+                           Element_linear_tetrahedral, Element_quadratic_tetrahedral, Element_linear_hexahedral)
 from ..material_zoo import (LinearIsotropic, LinearIsotropicPlaneStrain, LinearIsotropicPlaneStress, NeoHookean)
 from .inp_info_base import InpInfoBase
 
@@ -44,7 +45,8 @@ ELEMENT_CLASSES = {"CPE3": Element_linear_triangular, "CPS3": Element_linear_tri
                    "CPE4": Element_linear_quadrilateral, "CPS4": Element_linear_quadrilateral,
                    "CPS6": Element_quadratic_triangular, "CPE6": Element_quadratic_triangular,
                    "CPS8": Element_quadratic_quadrilateral, "CPE8": Element_quadratic_quadrilateral,
-                   "C3D4": Element_linear_tetrahedral, "C3D10": Element_quadratic_tetrahedral}
+                   "C3D4": Element_linear_tetrahedral, "C3D10": Element_quadratic_tetrahedral,
+                   "C3D8": Element_linear_hexahedral}
 
 
 class _Deck:

@@ -79,10 +79,11 @@ enum femcy_gpfield {
 /* assembly strategy (femcy_set_option FEMCY_OPT_ASSEMBLY) */
 enum femcy_assembly {
     FEMCY_ASM_GATHER = 0, /* owner-computes: one lane per stored block, deterministic            */
-    FEMCY_ASM_ATOMIC = 1, /* element scatter with f64 HW atomics (comparison / race check)        */
+    FEMCY_ASM_ATOMIC = 1, /* element scatter with f64 HW atomics (comparison / race check).  The host
+                             backend reports this value for its serial element-by-element scatter (no atomics) */
     FEMCY_ASM_ROWS = 2,   /* one wavefront per matrix row, LDS reduction, deterministic           */
     FEMCY_ASM_AUTO = 3,   /* default: ROWS4 for C3D10 (ROWS2 / ROWS if its LDS does not fit), PAIRS for the 2-D quadratic
-                             families (ROWS if its LDS does not fit), GATHER_SYM(_ROWSUM) otherwise */
+                             families and C3D8 (ROWS if its LDS does not fit), GATHER_SYM(_ROWSUM) otherwise */
     FEMCY_ASM_GATHER_SYM = 4, /* GATHER on the diagonal + upper blocks only, mirrored stores of K_ba = K_ab^T: 1.3x on C3D4 */
     FEMCY_ASM_GATHER_SYM_ROWSUM = 5, /* the same with the diagonal block from K_aa = -sum_{b != a} K_ab (partition of
                                 unity, checked on the element tables); AUTO picks it for npe <= 4 */
@@ -97,7 +98,8 @@ enum femcy_assembly {
                              column node, the element's whole record is read once per pair by coalesced 16-byte loads
                              (the row node's gradients come from the neighbouring lane), the geometric sums are reduced
                              in a wave-private LDS tile and the tile is written as 256-byte runs; any constant C.
-                             2-D families; AUTO picks it for CPE6 / CPS6 / CPE8 / CPS8 */
+                             2-D families and C3D8 (3 x 3 blocks; pair lists in step order, so no two lanes of one
+                             LDS add hit the same word); AUTO picks it for CPE6 / CPS6 / CPE8 / CPS8 and C3D8 */
 };
 
 enum femcy_option {
@@ -285,6 +287,11 @@ int femcy_set_material(femcy_ctx* ctx, int32_t kind, const double* C /*[s*s]*/, 
  * node adjacency -> blocked sliced-ELL matrix, element->slot map, node->element lists */
 int femcy_build_pattern(femcy_ctx* ctx);
 int femcy_get_pattern_info(femcy_ctx* ctx, femcy_pattern_info* out);
+/* the femcy_assembly mode the last femcy_assemble_K / femcy_residual_and_K ran, after AUTO and the LDS fall-backs
+ * resolved (the consistent tangent reports GATHER_SYM_ROWSUM / GATHER_SYM, the gather form it runs).  The host backend
+ * has one assembly, a serial element-by-element scatter, and reports FEMCY_ASM_ATOMIC.  FEMCY_EINVAL before the first
+ * assembly of the context, and after an assembly that was refused or failed. */
+int femcy_get_assembly_used(femcy_ctx* ctx, int32_t* mode);
 /* which row order femcy_build_pattern took (FEMCY_OPT_NODE_ORDER): used = 0 the caller's numbering, 1 + k = coordinate
  * order k; lines[0] = mean 128-byte cache lines per wavefront gather with the caller's numbering, lines[1 + k] = with
  * coordinate order k (0 where not evaluated) */
@@ -340,7 +347,9 @@ int femcy_dofset_scatter(femcy_ctx* ctx, int32_t id, int vec, const double* vals
  * femcy_loadset_neumann zero-fills vec[rhs] (reference :384) and writes the consistent nodal loads of
  * traction * (direction, or the outward unit normal n_nat (dx/dxi)^-1 / (|.| + 1e-30) when direction is NULL)
  * on the undeformed geometry; the facet size is |x1 - x0| (dm = 2) or the triangle area of the facet's first
- * three sorted nodes (dm = 3), as ELE.globalNormal computes it.  Sums per node run in a fixed order. */
+ * three sorted nodes (dm = 3), as ELE.globalNormal computes it.  A 3-D facet of four nodes (a hexahedron face)
+ * instead weights each facet point by its surface Jacobian (Nanson): da = |det J| |J^-T n_nat| w.  Sums per node
+ * run in a fixed order. */
 int femcy_loadset_create(femcy_ctx* ctx, int32_t nft, int32_t nfn, int32_t nip, const int32_t* ft_nodes,
                          const double* ft_N, const double* ft_dN, const double* ft_normal, const double* ft_weight,
                          int32_t nload, const int32_t* load_elem, const int32_t* load_ft, int32_t* id_out);
