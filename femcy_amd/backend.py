@@ -54,15 +54,14 @@ TUNE_PERSIST_VARIANT = 109   # persistent PCG variant bits (-1 default; femcy.h)
 TUNE_SKIP_OCCUPANCY_CHECK = 111
 TUNE_BARRIER_SPIN_LIMIT = 112
 TUNE_PERSIST_L2_ROWS = 113
-TUNE_ROWS4_TILE = 116       # ROWS4 assembly, round-5 experiment: 1000 GP + LCUT (tile write-out), 0 = off
 TUNE_SPMV_WG_PER_XCD = 101  # SpMV workgroups per XCD: 0 auto (512 beyond 512 tasks per XCD, else 256)
 TUNE_SPMV_ROT = 119         # SpMV task lists: -1 auto (by the spread of the row lengths), 0 plain, 1..63 rotated rounds, 64 balanced
-TUNE_ROWS4_ORDER = 118      # ROWS4 launch order: -1 auto, 0 longest first, 1 Morton / XCD-contiguous
 TUNE_PAIRS = 117            # PAIRS assembly knobs (femcy.h)
 TUNE_DIRECT_UPDATE = 115    # femcy_direct_solve tile update: -1 auto, 0 VALU, 1 / 2 matrix cores
 TUNE_PERSIST_MAX_MB = 114   # persistent PCG: streamed-matrix limit in MiB (0 = none, the default since round 5; 240 = rounds 2-4)
 OPT_OVERLAP = 9          # multi-rank, neighbour exchange: 1 (default) = exchange overlapped with the interior product
-ASM_GATHER, ASM_ATOMIC, ASM_ROWS, ASM_AUTO, ASM_GATHER_SYM, ASM_GATHER_SYM_ROWSUM, ASM_ROWS2, ASM_ROWS3, ASM_ROWS4, ASM_PAIRS = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
+ASM_GATHER, ASM_ATOMIC, ASM_ROWS, ASM_AUTO, ASM_GATHER_SYM, ASM_GATHER_SYM_ROWSUM, ASM_ROWS2, ASM_ROWS4, ASM_PAIRS = 0, 1, 2, 3, 4, 5, 6, 8, 9
+ASM_ROWS3 = 7               # retired: the HIP library refuses it (the name stays so that callers of the old list still import)
 
 EXPORTS = [
     "femcy_ctx_create", "femcy_ctx_destroy", "femcy_last_error", "femcy_version", "femcy_set_option", "femcy_sync",

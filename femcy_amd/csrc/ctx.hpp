@@ -159,10 +159,6 @@ struct Ctx {
     // ---- blocked SELL-64 matrix (lane = node, diagonal block in slot 0)
     int32_t nslices = 0;
     int32_t* d_asm_order = nullptr;   // row-centric assembly (rows4): slices by decreasing work (workgroup b takes entry b)
-    int32_t* d_asm_order_near = nullptr;   // ... or in Morton order of their centroids, taken in XCD-contiguous ranges (records
-                                      // beyond the Infinity Cache: FEMCY_TUNE_ROWS4_ORDER)
-    int32_t* d_asm_order_id = nullptr;     // ... or in storage order (experiments)
-    int tune_rows4_order = -1;        // -1 auto (by the size of the element records), 0 longest first, 1 locality
     XcdRanges xcd{};                  // SpMV: slice range per XCD
     int32_t spmv_grid = 0;            // 8 * max blocks per XCD
     int32_t spmv_wps = 1;             // wavefronts per slice (1, 2 or 4)
@@ -201,7 +197,7 @@ struct Ctx {
     // pair lists of FEMCY_ASM_PAIRS (pattern.cpp: ensure_pairs, built on first use): per chunk of 16 (or 8) consecutive storage
     // positions the (row, incident element) pairs in (row, ascending element) order -- code e*npe+la and row inside the chunk;
     // 3-D: in step order, the s-th element of every row of the chunk, padded to whole steps
-    std::vector<int32_t> h_node_of, h_ne_ptr, h_ne_idx;
+    std::vector<int32_t> h_node_of, h_ne_ptr, h_ne_idx;   // what they are built from (build_pattern: PAIRS families only)
     int32_t* d_pr_ptr = nullptr;      // PairBatch descriptors (32 B) in PROCESSING order
     int32_t* d_pr_unit = nullptr;     // [units + 1] first batch of every wavefront's unit of chunks
     int32_t* d_pr_code = nullptr;     // [ne*npe + 64] row inside the chunk << 27 | e*npe+la
@@ -251,7 +247,6 @@ struct Ctx {
     // against 78.0 (profiles/r05_persist_hbm_c3d10.txt) -- the rule was stale.  What bounds the kernel is the vector
     // layout (<= 4 slices per wave), not the matrix: no byte limit by default any more (test knob: option 114)
     int64_t persist_max_bytes = (int64_t)1 << 40;
-    int tune_rows4_tile = 0;          // FEMCY_TUNE_ROWS4_TILE: 1000 GP + LCUT, 0 = off (round-5 experiment, kernels_assembly.hip)
     int opt_persist_rj = 4;           // block rows per slice kept in registers (test knob 105)
     int opt_persist_wgs = 0;          // test knob 107: workgroups of the launch (0 = one per CU; more than that cannot
                                       // be co-resident, the barrier times out and the solve falls back)
@@ -425,6 +420,13 @@ int probe_mailbox(Ctx* c, int32_t rounds, double* us_per_round);
 int probe_spmv(Ctx* c, int32_t reps, int32_t storage_order, double* us_per_launch);
 int spmv_public_storage_order(Ctx* c, const double* d_x, double* d_y);   // femcy_spmv through the storage-order kernel
 int64_t persist_streamed_bytes(Ctx* c);
+// FEMCY_ASM_PAIRS (kernels_assembly.hip) is instantiated for C3D8 and the 2-D families
+inline bool pairs_hex(const Ctx* c) { return c->dm == 3 && c->npe == 8 && c->nGP == 8; }
+inline bool pairs_instantiated(const Ctx* c) {
+    return pairs_hex(c) ||
+           (c->dm == 2 && ((c->npe == 8 && c->nGP == 4) || (c->npe == 6 && c->nGP == 3) || (c->npe == 4 && c->nGP == 4) ||
+                           (c->npe == 3 && c->nGP == 1)));
+}
 int ensure_pairs(Ctx* c, int rows_per_chunk, bool spatial_order, int chunks_per_wave);   // pattern.cpp: d_pr_unit / d_pr_ptr / d_pr_code for the current pattern
 int ensure_footprint(Ctx* c);   // pattern.cpp: d_lcol / d_fp_ptr / d_fp for the current pattern and spmv_wps
 int ensure_pos_vectors(Ctx* c);   // d_posb / d_posx (storage-order right-hand side / solution) + d_bcolp

@@ -249,7 +249,7 @@ int femcy_ctx_destroy(femcy_ctx* ctx) {
     dev_free(&c->d_slice_len); dev_free(&c->d_slice_off); dev_free(&c->d_rowlen); dev_free(&c->d_bcol);
     dev_free(&c->d_pos); dev_free(&c->d_node_of);
     dev_free(&c->d_Kvals); dev_free(&c->d_slotj); dev_free(&c->d_ctr_ptr); dev_free(&c->d_ctr); dev_free(&c->d_tpos);
-    dev_free(&c->d_ne_ptr); dev_free(&c->d_ne_idx); dev_free(&c->d_asm_order); dev_free(&c->d_asm_order_near); dev_free(&c->d_asm_order_id); dev_free(&c->d_spmv_perm);
+    dev_free(&c->d_ne_ptr); dev_free(&c->d_ne_idx); dev_free(&c->d_asm_order); dev_free(&c->d_spmv_perm);
     dev_free(&c->d_pr_ptr); dev_free(&c->d_pr_unit); dev_free(&c->d_pr_code);
     dev_free(&c->d_dsdx); dev_free(&c->d_vol); dev_free(&c->d_F); dev_free(&c->d_sigma);
     dev_free(&c->d_strain); dev_free(&c->d_mises); dev_free(&c->d_energy); dev_free(&c->d_fe);
@@ -301,6 +301,7 @@ int femcy_set_option(femcy_ctx* ctx, int option, int64_t value) {
     switch (option) {
         case FEMCY_OPT_ASSEMBLY:
             FEMCY_REQUIRE(value >= FEMCY_ASM_GATHER && value <= FEMCY_ASM_PAIRS, "bad assembly mode %lld", (long long)value);
+            FEMCY_REQUIRE(value != 7, "assembly mode 7 is retired");
             c->opt_assembly = (int)value;
             break;
         case FEMCY_OPT_DIRECT_MAX_BYTES:
@@ -374,11 +375,6 @@ int femcy_set_option(femcy_ctx* ctx, int option, int64_t value) {
             break;
         case FEMCY_TUNE_DIRECT_UPDATE:
             return direct_set_update_variant(c, value);
-        case FEMCY_TUNE_ROWS4_TILE:
-            FEMCY_REQUIRE(value == 0 || ((value / 1000 == 2 || value / 1000 == 4) && value % 1000 > 0),
-                          "ROWS4 tile write-out: 0 (off) or 1000 GP + LCUT with GP 2 or 4 and LCUT > 0 blocks");
-            c->tune_rows4_tile = (int)value;
-            break;
         case FEMCY_TUNE_SPMV_ROT:
             FEMCY_REQUIRE(value >= -1 && value <= 64, "SpMV task lists: -1 (by the spread of the row lengths), 0 (plain), 1 .. 63 (rounds rotated), 64 (balanced by the host)");
             c->opt_spmv_rot = (int32_t)value;
@@ -386,10 +382,6 @@ int femcy_set_option(femcy_ctx* ctx, int option, int64_t value) {
                 pcg_graph_reset(c);
                 spmv_split(c);
             }
-            break;
-        case FEMCY_TUNE_ROWS4_ORDER:
-            FEMCY_REQUIRE(value >= -1 && value <= 3, "ROWS4 launch order: -1 auto, 0 longest slices first, 1 Morton order in XCD-contiguous ranges");
-            c->tune_rows4_order = (int)value;
             break;
         case FEMCY_TUNE_PAIRS:
             if (value == -1) value = FEMCY_PAIRS_DEFAULT;

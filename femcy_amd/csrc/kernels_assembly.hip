@@ -5,7 +5,9 @@
 //   get_dsdx_and_vol             stiffnessMtrx.py:132-150   -> k_geom
 //   get_deformation_gradient     stiffnessMtrx.py:532-556   -> k_geom<STRESS=true>
 //   constitutiveOfLargeDeform x4 material_zoo/*.py          -> cauchy_large()
-//   assemble_stiffnessMtrx       stiffnessMtrx.py:161-186   -> k_assemble_gather / k_assemble_atomic
+//   assemble_stiffnessMtrx       stiffnessMtrx.py:161-186   -> k_assemble_gather (+ k_diag_from_rowsum), k_assemble_rows,
+//                                                              k_assemble_rows2, k_assemble_rows4, k_assemble_pairs,
+//                                                              k_assemble_atomic (FEMCY_ASM_*: launch_assemble)
 //   assemble_nodal_force_GN_kernel  stiffnessMtrx.py:620-644 -> k_nodal_force
 //   dirichletBC_* kernels        stiffnessMtrx.py:279-341   -> k_dirichlet_zero
 //
@@ -17,6 +19,12 @@
 //     of every (element, Gauss point) that touches it in a fixed order and writes the block once,
 //     fully coalesced (8*nnz bytes reach HBM, no zero-fill pass, no atomics, bit-reproducible).
 //     The atomic variant (f64 global_atomic_add) is kept for comparison and as the race check.
+//   * The row-centric assemblies (rows, rows2, rows4, pairs) are deterministic too: each sums a block's
+//     contributions in a fixed order of its own, not in the reference's order, with ds_add_f64, and
+//     relies on the adds of one instruction to the same LDS address being applied in lane order.
+//     PAIRS forms K = T (sum S): it sums the geometric products S of a block and applies the map T of
+//     the material constants once per stored block (its 3-D lists, in step order, never put two adds
+//     of one instruction on the same address).
 //   * B has 3 (3-D) / 2 (2-D) non-zeros per column; B^T C B is evaluated on those only, in the same
 //     ascending Voigt order as the reference's dense products, so the only rounding differences are
 //     FMA contraction and the (order-free in the reference) accumulation order over elements.
@@ -755,212 +763,6 @@ __global__ void __launch_bounds__(256) k_assemble_rows2(int32_t nslices, int32_t
 #undef ROW_L
 }
 
-// row-centric assembly, third form (round 3): k_assemble_rows2 with the write-out of EIGHT adjacent rows at a time.
-// rows2 writes a finished row as 16-byte pieces, one per block entry pair, 1 KiB apart (the lane-interleaved SELL
-// layout is made for the product): every 128-byte line of K is touched by eight rows at eight different times, the
-// L2 fetches the line for the first partial write (read-for-fill) and often writes it back more than once --
-// profiles/r02_pmc_rows2_c3d10.txt: FETCH 563 MB + WRITE 515 MB for 357 MB of K + 123 MB of records.  Here wave w
-// of the workgroup takes rows 8 g + 2 w and 8 g + 2 w + 1 of group g (two accumulators per wave), the four waves meet
-// at the end of the group, and all 256 threads write the group: eight lanes x 16 bytes = one whole 128-byte line per
-// (block, entry pair), 64 bytes for the trailing entry plane -- no line is written twice, none is fetched.  Two
-// workgroup barriers per 8 rows (rows2's experiment with 4-row / 64-byte write-outs paid two per row).
-// Everything else (LDS-staged records, the three-deep software pipeline over passes, lanes = (element, column != row)
-// pairs, row-sum diagonal, 30-flop blocks for cubic C, fixed order => bit-reproducible) is rows2's.
-template <int NPE, int NGP, bool CUBIC>
-__global__ void __launch_bounds__(256) k_assemble_rows3(int32_t nslices, int32_t nn, int32_t Lmax,
-                                                        const int32_t* __restrict__ ne_ptr,
-                                                        const int32_t* __restrict__ ne_idx,
-                                                        const uint16_t* __restrict__ slotj,
-                                                        const int32_t* __restrict__ rowlen,
-                                                        const int32_t* __restrict__ node_of,
-                                                        const int64_t* __restrict__ slice_off,
-                                                        const double* __restrict__ dsdx, const double* __restrict__ vol,
-                                                        const double* __restrict__ C, double c11, double c12, double c44,
-                                                        double* __restrict__ Kvals) {
-    constexpr int DM = 3, DD = 9, T = NPE - 1, EPC = 64 / T, RD = NGP * NPE * DM, P16 = RD / 2;
-    constexpr int NIT = (EPC * P16 + 63) / 64;                   // 16-byte pieces per lane and pass (C3D10: 7)
-    constexpr int VOLW = (EPC * NGP + 1) & ~1, CODEW = (EPC + 1) / 2 * 2 / 2 + 1;
-    static_assert(RD % 2 == 0, "records are staged in 16-byte pieces");
-    static_assert(EPC * NGP <= 64, "one vol value per lane and pass");
-    extern __shared__ __attribute__((aligned(16))) double lds_rows3[];
-    __shared__ int32_t gL[8];                                    // row lengths of the group being written
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int accw = (Lmax * DD + 1) & ~1;
-    const int wstride = EPC * RD + VOLW + 2 * accw + 2 * CODEW;  // doubles per wave
-    double* rec = lds_rows3 + (size_t)wave * wstride;
-    double* vl = rec + EPC * RD;
-    double* acc0 = vl + VOLW;                                    // two row accumulators: rows 2 w and 2 w + 1 of a group
-    int32_t* codes = reinterpret_cast<int32_t*>(acc0 + 2 * accw);
-    const int32_t s = blockIdx.x;
-    if (s >= nslices) return;
-    const int64_t off = slice_off[s];
-    const int32_t nvalid = min(SLICE, nn - s * SLICE);           // valid rows are a prefix of the slice
-    const int ngroups = (nvalid + 7) / 8;
-
-    // ---- the wave's rows: its i-th row is slice lane 8 (i / 2) + 2 wave + (i % 2); lane i holds the metadata
-    constexpr int RPW = SLICE / 4;
-    int32_t m_L = 0, m_k0 = 0, m_cnt = 0;
-    bool m_valid = false;
-    if (lane < RPW) {
-        const int32_t a = node_of[(int64_t)s * SLICE + 8 * (lane >> 1) + 2 * wave + (lane & 1)];
-        if (a >= 0) {
-            m_valid = true;
-            m_L = rowlen[a];
-            m_k0 = ne_ptr[a];
-            m_cnt = ne_ptr[a + 1] - m_k0;
-        }
-    }
-    const int nrows = __popcll(__ballot(m_valid));               // valid rows are a prefix in i as well
-#define ROW_CNT(i) __builtin_amdgcn_readlane(m_cnt, (i))
-#define ROW_K0(i) __builtin_amdgcn_readlane(m_k0, (i))
-#define ROW_L(i) __builtin_amdgcn_readlane(m_L, (i))
-    auto advance = [&](int& i, int& c0) {
-        c0 += EPC;
-        if (i < nrows && c0 >= ROW_CNT(i)) {
-            ++i;
-            c0 = 0;
-        }
-    };
-    auto load_codes = [&](int i, int c0) -> int32_t {           // lane q: (element, local row node) code of element q
-        if (i >= nrows) return 0;
-        const int32_t nE = min(EPC, ROW_CNT(i) - c0);
-        return lane < nE ? ne_idx[ROW_K0(i) + c0 + lane] : 0;
-    };
-    double2 R[NIT];
-    double V = 0.0;
-    int32_t JS = 0;
-#define LOAD_RECORDS(code_, i_, c0_)                                                                  \
-    if ((i_) < nrows) {                                                                               \
-        const int32_t nE_ = min(EPC, ROW_CNT(i_) - (c0_));                                            \
-        _Pragma("unroll") for (int u = 0; u < NIT; ++u) {                                             \
-            const int32_t p_ = lane + 64 * u;                                                         \
-            const int32_t q_ = p_ / P16, w_ = p_ - q_ * P16;                                          \
-            const int64_t e_ = __shfl((code_), q_, 64) / NPE;                                         \
-            if (p_ < nE_ * P16) R[u] = reinterpret_cast<const double2*>(dsdx + e_ * RD)[w_];          \
-        }                                                                                             \
-        const int32_t qv_ = lane / NGP, gv_ = lane - qv_ * NGP;                                       \
-        const int64_t ev_ = __shfl((code_), qv_, 64) / NPE;                                           \
-        if (lane < nE_ * NGP) V = vol[ev_ * NGP + gv_];                                               \
-        const int32_t qt_ = lane / T, jb_ = lane - qt_ * T;                                           \
-        const int32_t ct_ = __shfl((code_), qt_, 64);                                                 \
-        const int32_t lat_ = ct_ % NPE;                                                               \
-        if (lane < nE_ * T) JS = slotj[(int64_t)ct_ * NPE + jb_ + (jb_ >= lat_ ? 1 : 0)];             \
-    }
-#pragma unroll
-    for (int u = 0; u < NIT; ++u) R[u] = make_double2(0.0, 0.0);
-
-    int i0 = 0, c00 = 0, i1 = 0, c01 = 0, i2 = 0, c02 = 0;
-    advance(i1, c01);
-    i2 = i1;
-    c02 = c01;
-    advance(i2, c02);
-    int32_t code_c = load_codes(i0, c00);
-    int32_t code_n = load_codes(i1, c01);
-    LOAD_RECORDS(code_c, i0, c00)
-
-    for (int g = 0; g < ngroups; ++g) {
-        // both accumulators of the wave start at zero (the previous group has been written: second barrier below)
-        for (int h = 0; h < 2; ++h) {
-            const int i = 2 * g + h;
-            if (i < nrows) {
-                double* acc = acc0 + h * accw;
-                for (int idx = lane; idx < ROW_L(i) * DD; idx += 64) acc[idx] = 0.0;
-            }
-        }
-        while (i0 < nrows && (i0 >> 1) == g) {
-            double* acc = acc0 + (i0 & 1) * accw;
-            const int32_t cnt = ROW_CNT(i0);
-            const int32_t nE = max(0, min(EPC, cnt - c00));
-            wave_lds_sync();                                        // the previous pass is done with rec / vl / codes
-            if (lane < nE) codes[lane] = code_c;
-#pragma unroll
-            for (int u = 0; u < NIT; ++u) {
-                const int32_t p = lane + 64 * u;
-                const int32_t q = p / P16, w = p - q * P16;
-                if (p < nE * P16) reinterpret_cast<double2*>(rec + q * RD)[w] = R[u];
-            }
-            if (lane < nE * NGP) vl[lane] = V;
-            int32_t j = JS;
-            asm volatile("" : "+v"(j));     // consume JS here (see k_assemble_rows2)
-            LOAD_RECORDS(code_n, i1, c01)
-            const int32_t code_nn = load_codes(i2, c02);
-            wave_lds_sync();
-            if (lane < nE * T) {
-                const int32_t q = lane / T, jb = lane - q * T;
-                const int32_t code = codes[q];
-                const int32_t la = code % NPE;
-                const int32_t lb = jb + (jb >= la ? 1 : 0);         // every column node of the element but the row node
-                double blk[DD];
-#pragma unroll
-                for (int k = 0; k < DD; ++k) blk[k] = 0.0;
-#pragma unroll
-                for (int gp = 0; gp < NGP; ++gp) {
-                    const double* ga = rec + q * RD + (gp * NPE + la) * DM;
-                    const double* gb = rec + q * RD + (gp * NPE + lb) * DM;
-                    if (CUBIC) kblock_cubic3(ga, gb, c11, c12, c44, vl[q * NGP + gp], blk);
-                    else kblock_add<3>(ga, gb, C, vl[q * NGP + gp], blk);
-                }
-#pragma unroll
-                for (int k = 0; k < DD; ++k) atomicAdd(&acc[j * DD + k], blk[k]);
-            }
-            if (c00 + EPC >= cnt) {                                 // last pass of the row: diagonal from the row sum
-                const int32_t L = ROW_L(i0);
-                wave_lds_sync();
-                if (lane < 63) {
-                    const int jj = lane / DD, k = lane - jj * DD;
-                    double t = 0.0;
-                    for (int32_t jx = 1 + jj; jx < L; jx += 7) t += acc[jx * DD + k];
-                    rec[lane] = t;
-                }
-                wave_lds_sync();
-                if (lane < DD) {
-                    double t = 0.0;
-#pragma unroll
-                    for (int jj = 0; jj < 7; ++jj) t += rec[jj * DD + lane];
-                    acc[lane] = -t;
-                }
-                if (lane == 0) gL[2 * wave + (i0 & 1)] = L;
-            }
-            i0 = i1; c00 = c01;
-            i1 = i2; c01 = c02;
-            advance(i2, c02);
-            code_c = code_n;
-            code_n = code_nn;
-        }
-        // ---- the group's eight rows are complete: all threads write them, whole lines at a time
-        __syncthreads();
-        {
-            const int r8 = threadIdx.x & 7;                          // row of the group
-            const int rr = 8 * g + r8;                               // slice lane
-            const bool rv = rr < nvalid;
-            const int32_t Lr = rv ? gL[r8] : 0;
-            int32_t Lg = 0;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) Lg = max(Lg, (8 * g + q < nvalid) ? gL[q] : 0);
-            const double* accr = lds_rows3 + (size_t)(r8 >> 1) * wstride + (EPC * RD + VOLW) + (r8 & 1) * accw;
-            double* __restrict__ Krow = Kvals + off * (int64_t)(DD * SLICE);
-            for (int idx = threadIdx.x >> 3; idx < Lg * 5; idx += 32) {
-                const int j = idx / 5, pc = idx - j * 5;
-                double* dst = Krow + (int64_t)j * (DD * SLICE);
-                const bool has = j < Lr;                             // rows shorter than the group's longest: zero blocks
-                if (rv) {
-                    if (pc < 4) {
-                        reinterpret_cast<double2*>(dst + pc * (2 * SLICE))[rr] =
-                            has ? make_double2(accr[j * DD + 2 * pc], accr[j * DD + 2 * pc + 1]) : make_double2(0.0, 0.0);
-                    } else {
-                        dst[4 * (2 * SLICE) + rr] = has ? accr[j * DD + 8] : 0.0;
-                    }
-                }
-            }
-        }
-        __syncthreads();
-    }
-#undef LOAD_RECORDS
-#undef ROW_CNT
-#undef ROW_K0
-#undef ROW_L
-}
-
 // scatter assembly with hardware f64 atomics: one lane per element-local (a,b) block
 template <int DM>
 __global__ void __launch_bounds__(256) k_assemble_atomic(int64_t npair, int32_t npe, int32_t nGP,
@@ -1006,15 +808,8 @@ __global__ void __launch_bounds__(256) k_assemble_atomic(int64_t npair, int32_t 
 //   * at the end of a pair of rows each lane takes one stored block (32 per trip: one trip for most rows) out of LDS,
 //     leaves zeros, applies the material constants and stores its five pieces.
 // Deterministic for the same reason as rows2 (fixed step order, ds_add_f64 of one instruction applied in lane order).
-//
-// GP > 0 (round 5, the verdict's "a wave owns adjacent rows and writes whole lines from its own LDS tile"; experiment,
-// FEMCY_TUNE_ROWS4_TILE = 1000 GP + LCUT): in slices no wider than `lcut` blocks a wave owns 16 CONSECUTIVE rows, keeps the finished
-// rows of GP pairs (2 GP adjacent rows) in a tile of its own LDS and writes them out together: a store instruction
-// then covers 32 GP contiguous bytes of 32 / GP slots instead of 32 bytes of 32 slots -- no workgroup barrier (rows3
-// lost 57 us to one).  Wider slices (the corner nodes' rows) run as before.
-template <int NPE, int NGP, bool CUBIC, int GP>
-__global__ void __launch_bounds__(256) k_assemble_rows4(int32_t nslices, int32_t Lmax, int32_t lcut, int32_t wstride,
-                                                        int32_t xcdc, const int32_t* __restrict__ order,
+template <int NPE, int NGP, bool CUBIC>
+__global__ void __launch_bounds__(256) k_assemble_rows4(int32_t nslices, int32_t Lmax, const int32_t* __restrict__ order,
                                                         const int32_t* __restrict__ ne_ptr,
                                                         const int32_t* __restrict__ ne_idx,
                                                         const uint16_t* __restrict__ slotj,
@@ -1035,32 +830,23 @@ __global__ void __launch_bounds__(256) k_assemble_rows4(int32_t nslices, int32_t
     const int grp = lane >> 5, gl = lane & 31, gbase = grp * G;
     const int q = gl / NPE, t = gl - q * NPE;                    // element of the step, column node
     const int accw = (Lmax * DD + 1) & ~1;
-    constexpr int RG = GP ? 2 * GP : 2;                          // rows of a tile
-    const int accw_t = (lcut * DD) | 1;                          // an odd number of doubles: the rows of a tile start in different banks
-    double* wbase = lds_rows4 + (size_t)wave * wstride;
     // workgroup b takes the b-th slice in order of decreasing work (pattern.cpp: `asm_order`).  Workgroups are dispatched
     // in index order and run on XCD b % 8 (observed; speed only): longest first gives every XCD an even share of every
     // weight class and lets the short slices fill the tail.  Round 4: in plain slice order a row order whose long rows
     // recur with a period that is a multiple of 8 slices (the coordinate orders of FEMCY_OPT_NODE_ORDER) put twice the
     // work on one XCD -- 303 -> 483 us with identical instruction counts, profiles/r04_pmc_rows4_node_order.txt --
     // and contiguous per-XCD ranges (balanced by blocks: 392 us, by work: 355 us) lose the mixing of long and short
-    // slices the caller's numbering happens to have (its corner rows come first)
-    // round 6 (`xcdc`, with `order` = the slices in Morton order of their centroids): workgroup b takes entry b / 8 of XCD
-    // (b % 8)'s CONTIGUOUS eighth of the order -- on a mesh whose element records exceed the Infinity Cache (C3D10 k = 12:
-    // 0.99 GB) the kernel was bound by re-fetching every record once per node of its element from HBM (FETCH 5.9 GB
-    // reported for 2.8 GB of K, profiles/r06_pmc_c3d10_k12_first.txt); neighbouring slices on one L2 find them there
-    int32_t wgi = (int32_t)blockIdx.x;
-    if (xcdc) wgi = (wgi & 7) * ((int32_t)gridDim.x >> 3) + (wgi >> 3);
+    // slices the caller's numbering happens to have (its corner rows come first).  Round 6: slices in Morton order in
+    // XCD-contiguous ranges, for records beyond the Infinity Cache, measured slower at every size
+    const int32_t wgi = (int32_t)blockIdx.x;
     if (wgi >= nslices) return;
     const int32_t s = __builtin_amdgcn_readfirstlane(order[wgi]);
     const int64_t off_v = slice_off[s];
     const int64_t off = ((int64_t)__builtin_amdgcn_readfirstlane((int32_t)(off_v >> 32)) << 32) |
                         (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)off_v);
-    const bool tile = GP > 0 && __builtin_amdgcn_readfirstlane((int32_t)(slice_off[s + 1] - off_v)) <= lcut;   // the slice's width
-    double* rec = wbase + (size_t)grp * (tile ? EPG * RD + VOLW + 2 : EPG * RD + VOLW + accw + 2);     // this half's records
+    double* rec = lds_rows4 + (size_t)(2 * wave + grp) * (EPG * RD + VOLW + accw + 2);   // this half's records
     double* vl = rec + EPG * RD;
-    double* acc = vl + VOLW;                                     // pair layout: this half's row
-    double* tbase = wbase + 2 * (EPG * RD + VOLW + 2);           // tile layout: RG rows of accw_t
+    double* acc = vl + VOLW;                                     // this half's row
 
     // ---- the wave's rows: pair b = slice lanes 8 b + 2 wave and + 1 -- ADJACENT rows, so that the two halves of a
     // store instruction write neighbouring 16-byte pieces of the same line (one request instead of two), and the eight
@@ -1070,7 +856,7 @@ __global__ void __launch_bounds__(256) k_assemble_rows4(int32_t nslices, int32_t
     int32_t m_L = 0, m_k0 = 0, m_cnt = 0;
     bool m_valid = false;
     if (lane < RPW) {
-        const int32_t a = node_of[(int64_t)s * SLICE + (tile ? RPW * wave + lane : 8 * (lane >> 1) + 2 * wave + (lane & 1))];
+        const int32_t a = node_of[(int64_t)s * SLICE + 8 * (lane >> 1) + 2 * wave + (lane & 1)];
         if (a >= 0) {
             m_valid = true;
             m_L = rowlen[a];
@@ -1153,13 +939,9 @@ __global__ void __launch_bounds__(256) k_assemble_rows4(int32_t nslices, int32_t
             cnewB = load_codes(b3, c03);
     R4_LOAD_RECORDS(RA, VA, JA, code0, b0, c00)
     R4_LOAD_RECORDS(RB, VB, JB, code1, b1, c01)
-    if (tile) {
-        for (int idx = lane; idx < RG * accw_t; idx += 64) tbase[idx] = 0.0;
-    } else {
-        for (int idx = gl; idx < accw; idx += G) acc[idx] = 0.0; // every row leaves the slots it used zeroed
-    }
+    for (int idx = gl; idx < accw; idx += G) acc[idx] = 0.0;     // every row leaves the slots it used zeroed
 
-    auto compute = [&](int32_t nE, int32_t j, int32_t la, double* __restrict__ acc) {
+    auto compute = [&](int32_t nE, int32_t j, int32_t la) {
         if (gl < nE * NPE) {
             double blk[DD];
 #pragma unroll
@@ -1188,35 +970,6 @@ __global__ void __launch_bounds__(256) k_assemble_rows4(int32_t nslices, int32_t
     };
     auto pair_end = [&](int b) {                                // the pair is complete: constants, write-out, zeros
         double* __restrict__ Krow = Kvals + off * (int64_t)(DD * SLICE);
-        if (GP > 0 && tile) {
-            constexpr int GPD = GP ? GP : 1;
-            if ((b % GPD) != GPD - 1 && b != npairs - 1) return; // the tile is not complete yet
-            const int g0 = (b / GPD) * GPD;                      // its first pair
-            int32_t Lg = 0;
-#pragma unroll
-            for (int i = 0; i < RG; ++i) Lg = max(Lg, __builtin_amdgcn_readlane(m_L, 2 * g0 + i));    // rows >= nrows: 0
-            const int rt = lane % RG, r = RPW * wave + 2 * g0 + rt;
-            double* trow = tbase + rt * accw_t;
-            wave_lds_sync();                                     // the atomics of the last step have landed
-            for (int32_t jb = lane / RG; jb < Lg; jb += 64 / RG) {      // shorter rows of the tile: zero blocks, as stored
-                double S[DD], Kb[DD];
-#pragma unroll
-                for (int k = 0; k < DD; ++k) S[k] = trow[jb * DD + k];
-#pragma unroll
-                for (int k = 0; k < DD; ++k) trow[jb * DD + k] = 0.0;
-                if (CUBIC) cubic_from_outer3(S, c11, c12, c44, Kb);
-                else {
-#pragma unroll
-                    for (int k = 0; k < DD; ++k) Kb[k] = S[k];
-                }
-                double* dst = Krow + (int64_t)jb * (DD * SLICE);
-#pragma unroll
-                for (int pc = 0; pc < 4; ++pc)
-                    reinterpret_cast<double2*>(dst + pc * (2 * SLICE))[r] = make_double2(Kb[2 * pc], Kb[2 * pc + 1]);
-                dst[4 * (2 * SLICE) + r] = Kb[8];
-            }
-            return;
-        }
         const int32_t L = R4_ROWVAL(m_L, b);                    // rows >= nrows: 0
         const int r = 8 * b + 2 * wave + grp;
         int32_t ln = gl;
@@ -1238,20 +991,10 @@ __global__ void __launch_bounds__(256) k_assemble_rows4(int32_t nslices, int32_t
             if (Kb[0] + Kb[1] + Kb[2] + Kb[3] + Kb[4] + Kb[5] + Kb[6] + Kb[7] + Kb[8] == 1.2345) acc[jb * DD] = (double)r;   // probe: no stores
 #else
             double* dst = Krow + (int64_t)jb * (DD * SLICE);
-#ifdef FEMCY_ROWS4_NT_STORES    /* experiment: K written past the L2 (profiles/r03_rows4_probe.txt) */
-            typedef double d2v __attribute__((ext_vector_type(2)));
-#pragma unroll
-            for (int pc = 0; pc < 4; ++pc) {
-                d2v v2 = {Kb[2 * pc], Kb[2 * pc + 1]};
-                __builtin_nontemporal_store(v2, reinterpret_cast<d2v*>(dst + pc * (2 * SLICE)) + r);
-            }
-            __builtin_nontemporal_store(Kb[8], dst + 4 * (2 * SLICE) + r);
-#else
 #pragma unroll
             for (int pc = 0; pc < 4; ++pc)
                 reinterpret_cast<double2*>(dst + pc * (2 * SLICE))[r] = make_double2(Kb[2 * pc], Kb[2 * pc + 1]);
             dst[4 * (2 * SLICE) + r] = Kb[8];
-#endif
 #endif
         }
     };
@@ -1274,7 +1017,7 @@ __global__ void __launch_bounds__(256) k_assemble_rows4(int32_t nslices, int32_t
         CN_ = load_codes(b4, c04);                                                                    \
         R4_LOAD_RECORDS(R_, V_, J_, code2, b2, c02)                                                   \
         wave_lds_sync();                                                                              \
-        compute(nE, j, la, (GP > 0 && tile) ? tbase + ((b0 % (GP ? GP : 1)) * 2 + grp) * accw_t : acc); \
+        compute(nE, j, la);                                                                           \
         if (b0 < npairs && c00 + 1 >= steps_of(b0) && !ROWS2_PROBE_BIT(32)) pair_end(b0);             \
         b0 = b1; c00 = c01; b1 = b2; c01 = c02; b2 = b3; c02 = c03; b3 = b4; c03 = c04;               \
         advance(b4, c04);                                                                             \
@@ -1819,18 +1562,33 @@ int launch_geom(Ctx* c, const double* d_u, unsigned what) {
     return FEMCY_OK;
 }
 
-// FEMCY_ASM_PAIRS: instantiated element families, LDS of a workgroup (four chunk tiles [dm^2][rows per wave][Lmax | 1])
-static bool pairs_hex(const Ctx* c) { return c->dm == 3 && c->npe == 8 && c->nGP == 8; }
-static bool pairs_instantiated(const Ctx* c) {
-    return pairs_hex(c) ||
-           (c->dm == 2 && ((c->npe == 8 && c->nGP == 4) || (c->npe == 6 && c->nGP == 3) || (c->npe == 4 && c->nGP == 4) ||
-                           (c->npe == 3 && c->nGP == 1)));
-}
+// LDS of a workgroup (four waves) of the LDS-bound assembly modes; the AUTO choice and the launch use the same size
+static bool lds_fits(const Ctx* c, size_t lds) { return lds + 512 <= (size_t)c->small_max_lds; }
+// FEMCY_ASM_PAIRS (pairs_instantiated: ctx.hpp): four chunk tiles [dm^2][rows per wave][Lmax | 1]
 static bool pairs_fits(const Ctx* c) { return (int64_t)c->ne * c->npe < ((int64_t)1 << 27); }   // the packed pair word
 static int pairs_rpw(const Ctx* c) { return ((c->tune_pairs >> 1) & 3) == 1 ? 8 : 16; }
 static size_t pairs_lds(const Ctx* c) {
     return (size_t)4 * c->dm * c->dm * pairs_rpw(c) * (c->max_row_blocks | 1) * sizeof(double);
 }
+// FEMCY_ASM_ROWS2 (C3D10 / C3D4 tables whose gradients sum to zero): per wave the records of 64 / (npe - 1) elements,
+// their volumes, the row accumulator and the pass codes
+static bool rows2_instantiated(const Ctx* c) {
+    return c->dm == 3 && c->dN_sums_to_zero && ((c->npe == 10 && c->nGP == 4) || (c->npe == 4 && c->nGP == 1));
+}
+static size_t rows2_lds(const Ctx* c) {
+    const int T = c->npe - 1, EPC = 64 / T, RD = c->nGP * c->npe * 3;
+    const int volw = (EPC * c->nGP + 1) & ~1, codew = (EPC + 1) / 2 * 2 / 2 + 1, accw = (c->max_row_blocks * 9 + 1) & ~1;
+    return (size_t)4 * (EPC * RD + volw + accw + 2 * codew) * sizeof(double);
+}
+// FEMCY_ASM_ROWS4 (C3D10): per half wave the records of three elements, their volumes and the row accumulator
+static bool rows4_instantiated(const Ctx* c) { return c->dm == 3 && c->npe == 10 && c->nGP == 4; }
+static size_t rows4_lds(const Ctx* c) {
+    const int EPG = 32 / c->npe, RD = c->nGP * c->npe * 3;
+    const int volw = (EPG * c->nGP + 1) & ~1, accw = (c->max_row_blocks * 9 + 1) & ~1;
+    return (size_t)4 * 2 * (EPG * RD + volw + accw + 2) * sizeof(double);
+}
+// FEMCY_ASM_ROWS: four rows of dm x dm blocks
+static size_t rows_lds(const Ctx* c) { return (size_t)4 * c->max_row_blocks * c->dm * c->dm * sizeof(double); }
 // T[(i,k)][(j,l)] = C[v(i,j)][v(k,l)], v = the Voigt index of the reference's B matrices (kblock_add)
 template <int DM>
 static SumMap<DM * DM> sum_map(const Ctx* c) {
@@ -1844,25 +1602,73 @@ static SumMap<DM * DM> sum_map(const Ctx* c) {
     return m;
 }
 
+// the mode an assembly runs: AUTO resolved; an explicit mode refused where it is not instantiated or does not fit
+static int assembly_mode(const Ctx* c, int* out) {
+    int mode = c->opt_assembly;
+    if (mode == FEMCY_ASM_AUTO) {
+        if (c->npe <= 4) {
+            mode = c->dN_sums_to_zero ? FEMCY_ASM_GATHER_SYM_ROWSUM : FEMCY_ASM_GATHER_SYM;
+        } else if (rows4_instantiated(c)) {
+            // C3D10: two rows per wave (round 3: 386 -> 307 us on the bench mesh) when its accumulators fit the LDS; it
+            // computes the diagonal block like the others, so it does not need element tables whose gradients sum to
+            // zero.  A mesh with high-valence nodes may need more LDS than a workgroup may allocate: ROWS2, then ROWS
+            if (lds_fits(c, rows4_lds(c))) mode = FEMCY_ASM_ROWS4;
+            else if (rows2_instantiated(c) && lds_fits(c, rows2_lds(c))) mode = FEMCY_ASM_ROWS2;
+            else mode = FEMCY_ASM_ROWS;
+        } else if (pairs_instantiated(c) && pairs_fits(c) && lds_fits(c, pairs_lds(c))) {
+            // round 6: the 2-D quadratic families (many short rows) -- 16 rows per wave, pair lists in storage order;
+            // C3D8 (27 blocks and 8 incident elements per interior row, a 1.5 KiB record per element): the same kernel
+            // with 3 x 3 blocks, 8 pairs per step, lists in step order (ensure_pairs)
+            mode = FEMCY_ASM_PAIRS;
+        } else {
+            mode = FEMCY_ASM_ROWS;
+        }
+    }
+    switch (mode) {
+        case FEMCY_ASM_GATHER_SYM_ROWSUM:
+            FEMCY_REQUIRE(c->dN_sums_to_zero, "row-sum diagonal needs element tables with sum_a dN_a = 0");
+            break;
+        case FEMCY_ASM_ROWS:
+            FEMCY_REQUIRE(lds_fits(c, rows_lds(c)), "ROWS assembly: a row of %d blocks does not fit the LDS", c->max_row_blocks);
+            break;
+        case FEMCY_ASM_ROWS2:
+            FEMCY_REQUIRE(rows2_instantiated(c), "ROWS2 assembly is instantiated for C3D10 / C3D4 tables with sum_a dN_a = 0 "
+                          "(npe %d, nGP %d)", c->npe, c->nGP);
+            FEMCY_REQUIRE(lds_fits(c, rows2_lds(c)), "ROWS2 assembly needs %zu B of LDS per workgroup (longest row: %d "
+                          "blocks), the device allows %d", rows2_lds(c), c->max_row_blocks, c->small_max_lds);
+            break;
+        case FEMCY_ASM_ROWS4:
+            FEMCY_REQUIRE(rows4_instantiated(c), "ROWS4 assembly is instantiated for C3D10 (npe %d, nGP %d)", c->npe, c->nGP);
+            FEMCY_REQUIRE(lds_fits(c, rows4_lds(c)), "ROWS4 assembly needs %zu B of LDS per workgroup (longest row: %d "
+                          "blocks), the device allows %d", rows4_lds(c), c->max_row_blocks, c->small_max_lds);
+            break;
+        case FEMCY_ASM_PAIRS:
+            FEMCY_REQUIRE(pairs_instantiated(c), "PAIRS assembly is instantiated for the 2-D families and C3D8 (npe %d, nGP "
+                          "%d, dm %d)", c->npe, c->nGP, c->dm);
+            FEMCY_REQUIRE(pairs_fits(c), "PAIRS assembly packs (row, element, local node) into 32 bits: ne * npe must stay "
+                          "below 2^27");
+            FEMCY_REQUIRE(lds_fits(c, pairs_lds(c)), "PAIRS assembly needs %zu B of LDS per workgroup (longest row: %d "
+                          "blocks), the device allows %d", pairs_lds(c), c->max_row_blocks, c->small_max_lds);
+            break;
+    }
+    *out = mode;
+    return FEMCY_OK;
+}
+
+// K_aa = -sum_{b != a} K_ab (FEMCY_ASM_GATHER_SYM_ROWSUM and the consistent tangent)
+static void launch_diag_from_rowsum(Ctx* c, int bs) {
+    const int gd = (int)(((int64_t)c->nslices * SLICE + bs - 1) / bs);
+    if (c->dm == 3)
+        hipLaunchKernelGGL((k_diag_from_rowsum<3>), dim3(gd), dim3(bs), 0, c->stream, c->nslices, c->d_node_of,
+                           c->d_rowlen, c->d_slice_off, c->d_Kvals);
+    else
+        hipLaunchKernelGGL((k_diag_from_rowsum<2>), dim3(gd), dim3(bs), 0, c->stream, c->nslices, c->d_node_of,
+                           c->d_rowlen, c->d_slice_off, c->d_Kvals);
+}
+
 int launch_assemble(Ctx* c) {
     const int bs = 256;
     size_t th = timing_begin(c, T_ASM);
-    int mode = c->opt_assembly;
-    if (mode == FEMCY_ASM_AUTO) {
-        mode = (c->npe > 4) ? ((c->dm == 3 && c->npe == 10 && c->nGP == 4 && c->dN_sums_to_zero) ? FEMCY_ASM_ROWS2 : FEMCY_ASM_ROWS)
-                            : (c->dN_sums_to_zero ? FEMCY_ASM_GATHER_SYM_ROWSUM : FEMCY_ASM_GATHER_SYM);
-        // C3D10: two rows per wave (round 3: 386 -> 307 us on the bench mesh) when its accumulators fit the LDS; it computes
-        // the diagonal block like the others, so it does not need element tables whose gradients sum to zero
-        if (c->dm == 3 && c->npe == 10 && c->nGP == 4) {
-            const size_t lds4 = (size_t)4 * 2 * (3 * 120 + 12 + ((c->max_row_blocks * 9 + 1) & ~1) + 2) * sizeof(double);
-            if (lds4 + 512 <= (size_t)c->small_max_lds) mode = FEMCY_ASM_ROWS4;
-        }
-        // round 6: the 2-D quadratic families (many short rows) -- 16 rows per wave, pair lists in storage order
-        // C3D8 (27 blocks and 8 incident elements per interior row, a 1.5 KiB record per element): the same kernel with
-        // 3 x 3 blocks, 8 pairs per step, lists in step order (ensure_pairs)
-        if ((c->dm == 2 && c->npe > 4) || pairs_hex(c))
-            if (pairs_instantiated(c) && pairs_fits(c) && pairs_lds(c) + 512 <= (size_t)c->small_max_lds) mode = FEMCY_ASM_PAIRS;
-    }
     if (c->opt_tangent == 1) {
         FEMCY_REQUIRE(c->mat_kind != FEMCY_MAT_PSTRESS, "the consistent tangent is not available for plane stress");
         const bool neo = c->mat_kind == FEMCY_MAT_NEOHOOKE;
@@ -1879,153 +1685,63 @@ int launch_assemble(Ctx* c) {
             hipLaunchKernelGGL((k_assemble_gather_consistent<2>), dim3(grid), dim3(bs), 0, c->stream, npos, c->npe, c->nGP,
                                c->d_ctr_ptr, c->d_ctr, c->d_dsdx, c->d_vol, c->d_F, c->d_sigma, neo, lam, mu,
                                c->mat_params[0], c->mat_params[1], c->d_tpos, skip, c->d_Kvals);
-        if (skip) {
-            const int64_t nposd = (int64_t)c->nslices * SLICE;
-            const int gd = (int)((nposd + bs - 1) / bs);
-            if (c->dm == 3)
-                hipLaunchKernelGGL((k_diag_from_rowsum<3>), dim3(gd), dim3(bs), 0, c->stream, c->nslices, c->d_node_of,
-                                   c->d_rowlen, c->d_slice_off, c->d_Kvals);
-            else
-                hipLaunchKernelGGL((k_diag_from_rowsum<2>), dim3(gd), dim3(bs), 0, c->stream, c->nslices, c->d_node_of,
-                                   c->d_rowlen, c->d_slice_off, c->d_Kvals);
-        }
+        if (skip) launch_diag_from_rowsum(c, bs);
         timing_end(c, th);
         FEMCY_HIP(hipGetLastError());
         c->asm_used = skip ? FEMCY_ASM_GATHER_SYM_ROWSUM : FEMCY_ASM_GATHER_SYM;   // the gather form of the consistent tangent
         return FEMCY_OK;
     }
-    if (mode == FEMCY_ASM_ROWS3) {
-        FEMCY_REQUIRE(c->dm == 3 && c->dN_sums_to_zero && ((c->npe == 10 && c->nGP == 4) || (c->npe == 4 && c->nGP == 1)),
-                      "ROWS3 assembly is instantiated for C3D10 / C3D4 tables with sum_a dN_a = 0 (npe %d, nGP %d)", c->npe, c->nGP);
-        const int T = c->npe - 1, EPC = 64 / T, RD = c->nGP * c->npe * 3;
-        const int volw = (EPC * c->nGP + 1) & ~1, codew = (EPC + 1) / 2 * 2 / 2 + 1, accw = (c->max_row_blocks * 9 + 1) & ~1;
-        const size_t lds = (size_t)4 * (EPC * RD + volw + 2 * accw + 2 * codew) * sizeof(double);
-        if (lds + 512 > (size_t)c->small_max_lds) {
-            FEMCY_REQUIRE(c->opt_assembly == FEMCY_ASM_AUTO, "ROWS3 assembly needs %zu B of LDS per workgroup (longest row: %d "
-                          "blocks), the device allows %d", lds, c->max_row_blocks, c->small_max_lds);
-            mode = FEMCY_ASM_ROWS2;
-        }
-#define FEMCY_ROWS3(NPE_, NGP_, CUB_)                                                                                  \
+    int mode;
+    int rc = assembly_mode(c, &mode);
+    if (rc) return rc;
+// a kernel whose LDS exceeds the default limit of a launch (48 KiB) is allowed more first
+#define FEMCY_LDS_LAUNCH(KERNEL_, GRID_, LDS_, ...)                                                                    \
     do {                                                                                                               \
-        if (lds > 48 * 1024)                                                                                           \
-            FEMCY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_assemble_rows3<NPE_, NGP_, CUB_>),          \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                      \
-        hipLaunchKernelGGL((k_assemble_rows3<NPE_, NGP_, CUB_>), dim3(c->nslices), dim3(bs), lds, c->stream, c->nslices, \
-                           c->nn, c->max_row_blocks, c->d_ne_ptr, c->d_ne_idx, c->d_slotj, c->d_rowlen, c->d_node_of,  \
-                           c->d_slice_off, c->d_dsdx, c->d_vol, c->d_C, c->cubic[0], c->cubic[1], c->cubic[2],         \
-                           c->d_Kvals);                                                                                \
+        if ((LDS_) > 48 * 1024)                                                                                        \
+            FEMCY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&KERNEL_),                                     \
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS_)));                   \
+        hipLaunchKernelGGL((KERNEL_), dim3(GRID_), dim3(bs), (LDS_), c->stream, __VA_ARGS__);                          \
     } while (0)
-        if (mode == FEMCY_ASM_ROWS3) {
-            if (c->npe == 10) { if (c->C_is_cubic) FEMCY_ROWS3(10, 4, true); else FEMCY_ROWS3(10, 4, false); }
-            else              { if (c->C_is_cubic) FEMCY_ROWS3(4, 1, true); else FEMCY_ROWS3(4, 1, false); }
-        }
-#undef FEMCY_ROWS3
-    }
-    if (mode == FEMCY_ASM_ROWS2) {
-        FEMCY_REQUIRE(c->dm == 3 && c->dN_sums_to_zero && ((c->npe == 10 && c->nGP == 4) || (c->npe == 4 && c->nGP == 1)),
-                      "ROWS2 assembly is instantiated for C3D10 / C3D4 tables with sum_a dN_a = 0 (npe %d, nGP %d)", c->npe, c->nGP);
-        const int T = c->npe - 1, EPC = 64 / T, RD = c->nGP * c->npe * 3;
-        const int volw = (EPC * c->nGP + 1) & ~1, codew = (EPC + 1) / 2 * 2 / 2 + 1, accw = (c->max_row_blocks * 9 + 1) & ~1;
-#ifdef FEMCY_ROWS2_LDS_PAD      /* occupancy experiments: fewer workgroups per CU (profiles/r03_rows2_probe.txt) */
-        const size_t lds = (size_t)4 * (EPC * RD + volw + accw + 2 * codew) * sizeof(double) + FEMCY_ROWS2_LDS_PAD;
-#else
-        const size_t lds = (size_t)4 * (EPC * RD + volw + accw + 2 * codew) * sizeof(double);
-#endif
-        // the accumulator of a row grows with the longest row of the mesh (288 B per block): an unstructured mesh with
-        // high-valence nodes can exceed what a workgroup may allocate -- AUTO then takes ROWS (its LDS is 4 rows only)
-        if (lds + 512 > (size_t)c->small_max_lds) {
-            FEMCY_REQUIRE(c->opt_assembly == FEMCY_ASM_AUTO, "ROWS2 assembly needs %zu B of LDS per workgroup (longest row: %d "
-                          "blocks), the device allows %d", lds, c->max_row_blocks, c->small_max_lds);
-            mode = FEMCY_ASM_ROWS;
-        }
+    switch (mode) {
+        case FEMCY_ASM_ROWS2: {
+            const size_t lds = rows2_lds(c);
 #define FEMCY_ROWS2(NPE_, NGP_, CUB_)                                                                                  \
-    do {                                                                                                               \
-        if (lds > 48 * 1024)                                                                                           \
-            FEMCY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_assemble_rows2<NPE_, NGP_, CUB_>),          \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                      \
-        hipLaunchKernelGGL((k_assemble_rows2<NPE_, NGP_, CUB_>), dim3(c->nslices), dim3(bs), lds, c->stream, c->nslices, \
-                           c->max_row_blocks, c->d_ne_ptr, c->d_ne_idx, c->d_slotj, c->d_rowlen, c->d_node_of,         \
-                           c->d_slice_off, c->d_dsdx, c->d_vol, c->d_C, c->cubic[0], c->cubic[1], c->cubic[2],         \
-                           c->d_Kvals);                                                                                \
-    } while (0)
-        if (mode == FEMCY_ASM_ROWS2) {
+    FEMCY_LDS_LAUNCH((k_assemble_rows2<NPE_, NGP_, CUB_>), c->nslices, lds, c->nslices, c->max_row_blocks, c->d_ne_ptr, \
+                     c->d_ne_idx, c->d_slotj, c->d_rowlen, c->d_node_of, c->d_slice_off, c->d_dsdx, c->d_vol, c->d_C,  \
+                     c->cubic[0], c->cubic[1], c->cubic[2], c->d_Kvals)
             if (c->npe == 10) { if (c->C_is_cubic) FEMCY_ROWS2(10, 4, true); else FEMCY_ROWS2(10, 4, false); }
             else              { if (c->C_is_cubic) FEMCY_ROWS2(4, 1, true); else FEMCY_ROWS2(4, 1, false); }
-        }
 #undef FEMCY_ROWS2
-    }
-    if (mode == FEMCY_ASM_ROWS4) {
-        FEMCY_REQUIRE(c->dm == 3 && c->npe == 10 && c->nGP == 4, "ROWS4 assembly is instantiated for C3D10 (npe %d, nGP %d)",
-                      c->npe, c->nGP);
-        const int EPG = 32 / c->npe, RD = c->nGP * c->npe * 3;
-#ifdef FEMCY_ROWS4_FAKE_LMAX    /* occupancy experiment only: WRONG results for longer rows */
-        const int R4_LMAX = FEMCY_ROWS4_FAKE_LMAX;
-#else
-        const int R4_LMAX = c->max_row_blocks;
-#endif
-        const int volw = (EPG * c->nGP + 1) & ~1, accw = (R4_LMAX * 9 + 1) & ~1;
-        // experiment (round 5): FEMCY_TUNE_ROWS4_TILE = 1000 GP + LCUT -- whole-line write-out from a wave's own LDS tile,
-        // see the kernel; 0 (default) = off
-        const int r4_gp = c->tune_rows4_tile / 1000, r4_lcut = c->tune_rows4_tile % 1000;
-        const int wpair = 2 * (EPG * RD + volw + accw + 2);
-        const int wtile = r4_gp ? 2 * (EPG * RD + volw + 2) + 2 * r4_gp * ((r4_lcut * 9) | 1) + 1 : 0;
-        const int wstride = (std::max(wpair, wtile) + 1) & ~1;
-        const size_t lds = (size_t)4 * wstride * sizeof(double);
-        FEMCY_REQUIRE(lds + 512 <= (size_t)c->small_max_lds, "ROWS4 assembly needs %zu B of LDS per workgroup (longest row: %d "
-                      "blocks), the device allows %d", lds, c->max_row_blocks, c->small_max_lds);
-        // launch order: by decreasing work.  The locality order (FEMCY_TUNE_ROWS4_ORDER = 1) was built for meshes whose
-        // records exceed the Infinity Cache and MEASURED slower at every size (124 k / 295 k / 995 k C3D10: 301 -> 354,
-        // 754 -> 852, 2 477 -> 2 679 us, profiles/r06_rows4_order.txt) although it removes the re-fetches: this kernel is
-        // bound by its LDS / request rate and by the balance of long and short slices, not by HBM -- kept as a knob
-        const bool r4_near = c->tune_rows4_order == 1;
-        const bool r4_natural = c->tune_rows4_order >= 2;      // experiments: 2 = storage order in XCD-contiguous ranges, 3 = storage order round-robin
-        const int r4_grid = (r4_near || c->tune_rows4_order == 2) ? (c->nslices + 7) / 8 * 8 : c->nslices;
-#define FEMCY_ROWS4(CUB_, GP_)                                                                                         \
-    do {                                                                                                               \
-        if (lds > 48 * 1024)                                                                                           \
-            FEMCY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_assemble_rows4<10, 4, CUB_, GP_>),          \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                      \
-        hipLaunchKernelGGL((k_assemble_rows4<10, 4, CUB_, GP_>), dim3(r4_grid), dim3(bs), lds, c->stream, c->nslices,  \
-                           R4_LMAX, r4_lcut, wstride, (r4_near || c->tune_rows4_order == 2) ? 1 : 0,                   \
-                           (const int32_t*)(r4_natural ? c->d_asm_order_id : (r4_near ? c->d_asm_order_near : c->d_asm_order)), \
-                           c->d_ne_ptr, c->d_ne_idx,                                                                   \
-                           c->d_slotj, c->d_rowlen, c->d_node_of,                                                      \
-                           c->d_slice_off, c->d_dsdx, c->d_vol, c->d_C, c->cubic[0], c->cubic[1], c->cubic[2],         \
-                           c->d_Kvals);                                                                                \
-    } while (0)
-        if (r4_gp == 2) { if (c->C_is_cubic) FEMCY_ROWS4(true, 2); else FEMCY_ROWS4(false, 2); }
-        else if (r4_gp == 4) { if (c->C_is_cubic) FEMCY_ROWS4(true, 4); else FEMCY_ROWS4(false, 4); }
-        else { if (c->C_is_cubic) FEMCY_ROWS4(true, 0); else FEMCY_ROWS4(false, 0); }
+            break;
+        }
+        case FEMCY_ASM_ROWS4: {
+            // one workgroup per slice, slices by decreasing work (d_asm_order)
+            const size_t lds = rows4_lds(c);
+#define FEMCY_ROWS4(CUB_)                                                                                              \
+    FEMCY_LDS_LAUNCH((k_assemble_rows4<10, 4, CUB_>), c->nslices, lds, c->nslices, c->max_row_blocks,                  \
+                     (const int32_t*)c->d_asm_order, c->d_ne_ptr, c->d_ne_idx, c->d_slotj, c->d_rowlen, c->d_node_of,  \
+                     c->d_slice_off, c->d_dsdx, c->d_vol, c->d_C, c->cubic[0], c->cubic[1], c->cubic[2], c->d_Kvals)
+            if (c->C_is_cubic) FEMCY_ROWS4(true); else FEMCY_ROWS4(false);
 #undef FEMCY_ROWS4
-    } else if (mode == FEMCY_ASM_ROWS2 || mode == FEMCY_ASM_ROWS3) {
-    } else if (mode == FEMCY_ASM_PAIRS) {
-        FEMCY_REQUIRE(pairs_instantiated(c), "PAIRS assembly is instantiated for the 2-D families and C3D8 (npe %d, nGP %d, dm %d)",
-                      c->npe, c->nGP, c->dm);
-        FEMCY_REQUIRE(pairs_fits(c), "PAIRS assembly packs (row, element, local node) into 32 bits: ne * npe must stay below 2^27");
-        // FEMCY_TUNE_PAIRS: bit 0 = XCD-contiguous ranges of the processing order, bits 1-2 = rows per wave (0: 16, 1: 8),
-        // bits 3-4 = steps of records in flight (0: 2, 1: 3, 2: 4), bit 5 = chunks in Morton order of their centroids,
-        // bits 6-9 = chunks per wave - 1
-        const int tp = c->tune_pairs;
-        const int cpw = 1 + ((tp >> 6) & 15);
-        const int rpw = pairs_rpw(c), depth = 2 + ((tp >> 3) & 3);
-        const bool xcdc = (tp & 1) != 0;
-        const size_t lds = pairs_lds(c);
-        FEMCY_REQUIRE(lds + 512 <= (size_t)c->small_max_lds, "PAIRS assembly needs %zu B of LDS per workgroup (longest row: %d "
-                      "blocks), the device allows %d", lds, c->max_row_blocks, c->small_max_lds);
-        int rc = ensure_pairs(c, rpw, (tp & 32) != 0, cpw);
-        if (rc) return rc;
-        const int32_t nchunks = c->nslices * (SLICE / rpw);
-        const int32_t nunits = (nchunks + cpw - 1) / cpw;
-        const int grid = ((nunits + 3) / 4 + 7) / 8 * 8;
+            break;
+        }
+        case FEMCY_ASM_PAIRS: {
+            // FEMCY_TUNE_PAIRS: bit 0 = XCD-contiguous ranges of the processing order, bits 1-2 = rows per wave (0: 16, 1: 8),
+            // bits 3-4 = steps of records in flight (0: 2, 1: 3, 2: 4), bit 5 = chunks in Morton order of their centroids,
+            // bits 6-9 = chunks per wave - 1
+            const int tp = c->tune_pairs;
+            const int cpw = 1 + ((tp >> 6) & 15);
+            const int rpw = pairs_rpw(c), depth = 2 + ((tp >> 3) & 3);
+            const bool xcdc = (tp & 1) != 0;
+            const size_t lds = pairs_lds(c);
+            if ((rc = ensure_pairs(c, rpw, (tp & 32) != 0, cpw))) return rc;
+            const int32_t nchunks = c->nslices * (SLICE / rpw);
+            const int32_t nunits = (nchunks + cpw - 1) / cpw;
+            const int grid = ((nunits + 3) / 4 + 7) / 8 * 8;
 #define FEMCY_PAIRS_K(NPE_, NGP_, DM_, RPW_, DEPTH_, X_)                                                               \
-    do {                                                                                                               \
-        if (lds > 48 * 1024)                                                                                           \
-            FEMCY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_assemble_pairs<NPE_, NGP_, DM_, RPW_, DEPTH_, X_>), \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                      \
-        hipLaunchKernelGGL((k_assemble_pairs<NPE_, NGP_, DM_, RPW_, DEPTH_, X_>), dim3(grid), dim3(bs), lds, c->stream, \
-                           nunits, c->max_row_blocks, c->d_pr_unit, (const PairBatch*)c->d_pr_ptr, c->d_pr_code,            \
-                           c->d_slotj, c->d_dsdx, c->d_vol, sum_map<DM_>(c), c->d_Kvals);                            \
-    } while (0)
+    FEMCY_LDS_LAUNCH((k_assemble_pairs<NPE_, NGP_, DM_, RPW_, DEPTH_, X_>), grid, lds, nunits, c->max_row_blocks,      \
+                     c->d_pr_unit, (const PairBatch*)c->d_pr_ptr, c->d_pr_code, c->d_slotj, c->d_dsdx, c->d_vol,       \
+                     sum_map<DM_>(c), c->d_Kvals)
 #define FEMCY_PAIRS_D(NPE_, NGP_, DM_, RPW_, X_)                                                                       \
     do {                                                                                                               \
         if (depth == 2) FEMCY_PAIRS_K(NPE_, NGP_, DM_, RPW_, 2, X_);                                                   \
@@ -2037,67 +1753,60 @@ int launch_assemble(Ctx* c) {
         if (rpw == 16) { if (xcdc) FEMCY_PAIRS_D(NPE_, NGP_, DM_, 16, true); else FEMCY_PAIRS_D(NPE_, NGP_, DM_, 16, false); } \
         else           { if (xcdc) FEMCY_PAIRS_D(NPE_, NGP_, DM_, 8, true); else FEMCY_PAIRS_D(NPE_, NGP_, DM_, 8, false); }   \
     } while (0)
-        if (pairs_hex(c)) FEMCY_PAIRS(8, 8, 3);
-        else if (c->npe == 8) FEMCY_PAIRS(8, 4, 2);
-        else if (c->npe == 6) FEMCY_PAIRS(6, 3, 2);
-        else if (c->npe == 4) FEMCY_PAIRS(4, 4, 2);
-        else FEMCY_PAIRS(3, 1, 2);
+            if (pairs_hex(c)) FEMCY_PAIRS(8, 8, 3);
+            else if (c->npe == 8) FEMCY_PAIRS(8, 4, 2);
+            else if (c->npe == 6) FEMCY_PAIRS(6, 3, 2);
+            else if (c->npe == 4) FEMCY_PAIRS(4, 4, 2);
+            else FEMCY_PAIRS(3, 1, 2);
 #undef FEMCY_PAIRS_K
 #undef FEMCY_PAIRS_D
 #undef FEMCY_PAIRS
-    } else if (mode == FEMCY_ASM_ROWS) {
-        const int grid = std::min((c->nn + 3) / 4, 256 * 16);
-        const size_t lds = (size_t)4 * c->max_row_blocks * c->dm * c->dm * sizeof(double);
-        FEMCY_REQUIRE(lds + 512 <= (size_t)c->small_max_lds, "ROWS assembly: a row of %d blocks does not fit the LDS",
-                      c->max_row_blocks);
-        if (lds > 48 * 1024)
-            FEMCY_HIP(hipFuncSetAttribute(c->dm == 3 ? reinterpret_cast<const void*>(&k_assemble_rows<3>)
-                                                     : reinterpret_cast<const void*>(&k_assemble_rows<2>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        if (c->dm == 3)
-            hipLaunchKernelGGL((k_assemble_rows<3>), dim3(grid), dim3(bs), lds, c->stream, c->nn, c->npe, c->nGP,
-                               c->max_row_blocks, c->d_ne_ptr, c->d_ne_idx, c->d_slotj, c->d_rowlen, c->d_pos, c->d_slice_off,
-                               c->d_dsdx, c->d_vol, c->d_C, c->d_Kvals);
-        else
-            hipLaunchKernelGGL((k_assemble_rows<2>), dim3(grid), dim3(bs), lds, c->stream, c->nn, c->npe, c->nGP,
-                               c->max_row_blocks, c->d_ne_ptr, c->d_ne_idx, c->d_slotj, c->d_rowlen, c->d_pos, c->d_slice_off,
-                               c->d_dsdx, c->d_vol, c->d_C, c->d_Kvals);
-    } else if (mode == FEMCY_ASM_ATOMIC) {
-        FEMCY_HIP(hipMemsetAsync(c->d_Kvals, 0, (size_t)c->stored_rows * c->dm * c->dm * SLICE * sizeof(double),
-                                 c->stream));
-        const int64_t npair = (int64_t)c->ne * c->npe * c->npe;
-        const int grid = (int)((npair + bs - 1) / bs);
-        if (c->dm == 3)
-            hipLaunchKernelGGL((k_assemble_atomic<3>), dim3(grid), dim3(bs), 0, c->stream, npair, c->npe, c->nGP,
-                               c->d_elems, c->d_slotj, c->d_pos, c->d_slice_off, c->d_dsdx, c->d_vol, c->d_C, c->d_Kvals);
-        else
-            hipLaunchKernelGGL((k_assemble_atomic<2>), dim3(grid), dim3(bs), 0, c->stream, npair, c->npe, c->nGP,
-                               c->d_elems, c->d_slotj, c->d_pos, c->d_slice_off, c->d_dsdx, c->d_vol, c->d_C, c->d_Kvals);
-    } else {
-        const int64_t npos = c->stored_rows * SLICE;
-        const int grid = (int)((npos + bs - 1) / bs);
-        const bool rowsum = mode == FEMCY_ASM_GATHER_SYM_ROWSUM;
-        FEMCY_REQUIRE(!rowsum || c->dN_sums_to_zero, "row-sum diagonal needs element tables with sum_a dN_a = 0");
+            break;
+        }
+        case FEMCY_ASM_ROWS: {
+            const int grid = std::min((c->nn + 3) / 4, 256 * 16);
+            const size_t lds = rows_lds(c);
+            if (c->dm == 3)
+                FEMCY_LDS_LAUNCH((k_assemble_rows<3>), grid, lds, c->nn, c->npe, c->nGP, c->max_row_blocks, c->d_ne_ptr,
+                                 c->d_ne_idx, c->d_slotj, c->d_rowlen, c->d_pos, c->d_slice_off, c->d_dsdx, c->d_vol, c->d_C,
+                                 c->d_Kvals);
+            else
+                FEMCY_LDS_LAUNCH((k_assemble_rows<2>), grid, lds, c->nn, c->npe, c->nGP, c->max_row_blocks, c->d_ne_ptr,
+                                 c->d_ne_idx, c->d_slotj, c->d_rowlen, c->d_pos, c->d_slice_off, c->d_dsdx, c->d_vol, c->d_C,
+                                 c->d_Kvals);
+            break;
+        }
+        case FEMCY_ASM_ATOMIC: {
+            FEMCY_HIP(hipMemsetAsync(c->d_Kvals, 0, (size_t)c->stored_rows * c->dm * c->dm * SLICE * sizeof(double),
+                                     c->stream));
+            const int64_t npair = (int64_t)c->ne * c->npe * c->npe;
+            const int grid = (int)((npair + bs - 1) / bs);
+            if (c->dm == 3)
+                hipLaunchKernelGGL((k_assemble_atomic<3>), dim3(grid), dim3(bs), 0, c->stream, npair, c->npe, c->nGP,
+                                   c->d_elems, c->d_slotj, c->d_pos, c->d_slice_off, c->d_dsdx, c->d_vol, c->d_C, c->d_Kvals);
+            else
+                hipLaunchKernelGGL((k_assemble_atomic<2>), dim3(grid), dim3(bs), 0, c->stream, npair, c->npe, c->nGP,
+                                   c->d_elems, c->d_slotj, c->d_pos, c->d_slice_off, c->d_dsdx, c->d_vol, c->d_C, c->d_Kvals);
+            break;
+        }
+        default: {   // FEMCY_ASM_GATHER, FEMCY_ASM_GATHER_SYM, FEMCY_ASM_GATHER_SYM_ROWSUM
+            const int64_t npos = c->stored_rows * SLICE;
+            const int grid = (int)((npos + bs - 1) / bs);
+            const bool rowsum = mode == FEMCY_ASM_GATHER_SYM_ROWSUM;
+            const bool sym = mode == FEMCY_ASM_GATHER_SYM || rowsum;
 #define FEMCY_GATHER(DM_, SYM_, CUB_)                                                                                  \
     hipLaunchKernelGGL((k_assemble_gather<DM_, SYM_, CUB_>), dim3(grid), dim3(bs), 0, c->stream, npos, c->npe, c->nGP, \
                        c->d_ctr_ptr, c->d_ctr, c->d_tpos, c->d_dsdx, c->d_vol, c->d_C, c->cubic[0], c->cubic[1],        \
                        c->cubic[2], c->d_Kvals, rowsum ? 1 : 0)
-        const bool sym = mode == FEMCY_ASM_GATHER_SYM || rowsum;
-        if (c->dm == 3 && c->C_is_cubic) { if (sym) FEMCY_GATHER(3, true, true); else FEMCY_GATHER(3, false, true); }
-        else if (c->dm == 3)             { if (sym) FEMCY_GATHER(3, true, false); else FEMCY_GATHER(3, false, false); }
-        else                             { if (sym) FEMCY_GATHER(2, true, false); else FEMCY_GATHER(2, false, false); }
+            if (c->dm == 3 && c->C_is_cubic) { if (sym) FEMCY_GATHER(3, true, true); else FEMCY_GATHER(3, false, true); }
+            else if (c->dm == 3)             { if (sym) FEMCY_GATHER(3, true, false); else FEMCY_GATHER(3, false, false); }
+            else                             { if (sym) FEMCY_GATHER(2, true, false); else FEMCY_GATHER(2, false, false); }
 #undef FEMCY_GATHER
-        if (rowsum) {
-            const int64_t nposd = (int64_t)c->nslices * SLICE;
-            const int gd = (int)((nposd + bs - 1) / bs);
-            if (c->dm == 3)
-                hipLaunchKernelGGL((k_diag_from_rowsum<3>), dim3(gd), dim3(bs), 0, c->stream, c->nslices, c->d_node_of,
-                                   c->d_rowlen, c->d_slice_off, c->d_Kvals);
-            else
-                hipLaunchKernelGGL((k_diag_from_rowsum<2>), dim3(gd), dim3(bs), 0, c->stream, c->nslices, c->d_node_of,
-                                   c->d_rowlen, c->d_slice_off, c->d_Kvals);
+            if (rowsum) launch_diag_from_rowsum(c, bs);
+            break;
         }
     }
+#undef FEMCY_LDS_LAUNCH
     timing_end(c, th);
     FEMCY_HIP(hipGetLastError());
     c->asm_used = mode;

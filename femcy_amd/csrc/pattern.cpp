@@ -280,6 +280,8 @@ static void spatial_order(const Ctx* c, const std::vector<int32_t>& node_of, int
 int ensure_pairs(Ctx* c, int RPW, bool spatial, int cpw) {
     const int64_t key = ((c->pattern_serial * 64 + RPW) * 2 + (spatial ? 1 : 0)) * 64 + cpw;
     if (c->pairs_serial == key) return FEMCY_OK;
+    FEMCY_REQUIRE(!c->h_node_of.empty(), "PAIRS assembly: build the pattern after femcy_set_element (build_pattern keeps "
+                  "the node -> element lists for the PAIRS families only)");
     const int64_t npos = (int64_t)c->nslices * SLICE;
     const int64_t nchunks = npos / RPW;
     const int dm = c->dm;
@@ -635,12 +637,6 @@ int build_pattern(Ctx* c) {
         }
         std::stable_sort(asm_order.begin(), asm_order.end(), [&](int32_t x, int32_t y) { return work[x] > work[y]; });
     }
-    // ... and by locality (round 6): the same kernel on a mesh whose element records exceed the Infinity Cache is bound by
-    // re-fetching them -- every record once per node of its element, from whichever XCD the row's slice landed on.
-    // Slices in Morton order of their centroids, XCD-contiguous ranges of that order (the kernel's `xcdc` mapping).
-    std::vector<int32_t> asm_order_near(nslices);
-    for (int32_t s = 0; s < nslices; ++s) asm_order_near[s] = s;
-    spatial_order(c, node_of, SLICE, asm_order_near);
 
     // ---- commit to the context
     c->nslices = nslices;
@@ -653,9 +649,15 @@ int build_pattern(Ctx* c) {
     c->h_rowlen = rowlen;
     c->h_pos = pos;
     c->h_bcol = bcol;
-    c->h_node_of = node_of;
-    c->h_ne_ptr = ne_ptr;
-    c->h_ne_idx = ne_idx;
+    if (pairs_instantiated(c)) {                // ensure_pairs is their only reader
+        c->h_node_of = node_of;
+        c->h_ne_ptr = ne_ptr;
+        c->h_ne_idx = ne_idx;
+    } else {
+        c->h_node_of = {};
+        c->h_ne_ptr = {};
+        c->h_ne_idx = {};
+    }
     spmv_split(c);
 
     int rc;
@@ -672,12 +674,6 @@ int build_pattern(Ctx* c) {
     if ((rc = upload(&c->d_ne_ptr, ne_ptr))) return rc;
     if ((rc = upload(&c->d_ne_idx, ne_idx))) return rc;
     if ((rc = upload(&c->d_asm_order, asm_order))) return rc;
-    if ((rc = upload(&c->d_asm_order_near, asm_order_near))) return rc;
-    {
-        std::vector<int32_t> ident(nslices);
-        for (int32_t s = 0; s < nslices; ++s) ident[s] = s;
-        if ((rc = upload(&c->d_asm_order_id, ident))) return rc;
-    }
 
     if (c->d_Kvals) (void)hipFree(c->d_Kvals);
     size_t kbytes = (size_t)stored_rows * dm * dm * SLICE * sizeof(double);

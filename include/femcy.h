@@ -90,8 +90,7 @@ enum femcy_assembly {
     FEMCY_ASM_ROWS2 = 6,  /* ROWS with the element records staged in LDS, one workgroup per 64-row slice, row-sum
                              diagonal, geometric-sum blocks for cubic-pattern C: AUTO's choice for C3D10 until round 3;
                              instantiated for C3D10 and C3D4 tables whose gradients sum to zero */
-    FEMCY_ASM_ROWS3 = 7,  /* ROWS2 with eight adjacent rows finished together and written as whole 128-byte lines
-                             (no read-for-fill of K: round 3) */
+    /* 7: retired (ROWS3) */
     FEMCY_ASM_ROWS4 = 8,  /* two rows per wavefront at a time (half a wave each, three incident elements per step, the
                              diagonal block computed like the others): round 3, C3D10; AUTO picks it there */
     FEMCY_ASM_PAIRS = 9   /* round 6: a wavefront owns 8 (or 16) adjacent rows of a slice; lanes = (row, incident element) pair x
@@ -208,15 +207,8 @@ enum femcy_option {
                                         matrix cores (v_mfma_f64_16x16x4_f64), one tile pair per workgroup, 2 = matrix
                                         cores, 2 x 2 tile pairs per workgroup, 3 = 1 on two streams: the tiles the next panel
                                         needs first, the rest beside that panel (tests, comparison records)          */
-    FEMCY_TUNE_ROWS4_TILE = 116,     /* FEMCY_ASM_ROWS4 (C3D10), experiment of round 5: 1000 GP + LCUT = in slices no wider than
-                                        LCUT blocks a wave owns 16 consecutive rows and writes 2 GP adjacent rows (GP 2 or 4)
-                                        at a time from a tile of its own LDS (64 / 128 contiguous bytes per slot instead
-                                        of 32); 0 = off (default: 288 - 295 us against 295, profiles/r05_pmc_rows4_tile.txt) */
-    FEMCY_TUNE_ROWS4_ORDER = 118,    /* FEMCY_ASM_ROWS4 launch order: 0 = slices by decreasing work, round-robin over the XCDs (even
-                                        shares of every weight class: best while the element records sit in the Infinity
-                                        Cache), 1 = slices in Morton order of their centroids, XCD-contiguous ranges (records
-                                        re-used inside one L2: best beyond it), -1 (default) = by the size of the records;
-                                        the same bits of K either way */
+    /* 116: retired (ROWS4_TILE) */
+    /* 118: retired (ROWS4_ORDER) */
     FEMCY_TUNE_SPMV_ROT = 119,       /* SpMV task lists of the workgroups of an XCD.  0 = task b + i * (workgroups per XCD) in round i
                                         (rounds 1-5: always the same position of the length-sorted window); 1 .. 63 = the
                                         position advances by this many tasks per round; 64 = lists balanced by the host, round

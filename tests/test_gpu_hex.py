@@ -79,7 +79,7 @@ def test_auto_takes_the_hex_path_deterministically():
     ctx.close()
 
 
-@pytest.mark.parametrize("mode", [be.ASM_ROWS2, be.ASM_ROWS3, be.ASM_ROWS4])
+@pytest.mark.parametrize("mode", [be.ASM_ROWS2, be.ASM_ROWS4])
 def test_c3d10_only_modes_refuse_hexahedra(mode):
     nodes, el = MESHES["small"]
     ctx = hc.make_ctx(nodes, el)
@@ -88,6 +88,20 @@ def test_c3d10_only_modes_refuse_hexahedra(mode):
         ctx.assemble_K(-1)
     with pytest.raises(be.FemcyError, match="no assembly has run"):    # a refused assembly reports no mode
         ctx.assembly_used()
+    ctx.close()
+
+
+def test_retired_assembly_options_are_refused():
+    """assembly mode 7 and tuning options 116 / 118 (retired assembly experiments) are refused and change nothing"""
+    nodes, el = MESHES["small"]
+    ctx = hc.make_ctx(nodes, el)
+    with pytest.raises(be.FemcyError, match="retired"):
+        ctx.set_option(be.OPT_ASSEMBLY, 7)
+    for option, value in ((116, 0), (116, 2028), (118, 0), (118, 1)):
+        with pytest.raises(be.FemcyError, match="unknown option"):
+            ctx.set_option(option, value)
+    ctx.assemble_K(-1)
+    assert ctx.assembly_used() == be.ASM_PAIRS                          # still AUTO
     ctx.close()
 
 

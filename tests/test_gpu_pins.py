@@ -42,7 +42,7 @@ def test_one_element_Ke_equals_exact_integration(gpu_ctx_factory, etype):
     el = np.arange(X.shape[0], dtype=np.int32)[None, :]
     mat = SimpleNamespace(kind=be_kind("lin3d"), C=C, params=np.array([1.0, 0.25]))
     ctx = _ctx(gpu_ctx_factory, X, el, _ele(etype), mat)
-    modes = [be.ASM_GATHER, be.ASM_GATHER_SYM, be.ASM_GATHER_SYM_ROWSUM, be.ASM_ROWS, be.ASM_ROWS2, be.ASM_ROWS3, be.ASM_ATOMIC, be.ASM_AUTO]
+    modes = [be.ASM_GATHER, be.ASM_GATHER_SYM, be.ASM_GATHER_SYM_ROWSUM, be.ASM_ROWS, be.ASM_ROWS2, be.ASM_ATOMIC, be.ASM_AUTO]
     if etype == "C3D10":
         modes.append(be.ASM_ROWS4)
     for mode in modes:
@@ -96,7 +96,7 @@ def test_unreferenced_nodes_and_two_elements_sharing_a_face(gpu_ctx_factory, ety
     assert np.abs(Ko.toarray()[:3 * npe, :3 * npe] - Ke).max() < 2.0 * np.abs(Ke).max()      # sanity: same scale
     mat = SimpleNamespace(kind=be_kind("lin3d"), C=C, params=np.array([1.0, 0.25]))
     ctx = _ctx(gpu_ctx_factory, nodes, el, _ele(etype), mat)
-    modes = [be.ASM_GATHER, be.ASM_GATHER_SYM, be.ASM_GATHER_SYM_ROWSUM, be.ASM_ROWS, be.ASM_ROWS2, be.ASM_ROWS3, be.ASM_ATOMIC, be.ASM_AUTO]
+    modes = [be.ASM_GATHER, be.ASM_GATHER_SYM, be.ASM_GATHER_SYM_ROWSUM, be.ASM_ROWS, be.ASM_ROWS2, be.ASM_ATOMIC, be.ASM_AUTO]
     if etype == "C3D10":
         modes.append(be.ASM_ROWS4)
     for mode in modes:

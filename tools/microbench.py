@@ -47,7 +47,7 @@ def main():
         user_api.user_dirichletBC_values(u, tw, 3, d, m["nodes"], 0.05)
     ctx.upload(be.VEC_DOF, u)
     for mode, nm in ((be.ASM_GATHER, "gather"), (be.ASM_GATHER_SYM, "gather-sym"), (be.ASM_GATHER_SYM_ROWSUM, "gather-sym-rowsum"), (be.ASM_ROWS, "rows"),
-                     (be.ASM_ROWS2, "rows2"), (be.ASM_ROWS3, "rows3"), (be.ASM_ROWS4, "rows4"), (be.ASM_ATOMIC, "atomic")):
+                     (be.ASM_ROWS2, "rows2"), (be.ASM_ROWS4, "rows4"), (be.ASM_ATOMIC, "atomic")):
         if mode == be.ASM_ROWS4 and not quad:
             continue                                   # instantiated for C3D10
         ctx.set_option(be.OPT_ASSEMBLY, mode)
