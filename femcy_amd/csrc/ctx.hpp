@@ -405,7 +405,7 @@ int launch_extrapolate(Ctx* c, const double* d_E, const double* d_field, int wid
 int launch_energy_sum(Ctx* c, double* total);
 int launch_assemble(Ctx* c);
 int launch_nodal_force(Ctx* c, double* d_f);
-int launch_neumann(Ctx* c, const Ctx::LoadSet& ls, double traction, bool along_normal, double* d_rhs);
+int launch_neumann(Ctx* c, const Ctx::LoadSet& ls, double traction, bool along_normal, double* d_rhs, bool add);
 // pos_space: x and y are in STORAGE order (entry p * dm + c belongs to the node at storage position p = slice * 64 + lane;
 // the padding lanes of the last slice hold zeros) -- the form the three-kernel PCG runs in since round 4
 int launch_spmv(Ctx* c, const double* d_x, double* d_y, double* d_partials, int* nblocks_out, bool pos_space = false);
@@ -420,10 +420,11 @@ int probe_mailbox(Ctx* c, int32_t rounds, double* us_per_round);
 int probe_spmv(Ctx* c, int32_t reps, int32_t storage_order, double* us_per_launch);
 int spmv_public_storage_order(Ctx* c, const double* d_x, double* d_y);   // femcy_spmv through the storage-order kernel
 int64_t persist_streamed_bytes(Ctx* c);
-// FEMCY_ASM_PAIRS (kernels_assembly.hip) is instantiated for C3D8 and the 2-D families
+// FEMCY_ASM_PAIRS (kernels_assembly.hip) is instantiated for C3D8, C3D6 and the 2-D families
 inline bool pairs_hex(const Ctx* c) { return c->dm == 3 && c->npe == 8 && c->nGP == 8; }
+inline bool pairs_wedge(const Ctx* c) { return c->dm == 3 && c->npe == 6 && c->nGP == 6; }
 inline bool pairs_instantiated(const Ctx* c) {
-    return pairs_hex(c) ||
+    return pairs_hex(c) || pairs_wedge(c) ||
            (c->dm == 2 && ((c->npe == 8 && c->nGP == 4) || (c->npe == 6 && c->nGP == 3) || (c->npe == 4 && c->nGP == 4) ||
                            (c->npe == 3 && c->nGP == 1)));
 }

@@ -994,18 +994,37 @@ int femcy_loadset_create(femcy_ctx* ctx, int32_t nft, int32_t nfn, int32_t nip, 
     return FEMCY_OK;
 }
 
-int femcy_loadset_neumann(femcy_ctx* ctx, int32_t id, double traction, const double* direction, int rhs_vec) {
-    CTX_OR_FAIL(ctx);
+static int loadset_neumann(Ctx* c, int32_t id, double traction, const double* direction, int rhs_vec, bool add) {
     VEC_OR_FAIL(rhs_vec);
     FEMCY_REQUIRE(id >= 0 && (size_t)id < c->loadsets.size(), "unknown load set %d", (int)id);
+    FEMCY_REQUIRE(!add || !c->comm || rhs_vec != FEMCY_VEC_TMP1, "femcy_loadset_neumann_add on several ranks sums the "
+                  "interface through vector TMP1: it cannot be the right-hand side");
     const Ctx::LoadSet& ls = c->loadsets[id];
     if (direction) {
         FEMCY_HIP(hipMemcpyAsync(ls.d_dir, direction, sizeof(double) * c->dm, hipMemcpyHostToDevice, c->stream));
         FEMCY_HIP(hipStreamSynchronize(c->stream));   // the host buffer is only borrowed for the call
     }
-    int rc = launch_neumann(c, ls, traction, direction == nullptr, c->d_vec[rhs_vec]);
-    if (rc) return rc;
-    return iface_sum(c, c->d_vec[rhs_vec]);    // multi-rank: each rank loads the facets of its own elements
+    double* rhs = c->d_vec[rhs_vec];
+    int rc;
+    if (add && c->comm) {   // multi-rank: only this set's loads are summed over the interface, then added
+        double* tmp = c->d_vec[FEMCY_VEC_TMP1];
+        if ((rc = launch_neumann(c, ls, traction, direction == nullptr, tmp, false))) return rc;
+        if ((rc = iface_sum(c, tmp))) return rc;
+        return vec_axpy(c, rhs, rhs, 1.0, tmp);
+    }
+    if ((rc = launch_neumann(c, ls, traction, direction == nullptr, rhs, add))) return rc;
+    if (add) return FEMCY_OK;
+    return iface_sum(c, rhs);                  // multi-rank: each rank loads the facets of its own elements
+}
+
+int femcy_loadset_neumann(femcy_ctx* ctx, int32_t id, double traction, const double* direction, int rhs_vec) {
+    CTX_OR_FAIL(ctx);
+    return loadset_neumann(c, id, traction, direction, rhs_vec, false);
+}
+
+int femcy_loadset_neumann_add(femcy_ctx* ctx, int32_t id, double traction, const double* direction, int rhs_vec) {
+    CTX_OR_FAIL(ctx);
+    return loadset_neumann(c, id, traction, direction, rhs_vec, true);
 }
 
 int femcy_spmv(femcy_ctx* ctx, int x_vec, int y_vec) {

@@ -104,7 +104,9 @@ __global__ void __launch_bounds__(256) k_geom(int32_t ne, int32_t nGP, const dou
     // round 6: so do the records of elements with several Gauss points whatever their width (CPE8: 16 doubles per Gauss
     // point, four Gauss points -- a lane's 128 contiguous bytes 512 bytes from its neighbour's: 64 partial lines per store
     // instruction), in chunks of the largest divisor of the record width up to 16
-    constexpr int CHK = WG % 16 == 0 ? 16 : WG % 15 == 0 ? 15 : WG % 12 == 0 ? 12 : WG % 8 == 0 ? 8 : WG % 6 == 0 ? 6 : 1;
+    // (C3D6: 18 = 2 x 9, so that a chunk also holds an F / sigma record of 9 doubles)
+    constexpr int CHK = WG % 16 == 0 ? 16 : WG % 15 == 0 ? 15 : WG % 12 == 0 ? 12 : WG % 9 == 0 ? 9 : WG % 8 == 0 ? 8 :
+                        WG % 6 == 0 ? 6 : 1;
     constexpr bool WIDE = CHK > 1;
     // the F / sigma records (WT doubles) go through the same staging area as the gradient chunks
     static_assert(!WIDE || (STAGE ? WG : CHK) >= WT, "stage_lds is smaller than one F / sigma record");
@@ -1092,10 +1094,11 @@ struct SumMap {
 // requested a batch earlier and whose descriptor two batches earlier (scalar loads): the chain descriptor -> codes ->
 // records is paid once per wave.  The write-out leaves the tile zeroed (each LDS word is read and cleared by one lane).
 constexpr int PAIR_ROW_SHIFT = 27;  // pair word: row inside the chunk << 27 | element * npe + local node (ensure_pairs)
-// 3-D lists (C3D8) are in STEP order: the s-th incident element of every row of the chunk, then the (s+1)-th, with a
-// padding word (INT32_MIN: a negative row) where a row has fewer elements.  The PPW = 8 pairs of one step then
-// belong to distinct rows, so no two lanes of one ds_add_f64 address the same LDS word and the bits of K are fixed by
-// the list order alone (not by how the hardware orders same-address adds inside one instruction).
+// 3-D lists (C3D8, C3D6) are in STEP order: the s-th incident element of every row of the chunk, then the (s+1)-th, with
+// a padding word (INT32_MIN: a negative row) where a row has fewer elements, and every step padded to a multiple of PPW
+// (C3D6: PPW = 10, a step of 8 rows takes 10 words, of 16 rows 20; batches of 60 words).  The PPW pairs of one kernel
+// step then belong to distinct rows, so no two lanes of one ds_add_f64 address the same LDS word and the bits of K are
+// fixed by the list order alone (not by how the hardware orders same-address adds inside one instruction).
 struct PairBatch {
     int32_t chunk, p0, nb, L;       // chunk id (slice * (64 / RPW) + part), first pair, pairs (<= 64), slice width in blocks
     int64_t off;                    // slice_off of the chunk's slice
@@ -1465,18 +1468,22 @@ __global__ void __launch_bounds__(128) k_neumann_contrib(int32_t nload, int32_t 
 __global__ void __launch_bounds__(128) k_neumann_gather(int32_t nnode, int32_t dm, const int32_t* __restrict__ ld_node,
                                                         const int32_t* __restrict__ ld_ptr,
                                                         const int32_t* __restrict__ ld_slot,
-                                                        const double* __restrict__ contrib, double* __restrict__ rhs) {
+                                                        const double* __restrict__ contrib, int add,
+                                                        double* __restrict__ rhs) {
     const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nnode) return;
     for (int d = 0; d < dm; ++d) {
         double s = 0.0;
         for (int32_t k = ld_ptr[i]; k < ld_ptr[i + 1]; ++k) s += contrib[(int64_t)ld_slot[k] * dm + d];
-        rhs[(int64_t)ld_node[i] * dm + d] = s;
+        double* dst = rhs + (int64_t)ld_node[i] * dm + d;
+        *dst = add ? *dst + s : s;
     }
 }
 
-int launch_neumann(Ctx* c, const Ctx::LoadSet& ls, double traction, bool along_normal, double* d_rhs) {
-    FEMCY_HIP(hipMemsetAsync(d_rhs, 0, sizeof(double) * c->n, c->stream));
+// add = false: rhs is zero-filled first (femcy_loadset_neumann); true: the set's node sums are added to rhs
+// (femcy_loadset_neumann_add: a second facet arity of the same surface)
+int launch_neumann(Ctx* c, const Ctx::LoadSet& ls, double traction, bool along_normal, double* d_rhs, bool add) {
+    if (!add) FEMCY_HIP(hipMemsetAsync(d_rhs, 0, sizeof(double) * c->n, c->stream));
     if (ls.nload == 0) return FEMCY_OK;
     const int bs = 128;
     const double* dir = along_normal ? nullptr : ls.d_dir;
@@ -1489,7 +1496,7 @@ int launch_neumann(Ctx* c, const Ctx::LoadSet& ls, double traction, bool along_n
                            c->npe, ls.nfn, ls.nip, c->d_nodes, c->d_elems, ls.d_elem, ls.d_ft, ls.d_ft_nodes, ls.d_N,
                            ls.d_dN, ls.d_normal, ls.d_weight, traction, dir, ls.d_contrib);
     hipLaunchKernelGGL(k_neumann_gather, dim3((ls.nnode + bs - 1) / bs), dim3(bs), 0, c->stream, ls.nnode, c->dm,
-                       ls.d_node, ls.d_ptr, ls.d_slot, ls.d_contrib, d_rhs);
+                       ls.d_node, ls.d_ptr, ls.d_slot, ls.d_contrib, add ? 1 : 0, d_rhs);
     FEMCY_HIP(hipGetLastError());
     return FEMCY_OK;
 }
@@ -1552,6 +1559,7 @@ int launch_geom(Ctx* c, const double* d_u, unsigned what) {
     FEMCY_DISPATCH_ELEMENT(4, 3, GEOM_CALL)
     FEMCY_DISPATCH_ELEMENT(10, 3, GEOM_CALL)
     FEMCY_DISPATCH_ELEMENT(8, 3, GEOM_CALL)
+    FEMCY_DISPATCH_ELEMENT(6, 3, GEOM_CALL)
 #undef GEOM_CALL
     timing_end(c, th);
     if (!launched) {
@@ -1618,8 +1626,13 @@ static int assembly_mode(const Ctx* c, int* out) {
         } else if (pairs_instantiated(c) && pairs_fits(c) && lds_fits(c, pairs_lds(c))) {
             // round 6: the 2-D quadratic families (many short rows) -- 16 rows per wave, pair lists in storage order;
             // C3D8 (27 blocks and 8 incident elements per interior row, a 1.5 KiB record per element): the same kernel
-            // with 3 x 3 blocks, 8 pairs per step, lists in step order (ensure_pairs)
+            // with 3 x 3 blocks, 8 pairs per step, lists in step order (ensure_pairs); C3D6 (21 blocks, 12 elements,
+            // 912 B): 10 pairs per step, 2.0 x GATHER_SYM_ROWSUM on the 2 M-wedge plate (profiles/wedge_asm_record.json)
             mode = FEMCY_ASM_PAIRS;
+        } else if (pairs_wedge(c)) {
+            // C3D6 whose pair tile does not fit (high-valence nodes): the faster generic mode of the same record,
+            // GATHER_SYM_ROWSUM (3.67 ms against 4.24 for ROWS); it needs no LDS
+            mode = c->dN_sums_to_zero ? FEMCY_ASM_GATHER_SYM_ROWSUM : FEMCY_ASM_GATHER_SYM;
         } else {
             mode = FEMCY_ASM_ROWS;
         }
@@ -1643,8 +1656,8 @@ static int assembly_mode(const Ctx* c, int* out) {
                           "blocks), the device allows %d", rows4_lds(c), c->max_row_blocks, c->small_max_lds);
             break;
         case FEMCY_ASM_PAIRS:
-            FEMCY_REQUIRE(pairs_instantiated(c), "PAIRS assembly is instantiated for the 2-D families and C3D8 (npe %d, nGP "
-                          "%d, dm %d)", c->npe, c->nGP, c->dm);
+            FEMCY_REQUIRE(pairs_instantiated(c), "PAIRS assembly is instantiated for the 2-D families, C3D8 and C3D6 (npe %d, "
+                          "nGP %d, dm %d)", c->npe, c->nGP, c->dm);
             FEMCY_REQUIRE(pairs_fits(c), "PAIRS assembly packs (row, element, local node) into 32 bits: ne * npe must stay "
                           "below 2^27");
             FEMCY_REQUIRE(lds_fits(c, pairs_lds(c)), "PAIRS assembly needs %zu B of LDS per workgroup (longest row: %d "
@@ -1754,6 +1767,7 @@ int launch_assemble(Ctx* c) {
         else           { if (xcdc) FEMCY_PAIRS_D(NPE_, NGP_, DM_, 8, true); else FEMCY_PAIRS_D(NPE_, NGP_, DM_, 8, false); }   \
     } while (0)
             if (pairs_hex(c)) FEMCY_PAIRS(8, 8, 3);
+            else if (pairs_wedge(c)) FEMCY_PAIRS(6, 6, 3);
             else if (c->npe == 8) FEMCY_PAIRS(8, 4, 2);
             else if (c->npe == 6) FEMCY_PAIRS(6, 3, 2);
             else if (c->npe == 4) FEMCY_PAIRS(4, 4, 2);

@@ -274,9 +274,12 @@ static void spatial_order(const Ctx* c, const std::vector<int32_t>& node_of, int
 // a slice) and walks the (row, incident element) pairs of its rows, NPE lanes per pair.  The list is in storage order, so
 // the kernel's chain is pr_ptr (scalar) -> codes (one coalesced load) -> records, instead of node_of -> ne_ptr -> ne_idx
 // -> records.  Order inside a chunk: by row, then ascending element = the summation order of every stored block.
-// 3-D (C3D8): step order instead -- the s-th incident element of rows 0 .. RPW-1, then the (s+1)-th, a padding word
-// (INT32_MIN) where a row has no s-th element -- so that the 8 pairs of one kernel step are 8 distinct rows (RPW is 8 or
-// 16) and no LDS word receives two adds from one instruction.  Every block still sums its elements in ascending order.
+// 3-D (C3D8, C3D6): step order instead -- the s-th incident element of rows 0 .. RPW-1, then the (s+1)-th, a padding
+// word (INT32_MIN) where a row has no s-th element -- so that the PPW = 64 / npe pairs of one kernel step are distinct
+// rows and no LDS word receives two adds from one instruction.  Every block still sums its elements in ascending order.
+// Where PPW does not divide RPW (C3D6: PPW 10, RPW 8 or 16) every step is padded to a multiple of PPW and a chunk is cut
+// into batches of a multiple of PPW words, so that a kernel step never spans two list steps; for C3D8 both paddings are
+// zero and the lists are those of a plain step order.  A final pass over the batches checks the property.
 int ensure_pairs(Ctx* c, int RPW, bool spatial, int cpw) {
     const int64_t key = ((c->pattern_serial * 64 + RPW) * 2 + (spatial ? 1 : 0)) * 64 + cpw;
     if (c->pairs_serial == key) return FEMCY_OK;
@@ -286,6 +289,9 @@ int ensure_pairs(Ctx* c, int RPW, bool spatial, int cpw) {
     const int64_t nchunks = npos / RPW;
     const int dm = c->dm;
     const bool steps = dm == 3;
+    const int PPW = 64 / c->npe;                                  // pairs per kernel step (kernels_assembly.hip)
+    const int SW = steps ? (RPW + PPW - 1) / PPW * PPW : RPW;     // words per list step
+    const int BAT = steps ? 64 / PPW * PPW : 64;                  // words per batch
     auto nelem = [&](int64_t ch, int r) {
         const int32_t a = c->h_node_of[(size_t)ch * RPW + r];
         return a >= 0 ? c->h_ne_ptr[a + 1] - c->h_ne_ptr[a] : 0;
@@ -297,7 +303,7 @@ int ensure_pairs(Ctx* c, int RPW, bool spatial, int cpw) {
             cnt += nelem(ch, r);
             mx = std::max(mx, nelem(ch, r));
         }
-        ptr[ch + 1] = ptr[ch] + (steps ? mx * RPW : cnt);
+        ptr[ch + 1] = ptr[ch] + (steps ? mx * SW : cnt);
     }
     std::vector<int32_t> code((size_t)ptr[nchunks] + 64, 0);    // + 64 zeros: the list of an empty chunk is read, not used
     parallel_for(nchunks, [&](int64_t lo, int64_t hi, int) {
@@ -305,9 +311,9 @@ int ensure_pairs(Ctx* c, int RPW, bool spatial, int cpw) {
             int32_t w = ptr[ch];
             if (steps) {
                 for (int32_t st = 0; w < ptr[ch + 1]; ++st)
-                    for (int r = 0; r < RPW; ++r) {
-                        const int32_t a = c->h_node_of[(size_t)ch * RPW + r];
-                        code[w++] = st < nelem(ch, r) ? c->h_ne_idx[c->h_ne_ptr[a] + st] | (r << 27) : INT32_MIN;
+                    for (int r = 0; r < SW; ++r) {
+                        const int32_t a = r < RPW ? c->h_node_of[(size_t)ch * RPW + r] : -1;
+                        code[w++] = r < RPW && st < nelem(ch, r) ? c->h_ne_idx[c->h_ne_ptr[a] + st] | (r << 27) : INT32_MIN;
                     }
                 continue;
             }
@@ -329,7 +335,7 @@ int ensure_pairs(Ctx* c, int RPW, bool spatial, int cpw) {
     std::vector<int32_t> order((size_t)nchunks);
     for (int64_t ch = 0; ch < nchunks; ++ch) order[ch] = (int32_t)ch;
     if (spatial) spatial_order(c, c->h_node_of, RPW, order);
-    // batches (<= 64 pairs of one chunk) in processing order (kernels_assembly.hip: PairBatch, 32 bytes) and the first
+    // batches (<= BAT pairs of one chunk) in processing order (kernels_assembly.hip: PairBatch, 32 bytes) and the first
     // batch of every unit of `cpw` chunks (one wavefront's work)
     std::vector<int32_t> desc, unit_ptr;
     desc.reserve((size_t)nchunks * 8);
@@ -339,14 +345,34 @@ int ensure_pairs(Ctx* c, int RPW, bool spatial, int cpw) {
         const int64_t s = (int64_t)ch * RPW / SLICE;
         const int64_t off = c->h_slice_off[s];
         const int32_t np = ptr[ch + 1] - ptr[ch];
-        const int32_t nbat = std::max(1, (np + 63) / 64);
+        const int32_t nbat = std::max(1, (np + BAT - 1) / BAT);
         for (int32_t bb = 0; bb < nbat; ++bb) {
-            int32_t d8[8] = {ch, ptr[ch] + 64 * bb, std::min(64, np - 64 * bb), c->h_slice_len[s], 0, 0, bb + 1 == nbat ? 1 : 0, 0};
+            int32_t d8[8] = {ch, ptr[ch] + BAT * bb, std::min(BAT, np - BAT * bb), c->h_slice_len[s], 0, 0,
+                             bb + 1 == nbat ? 1 : 0, 0};
             memcpy(&d8[4], &off, 8);
             desc.insert(desc.end(), d8, d8 + 8);
         }
     }
     unit_ptr.push_back((int32_t)(desc.size() / 8));
+    if (steps) {   // the PPW words of every kernel step (pairs p0 + k PPW .. of a batch) name distinct rows
+        const size_t nb_total = desc.size() / 8;
+        bool distinct = true;
+        for (size_t i = 0; i < nb_total && distinct; ++i) {
+            const int32_t p0 = desc[i * 8 + 1], nb = desc[i * 8 + 2];
+            for (int32_t k = 0; k < nb && distinct; k += PPW) {
+                uint32_t seen = 0;
+                for (int32_t j = k; j < std::min(k + PPW, nb); ++j) {
+                    const int32_t wd = code[(size_t)p0 + j];
+                    if (wd < 0) continue;
+                    const uint32_t bit = 1u << (wd >> 27);
+                    distinct = distinct && !(seen & bit);
+                    seen |= bit;
+                }
+            }
+        }
+        FEMCY_REQUIRE(distinct, "PAIRS assembly: a step of the 3-D pair lists names one row twice (rows per chunk %d, "
+                      "pairs per step %d)", RPW, PPW);
+    }
     int rc;
     if ((rc = upload(&c->d_pr_unit, unit_ptr)) || (rc = upload(&c->d_pr_ptr, desc)) || (rc = upload(&c->d_pr_code, code))) return rc;
     c->pairs_serial = key;

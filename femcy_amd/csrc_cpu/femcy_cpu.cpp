@@ -870,14 +870,13 @@ int femcy_loadset_create(femcy_ctx* ctx, int32_t nft, int32_t nfn, int32_t nip, 
     return FEMCY_OK;
 }
 
-// neumannBC (stiffnessMtrx.py:369-411)
-int femcy_loadset_neumann(femcy_ctx* ctx, int32_t id, double traction, const double* direction, int rhs_vec) {
-    CTX_OR_FAIL(ctx);
+// neumannBC (stiffnessMtrx.py:369-411); add: the node sums are added to rhs instead of a zero-filled rhs
+static int loadset_neumann(femcy_ctx* c, int32_t id, double traction, const double* direction, int rhs_vec, bool add) {
     VEC_OR_FAIL(rhs_vec);
     REQUIRE(id >= 0 && (size_t)id < c->loadsets.size(), "unknown load set %d", (int)id);
     LoadSet& ls = c->loadsets[id];
     double* rhs = c->vec[rhs_vec].data();
-    std::fill(rhs, rhs + c->n, 0.0);                // reference :384
+    if (!add) std::fill(rhs, rhs + c->n, 0.0);      // reference :384
     const int dm = c->dm;
 #pragma omp parallel for schedule(static)
     for (int32_t l = 0; l < ls.nload; ++l) {
@@ -894,9 +893,20 @@ int femcy_loadset_neumann(femcy_ctx* ctx, int32_t id, double traction, const dou
         for (int dd = 0; dd < dm; ++dd) {
             double s = 0.0;
             for (int32_t k = ls.ptr[i]; k < ls.ptr[i + 1]; ++k) s += ls.contrib[(int64_t)ls.slot[k] * dm + dd];
-            rhs[(int64_t)ls.node[i] * dm + dd] = s;
+            double& dst = rhs[(int64_t)ls.node[i] * dm + dd];
+            dst = add ? dst + s : s;
         }
     return FEMCY_OK;
+}
+
+int femcy_loadset_neumann(femcy_ctx* ctx, int32_t id, double traction, const double* direction, int rhs_vec) {
+    CTX_OR_FAIL(ctx);
+    return loadset_neumann(c, id, traction, direction, rhs_vec, false);
+}
+
+int femcy_loadset_neumann_add(femcy_ctx* ctx, int32_t id, double traction, const double* direction, int rhs_vec) {
+    CTX_OR_FAIL(ctx);
+    return loadset_neumann(c, id, traction, direction, rhs_vec, true);
 }
 
 int femcy_spmv(femcy_ctx* ctx, int x_vec, int y_vec) {

@@ -11,5 +11,6 @@ for _order in ("linear", "quadratic"):
         globals()[_name] = getattr(import_module(f"{__name__}.{_name.lower()}"), _name)
         __all__.append(_name)
 from .element_linear_hexahedral import Element_linear_hexahedral   # noqa: E402  (no quadratic hexahedron)
-__all__.append("Element_linear_hexahedral")
+from .element_linear_wedge import Element_linear_wedge   # noqa: E402  (no quadratic wedge)
+__all__ += ["Element_linear_hexahedral", "Element_linear_wedge"]
 del _order, _shape, _name

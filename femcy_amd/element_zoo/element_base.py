@@ -38,6 +38,8 @@ class ElementBase(abc.ABC):
         self.gaussPoints = HostField(self._gauss_points)
         self.gaussWeights = HostField(self._gauss_weights)
         self.gaussPoints_visualize = self.gaussPoints
+        # the point count of the first facet; an element with facets of two arities (wedge) has one per arity:
+        # facet_tables(nfn)["nip"]
         self.integPointNum_eachFacet = len(next(iter(self.facet_point_weights.values())))
 
     # ---- shape functions: subclasses implement the two *_pyscope methods ---------------
@@ -62,11 +64,25 @@ class ElementBase(abc.ABC):
                 "w": np.ascontiguousarray(self.gaussWeights, dtype=np.float64),
                 "voigt_kind": VOIGT_2D if self.dm == 2 else VOIGT_3D}
 
-    def facet_tables(self) -> dict:
+    def facet_arities(self) -> List[int]:
+        """the node counts of the element's facets, ascending (the wedge has triangles and quadrilaterals)."""
+        return sorted({len(k) for k in self.facet_natural_coos})
+
+    def facet_tables(self, nfn: int = None) -> dict:
         """the facet dictionaries (facet_natural_coos / facet_point_weights / facet_natural_normals, keyed by the
-        sorted local node tuple) as the plain arrays femcy_loadset_create takes; facet type = position of the key."""
+        sorted local node tuple) as the plain arrays femcy_loadset_create takes; facet type = position of the key.
+        nfn selects the facets of nfn nodes (one load set per facet arity); None takes every facet, which needs an
+        element with one facet arity."""
         keys = list(self.facet_natural_coos.keys())
-        nip = self.integPointNum_eachFacet
+        if nfn is None:
+            if len(self.facet_arities()) > 1:
+                raise ValueError(f"{type(self).__name__} has facets of {self.facet_arities()} nodes: pass nfn")
+            nip = self.integPointNum_eachFacet
+        else:
+            keys = [k for k in keys if len(k) == nfn]
+            if not keys:
+                raise ValueError(f"{type(self).__name__} has no facet of {nfn} nodes")
+            nip = len(self.facet_point_weights[keys[0]])
         coos = np.array([[self.facet_natural_coos[k][i] for i in range(nip)] for k in keys], dtype=np.float64)
         return {"keys": keys, "nft": len(keys), "nfn": len(keys[0]), "nip": nip,
                 "ft_nodes": np.ascontiguousarray(keys, dtype=np.int32),
@@ -119,6 +135,21 @@ class ElementBase(abc.ABC):
         sorted nodes, so that it does not depend on how neighbours would split a shared face; `mesh` and the map are then
         keyed by faces, and the outer faces are split into two triangles each."""
         el = np.asarray(elements)
+        if getattr(self, "_quad_faces", None) and getattr(self, "_tri_faces", None):
+            # faces of both kinds (wedge): each kind keyed by its sorted nodes; `mesh` is then a list of face keys of
+            # both sizes, and the outer surface the outer triangles plus two triangles per outer quadrilateral
+            face2ele = {}
+            outer = []
+            for cycles, split in ((self._tri_faces, [[0, 1, 2]]), (self._quad_faces, [[0, 1, 2], [0, 2, 3]])):
+                faces = np.concatenate([el[:, list(f)] for f in cycles], axis=0)
+                owner = np.tile(np.arange(el.shape[0]), len(cycles))
+                keys = np.sort(faces, axis=1)
+                _, inv, cnt = np.unique(keys, axis=0, return_inverse=True, return_counts=True)
+                for f, e in zip(map(tuple, keys.tolist()), owner.tolist()):
+                    face2ele.setdefault(f, set()).add(e)
+                out = faces[cnt[inv.ravel()] == 1]
+                outer += [out[:, t] for t in split]
+            return list(face2ele.keys()), face2ele, np.concatenate(outer, axis=0)
         if getattr(self, "_quad_faces", None):
             quads = np.concatenate([el[:, list(f)] for f in self._quad_faces], axis=0)
             owner = np.tile(np.arange(el.shape[0]), len(self._quad_faces))

@@ -141,11 +141,7 @@ def plate_hex(nx: int, ny: int, nz: int, perturb: float = 0.0, seed: int = 0,
     nodes, base, corner_off = _plate_cells(nx, ny, nz, box)
     hexes = (base[:, None] + corner_off[_HEX_CORNERS][None, :]).astype(np.int32, copy=False)
     if perturb:
-        h = min(box[0] / nx, box[1] / ny, box[2] / nz)
-        inner = np.all((nodes > 1e-9 * max(box)) & (nodes < np.asarray(box) * (1 - 1e-12)), axis=1)
-        rng = np.random.default_rng(seed)
-        nodes = nodes.copy()
-        nodes[inner] += rng.uniform(-perturb * h, perturb * h, size=(int(inner.sum()), 3))
+        nodes = _perturb(nodes, nx, ny, nz, perturb, seed, box)
     return nodes, hexes
 
 
@@ -155,6 +151,47 @@ def twist_plate_hex(nx: int, ny: int, nz: int, perturb: float = 0.0, seed: int =
     nodes, el = plate_hex(nx, ny, nz, perturb, seed)
     dirichlet, node_sets = twist_plate_bcs(nodes)
     return {"nodes": nodes, "elements": el, "etype": "C3D8", "node_sets": node_sets,
+            "dirichlet_bc_info": dirichlet, "neumann_bc_info": [],
+            "elastic": (2.0e11, 0.3), "geometric_nonlinear": True,
+            "time_incs": {"ini_inc": 0.05, "max_time": 1.0, "min_inc": 1e-5, "max_inc": 0.05},
+            "cells": (nx, ny, nz)}
+
+
+# two C3D6 wedges per cell of `plate_grid`, cut along the cell's diagonal from corner 1 to corner 2 (x = 1, y = 0 to
+# x = 0, y = 1): the triangles are normal to z and counter-clockwise seen from +z, node k + 3 above node k
+_WEDGE_CORNERS = [[0, 1, 2, 4, 5, 6], [1, 3, 2, 5, 7, 6]]
+
+
+def _perturb(nodes, nx, ny, nz, perturb, seed, box):
+    """the nodes off the box faces moved by a seeded uniform offset of up to perturb x the smallest cell size per
+    coordinate (plate_hex, plate_wedge)."""
+    h = min(box[0] / nx, box[1] / ny, box[2] / nz)
+    inner = np.all((nodes > 1e-9 * max(box)) & (nodes < np.asarray(box) * (1 - 1e-12)), axis=1)
+    rng = np.random.default_rng(seed)
+    nodes = nodes.copy()
+    nodes[inner] += rng.uniform(-perturb * h, perturb * h, size=(int(inner.sum()), 3))
+    return nodes
+
+
+def plate_wedge(nx: int, ny: int, nz: int, perturb: float = 0.0, seed: int = 0,
+                box: Tuple[float, float, float] = BOX):
+    """nodes of `plate_grid` and its cells as C3D6 wedges i32[2*nx*ny*nz, 6] (Abaqus order, positive volume), every
+    cell cut into two prisms along the same diagonal of its z faces, so that an interior node has 12 incident wedges
+    and 21 neighbours (itself included).  perturb as in `plate_hex`."""
+    nodes, base, corner_off = _plate_cells(nx, ny, nz, box)
+    wedges = (base[:, None, None] + corner_off[np.asarray(_WEDGE_CORNERS)][None, :, :]).reshape(-1, 6)
+    wedges = wedges.astype(np.int32, copy=False)
+    if perturb:
+        nodes = _perturb(nodes, nx, ny, nz, perturb, seed, box)
+    return nodes, wedges
+
+
+def twist_plate_wedge(nx: int, ny: int, nz: int, perturb: float = 0.0, seed: int = 0) -> Dict:
+    """the twist-plate model on C3D6 wedges (two per cell of `plate_grid`), with the nodes and boundary conditions of
+    `twist_plate_hex`.  192 x 24 x 216 cells: 1 990 656 wedges on 1 047 025 nodes."""
+    nodes, el = plate_wedge(nx, ny, nz, perturb, seed)
+    dirichlet, node_sets = twist_plate_bcs(nodes)
+    return {"nodes": nodes, "elements": el, "etype": "C3D6", "node_sets": node_sets,
             "dirichlet_bc_info": dirichlet, "neumann_bc_info": [],
             "elastic": (2.0e11, 0.3), "geometric_nonlinear": True,
             "time_incs": {"ini_inc": 0.05, "max_time": 1.0, "min_inc": 1e-5, "max_inc": 0.05},

@@ -28,7 +28,8 @@ import numpy as np
 
 from ..element_zoo import (Element_linear_triangular, Element_linear_quadrilateral,
                            Element_quadratic_triangular, Element_quadratic_quadrilateral,
-                           Element_linear_tetrahedral, Element_quadratic_tetrahedral, Element_linear_hexahedral)
+                           Element_linear_tetrahedral, Element_quadratic_tetrahedral, Element_linear_hexahedral,
+                           Element_linear_wedge)
 from ..material_zoo import (LinearIsotropic, LinearIsotropicPlaneStrain, LinearIsotropicPlaneStress, NeoHookean)
 from .inp_info_base import InpInfoBase
 
@@ -46,7 +47,7 @@ ELEMENT_CLASSES = {"CPE3": Element_linear_triangular, "CPS3": Element_linear_tri
                    "CPS6": Element_quadratic_triangular, "CPE6": Element_quadratic_triangular,
                    "CPS8": Element_quadratic_quadrilateral, "CPE8": Element_quadratic_quadrilateral,
                    "C3D4": Element_linear_tetrahedral, "C3D10": Element_quadratic_tetrahedral,
-                   "C3D8": Element_linear_hexahedral}
+                   "C3D8": Element_linear_hexahedral, "C3D6": Element_linear_wedge}
 
 
 class _Deck:

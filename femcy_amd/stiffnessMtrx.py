@@ -365,31 +365,43 @@ class System_of_equations:
     def dirichletBC_val(self, nodeSet, dm_specified: int, sval: float):
         self.ctx.dofset_fill(self._dofset(nodeSet, dm_specified), be.VEC_DOF, sval)
 
-    def _loadset(self, load_facets) -> int:
-        """device load set of one *Dsload surface, built once per face set: owning element of each facet
+    def _loadset(self, load_facets) -> list:
+        """device load sets of one *Dsload surface, built once per face set: owning element of each facet
         (body.boundary, reference :386) and the facet's type = position of its sorted local node tuple in the
-        element plugin's facet tables (reference :388-392)."""
+        element plugin's facet tables (reference :388-392).  One set per facet arity of the element, fewest nodes
+        first, empty where the surface has no facet of that arity: a wedge surface can hold triangles and
+        quadrilaterals, and a load set has one arity.  The number of sets depends on the element alone, so every rank
+        of a partitioned run makes the same collective calls in neumannBC, whichever facets it holds."""
         key = frozenset(tuple(f) for f in load_facets)           # by content: repeated solve() calls reuse the device set
         if key not in self._loadsets:
             boundary = self.body.get_boundary()
+            arities = self.ELE.facet_arities()
             facets = [tuple(f) for f in load_facets]
-            if not facets:       # a rank of a partitioned run that holds none of the loaded facets
-                self._loadsets[key] = (self.ctx.loadset(self.ELE, np.zeros(0, np.int32), np.zeros(0, np.int32)), load_facets)
-                return self._loadsets[key][0]
-            elem = np.fromiter((boundary[f] for f in facets), dtype=np.int64, count=len(facets))
-            fnodes = np.asarray(facets, dtype=np.int64).reshape(len(facets), -1)
-            conn = self.body.np_elements[elem]                                            # [nf, npe]
-            local = np.sort((conn[:, None, :] == fnodes[:, :, None]).argmax(axis=2), axis=1)   # sorted local ids
-            keys = self.ELE.facet_tables()["keys"]
-            type_of = {k: i for i, k in enumerate(keys)}
-            ft = np.fromiter((type_of[tuple(r)] for r in local.tolist()), dtype=np.int32, count=len(facets))
-            self._loadsets[key] = (self.ctx.loadset(self.ELE, elem, ft), load_facets)
+            sets = []
+            for nfn in arities:
+                fk = [f for f in facets if len(f) == nfn]
+                if not fk:       # no loaded facet of this arity (on this rank of a partitioned run)
+                    sets.append(self.ctx.loadset(self.ELE, np.zeros(0, np.int32), np.zeros(0, np.int32),
+                                                 nfn if len(arities) > 1 else None))
+                    continue
+                elem = np.fromiter((boundary[f] for f in fk), dtype=np.int64, count=len(fk))
+                fnodes = np.asarray(fk, dtype=np.int64).reshape(len(fk), -1)
+                conn = self.body.np_elements[elem]                                            # [nf, npe]
+                local = np.sort((conn[:, None, :] == fnodes[:, :, None]).argmax(axis=2), axis=1)   # sorted local ids
+                keys = self.ELE.facet_tables(nfn if len(arities) > 1 else None)["keys"]
+                type_of = {k: i for i, k in enumerate(keys)}
+                ft = np.fromiter((type_of[tuple(r)] for r in local.tolist()), dtype=np.int32, count=len(fk))
+                sets.append(self.ctx.loadset(self.ELE, elem, ft, nfn if len(arities) > 1 else None))
+            self._loadsets[key] = (sets, load_facets)
         return self._loadsets[key][0]
 
     def neumannBC(self, load_facets, load_val: float, load_dir=np.array([])):
         """consistent nodal loads of a surface traction (dead load on the undeformed geometry), evaluated on the
-        device.  rhs is refreshed on every call, as in the reference (:384)."""
-        self.ctx.loadset_neumann(self._loadset(load_facets), load_val, load_dir, be.VEC_RHS)
+        device.  rhs is refreshed on every call, as in the reference (:384): the first load set (fewest facet nodes)
+        overwrites it, a second arity's set is added to it (an empty set adds nothing, but it still takes part in the
+        interface sum of a partitioned run)."""
+        for i, ls in enumerate(self._loadset(load_facets)):
+            self.ctx.loadset_neumann(ls, load_val, load_dir, be.VEC_RHS, add=i > 0)
 
     def impose_boundary_condition(self, boundary_conditions: dict):
         for nb in boundary_conditions["neumannBCs"]:

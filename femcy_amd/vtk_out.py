@@ -10,14 +10,17 @@ _VTK = {("tri", 3): (5, [0, 1, 2]), ("tri", 6): (22, [0, 1, 2, 3, 4, 5]),
         # 5:(1,2) 6:(2,0) 7:(0,3) 8:(3,1) 9:(2,3).  VTK quadratic tet edges: (0,1)(1,2)(2,0)(0,3)(1,3)(2,3)
         ("tet", 4): (10, [0, 1, 2, 3]), ("tet", 10): (24, [0, 1, 2, 3, 4, 5, 6, 7, 8, 9]),
         # C3D8: the Abaqus node order is VTK_HEXAHEDRON's
-        ("hex", 8): (12, [0, 1, 2, 3, 4, 5, 6, 7])}
+        ("hex", 8): (12, [0, 1, 2, 3, 4, 5, 6, 7]),
+        # C3D6: VTK_WEDGE wants its triangle (0, 1, 2) to face away from (3, 4, 5), i.e. (0, 1, 2) counter-clockwise
+        # seen from (3, 4, 5); Abaqus' bottom triangle is counter-clockwise seen from outside, below it: swap 1 <-> 2
+        ("wedge", 6): (13, [0, 2, 1, 3, 5, 4])}
 
 
 def write_vtk(path: str, system, title: str = "femcy_amd result"):
     nodes = np.asarray(system.body.np_nodes)
     el = np.asarray(system.body.np_elements)
     dm, npe = nodes.shape[1], el.shape[1]
-    family = ("hex" if npe == 8 else "tet") if dm == 3 else ("tri" if npe in (3, 6) else "quad")
+    family = {8: "hex", 6: "wedge"}.get(npe, "tet") if dm == 3 else ("tri" if npe in (3, 6) else "quad")
     ctype, perm = _VTK[(family, npe)]
     u = system.dof.to_numpy().reshape(-1, dm)
     pts = np.zeros((nodes.shape[0], 3))

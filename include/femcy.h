@@ -83,7 +83,8 @@ enum femcy_assembly {
                              backend reports this value for its serial element-by-element scatter (no atomics) */
     FEMCY_ASM_ROWS = 2,   /* one wavefront per matrix row, LDS reduction, deterministic           */
     FEMCY_ASM_AUTO = 3,   /* default: ROWS4 for C3D10 (ROWS2 / ROWS if its LDS does not fit), PAIRS for the 2-D quadratic
-                             families and C3D8 (ROWS if its LDS does not fit), GATHER_SYM(_ROWSUM) otherwise */
+                             families, C3D8 and C3D6 (if its LDS does not fit: GATHER_SYM_ROWSUM for C3D6, ROWS for the
+                             others), GATHER_SYM(_ROWSUM) otherwise */
     FEMCY_ASM_GATHER_SYM = 4, /* GATHER on the diagonal + upper blocks only, mirrored stores of K_ba = K_ab^T: 1.3x on C3D4 */
     FEMCY_ASM_GATHER_SYM_ROWSUM = 5, /* the same with the diagonal block from K_aa = -sum_{b != a} K_ab (partition of
                                 unity, checked on the element tables); AUTO picks it for npe <= 4 */
@@ -97,8 +98,9 @@ enum femcy_assembly {
                              column node, the element's whole record is read once per pair by coalesced 16-byte loads
                              (the row node's gradients come from the neighbouring lane), the geometric sums are reduced
                              in a wave-private LDS tile and the tile is written as 256-byte runs; any constant C.
-                             2-D families and C3D8 (3 x 3 blocks; pair lists in step order, so no two lanes of one
-                             LDS add hit the same word); AUTO picks it for CPE6 / CPS6 / CPE8 / CPS8 and C3D8 */
+                             2-D families, C3D8 and C3D6 (3 x 3 blocks; pair lists in step order, each step padded to
+                             a multiple of the pairs per kernel step, so no two lanes of one LDS add hit the same word);
+                             AUTO picks it for CPE6 / CPS6 / CPE8 / CPS8, C3D8 and C3D6 */
 };
 
 enum femcy_option {
@@ -339,14 +341,21 @@ int femcy_dofset_scatter(femcy_ctx* ctx, int32_t id, int vec, const double* vals
  * femcy_loadset_neumann zero-fills vec[rhs] (reference :384) and writes the consistent nodal loads of
  * traction * (direction, or the outward unit normal n_nat (dx/dxi)^-1 / (|.| + 1e-30) when direction is NULL)
  * on the undeformed geometry; the facet size is |x1 - x0| (dm = 2) or the triangle area of the facet's first
- * three sorted nodes (dm = 3), as ELE.globalNormal computes it.  A 3-D facet of four nodes (a hexahedron face)
- * instead weights each facet point by its surface Jacobian (Nanson): da = |det J| |J^-T n_nat| w.  Sums per node
- * run in a fixed order. */
+ * three sorted nodes (dm = 3), as ELE.globalNormal computes it.  A 3-D facet of four nodes (a hexahedron face, a
+ * wedge's quadrilateral face) instead weights each facet point by its surface Jacobian (Nanson):
+ * da = |det J| |J^-T n_nat| w.  Sums per node run in a fixed order.
+ * A load set has one facet arity (nfn, nip).  The C3D6 wedge has faces of both kinds -- S1 / S2 are triangles (nfn 3,
+ * three points of weight 1/3), S3 / S4 / S5 quadrilaterals (nfn 4, 2 x 2 Gauss points) -- so a wedge surface is two load
+ * sets: femcy_loadset_neumann on the triangle set, then femcy_loadset_neumann_add on the quadrilateral set.
+ * femcy_loadset_neumann_add is femcy_loadset_neumann without the zero-fill: it adds the set's node sums to vec[rhs]
+ * (several ranks: it sums its own loads over the interface in vector TMP1, which must then not be vec[rhs]). */
 int femcy_loadset_create(femcy_ctx* ctx, int32_t nft, int32_t nfn, int32_t nip, const int32_t* ft_nodes,
                          const double* ft_N, const double* ft_dN, const double* ft_normal, const double* ft_weight,
                          int32_t nload, const int32_t* load_elem, const int32_t* load_ft, int32_t* id_out);
 int femcy_loadset_neumann(femcy_ctx* ctx, int32_t id, double traction, const double* direction /*[dm] or NULL*/,
                           int rhs_vec);
+int femcy_loadset_neumann_add(femcy_ctx* ctx, int32_t id, double traction, const double* direction /*[dm] or NULL*/,
+                              int rhs_vec);
 /* compute_Ad (conjugateGradientSolver.py:53-58): vec[y] = K vec[x] */
 int femcy_spmv(femcy_ctx* ctx, int x_vec, int y_vec);
 /* ConjugateGradientSolver_rowMajor.re_init + solve (conjugateGradientSolver.py:32-51, 103-127):
