@@ -43,8 +43,6 @@ OPT_ASSEMBLY, OPT_PCG_POLL, OPT_TIMING, OPT_SPMV_VARIANT, OPT_EW_GRID, OPT_PCG_G
 OPT_TANGENT = 7          # 0 = the reference's matrix (default), 1 = consistent tangent (extension)
 OPT_EXCHANGE = 8         # multi-rank: 0 = packed all-reduce (default), 1 = neighbour send/recv
 OPT_PCG_STORAGE_ORDER = 13   # 1 (default) = the single-rank three-launch PCG keeps its vectors in storage order
-OPT_PCG_FUSED_UPDATE = 15    # 1 = one vector kernel per iteration in the single-rank three-launch PCG (default 0: measured slower)
-OPT_SPMV_FOOTPRINT = 16      # 1 = storage-order product with the wave's x footprint staged in LDS
 OPT_DIRECT_MAX_BYTES = 17   # femcy_direct_solve: largest band it may allocate (bytes, default 48 GiB)
 OPT_NODE_ORDER = 14      # 0 = caller's numbering, 1 (default) = measured choice among coordinate orders, 2 + k = forced (before build_pattern)
 OPT_PCG_PERSIST = 11     # 1 (default) = persistent one-launch PCG (single rank, <= ~7e5 DOF, matrix <= Infinity Cache); 2 = any matrix size

@@ -118,7 +118,6 @@ struct PcgState {
     int32_t it_k3;   // iteration index handed from k_update_xr to k_update_d
     int32_t done;    // 0 running, 1 converged, 2 NaN/breakdown: written by k_update_d, tested by k_spmv / k_update_xr
     int32_t skip;    // `done` as k_update_xr saw it, handed to the k_update_d of the same iteration
-    unsigned long long xround;   // launches of k_update_fused so far (its granule tag); never reset by a solve
 };
 
 // contiguous slice range of each XCD for the SpMV (balanced by stored blocks), passed by value
@@ -166,6 +165,8 @@ struct Ctx {
     bool vec_nt = false;              // PCG vector kernels with non-temporal accesses
     int opt_vec_nt = -1;              // -1 auto (same rule as the matrix stream), 0 / 1 forced (test knob 103)
     int opt_spmv_nt = -1;             // -1 auto, 0 / 1 forced (test knob 102)
+    int spmv_keep_permille = 0;       // NT SpMV: share of every XCD's slice range kept on the default cache policy
+    int opt_spmv_keep = -1;           // -1 auto (235 MB of the matrix), else per mille (tuning knob 110)
     int32_t spmv_bpx_cap = 0;         // SpMV workgroups per XCD (larger slice ranges are looped in the kernel); 0 = by the
                                       // size of the matrix (spmv_cap_auto), FEMCY_TUNE_SPMV_WG_PER_XCD fixes it
     int32_t spmv_cap_auto = 256;      // spmv_split: 512 for long ranges of a large matrix, else 256
@@ -264,21 +265,9 @@ struct Ctx {
     int64_t pattern_serial = 0;       // bumped by femcy_build_pattern
     double* d_persist = nullptr;      // d double buffer, partials, granules, barrier counters
     int64_t persist_cap = 0;
+    // ---- three-launch PCG with its vectors in storage order (single rank)
     int32_t* d_bcolp = nullptr;       // block columns as storage positions (PCG with its vectors in storage order)
     int64_t bcolp_serial = -1;
-    // ---- footprint product (k_spmv_fp): per (slice, wave part) the sorted list of storage positions its block rows
-    // refer to, and the block columns as 16-bit indices into that list; the wave stages x of its footprint in LDS with
-    // coalesced loads and gathers from there
-    int opt_spmv_fp = 0;              // FEMCY_OPT_SPMV_FOOTPRINT (0 off, 1 on where the footprints fit the LDS)
-    uint16_t* d_lcol = nullptr;       // [stored_rows * 64]
-    int32_t* d_fp_ptr = nullptr;      // [nslices * wps + 1]
-    int32_t* d_fp = nullptr;
-    int32_t fp_cap = 0;               // longest footprint (entries), 0 = not usable
-    int64_t fp_serial = -1;           // pattern_serial * 8 + wps the arrays were built for
-    int opt_fused_update = 0;         // FEMCY_OPT_PCG_FUSED_UPDATE: single-rank three-launch loop with ONE vector kernel per iteration
-                                      // (measured slower than the two kernels: default off)
-    bool fused_failed = false;        // its in-kernel exchange timed out once: two kernels from then on
-    double* d_fused = nullptr;        // granules of k_update_fused ([1024][2] x 16 B)
     int opt_pos_space = 1;            // FEMCY_OPT_PCG_STORAGE_ORDER: the three-kernel PCG of a single rank keeps r, d, M, Ad, x
                                       // in storage order (gathers of neighbouring lanes then hit neighbouring addresses)
     double* d_posb = nullptr;         // right-hand side / solution in storage order
@@ -293,8 +282,6 @@ struct Ctx {
     char* d_probe = nullptr;          // femcy_probe_stream's buffer
     int64_t probe_cap = 0;
     // ---- one-launch PCG for small systems (k_pcg_small)
-    int spmv_keep_permille = 0;       // NT SpMV: share of every XCD's slice range kept on the default cache policy
-    int opt_spmv_keep = -1;           // -1 auto (235 MB of the matrix), else per mille (tuning knob 110)
     int opt_small_rr = -1;            // test knob 108: block rows per wave of the small-system PCG kept in registers
     int opt_small = 1;                // FEMCY_OPT_PCG_SMALL
     int small_max_lds = 65536;        // LDS a workgroup may allocate (device attribute, femcy_ctx_create)
@@ -429,7 +416,6 @@ inline bool pairs_instantiated(const Ctx* c) {
                            (c->npe == 3 && c->nGP == 1)));
 }
 int ensure_pairs(Ctx* c, int rows_per_chunk, bool spatial_order, int chunks_per_wave);   // pattern.cpp: d_pr_unit / d_pr_ptr / d_pr_code for the current pattern
-int ensure_footprint(Ctx* c);   // pattern.cpp: d_lcol / d_fp_ptr / d_fp for the current pattern and spmv_wps
 int ensure_pos_vectors(Ctx* c);   // d_posb / d_posx (storage-order right-hand side / solution) + d_bcolp
 int ensure_bcolp(Ctx* c);   // d_bcolp = pos[bcol]: block columns as storage positions
 int pcg_persist_solve(Ctx* c, const double* d_b, double* d_x, double eps, int32_t maxit, bool* handled);

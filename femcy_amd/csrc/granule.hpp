@@ -1,4 +1,4 @@
-// Tagged-granule exchange between the workgroups of one persistent launch (k_pcg_persist, k_pcg_small).
+// Tagged-granule exchange between the workgroups of one persistent launch (k_pcg_persist, k_probe_exchange).
 // A granule is one naturally aligned 16-byte {f64 value, u64 tag} written by ONE sc1 store (observed untorn on
 // gfx950, MI355X_MICROARCH.md "Valid forms": R2); the tag is a launch-wide round number (1, 2, 3, ...; the arrays are
 // zeroed before the launch), so a granule validates itself: no counter, no flag, no re-arming.  A workgroup may write
@@ -35,9 +35,6 @@ __device__ __forceinline__ bool granule_sweep(const __amdgpu_buffer_rsrc_t rs, i
                                               uint32_t spin_limit, double (&out)[NV], const int (&op)[NV]) {
     const int lane = threadIdx.x & 63;
     uint32_t spins = 0;
-#ifdef FEMCY_SWEEP_PRIO
-    __builtin_amdgcn_s_setprio(FEMCY_SWEEP_PRIO);   /* experiment: the sweeping wave ahead of the CU's streaming waves */
-#endif
     for (;;) {
         double acc[NV];
 #pragma unroll
@@ -56,19 +53,13 @@ __device__ __forceinline__ bool granule_sweep(const __amdgpu_buffer_rsrc_t rs, i
                 acc[v] = op[v] ? fmax(acc[v], val) : acc[v] + val;
             }
         }
-#ifdef FEMCY_SWEEP_PRIO
-        if (__any(poison) || __all(ok)) __builtin_amdgcn_s_setprio(0);
-#endif
         if (__any(poison)) return false;
         if (__all(ok)) {
 #pragma unroll
             for (int v = 0; v < NV; ++v) out[v] = op[v] ? wave_max(acc[v]) : wave_sum(acc[v]);
             return true;
         }
-#ifndef FEMCY_GRANULE_SLEEP
-#define FEMCY_GRANULE_SLEEP 1      /* s_sleep units (64 cycles) between sweeps; 0 = poll back to back (measured: no gain) */
-#endif
-        if (FEMCY_GRANULE_SLEEP) __builtin_amdgcn_s_sleep(FEMCY_GRANULE_SLEEP);
+        __builtin_amdgcn_s_sleep(1);      // 64 cycles between sweeps; polling back to back measured no gain
         if (++spins > spin_limit) return false;
     }
 }

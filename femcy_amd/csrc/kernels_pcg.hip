@@ -28,7 +28,6 @@
 #include <hip/hip_ext.h>
 #include "ctx.hpp"
 #include "wave_reduce.hpp"
-#include "granule.hpp"
 
 namespace femcy {
 
@@ -163,15 +162,12 @@ __global__ void __launch_bounds__(BS) k_spmv(int32_t nn, XcdRanges xr, const int
             // pairs of entries as double2 (16 B per lane, 1 KiB per wave instruction); see kv_index()
             const double2* __restrict__ vp = reinterpret_cast<const double2*>(vals + off * (int64_t)(DD * SLICE)) + lane;
             const double* __restrict__ vs = vals + off * (int64_t)(DD * SLICE) + NP * (2 * SLICE) + lane;
-#ifndef FEMCY_SPMV_UNROLL
-#define FEMCY_SPMV_UNROLL 2
-#endif
             // NT (matrix beyond the Infinity Cache): the first keep_permille/1000 of every XCD's slice range is still
             // loaded with the default policy, so that this part stays in the Infinity Cache from one product to the
             // next while the rest streams past it without allocating
             auto rows = [&](auto nt_tag) {
                 constexpr bool N = decltype(nt_tag)::value;
-#pragma unroll FEMCY_SPMV_UNROLL
+#pragma unroll 2   // depths 1 / 3 / 4: slower or inside the run-to-run band (profiles/r06_spmv_unroll.txt)
                 for (int32_t j = j0; j < j1; ++j) {
                     const int32_t col = N ? __builtin_nontemporal_load(&bc[(int64_t)j * SLICE]) : bc[(int64_t)j * SLICE];
                     double xv[DM];
@@ -220,125 +216,6 @@ __global__ void __launch_bounds__(BS) k_spmv(int32_t nn, XcdRanges xr, const int
                     y[a * DM + r] = real ? acc[r] : 0.0;
                     if (real) dot += x[a * DM + r] * acc[r];
                 }
-            }
-        }
-    }
-    if (partials) {
-        const double t = block_sum(dot, sm);
-        if (threadIdx.x == 0) partials[blockIdx.x] = t;
-    }
-}
-
-// ---- footprint product (round 4, storage order only; ensure_footprint in pattern.cpp).  Same partition of the work as
-// k_spmv -- XCD-contiguous slice ranges, WPS waves per slice, matrix stream policy -- but x is not gathered from global
-// memory block by block: the wave first stages the x entries of its FOOTPRINT (the sorted distinct positions its block
-// rows refer to) in its own LDS region with coalesced 16 + 8 byte loads, then reads them from there through 16-bit
-// local column indices.  A wave-level LDS sync suffices (no workgroup barrier: the region is the wave's own).
-__device__ __forceinline__ void fp_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-template <int DM, int WPS, bool NT>
-__global__ void __launch_bounds__(BS) k_spmv_fp(int32_t npos, XcdRanges xr, const int32_t* __restrict__ slice_len,
-                                                const int64_t* __restrict__ slice_off,
-                                                const uint16_t* __restrict__ lcol, const int32_t* __restrict__ fp_ptr,
-                                                const int32_t* __restrict__ fp, const double* __restrict__ vals,
-                                                const double* __restrict__ x, double* __restrict__ y,
-                                                double* __restrict__ partials, const int32_t* __restrict__ done,
-                                                int32_t keep_permille, int32_t nreal, int32_t fcap, int32_t rot,
-                                                const int32_t* __restrict__ perm, int32_t perm_rounds) {
-    extern __shared__ __attribute__((aligned(16))) double xs_all[];      // [BS / 64][fcap][DM]
-    __shared__ double sm[BS / 64];
-    __shared__ double red[(WPS > 1) ? (BS / 64) * 64 * DM : 1];
-    if (done && *done) return;
-    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, (int)std::min<size_t>((size_t)npos * DM * sizeof(double), 0x7fffffffu), 0x00020000);
-    constexpr int SPB = (BS / 64) / WPS;
-    constexpr int DD = DM * DM, NP = DD / 2;
-    const int k = blockIdx.x % NXCD;
-    const int bpx = gridDim.x / NXCD;
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int part = wave % WPS;
-    double* __restrict__ xs = xs_all + (size_t)wave * fcap * DM;
-    const int s_end = xr.start[k + 1];
-    const int ntask = (s_end - xr.start[k] + SPB - 1) / SPB;
-    double dot = 0.0;
-    const int wgx = blockIdx.x / NXCD;
-    for (int rnd = 0; rnd * bpx < ntask; ++rnd) {                     // rotated rounds: see k_spmv
-        const int task = rnd * bpx + (perm ? perm[((size_t)k * perm_rounds + rnd) * bpx + wgx] : spmv_rot<SLICE / SPB>(wgx, rnd, bpx, rot));
-        const int s = xr.start[k] + task * SPB + wave / WPS;
-        const bool active = s < s_end;
-        double acc[DM];
-#pragma unroll
-        for (int r = 0; r < DM; ++r) acc[r] = 0.0;
-        if (active) {
-            const int32_t L = slice_len[s];
-            const int32_t chunk = (L + WPS - 1) / WPS;
-            const int32_t j0 = part * chunk, j1 = min(L, j0 + chunk);
-            const int64_t off = slice_off[s];
-            // ---- stage the footprint (the previous task's reads of this region are complete: same wave, program order)
-            const int32_t f0 = fp_ptr[(int64_t)s * WPS + part], F = fp_ptr[(int64_t)s * WPS + part + 1] - f0;
-            fp_wave_sync();
-            for (int32_t i = lane; i < F; i += 64) {
-                const int32_t p = NT ? __builtin_nontemporal_load(&fp[f0 + i]) : fp[f0 + i];
-                double xv[DM];
-                gather_x<DM>(xrsrc, p, xv);
-#pragma unroll
-                for (int cc = 0; cc < DM; ++cc) xs[i * DM + cc] = xv[cc];
-            }
-            fp_wave_sync();
-            const uint16_t* __restrict__ lc = lcol + off * SLICE + lane;
-            const double2* __restrict__ vp = reinterpret_cast<const double2*>(vals + off * (int64_t)(DD * SLICE)) + lane;
-            const double* __restrict__ vs = vals + off * (int64_t)(DD * SLICE) + NP * (2 * SLICE) + lane;
-            auto rows = [&](auto nt_tag) {
-                constexpr bool N = decltype(nt_tag)::value;
-#pragma unroll FEMCY_SPMV_UNROLL
-                for (int32_t j = j0; j < j1; ++j) {
-                    const int32_t col = N ? __builtin_nontemporal_load(&lc[(int64_t)j * SLICE]) : lc[(int64_t)j * SLICE];
-                    double e[DD];
-#pragma unroll
-                    for (int kp = 0; kp < NP; ++kp) {
-                        typedef double nt_d2 __attribute__((ext_vector_type(2)));
-                        const nt_d2* tp = reinterpret_cast<const nt_d2*>(&vp[(int64_t)j * (DD * SLICE / 2) + kp * SLICE]);
-                        const nt_d2 t = N ? __builtin_nontemporal_load(tp) : *tp;
-                        e[2 * kp] = t.x;
-                        e[2 * kp + 1] = t.y;
-                    }
-                    if (DD & 1) e[DD - 1] = N ? __builtin_nontemporal_load(&vs[(int64_t)j * (DD * SLICE)]) : vs[(int64_t)j * (DD * SLICE)];
-                    double xv[DM];
-#pragma unroll
-                    for (int cc = 0; cc < DM; ++cc) xv[cc] = xs[col * DM + cc];
-#pragma unroll
-                    for (int r = 0; r < DM; ++r)
-#pragma unroll
-                        for (int cc = 0; cc < DM; ++cc) acc[r] += e[r * DM + cc] * xv[cc];
-                }
-            };
-            if (NT && (int64_t)(s - xr.start[k]) * 1000 >= (int64_t)keep_permille * (s_end - xr.start[k]))
-                rows(std::true_type{});
-            else
-                rows(std::false_type{});
-        }
-        if (WPS > 1) {
-            __syncthreads();
-#pragma unroll
-            for (int r = 0; r < DM; ++r) red[(wave * DM + r) * 64 + lane] = acc[r];
-            __syncthreads();
-            if (part == 0) {
-#pragma unroll
-                for (int w = 1; w < WPS; ++w)
-#pragma unroll
-                    for (int r = 0; r < DM; ++r) acc[r] += red[((wave + w) * DM + r) * 64 + lane];
-            }
-        }
-        if (active && part == 0) {
-            const int64_t a = (int64_t)s * SLICE + lane;
-            const bool real = a < nreal;
-#pragma unroll
-            for (int r = 0; r < DM; ++r) {
-                y[a * DM + r] = real ? acc[r] : 0.0;
-                if (real) dot += x[a * DM + r] * acc[r];
             }
         }
     }
@@ -676,125 +553,6 @@ __global__ void __launch_bounds__(BS) k_update_d(XcdRanges er, int np2, const do
     }
 }
 
-// ---- round 4: the two vector kernels of an iteration as ONE launch (single rank; FEMCY_OPT_PCG_FUSED_UPDATE, default
-// OFF: measured 1.5 us per iteration SLOWER than the two kernels on MI355X -- a kernel boundary costs ~1.5 us here, a
-// grid-wide exchange 2.6-3.3 us, and the loads the boundary lets the second kernel issue early are serialised behind
-// the exchange; profiles/r04_ab_fused_update.txt.  Kept as a tested option and as the record of that measurement).  k_update_xr and k_update_d are
-// latency-bound launches (5.6-6.7 us each for 18-26 MB) separated by a kernel boundary whose only purpose is the
-// grid-wide (r.M.r, max|r|); here that reduction is an in-kernel exchange of tagged granules (granule.hpp: one 16-byte
-// write-through store per workgroup, one wave sweeps), r and M stay in registers across it and d / x are already
-// in flight when it starts: one boundary and 16 n bytes less per iteration.  Every thread owns <= U double2 of its
-// XCD's element range.  The tag is a launch counter kept in PcgState (never reset: tags grow for the life of the
-// context), so no granule is ever re-armed; every workgroup of the launch is resident (checked by the host) and the
-// sweep is bounded -- a time-out poisons the granules, sets done = 3 and the host redoes the solve with the two
-// kernels and stays there.
-template <bool NT, int U>
-__global__ void __launch_bounds__(BS) k_update_fused(XcdRanges er, int np1, const double* __restrict__ part1, PcgState* st,
-                                                     const double2* __restrict__ Ad, const double2* __restrict__ M,
-                                                     double2* __restrict__ r, double2* __restrict__ d,
-                                                     double2* __restrict__ x, double* __restrict__ slots,
-                                                     uint32_t spin_limit) {
-    __shared__ double sm1[BS / 64], sm2[BS / 64], bc[2];
-    __shared__ int s_fail;
-    if (st->done) return;          // written by an earlier launch only: every workgroup of this one reads the same value
-    const int G = gridDim.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int xk = blockIdx.x % NXCD;
-    const int64_t stride = (int64_t)(G / NXCD) * BS;
-    const int64_t lo = er.start[xk], hi = er.start[xk + 1];
-    const int64_t base = lo + (int64_t)(blockIdx.x / NXCD) * BS + tid;
-    if (tid == 0) s_fail = 0;
-    double pv[PU];
-#pragma unroll
-    for (int u = 0; u < PU; ++u) {
-        const int k = tid + u * BS;
-        pv[u] = part1[k < np1 ? k : MAX_PARTIALS];
-    }
-    double2 av[U], mv[U], rv[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const int64_t i = max(lo, min(base + u * stride, hi - 1));
-        av[u] = ld2<NT>(Ad + i);
-        mv[u] = ld2<NT>(M + i);
-        rv[u] = ld2<NT>(r + i);
-    }
-    const int it = st->iters;
-    const unsigned long long tag = st->xround + 1;      // stable: written by block 0 of the previous launch at its end
-    double v = 0.0;
-#pragma unroll
-    for (int u = 0; u < PU; ++u) v += pv[u];
-    for (int k = tid + PU * BS; k < np1; k += BS) v += part1[k];
-    const double dAd = block_sum(v, sm1);
-    const double rMr_old = st->rMr[it & 1];
-    const double alpha = rMr_old / dAd;
-    double rMr = 0.0, rm = 0.0;
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const int64_t i = base + u * stride;
-        if (i < hi) {
-            rv[u].x = rv[u].x - alpha * av[u].x;
-            rv[u].y = rv[u].y - alpha * av[u].y;
-            st2<NT>(r + i, rv[u]);
-            rMr += rv[u].x * mv[u].x * rv[u].x + rv[u].y * mv[u].y * rv[u].y;
-            rm = fmax(rm, fmax(nan_to_inf_abs(rv[u].x), nan_to_inf_abs(rv[u].y)));
-        }
-    }
-    // d and x of this thread: requested before the exchange, used behind it (av's registers are free now)
-    double2 dv[U], xv[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const int64_t i = max(lo, min(base + u * stride, hi - 1));
-        dv[u] = ld2<NT>(d + i);
-        xv[u] = ld2<NT>(x + i);
-    }
-    const double s = block_sum(rMr, sm1), m = block_max(rm, sm2);
-    const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc((void*)slots, 0, G * 2 * 16, 0x00020000);
-    if (wave == 0) {
-        if (lane == 0) granule_store(srsrc, 2 * blockIdx.x, s, tag);
-        if (lane == 1) granule_store(srsrc, 2 * blockIdx.x + 1, m, tag);
-        double o[2];
-        const int op[2] = {0, 1};
-        const bool okx = granule_sweep<2>(srsrc, 0, G, tag, spin_limit, o, op);
-        if (!okx && lane < 2) granule_store(srsrc, 2 * blockIdx.x + lane, 0.0, TAG_POISON);
-        if (lane == 0) {
-            bc[0] = o[0];
-            bc[1] = o[1];
-            if (!okx) s_fail = 1;
-        }
-    }
-    __syncthreads();
-    if (s_fail) {
-        // the time-out verdict wins over whatever workgroup 0 concludes from a sweep that happened to complete for it
-        // (the granule reads of one sweep are not atomic: verdicts can be mixed inside one launch)
-        if (tid == 0) atomicMax(&st->done, 3);
-        return;
-    }
-    const double rMr_new = bc[0], rmax = bc[1];
-    const double beta = rMr_new / rMr_old;
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const int64_t i = base + u * stride;
-        if (i < hi) {
-            xv[u].x = xv[u].x + alpha * dv[u].x;
-            xv[u].y = xv[u].y + alpha * dv[u].y;
-            dv[u].x = mv[u].x * rv[u].x + beta * dv[u].x;
-            dv[u].y = mv[u].y * rv[u].y + beta * dv[u].y;
-            st2<NT>(x + i, xv[u]);
-            st2<NT>(d + i, dv[u]);
-        }
-    }
-    if (blockIdx.x == 0 && tid == 0) {
-        st->rMr[(it + 1) & 1] = rMr_new;
-        st->rmax = rmax;
-        st->alpha = alpha;
-        st->iters = it + 1;
-        st->xround = tag;
-        if (rmax != rmax || isinf(rmax) || rMr_new != rMr_new)
-            atomicMax(&st->done, 2);
-        else if (rmax < st->eps * st->r0)
-            atomicMax(&st->done, 1);
-    }
-}
-
 // single-block reduction of the (r.M.r, max|r|) partials into one pair (multi-rank path)
 __global__ void __launch_bounds__(BS) k_sum_partials2(int np, const double* __restrict__ part2, double* out2) {
     __shared__ double sm1[BS / 64], sm2[BS / 64];
@@ -1019,44 +777,6 @@ static int launch_spmv_impl(Ctx* c, const double* d_x, double* d_y, double* d_pa
         else SPMV_LAUNCH_NT(DM_, WPS_, false);          \
     } while (0)
     const int wps = c->spmv_wps;
-    // storage order, single launch over all slices: the footprint product where its arrays exist and fit the LDS
-    if (pos_space && !slice_list && c->opt_spmv_fp) {
-        int rc = ensure_footprint(c);
-        if (rc) return rc;
-        const size_t lds = (size_t)(BS / 64) * c->fp_cap * c->dm * sizeof(double);
-        if (c->fp_cap > 0 && lds <= (size_t)60 * 1024) {
-#define SPMV_FP_ARGS                                                                                            \
-    c->nslices * SLICE, xr, (const int32_t*)c->d_slice_len, (const int64_t*)c->d_slice_off, (const uint16_t*)c->d_lcol,  \
-        (const int32_t*)c->d_fp_ptr, (const int32_t*)c->d_fp, (const double*)c->d_Kvals, d_x, d_y, d_partials, done,     \
-        (int32_t)c->spmv_keep_permille, c->nn, c->fp_cap, (int32_t)(c->spmv_rot == 64 ? 19 : c->spmv_rot), spmv_perm, c->spmv_perm_rounds
-#define SPMV_FP_LAUNCH_NT(DM_, WPS_, NT_)                                                                        \
-    do {                                                                                                        \
-        if (lds > 48 * 1024)                                                                                    \
-            FEMCY_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_spmv_fp<DM_, WPS_, NT_>),            \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));               \
-        if (ev)                                                                                                 \
-            hipExtLaunchKernelGGL((k_spmv_fp<DM_, WPS_, NT_>), dim3(grid), dim3(BS), lds, c->stream, ea, eb, 0, SPMV_FP_ARGS); \
-        else                                                                                                    \
-            hipLaunchKernelGGL((k_spmv_fp<DM_, WPS_, NT_>), dim3(grid), dim3(BS), lds, c->stream, SPMV_FP_ARGS); \
-    } while (0)
-#define SPMV_FP_LAUNCH(DM_, WPS_)                              \
-    do {                                                       \
-        if (c->spmv_nt) SPMV_FP_LAUNCH_NT(DM_, WPS_, true);    \
-        else SPMV_FP_LAUNCH_NT(DM_, WPS_, false);              \
-    } while (0)
-            if (c->dm == 3) {
-                if (wps == 1) SPMV_FP_LAUNCH(3, 1); else if (wps == 2) SPMV_FP_LAUNCH(3, 2); else SPMV_FP_LAUNCH(3, 4);
-            } else {
-                if (wps == 1) SPMV_FP_LAUNCH(2, 1); else if (wps == 2) SPMV_FP_LAUNCH(2, 2); else SPMV_FP_LAUNCH(2, 4);
-            }
-#undef SPMV_FP_LAUNCH
-#undef SPMV_FP_LAUNCH_NT
-#undef SPMV_FP_ARGS
-            FEMCY_HIP(hipGetLastError());
-            if (nblocks_out) *nblocks_out = grid;
-            return FEMCY_OK;
-        }
-    }
     if (c->dm == 3) {
         if (wps == 1) SPMV_LAUNCH(3, 1);
         else if (wps == 2) SPMV_LAUNCH(3, 2);
@@ -1660,30 +1380,6 @@ int pcg_solve(Ctx* c, const double* d_b, double* d_x, double eps, int32_t maxit,
     int64_t emax = 1;
     for (int k = 0; k < NXCD; ++k) emax = std::max<int64_t>(emax, er.start[k + 1] - er.start[k]);
     const int g = NXCD * (int)std::max<int64_t>(1, std::min<int64_t>((emax + BS - 1) / BS, std::max(1, c->ew_cap / NXCD)));
-    // one vector kernel per iteration (k_update_fused) when every thread can keep its share in registers (<= 8 double2)
-    // and all workgroups are resident; otherwise -- and across ranks, where a collective sits between the two -- the
-    // two kernels
-    int fused_g = 0, fused_u = 0;
-    if (!multi && c->opt_fused_update && !c->fused_failed) {
-        const int64_t bpx_min = (emax + (int64_t)BS * 8 - 1) / ((int64_t)BS * 8);
-        const int64_t bpx = std::max<int64_t>(bpx_min, g / NXCD);
-        if (bpx <= 128) {
-            const int64_t per = (emax + bpx * BS - 1) / (bpx * BS);
-            fused_u = per <= 1 ? 1 : (per <= 2 ? 2 : (per <= 4 ? 4 : 8));
-            fused_g = (int)bpx * NXCD;
-            const void* fn = nullptr;
-#define FEMCY_FUSED_FN(NT_) (fused_u == 1 ? (const void*)&k_update_fused<NT_, 1> : fused_u == 2 ? (const void*)&k_update_fused<NT_, 2> \
-                             : fused_u == 4 ? (const void*)&k_update_fused<NT_, 4> : (const void*)&k_update_fused<NT_, 8>)
-            fn = c->vec_nt ? FEMCY_FUSED_FN(true) : FEMCY_FUSED_FN(false);
-#undef FEMCY_FUSED_FN
-            if (!coresident(c, fn, BS, 0, fused_g)) fused_g = 0;
-        }
-        if (fused_g && !c->d_fused) {
-            FEMCY_HIP(dmalloc(&c->d_fused, 1024 * 2 * 16));
-            FEMCY_HIP(hipMemsetAsync(c->d_fused, 0, 1024 * 2 * 16, c->stream));
-        }
-    }
-    const bool fused = fused_g > 0;
     hipLaunchKernelGGL(k_pcg_init, dim3(g), dim3(BS), 0, c->stream, n2, (const double2*)vb, (const double2*)c->d_M,
                        (double2*)vx, (double2*)c->d_r, (double2*)c->d_d, (const uint8_t*)(multi ? c->d_owner : nullptr),
                        c->d_part2);
@@ -1743,21 +1439,6 @@ int pcg_solve(Ctx* c, const double* d_b, double* d_x, double eps, int32_t maxit,
                                    c->niface_local, c->d_iface_dof, c->d_iface_slot, c->d_commbuf, c->d_Ad);
             dAd_red = slot;
         }
-        if (fused) {
-#define FEMCY_FU(NT_, U_)                                                                                          \
-    hipLaunchKernelGGL((k_update_fused<NT_, U_>), dim3(fused_g), dim3(BS), 0, c->stream, er, np1, c->d_part1, c->d_state,  \
-                       (const double2*)c->d_Ad, (const double2*)c->d_M, (double2*)c->d_r, (double2*)c->d_d, (double2*)vx, \
-                       c->d_fused, c->barrier_spin_limit)
-#define FEMCY_FU_U(NT_)                                                                                            \
-    do {                                                                                                           \
-        if (fused_u == 1) FEMCY_FU(NT_, 1); else if (fused_u == 2) FEMCY_FU(NT_, 2);                               \
-        else if (fused_u == 4) FEMCY_FU(NT_, 4); else FEMCY_FU(NT_, 8);                                            \
-    } while (0)
-            if (c->vec_nt) FEMCY_FU_U(true); else FEMCY_FU_U(false);
-#undef FEMCY_FU_U
-#undef FEMCY_FU
-            return FEMCY_OK;
-        }
 #define FEMCY_XR(NT_, MU_)                                                                                         \
     hipLaunchKernelGGL((k_update_xr<NT_, MU_>), dim3(g), dim3(BS), 0, c->stream, er, np1, c->d_part1, dAd_red,       \
                        c->d_state, (const double2*)c->d_Ad, (const double2*)c->d_M, (double2*)c->d_r,                \
@@ -1785,7 +1466,7 @@ int pcg_solve(Ctx* c, const double* d_b, double* d_x, double eps, int32_t maxit,
     // iteration SLOWER at 548 535 DOF (GPU-bound), so "auto" (1) only uses it below 2e5 DOF; 2 forces it on
     const bool want_graph = c->opt_graph == 2 || (c->opt_graph == 1 && c->n < 200000);
     const bool use_graph = want_graph && !multi && !c->opt_timing && maxit >= P;
-    if (use_graph && (!c->pcg_graph || c->pcg_graph_x != vx || c->pcg_graph_iters != P || c->pcg_graph_g != g + 4096 * fused_g ||
+    if (use_graph && (!c->pcg_graph || c->pcg_graph_x != vx || c->pcg_graph_iters != P || c->pcg_graph_g != g ||
                       c->pcg_graph_np1 != c->spmv_grid)) {
         pcg_graph_reset(c);
         hipGraph_t graph = nullptr;
@@ -1802,7 +1483,7 @@ int pcg_solve(Ctx* c, const double* d_b, double* d_x, double eps, int32_t maxit,
         (void)hipGraphDestroy(graph);
         c->pcg_graph_x = vx;
         c->pcg_graph_iters = P;
-        c->pcg_graph_g = g + 4096 * fused_g;
+        c->pcg_graph_g = g;
         c->pcg_graph_np1 = c->spmv_grid;
     }
 
@@ -1823,15 +1504,6 @@ int pcg_solve(Ctx* c, const double* d_b, double* d_x, double eps, int32_t maxit,
         FEMCY_HIP(hipMemcpyAsync(c->h_state, c->d_state, sizeof(PcgState), hipMemcpyDeviceToHost, c->stream));
         FEMCY_HIP(hipStreamSynchronize(c->stream));
         if (c->h_state->done || it >= maxit) finished = true;
-    }
-    if (fused && c->h_state->done == 3) {
-        // the in-kernel exchange of k_update_fused timed out (a workgroup was not resident: shared GPU, CU mask): the
-        // solve is redone with the two vector kernels, which this context keeps from now on
-        c->fused_failed = true;
-        c->timing.barrier_timeouts++;
-        pcg_graph_reset(c);
-        timing_end(c, th);
-        return pcg_solve(c, d_b, d_x, eps, maxit, iters, r0, rmax);
     }
     if (pos) {
         const int pg = (npos + BS - 1) / BS;

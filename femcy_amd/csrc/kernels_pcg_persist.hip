@@ -275,12 +275,9 @@ __global__ void __launch_bounds__(PBS) k_pcg_persist(PersistPcg a) {
     constexpr int DD = DM * DM, NP = DD / 2;
     constexpr bool NT = (VAR & V_NT) != 0, A2A = (VAR & V_A2A) != 0, WIDE = (VAR & V_WIDE) != 0;
     constexpr bool INB = (VAR & V_INBAND) != 0;
-#ifndef FEMCY_PERSIST_OWN_DIAG
-#define FEMCY_PERSIST_OWN_DIAG 1
-#endif
     // block row 0 of a slice is the diagonal block: its column is the lane's own d, which is in registers -- no gather
     // for it (round 4: 27.30 -> 27.07 us per iteration at 1 M C3D4, bit-identical iterates; profiles/r04_persist_inband.txt)
-    constexpr bool OWN_DIAG = INB || (FEMCY_PERSIST_OWN_DIAG && WIDE);
+    constexpr bool OWN_DIAG = WIDE;                              // (INB implies WIDE, below)
     static_assert(!INB || (WIDE && A2A), "in-band validity of d is built on the storage-order, tagged-granule form");
     constexpr int NDB = INB ? 3 : 2;                             // buffers of the published d
     extern __shared__ __attribute__((aligned(16))) char lds_persist[];
@@ -466,13 +463,10 @@ __global__ void __launch_bounds__(PBS) k_pcg_persist(PersistPcg a) {
     // work skipping).  Tagged-granule form: wave 0 sweeps the granules during those windows, and VMEM returns in order
     // -- a prefetch of its own would sit in front of every sweep -- so wave 0 does not prefetch (the host hands it
     // one batch less of streamed rows instead)
-#ifndef FEMCY_INB_PREFETCH
-#define FEMCY_INB_PREFETCH 1
-#endif
     // (seven slices of 3 x 3 blocks per wave: 210 registers of vectors -- no prefetch buffer, its 76 registers are what
     // the shape does not have)
     constexpr bool PREFETCH = !(DM == 3 && SPW >= 7);
-    const int npf = (!PREFETCH || (a.dbg & 16) || (A2A && wave == 0) || (INB && !FEMCY_INB_PREFETCH)) ? 0 : max(0, min(CH, Ls[0] - JE(0)));
+    const int npf = (!PREFETCH || (a.dbg & 16) || (A2A && wave == 0)) ? 0 : max(0, min(CH, Ls[0] - JE(0)));
     int32_t pcol[CH];
     double pe[CH][DD];
     const int32_t jpf = npf > 0 ? JE(0) : 0;                               // (npf = 0: row 0's column, unused)
@@ -719,61 +713,6 @@ __global__ void __launch_bounds__(PBS) k_pcg_persist(PersistPcg a) {
                                 acc[t][r] += lvals[((q + u) * DD + r * DM + cc) * 64 + lane] * xg[u][cc];
                     }
             }
-#ifdef FEMCY_PERSIST_PIPE
-            // (round 5 experiment, not in the shipped build) software-pipelined stream: the loads of batch k + 1 are
-            // issued behind the gathers of batch k and travel while batch k is multiplied -- two batches of values in
-            // registers (A / B ping-pong), for matrices that stream from HBM rather than from the Infinity Cache
-            if (j < L && !PDBG(a, 1)) {
-                int32_t colA[CH], colB[CH];
-                double eA[CH][DD], eB[CH][DD];
-                int nbA = min(CH, L - j), nbB = 0;
-                load_rows(bcp, vp, vs, j, nbA, JE(t) + a.l2_rows, colA, eA);
-                for (;;) {
-                    {
-                        double xg[CH][DM];
-#pragma unroll
-                        for (int u = 0; u < CH; ++u) gather_d(colA[u], poff, xg[u]);
-                        __builtin_amdgcn_sched_barrier(0);
-                        const int32_t jn = j + nbA;
-                        nbB = max(0, min(CH, L - jn));
-                        load_rows(bcp, vp, vs, nbB > 0 ? jn : j, nbB, JE(t) + a.l2_rows, colB, eB);
-                        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int u = 0; u < CH; ++u)
-                            if (u < nbA) {
-#pragma unroll
-                                for (int r = 0; r < DM; ++r)
-#pragma unroll
-                                    for (int cc = 0; cc < DM; ++cc) acc[t][r] += eA[u][r * DM + cc] * xg[u][cc];
-                            }
-                        j = jn;
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                    if (nbB == 0) break;
-                    {
-                        double xg[CH][DM];
-#pragma unroll
-                        for (int u = 0; u < CH; ++u) gather_d(colB[u], poff, xg[u]);
-                        __builtin_amdgcn_sched_barrier(0);
-                        const int32_t jn = j + nbB;
-                        nbA = max(0, min(CH, L - jn));
-                        load_rows(bcp, vp, vs, nbA > 0 ? jn : j, nbA, JE(t) + a.l2_rows, colA, eA);
-                        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int u = 0; u < CH; ++u)
-                            if (u < nbB) {
-#pragma unroll
-                                for (int r = 0; r < DM; ++r)
-#pragma unroll
-                                    for (int cc = 0; cc < DM; ++cc) acc[t][r] += eB[u][r * DM + cc] * xg[u][cc];
-                            }
-                        j = jn;
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                    if (nbA == 0) break;
-                }
-            }
-#endif
             // streamed block rows, CH at a time: columns, then the values, then the gathers, then the multiplies
             while (j < L && !PDBG(a, 1)) {
                 const int nb = min(CH, L - j);
@@ -1181,9 +1120,7 @@ int ensure_bcolp(Ctx* c) {
 
 // default variant of the persistent kernel (FEMCY_TUNE_PERSIST_VARIANT = -1), chosen by the round-3 measurements
 // 
-#ifndef FEMCY_PERSIST_DEFAULT_VARIANT
-#define FEMCY_PERSIST_DEFAULT_VARIANT 6
-#endif
+constexpr int FEMCY_PERSIST_DEFAULT_VARIANT = 6;
 
 constexpr int PERSIST_MULTI_RETRY = 16;   // RCCL-loop solves after a cross-rank time-out before the one-launch path is tried again
 
@@ -1207,7 +1144,6 @@ bool persist_shape(const Ctx* c, PersistShape* out) {
     if (c->dm == 3) {
         if (per_wave > 7) return false;
         sh.SPW = per_wave > 3 ? per_wave : 3;
-        if (const char* e = getenv("FEMCY_DEBUG_FORCE_SPW")) sh.SPW = std::min(7, std::max(sh.SPW, atoi(e)));
         sh.rj = sh.SPW == 3 ? c->opt_persist_rj : (!on ? 0 : (sh.SPW == 4 ? 3 : (sh.SPW == 7 ? 0 : 1)));
     } else {
         if (per_wave > 8) return false;
@@ -1397,15 +1333,9 @@ int pcg_persist_solve(Ctx* c, const double* d_b, double* d_x, double eps, int32_
             else if (SPW == 6) { FEMCY_PERSIST_M(2, 6, 3, FEMCY_PERSIST_DEFAULT_VARIANT, true); }
             else { FEMCY_PERSIST_M(2, 8, 2, FEMCY_PERSIST_DEFAULT_VARIANT, true); }
         } else
-#ifdef FEMCY_PERSIST_ONLY_334     // compile-time experiments: one shape only
-        if (c->dm == 3 && SPW == 3 && c->opt_persist_rj == 4) { FEMCY_PERSIST_V(3, 3, 4) } else return FEMCY_OK;
-#else
         if (c->dm == 3 && SPW == 3) {
             if (c->opt_persist_rj == 5) { FEMCY_PERSIST_V(3, 3, 5) }
             else if (c->opt_persist_rj == 4) { FEMCY_PERSIST_V(3, 3, 4) }
-#ifdef FEMCY_PERSIST_PIPE
-            else if (c->opt_persist_rj == 2) { FEMCY_PERSIST_V(3, 3, 2) }
-#endif
             else { FEMCY_PERSIST_V(3, 3, 0) }
         } else if (c->dm == 3 && SPW == 4) {
             if (c->opt_persist_rj) { FEMCY_PERSIST_V(3, 4, 3) } else { FEMCY_PERSIST_V(3, 4, 0) }
@@ -1430,7 +1360,6 @@ int pcg_persist_solve(Ctx* c, const double* d_b, double* d_x, double eps, int32_
         } else {
             if (c->opt_persist_rj) { FEMCY_PERSIST_V(2, 8, 2) } else { FEMCY_PERSIST_V(2, 8, 0) }
         }
-#endif
 #undef FEMCY_PERSIST_V
 #undef FEMCY_PERSIST
 #undef FEMCY_PERSIST_M

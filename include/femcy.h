@@ -121,18 +121,8 @@ enum femcy_option {
                                    storage order (b permuted once, x permuted back at the end): lanes of a wavefront are
                                    rows of one length class in ascending order, so their gathers of d touch neighbouring
                                    addresses; 0 = node order (what multi-rank runs keep)                          */
-    FEMCY_OPT_PCG_FUSED_UPDATE = 15, /* 0 (default) = two vector kernels per iteration of the three-launch PCG; 1 = ONE (r update,
-                                   the grid-wide (r.M.r, max|r|) as an in-kernel exchange of tagged granules, d and x
-                                   update; single rank, <= 8 double2 per thread at <= 1024 resident workgroups; a
-                                   time-out of the exchange falls back to the two kernels for good).  Built and measured
-                                   in round 4: the exchange (2.6-3.3 us) costs more than the kernel boundary it removes
-                                   (1.5 us) -- 80.5 -> 82.0 us per iteration on the C3D10 plate, 42.3 -> 43.8 at 1 M C3D4
-                                   (profiles/r04_ab_fused_update.txt) -- so it stays an option                    */
-    FEMCY_OPT_SPMV_FOOTPRINT = 16, /* storage-order product of the three-launch PCG: 1 = every wave first stages the x entries
-                                   of its footprint (the sorted distinct positions its block rows refer to) in LDS with
-                                   coalesced loads and gathers from there through 16-bit local columns; 0 = gathers from
-                                   global memory per block (default: measured 0 ... 6 % faster than the footprint form,
-                                   profiles/r04_ab_footprint_product.txt)                                          */
+    /* 15: retired (PCG_FUSED_UPDATE) */
+    /* 16: retired (SPMV_FOOTPRINT) */
     FEMCY_OPT_DIRECT_MAX_BYTES = 17, /* femcy_direct_solve: largest band (bytes) it may allocate (default 48 GiB); a system
                                    whose band after reverse Cuthill-McKee is larger is refused with FEMCY_ENOMEM    */
     FEMCY_OPT_NODE_ORDER = 14,  /* internal row order of the matrix, set before femcy_build_pattern; vectors handed

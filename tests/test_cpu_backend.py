@@ -62,6 +62,22 @@ def test_cpu_backend_is_explicit_opt_in_only():
             del os.environ["FEMCY_BACKEND"]
 
 
+def test_cpu_backend_refuses_the_retired_pcg_options():
+    """options 15 (PCG_FUSED_UPDATE) and 16 (SPMV_FOOTPRINT) are retired on both backends: the host library no longer
+    lists them among its accepted no-ops; a live device-only knob is still accepted without effect"""
+    from femcy_amd import backend as be
+    ctx = be.Context(0, backend="cpu")
+    try:
+        for option in (15, 16):
+            for v in (0, 1):
+                with pytest.raises(be.FemcyError, match="unknown option"):
+                    ctx.set_option(option, v)
+        ctx.set_option(be.OPT_PCG_STORAGE_ORDER, 0)
+        ctx.set_option(be.OPT_PCG_STORAGE_ORDER, 1)
+    finally:
+        ctx.close()
+
+
 def test_cpu_context_in_process_solves_a_deck_system():
     """Context(backend='cpu') next to the default backend in one process: K, f and a PCG solve on the C3D4 twist deck
     against the oracle; results do not depend on the OpenMP thread count (fixed-chunk reductions, owner-computes rows)"""

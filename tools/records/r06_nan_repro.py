@@ -60,7 +60,6 @@ except be.FemcyError as e:
     attempt_with("keep permille 1000 (110)", 110, 1000, -1)
     attempt_with("graph off", be.OPT_PCG_GRAPH, 0, 1)
     attempt_with("poll 1", be.OPT_PCG_POLL, 1, 32)
-    attempt_with("fused update", be.OPT_PCG_FUSED_UPDATE, 1, 0)
     for attempt in range(2):
         try:
             print("retry", attempt, ctx.pcg(be.VEC_RESIDUAL, be.VEC_X, eps=0.0, maxit=20), flush=True)
