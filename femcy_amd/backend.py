@@ -69,7 +69,8 @@ EXPORTS = [
     "femcy_vec_sub", "femcy_vec_axpy", "femcy_vec_scale", "femcy_vec_norm", "femcy_vec_absmax",
     "femcy_assemble_K", "femcy_internal_force", "femcy_residual_and_K", "femcy_apply_dirichlet_linear", "femcy_apply_dirichlet_newton",
     "femcy_dofset_create", "femcy_dofset_dirichlet_newton", "femcy_dofset_dirichlet_linear", "femcy_dofset_fill",
-    "femcy_dofset_scatter", "femcy_loadset_create", "femcy_loadset_neumann", "femcy_loadset_neumann_add", "femcy_spmv", "femcy_pcg", "femcy_compute_strain_stress", "femcy_elastic_energy", "femcy_extrapolate",
+    "femcy_dofset_scatter", "femcy_dofset_add", "femcy_bodyload_create", "femcy_bodyload_weights", "femcy_bodyload_apply",
+    "femcy_loadset_create", "femcy_loadset_neumann", "femcy_loadset_neumann_add", "femcy_spmv", "femcy_pcg", "femcy_compute_strain_stress", "femcy_elastic_energy", "femcy_extrapolate",
     "femcy_get_K_ell", "femcy_get_K_bsr", "femcy_get_gp_field", "femcy_timing",
     "femcy_timing_reset", "femcy_comm_unique_id", "femcy_comm_local_id", "femcy_comm_init", "femcy_comm_info", "femcy_comm_set_neighbours",
     "femcy_comm_tune", "femcy_iface_sum",
@@ -159,7 +160,9 @@ def _bind(lib, kind):
         "femcy_apply_dirichlet_linear": [p, p, p, i32, cint], "femcy_apply_dirichlet_newton": [p, p, i32, cint],
         "femcy_dofset_create": [p, p, i32, C.POINTER(i32)], "femcy_dofset_dirichlet_newton": [p, i32, cint],
         "femcy_dofset_dirichlet_linear": [p, i32, f64, cint], "femcy_dofset_fill": [p, i32, cint, f64],
-        "femcy_dofset_scatter": [p, i32, cint, p],
+        "femcy_dofset_scatter": [p, i32, cint, p], "femcy_dofset_add": [p, i32, cint, f64],
+        "femcy_bodyload_create": [p, p, i32, p, C.POINTER(i32)], "femcy_bodyload_weights": [p, i32, p],
+        "femcy_bodyload_apply": [p, i32, p, cint, i32],
         "femcy_loadset_create": [p, i32, i32, i32, p, p, p, p, p, i32, p, p, C.POINTER(i32)],
         "femcy_loadset_neumann": [p, i32, f64, p, cint],
         "femcy_loadset_neumann_add": [p, i32, f64, p, cint],
@@ -421,6 +424,34 @@ class Context:
 
     def dofset_scatter(self, ds: int, vec_id: int, vals):
         self._call("femcy_dofset_scatter", int(ds), int(vec_id), _ptr(_f64(vals).ravel()))
+
+    def dofset_add(self, ds: int, vec_id: int, value: float):
+        """vec[dofs of the set] += value (*Cload)."""
+        self._call("femcy_dofset_add", int(ds), int(vec_id), float(value))
+
+    # device-resident body loads (*Dload GRAV / BX / BY / BZ)
+    def bodyload(self, ELE, elems=None) -> int:
+        """nodal weights m_a = sum N_a |det J| w over `elems` (None: every element) on the undeformed geometry."""
+        N = _f64(ELE.tables()["N"])
+        if N.shape != (self.nGP, self.npe):
+            raise FemcyError(f"shape-function table must be {self.nGP} x {self.npe}, got {N.shape}")
+        sel = None if elems is None else _i32(elems).ravel()
+        out = C.c_int32()
+        self._call("femcy_bodyload_create", _ptr(N), 0 if sel is None else sel.size,
+                   None if sel is None else (_ptr(sel) if sel.size else _ptr(np.zeros(1, np.int32))), C.byref(out))
+        return out.value
+
+    def bodyload_weights(self, bl: int) -> np.ndarray:
+        out = np.empty(self.nn, dtype=np.float64)
+        self._call("femcy_bodyload_weights", int(bl), _ptr(out))
+        return out
+
+    def bodyload_apply(self, bl: int, b, rhs_vec: int = VEC_RHS, add: bool = False):
+        """rhs = m_a * b (add: rhs += it); b = force per unit volume, dm components."""
+        b = _f64(b).ravel()
+        if b.size < self.dm:
+            raise FemcyError(f"body force needs {self.dm} components")
+        self._call("femcy_bodyload_apply", int(bl), _ptr(b), int(rhs_vec), 1 if add else 0)
 
     def spmv(self, x_vec: int, y_vec: int):
         self._call("femcy_spmv", int(x_vec), int(y_vec))

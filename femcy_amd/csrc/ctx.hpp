@@ -302,6 +302,10 @@ struct Ctx {
     };
     std::vector<LoadSet> loadsets;
 
+    // ---- device-resident body loads (femcy_bodyload_*): the nodal weights m_a of one element selection
+    struct BodyLoad { double* d_m; int32_t nsel; };
+    std::vector<BodyLoad> bodyloads;
+
     // ---- options / timing
     int opt_assembly = FEMCY_ASM_AUTO;
     int asm_used = -1;                // the mode the last assembly ran, AUTO resolved (femcy_get_assembly_used)
@@ -393,6 +397,8 @@ int launch_energy_sum(Ctx* c, double* total);
 int launch_assemble(Ctx* c);
 int launch_nodal_force(Ctx* c, double* d_f);
 int launch_neumann(Ctx* c, const Ctx::LoadSet& ls, double traction, bool along_normal, double* d_rhs, bool add);
+int launch_body_weights(Ctx* c, const double* d_N, const uint8_t* d_mask_or_null, double* d_we, double* d_m);
+int launch_body_apply(Ctx* c, const double* d_m, const double* b, bool add, double* d_f);
 // pos_space: x and y are in STORAGE order (entry p * dm + c belongs to the node at storage position p = slice * 64 + lane;
 // the padding lanes of the last slice hold zeros) -- the form the three-kernel PCG runs in since round 4
 int launch_spmv(Ctx* c, const double* d_x, double* d_y, double* d_partials, int* nblocks_out, bool pos_space = false);
@@ -430,6 +436,7 @@ int vec_sumsq(Ctx* c, const double* d, double* out);
 int vec_absmax(Ctx* c, const double* d, double* out);
 int vec_scatter(Ctx* c, double* d, const int32_t* d_idx, const double* d_vals, int32_t k);
 int vec_scatter_const(Ctx* c, double* d, const int32_t* d_idx, double val, int32_t k);
+int vec_scatter_add(Ctx* c, double* d, const int32_t* d_idx, double val, int32_t k);
 int ensure_scratch(Ctx* c, int64_t k);
 // comm.cpp
 int comm_unique_id(void* id128);

@@ -588,4 +588,31 @@ FEMCY_HD void neumann_facet(int32_t npe, int32_t nfn, int32_t nip, const double*
     }
 }
 
+// one element of a body load (*Dload GRAV / BX / BY / BZ): we[a] = sum_g N_a(xi_g) |det J_g| w_g on the UNDEFORMED
+// coordinates X (dead load on the reference volume).  The consistent nodal load of a uniform force b per unit volume
+// is we[a] * b.  dN[g][a][:] and N[g][a] are the plugin's tables at the Gauss points.
+template <int NPE, int DM>
+FEMCY_HD void body_weights_element(const double (&X)[NPE][DM], int32_t nGP, const double* __restrict__ dN,
+                                   const double* __restrict__ N, const double* __restrict__ w, double (&we)[NPE]) {
+#pragma unroll
+    for (int a = 0; a < NPE; ++a) we[a] = 0.0;
+    for (int32_t g = 0; g < nGP; ++g) {
+        const double* __restrict__ dNg = dN + g * NPE * DM;
+        const double* __restrict__ Ng = N + g * NPE;
+        double J[DM][DM], inv[DM][DM];
+#pragma unroll
+        for (int i = 0; i < DM; ++i)
+#pragma unroll
+            for (int j = 0; j < DM; ++j) {
+                double acc = 0.0;
+#pragma unroll
+                for (int a = 0; a < NPE; ++a) acc += X[a][i] * dNg[a * DM + j];
+                J[i][j] = acc;
+            }
+        const double vg = fabs(det_inv<DM>(J, inv)) * w[g];
+#pragma unroll
+        for (int a = 0; a < NPE; ++a) we[a] += Ng[a] * vg;
+    }
+}
+
 }  // namespace femcy

@@ -286,6 +286,8 @@ int femcy_ctx_destroy(femcy_ctx* ctx) {
         for (void* q : ptrs)
             if (q) (void)hipFree(q);
     }
+    for (auto& bl : c->bodyloads)
+        if (bl.d_m) (void)hipFree(bl.d_m);
     for (auto& p : c->ev_pool) {
         (void)hipEventDestroy(p.a);
         (void)hipEventDestroy(p.b);
@@ -509,6 +511,9 @@ int femcy_set_mesh(femcy_ctx* ctx, int32_t nn, int32_t dm, const double* nodes, 
     c->dofsets.clear();
     for (auto& ls : c->loadsets) loadset_free(ls);
     c->loadsets.clear();
+    for (auto& bl : c->bodyloads)
+        if (bl.d_m) (void)hipFree(bl.d_m);
+    c->bodyloads.clear();
     c->have_material = false;
     c->nn = nn; c->dm = dm; c->ne = ne; c->npe = npe;
     c->n = (int64_t)nn * dm;
@@ -871,6 +876,13 @@ int femcy_dofset_fill(femcy_ctx* ctx, int32_t id, int vec, double value) {
     return vec_scatter_const(c, c->d_vec[vec], ds.d_dofs, value, ds.k);
 }
 
+int femcy_dofset_add(femcy_ctx* ctx, int32_t id, int vec, double value) {
+    CTX_OR_FAIL(ctx);
+    VEC_OR_FAIL(vec);
+    DOFSET_OR_FAIL(id);
+    return vec_scatter_add(c, c->d_vec[vec], ds.d_dofs, value, ds.k);
+}
+
 int femcy_dofset_scatter(femcy_ctx* ctx, int32_t id, int vec, const double* vals) {
     CTX_OR_FAIL(ctx);
     VEC_OR_FAIL(vec);
@@ -1007,6 +1019,81 @@ int femcy_loadset_neumann(femcy_ctx* ctx, int32_t id, double traction, const dou
 int femcy_loadset_neumann_add(femcy_ctx* ctx, int32_t id, double traction, const double* direction, int rhs_vec) {
     CTX_OR_FAIL(ctx);
     return loadset_neumann(c, id, traction, direction, rhs_vec, true);
+}
+
+// ----------------------------------------------------------------------------------- body loads
+int femcy_bodyload_create(femcy_ctx* ctx, const double* N, int32_t nsel, const int32_t* sel_elems, int32_t* id_out) {
+    CTX_OR_FAIL(ctx);
+    FEMCY_REQUIRE(c->have_mesh && c->have_element && c->have_pattern,
+                  "femcy_bodyload_create needs the mesh, the element tables and the pattern (mesh=%d element=%d pattern=%d)",
+                  (int)c->have_mesh, (int)c->have_element, (int)c->have_pattern);
+    FEMCY_REQUIRE(N && id_out, "null shape-function table or id_out");
+    FEMCY_REQUIRE(sel_elems ? nsel >= 0 : true, "negative selection size %d", nsel);
+    std::vector<uint8_t> mask;
+    if (sel_elems) {
+        mask.assign((size_t)c->ne, 0);
+        for (int32_t i = 0; i < nsel; ++i) {
+            FEMCY_REQUIRE(sel_elems[i] >= 0 && sel_elems[i] < c->ne, "body load: element %d out of range", sel_elems[i]);
+            FEMCY_REQUIRE(!mask[sel_elems[i]], "body load: element %d selected twice", sel_elems[i]);
+            mask[sel_elems[i]] = 1;
+        }
+    }
+    Ctx::BodyLoad bl{nullptr, sel_elems ? nsel : c->ne};
+    double *d_N = nullptr, *d_we = nullptr;
+    uint8_t* d_mask = nullptr;
+    int rc = to_device(&d_N, N, sizeof(double) * c->nGP * c->npe);
+    if (!rc && sel_elems) rc = to_device(&d_mask, mask.data(), mask.size());
+    if (!rc && dmalloc(&d_we, sizeof(double) * (size_t)c->ne * c->npe) != hipSuccess) rc = FEMCY_ENOMEM;
+    if (!rc && dmalloc(&bl.d_m, sizeof(double) * (size_t)c->nn) != hipSuccess) rc = FEMCY_ENOMEM;
+    if (!rc) rc = launch_body_weights(c, d_N, d_mask, d_we, bl.d_m);
+    // the tables and the element records are scratch of this call: wait for the two kernels, then release them
+    if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) {
+        set_error("body load: the weight kernels failed");
+        rc = FEMCY_EHIP;
+    }
+    for (void* q : {(void*)d_N, (void*)d_we, (void*)d_mask})
+        if (q) (void)hipFree(q);
+    if (rc) {
+        if (bl.d_m) (void)hipFree(bl.d_m);
+        if (rc == FEMCY_ENOMEM) set_error("out of device memory for a body load on %d elements", c->ne);
+        return rc;
+    }
+    c->bodyloads.push_back(bl);
+    *id_out = (int32_t)c->bodyloads.size() - 1;
+    return FEMCY_OK;
+}
+
+#define BODYLOAD_OR_FAIL(id)                                                                        \
+    FEMCY_REQUIRE((id) >= 0 && (size_t)(id) < c->bodyloads.size(), "unknown body load %d", (int)(id)); \
+    const Ctx::BodyLoad& bl = c->bodyloads[(id)]
+
+int femcy_bodyload_weights(femcy_ctx* ctx, int32_t id, double* out) {
+    CTX_OR_FAIL(ctx);
+    BODYLOAD_OR_FAIL(id);
+    FEMCY_REQUIRE(out, "null output");
+    FEMCY_HIP(hipMemcpyAsync(out, bl.d_m, sizeof(double) * c->nn, hipMemcpyDeviceToHost, c->stream));
+    FEMCY_HIP(hipStreamSynchronize(c->stream));
+    return FEMCY_OK;
+}
+
+int femcy_bodyload_apply(femcy_ctx* ctx, int32_t id, const double* b, int rhs_vec, int32_t add) {
+    CTX_OR_FAIL(ctx);
+    VEC_OR_FAIL(rhs_vec);
+    BODYLOAD_OR_FAIL(id);
+    FEMCY_REQUIRE(b, "null force");
+    FEMCY_REQUIRE(!add || !c->comm || rhs_vec != FEMCY_VEC_TMP1, "femcy_bodyload_apply with add on several ranks sums the "
+                  "interface through vector TMP1: it cannot be the right-hand side");
+    double* rhs = c->d_vec[rhs_vec];
+    int rc;
+    if (add && c->comm) {   // multi-rank: only this load is summed over the interface, then added
+        double* tmp = c->d_vec[FEMCY_VEC_TMP1];
+        if ((rc = launch_body_apply(c, bl.d_m, b, false, tmp))) return rc;
+        if ((rc = iface_sum(c, tmp))) return rc;
+        return vec_axpy(c, rhs, rhs, 1.0, tmp);
+    }
+    if ((rc = launch_body_apply(c, bl.d_m, b, add != 0, rhs))) return rc;
+    if (add) return FEMCY_OK;
+    return iface_sum(c, rhs);                  // multi-rank: each rank weighs its own elements
 }
 
 int femcy_spmv(femcy_ctx* ctx, int x_vec, int y_vec) {

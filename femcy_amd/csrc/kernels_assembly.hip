@@ -1501,6 +1501,68 @@ int launch_neumann(Ctx* c, const Ctx::LoadSet& ls, double traction, bool along_n
     return FEMCY_OK;
 }
 
+// ---------------------------------------------------------------------------------- body loads
+// *Dload GRAV / BX / BY / BZ: a uniform force per unit volume.  Its consistent nodal load is m_a * b with the nodal
+// weights m_a = sum over the selected elements and their Gauss points of N_a |det J| w on the undeformed geometry, so
+// the element work is done once per body load (femcy_bodyload_create) and an increment only scales m by b.
+// Element pass in the shape of k_geom: one thread per element, the Gauss-point tables dN / N / w wave-uniform, node rows
+// by load_row, the record we[e][0..NPE) out through the LDS transpose of block_store (a wavefront stores 512 consecutive
+// bytes per instruction).  An element outside the selection (mask[e] == 0) leaves zeros.
+template <int NPE, int DM>
+__global__ void __launch_bounds__(256) k_body_weights(int32_t ne, int32_t nGP, const double* __restrict__ nodes,
+                                                      const int32_t* __restrict__ elems,
+                                                      const double* __restrict__ dN, const double* __restrict__ N,
+                                                      const double* __restrict__ w,
+                                                      const uint8_t* __restrict__ mask_or_null,
+                                                      double* __restrict__ we_out) {
+    __shared__ double stage_lds[257 * NPE];
+    const int32_t e0 = blockIdx.x * blockDim.x;
+    const int nvalid = min(256, ne - e0);
+    const bool valid = (int)threadIdx.x < nvalid;
+    const int32_t e = valid ? e0 + (int32_t)threadIdx.x : ne - 1;      // idle lanes recompute the last element, store nothing
+    double X[NPE][DM], we[NPE];
+#pragma unroll
+    for (int a = 0; a < NPE; ++a) load_row<DM>(nodes + (int64_t)elems[(int64_t)e * NPE + a] * DM, X[a]);
+    body_weights_element<NPE, DM>(X, nGP, dN, N, w, we);
+    if (mask_or_null && !mask_or_null[e]) {
+#pragma unroll
+        for (int a = 0; a < NPE; ++a) we[a] = 0.0;
+    }
+    block_store<NPE>(we_out + (int64_t)e0 * NPE, we, nvalid, stage_lds);
+}
+
+// owner-computes node sum in the style of k_nodal_force: half a wavefront per node, its lanes take the node's incident
+// elements (ne_idx = e*npe + la is the position in we) with stride 32, fixed xor tree, lane 0 stores: no atomics, the
+// same bits on every run
+__global__ void __launch_bounds__(256) k_body_gather(int32_t nn, const int32_t* __restrict__ ne_ptr,
+                                                     const int32_t* __restrict__ ne_idx,
+                                                     const double* __restrict__ we, double* __restrict__ m) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int32_t a = (int32_t)(t >> 5);
+    const int sub = (int)(t & 31);
+    double acc = 0.0;
+    if (a < nn) {
+        const int32_t k1 = ne_ptr[a + 1];
+        for (int32_t k = ne_ptr[a] + sub; k < k1; k += 32) acc += we[ne_idx[k]];
+    }
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 32);
+    if (a < nn && sub == 0) m[a] = acc;
+}
+
+// f[a*dm + i] = m[a] * b[i] (add: f += that); b travels in the kernel arguments.  The product is rounded before the
+// sum (no fused multiply-add), so that adding to a vector gives the bits of the two vectors added by the caller.
+template <int DM>
+__global__ void __launch_bounds__(256) k_body_apply(int64_t n, const double* __restrict__ m, double b0, double b1,
+                                                    double b2, int add, double* __restrict__ f) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int comp = (int)(i % DM);
+    const double b = comp == 0 ? b0 : (comp == 1 ? b1 : b2);
+    const double v = __dmul_rn(m[i / DM], b);
+    f[i] = add ? __dadd_rn(f[i], v) : v;
+}
+
 int launch_extrapolate(Ctx* c, const double* d_E, const double* d_field, int width, int comp, double* d_out) {
     const int64_t total = (int64_t)c->ne * c->npe;
     hipLaunchKernelGGL(k_extrapolate, dim3((int)((total + 255) / 256)), dim3(256), 0, c->stream, (int64_t)c->ne, c->npe,
@@ -1566,6 +1628,51 @@ int launch_geom(Ctx* c, const double* d_u, unsigned what) {
         set_error("no geometry kernel instantiated for npe=%d dm=%d", c->npe, c->dm);
         return FEMCY_ENOKERNEL;
     }
+    FEMCY_HIP(hipGetLastError());
+    return FEMCY_OK;
+}
+
+// nodal weights of a body load: element pass into d_we [ne][npe] (scratch of the caller), node gather into d_m [nn]
+int launch_body_weights(Ctx* c, const double* d_N, const uint8_t* d_mask_or_null, double* d_we, double* d_m) {
+    const int bs = 256, grid = (c->ne + bs - 1) / bs;
+    bool launched = false;
+    size_t th = timing_begin(c, T_GEOM);
+#define BODY_CALL                                                                                                   \
+    hipLaunchKernelGGL((k_body_weights<NPE, DM>), dim3(grid), dim3(bs), 0, c->stream, c->ne, c->nGP, c->d_nodes,    \
+                       c->d_elems, c->d_dN, d_N, c->d_w, d_mask_or_null, d_we)
+    FEMCY_DISPATCH_ELEMENT(3, 2, BODY_CALL)
+    FEMCY_DISPATCH_ELEMENT(4, 2, BODY_CALL)
+    FEMCY_DISPATCH_ELEMENT(6, 2, BODY_CALL)
+    FEMCY_DISPATCH_ELEMENT(8, 2, BODY_CALL)
+    FEMCY_DISPATCH_ELEMENT(4, 3, BODY_CALL)
+    FEMCY_DISPATCH_ELEMENT(10, 3, BODY_CALL)
+    FEMCY_DISPATCH_ELEMENT(8, 3, BODY_CALL)
+    FEMCY_DISPATCH_ELEMENT(6, 3, BODY_CALL)
+#undef BODY_CALL
+    if (launched) {
+        const int64_t threads = (int64_t)c->nn * 32;
+        hipLaunchKernelGGL(k_body_gather, dim3((unsigned)((threads + bs - 1) / bs)), dim3(bs), 0, c->stream, c->nn,
+                           c->d_ne_ptr, c->d_ne_idx, d_we, d_m);
+    }
+    timing_end(c, th);
+    if (!launched) {
+        set_error("no body-load kernel instantiated for npe=%d dm=%d", c->npe, c->dm);
+        return FEMCY_ENOKERNEL;
+    }
+    FEMCY_HIP(hipGetLastError());
+    return FEMCY_OK;
+}
+
+// d_f = m b (add: d_f += m b); b has c->dm entries
+int launch_body_apply(Ctx* c, const double* d_m, const double* b, bool add, double* d_f) {
+    const int bs = 256;
+    const unsigned grid = (unsigned)((c->n + bs - 1) / bs);
+    if (c->dm == 3)
+        hipLaunchKernelGGL((k_body_apply<3>), dim3(grid), dim3(bs), 0, c->stream, c->n, d_m, b[0], b[1], b[2],
+                           add ? 1 : 0, d_f);
+    else
+        hipLaunchKernelGGL((k_body_apply<2>), dim3(grid), dim3(bs), 0, c->stream, c->n, d_m, b[0], b[1], 0.0,
+                           add ? 1 : 0, d_f);
     FEMCY_HIP(hipGetLastError());
     return FEMCY_OK;
 }

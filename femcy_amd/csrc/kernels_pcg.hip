@@ -641,6 +641,11 @@ __global__ void k_scatter_const(int32_t k, const int32_t* __restrict__ idx, doub
     const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < k) v[idx[i]] = val;
 }
+// v[idx] += val (*Cload); the entries of idx are distinct DOFs of one node set
+__global__ void k_scatter_add(int32_t k, const int32_t* __restrict__ idx, double val, double* __restrict__ v) {
+    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < k) v[idx[i]] += val;
+}
 // mode 0: sum of squares, mode 1: max |.|; partials then a single-block finish into *out
 __global__ void __launch_bounds__(BS) k_reduce(int64_t n, const double* __restrict__ v, int mode,
                                                const uint8_t* __restrict__ owner, double* __restrict__ part) {
@@ -696,6 +701,12 @@ int vec_scatter(Ctx* c, double* d, const int32_t* d_idx, const double* d_vals, i
 int vec_scatter_const(Ctx* c, double* d, const int32_t* d_idx, double val, int32_t k) {
     if (k <= 0) return FEMCY_OK;
     hipLaunchKernelGGL(k_scatter_const, dim3((k + BS - 1) / BS), dim3(BS), 0, c->stream, k, d_idx, val, d);
+    FEMCY_HIP(hipGetLastError());
+    return FEMCY_OK;
+}
+int vec_scatter_add(Ctx* c, double* d, const int32_t* d_idx, double val, int32_t k) {
+    if (k <= 0) return FEMCY_OK;
+    hipLaunchKernelGGL(k_scatter_add, dim3((k + BS - 1) / BS), dim3(BS), 0, c->stream, k, d_idx, val, d);
     FEMCY_HIP(hipGetLastError());
     return FEMCY_OK;
 }

@@ -62,6 +62,9 @@ struct LoadSet {
     std::vector<int32_t> ft_nodes, elem, ft, node, ptr, slot;
     std::vector<double> N, dN, normal, weight, contrib;
 };
+struct BodyLoad {
+    std::vector<double> m;   // [nn] nodal weights
+};
 
 }  // namespace
 
@@ -86,6 +89,7 @@ struct femcy_ctx {
     std::vector<double> vec[FEMCY_VEC_COUNT], r, d, M, Ad;
     std::vector<DofSet> dofsets;
     std::vector<LoadSet> loadsets;
+    std::vector<BodyLoad> bodyloads;
     int opt_tangent = 0, opt_timing = 0;
     femcy_timing_t timing{};
     // femcy_direct_solve: band order of the current pattern (built on first use), storage limit
@@ -442,6 +446,7 @@ int femcy_set_mesh(femcy_ctx* ctx, int32_t nn, int32_t dm, const double* nodes, 
                 elems[k], nn);
     c->dofsets.clear();
     c->loadsets.clear();
+    c->bodyloads.clear();
     c->nn = nn; c->dm = dm; c->ne = ne; c->npe = npe;
     c->n = (int64_t)nn * dm;
     c->nodes.assign(nodes, nodes + (size_t)nn * dm);
@@ -813,6 +818,13 @@ int femcy_dofset_fill(femcy_ctx* ctx, int32_t id, int vec, double value) {
     for (int32_t dof : ds.dofs) c->vec[vec][dof] = value;
     return FEMCY_OK;
 }
+int femcy_dofset_add(femcy_ctx* ctx, int32_t id, int vec, double value) {
+    CTX_OR_FAIL(ctx);
+    VEC_OR_FAIL(vec);
+    DOFSET_OR_FAIL(id);
+    for (int32_t dof : ds.dofs) c->vec[vec][dof] += value;
+    return FEMCY_OK;
+}
 int femcy_dofset_scatter(femcy_ctx* ctx, int32_t id, int vec, const double* vals) {
     CTX_OR_FAIL(ctx);
     VEC_OR_FAIL(vec);
@@ -907,6 +919,98 @@ int femcy_loadset_neumann(femcy_ctx* ctx, int32_t id, double traction, const dou
 int femcy_loadset_neumann_add(femcy_ctx* ctx, int32_t id, double traction, const double* direction, int rhs_vec) {
     CTX_OR_FAIL(ctx);
     return loadset_neumann(c, id, traction, direction, rhs_vec, true);
+}
+
+// ----------------------------------------------------------------------------------- body loads
+}  // extern "C"
+namespace {
+// the element pass of the device's k_body_weights (csrc/element_math.hpp: body_weights_element), then the node sums in
+// ascending (element, local node) order
+template <int NPE, int DM>
+void body_weights(femcy_ctx* c, const double* N, const uint8_t* mask, std::vector<double>& m) {
+    std::vector<double> we((size_t)c->ne * NPE, 0.0);
+#pragma omp parallel for schedule(static)
+    for (int32_t e = 0; e < c->ne; ++e) {
+        if (mask && !mask[e]) continue;
+        double X[NPE][DM], w_e[NPE];
+        for (int a = 0; a < NPE; ++a)
+            for (int i = 0; i < DM; ++i) X[a][i] = c->nodes[(int64_t)c->elems[(int64_t)e * NPE + a] * DM + i];
+        body_weights_element<NPE, DM>(X, c->nGP, c->dN.data(), N, c->w.data(), w_e);
+        for (int a = 0; a < NPE; ++a) we[(size_t)e * NPE + a] = w_e[a];
+    }
+    m.assign((size_t)c->nn, 0.0);
+#pragma omp parallel for schedule(static)
+    for (int32_t a = 0; a < c->nn; ++a) {
+        double s = 0.0;
+        for (int32_t k = c->ne_ptr[a]; k < c->ne_ptr[a + 1]; ++k) s += we[c->ne_idx[k]];
+        m[a] = s;
+    }
+}
+}  // namespace
+extern "C" {
+
+int femcy_bodyload_create(femcy_ctx* ctx, const double* N, int32_t nsel, const int32_t* sel_elems, int32_t* id_out) {
+    CTX_OR_FAIL(ctx);
+    REQUIRE(c->have_mesh && c->have_element && c->have_pattern,
+            "femcy_bodyload_create needs the mesh, the element tables and the pattern (mesh=%d element=%d pattern=%d)",
+            (int)c->have_mesh, (int)c->have_element, (int)c->have_pattern);
+    REQUIRE(N && id_out, "null shape-function table or id_out");
+    REQUIRE(sel_elems ? nsel >= 0 : true, "negative selection size %d", nsel);
+    std::vector<uint8_t> mask;
+    if (sel_elems) {
+        mask.assign((size_t)c->ne, 0);
+        for (int32_t i = 0; i < nsel; ++i) {
+            REQUIRE(sel_elems[i] >= 0 && sel_elems[i] < c->ne, "body load: element %d out of range", sel_elems[i]);
+            REQUIRE(!mask[sel_elems[i]], "body load: element %d selected twice", sel_elems[i]);
+            mask[sel_elems[i]] = 1;
+        }
+    }
+    const uint8_t* mk = sel_elems ? mask.data() : nullptr;
+    BodyLoad bl;
+    const int key = c->npe * 10 + c->dm;
+    switch (key) {
+        case 32: body_weights<3, 2>(c, N, mk, bl.m); break;
+        case 42: body_weights<4, 2>(c, N, mk, bl.m); break;
+        case 62: body_weights<6, 2>(c, N, mk, bl.m); break;
+        case 82: body_weights<8, 2>(c, N, mk, bl.m); break;
+        case 43: body_weights<4, 3>(c, N, mk, bl.m); break;
+        case 103: body_weights<10, 3>(c, N, mk, bl.m); break;
+        case 83: body_weights<8, 3>(c, N, mk, bl.m); break;
+        case 63: body_weights<6, 3>(c, N, mk, bl.m); break;
+        default:
+            set_error("no body-load kernel instantiated for npe=%d dm=%d", c->npe, c->dm);
+            return FEMCY_ENOKERNEL;
+    }
+    c->bodyloads.push_back(std::move(bl));
+    *id_out = (int32_t)c->bodyloads.size() - 1;
+    return FEMCY_OK;
+}
+#define BODYLOAD_OR_FAIL(id)                                                                     \
+    REQUIRE((id) >= 0 && (size_t)(id) < c->bodyloads.size(), "unknown body load %d", (int)(id)); \
+    const BodyLoad& bl = c->bodyloads[(id)]
+int femcy_bodyload_weights(femcy_ctx* ctx, int32_t id, double* out) {
+    CTX_OR_FAIL(ctx);
+    BODYLOAD_OR_FAIL(id);
+    REQUIRE(out, "null output");
+    std::copy(bl.m.begin(), bl.m.end(), out);
+    return FEMCY_OK;
+}
+int femcy_bodyload_apply(femcy_ctx* ctx, int32_t id, const double* b, int rhs_vec, int32_t add) {
+    CTX_OR_FAIL(ctx);
+    VEC_OR_FAIL(rhs_vec);
+    BODYLOAD_OR_FAIL(id);
+    REQUIRE(b, "null force");
+    double* rhs = c->vec[rhs_vec].data();
+    const int dm = c->dm;
+    // the product is rounded before it is added (two passes: no fused multiply-add), as on the device
+    std::vector<double> f((size_t)c->n);
+    for (int32_t a = 0; a < c->nn; ++a)
+        for (int i = 0; i < dm; ++i) f[(size_t)a * dm + i] = bl.m[a] * b[i];
+    if (add)
+        for (int64_t i = 0; i < c->n; ++i) rhs[i] += f[i];
+    else
+        std::copy(f.begin(), f.end(), rhs);
+    return FEMCY_OK;
 }
 
 int femcy_spmv(femcy_ctx* ctx, int x_vec, int y_vec) {

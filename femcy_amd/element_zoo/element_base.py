@@ -5,8 +5,8 @@ dshape_dnat, *_pyscope twins, globalNormal, strainMtrx, getMesh, extrapolate and
 attributes dm, gaussPoints, gaussWeights, integPointNum_eachFacet, facet_natural_coos,
 facet_point_weights, facet_natural_normals, inp_surface_num) but is table-driven: a concrete
 element only declares its data and its two shape-function callables; everything else is generic
-numpy here.  What the HIP kernels consume is `tables()`: dN[nGP][npe][dm], w[nGP] and the Voigt
-pattern -- the derivative table depends only on the Gauss point, never on the element
+numpy here.  What the HIP kernels consume is `tables()`: dN[nGP][npe][dm], w[nGP], the Voigt
+pattern and, for body loads, N[nGP][npe] -- the derivative table depends only on the Gauss point, never on the element
 (SURVEY.md 2b), so it is staged once into LDS/constant memory by the device code.
 """
 import abc
@@ -60,7 +60,9 @@ class ElementBase(abc.ABC):
         gp = np.asarray(self.gaussPoints, dtype=np.float64)
         dN = np.ascontiguousarray(np.stack([self.dshape_dnat_pyscope(p) for p in gp]), dtype=np.float64)
         assert dN.shape == (gp.shape[0], self.npe, self.dm)
-        return {"nGP": gp.shape[0], "npe": self.npe, "dm": self.dm, "dN": dN,
+        N = np.ascontiguousarray(np.stack([self.shapeFunc_pyscope(p) for p in gp]), dtype=np.float64)
+        assert N.shape == (gp.shape[0], self.npe)
+        return {"nGP": gp.shape[0], "npe": self.npe, "dm": self.dm, "dN": dN, "N": N,
                 "w": np.ascontiguousarray(self.gaussWeights, dtype=np.float64),
                 "voigt_kind": VOIGT_2D if self.dm == 2 else VOIGT_3D}
 

@@ -51,6 +51,14 @@ class Part:
         pos = np.clip(pos, 0, self.l2g.size - 1)
         return pos[self.l2g[pos] == g]
 
+    def localize_elems(self, global_elem_ids) -> np.ndarray:
+        """global element ids -> local ids (positions in `elem_ids`), dropping elements this rank does not hold."""
+        g = np.asarray(global_elem_ids, dtype=np.int64)
+        order = np.argsort(self.elem_ids, kind="stable")
+        sorted_ids = np.asarray(self.elem_ids, dtype=np.int64)[order]
+        pos = np.clip(np.searchsorted(sorted_ids, g), 0, max(sorted_ids.size - 1, 0))
+        return order[pos[sorted_ids[pos] == g]] if sorted_ids.size else np.zeros(0, dtype=np.int64)
+
     def scatter_global(self, v_global: np.ndarray) -> np.ndarray:
         """restrict a global DOF vector to this rank's nodes."""
         return v_global.reshape(-1, self.dm)[self.l2g].ravel()
@@ -178,7 +186,10 @@ def gather_owned(parts: List[Part], local_vectors: List[np.ndarray], n_global: i
 class LocalDeck:
     """what `System_of_equations.solve` reads from an `InpInfo` (dirichlet_bc_info, neumann_bc_info, time_incs),
     restricted to one rank's sub-mesh: node sets become local node ids (nodes the rank does not hold are
-    dropped), face sets keep the facets of elements this rank holds, as local sorted node tuples."""
+    dropped), face sets keep the facets of elements this rank holds, as local sorted node tuples.  The element set of
+    a body force becomes the local ids of the rank's own elements (None, the whole mesh, stays None; a set the rank
+    holds nothing of becomes empty, so that every rank makes the same collective calls), a *Cload node set is handed
+    over like a Dirichlet node set."""
 
     def __init__(self, inp, part: Part, body):
         self.time_incs = inp.time_incs
@@ -199,3 +210,8 @@ class LocalDeck:
                     if lf in boundary:
                         faces.add(lf)
             self.neumann_bc_info.append(dict(nb, face_set=faces))
+        self.density = getattr(inp, "density", None)
+        self.body_force_info = [dict(bf, ele_set=None if bf["ele_set"] is None else part.localize_elems(bf["ele_set"]))
+                                for bf in getattr(inp, "body_force_info", ())]
+        self.cload_info = [dict(cl, node_set=part.localize_nodes(np.asarray(cl["node_set"])))
+                           for cl in getattr(inp, "cload_info", ())]

@@ -20,6 +20,10 @@ Reference behaviours that are kept on purpose:
   * `*Static` data -> ini_inc, max_time, min_inc, max_inc with ini_inc clipped to max_inc (:333-350);
   * 2-D elements accept only `*Elastic`; C3D* accept `*Elastic` and `*Hyperelastic, neo hooke`
     with D1 = 1/value (:294-316).
+
+Beyond the reference (it reads `*Dsload` only and skips the rest): `*Density` inside a `*Material` block -> density,
+`*Dload` GRAV / BX / BY / BZ -> body_force_info, `*Cload` -> cload_info (read_loads).  Any other `*Dload` type is
+refused by name instead of being skipped.
 """
 import sys
 from typing import Dict, List
@@ -121,6 +125,7 @@ class InpInfo(InpInfoBase):
         self.face_sets = self.read_face_set(file)
         self.dirichlet_bc_info, self.neumann_bc_info = self.get_boundary_condition(file)
         self.materials = self.read_material(file)
+        self.density, self.body_force_info, self.cload_info = self.read_loads(file)
         self.geometric_nonlinear = self.read_geometric_nonlinear(file)
         self.time_incs = self.read_time_inc(file)
 
@@ -182,6 +187,7 @@ class InpInfo(InpInfoBase):
                 labels = labels[keep]
         lut = np.full(int(labels.max()) + 1, -1, dtype=np.int64)
         lut[labels] = np.arange(labels.size)
+        self._label_lut = lut                                 # *Cload with a bare node label goes through the same map
         for eType in eSets:
             eSets[eType] = lut[eSets[eType]]
         return coords, eSets
@@ -266,6 +272,8 @@ class InpInfo(InpInfoBase):
         for line, block in _deck(fileName).keywords():        # *Material, then the type keyword and its data line
             if line[0:9] == "*Material":
                 expect_type = True
+            elif line[0:8].lower() == "*density":             # Abaqus/CAE writes it first; it is not the material type
+                continue
             elif expect_type:
                 expect_type = False
                 data = [t for t in block if t]
@@ -291,6 +299,78 @@ class InpInfo(InpInfoBase):
                 else:
                     raise ValueError("material type {} has not been supported now".format(key))
         return materials
+
+    # -------------------------------------------------------------------- density and loads
+    def read_loads(self, fileName):
+        """-> density (float or None), body_force_info, cload_info.
+        `*Density` (inside a `*Material` block, before or after the material type): the first number of its data.
+        `*Dload` data `[elset], GRAV, g, nx, ny[, nz]` and `[elset], BX|BY|BZ, value` -> {"ele_set": 0-based element
+        index array or None (whole mesh), "force": f64[dm] per unit volume}; GRAV gives density * g * n.
+        `*Cload` data `nset-or-node-label, dof, value` -> {"node_set", "dof", "val"} like a `*Boundary` entry; a bare
+        label is mapped to its position like the connectivity."""
+        dm = int(self.ELE.dm)
+        density, in_material = None, False
+        dloads, cloads = [], []
+        for line, block in _deck(fileName).keywords():
+            key = line.split(",")[0].strip().lower()
+            if key == "*material":
+                in_material = True
+            elif key == "*density" and in_material:
+                data = [t for t in block if t.strip()]
+                if not data:
+                    raise ValueError("*Density without a data line")
+                density = float(data[0].split(",")[0])
+            elif key == "*dload":
+                dloads += [[t.strip() for t in d.split(",")] for d in block if d.strip()]
+            elif key == "*cload":
+                cloads += [[t.strip() for t in d.split(",")] for d in block if d.strip()]
+        body_force_info = []
+        for f in dloads:
+            if len(f) < 3:
+                raise ValueError("*Dload data line needs `[elset], type, value`: {}".format(", ".join(f)))
+            if f[0] and f[0] not in self.ele_sets:
+                raise ValueError("*Dload: unknown element set {}".format(f[0]))
+            ele_set = self.ele_sets[f[0]] if f[0] else None
+            kind = f[1].upper()
+            force = np.zeros(dm)
+            if kind == "GRAV":
+                if density is None:
+                    raise ValueError("*Dload GRAV needs a *Density in the *Material block")
+                n = [float(t) for t in f[3:6] if t]
+                if len(n) < 2:
+                    raise ValueError("*Dload GRAV needs `g, nx, ny[, nz]`: {}".format(", ".join(f)))
+                n = (n + [0.0])[:3]
+                if dm == 2 and n[2] != 0.0:
+                    raise ValueError("*Dload GRAV with a z component on a 2-D mesh")
+                force[:] = density * float(f[2]) * np.asarray(n[:dm])
+            elif kind in ("BX", "BY", "BZ"):
+                comp = "XYZ".index(kind[1])
+                if comp >= dm:
+                    raise ValueError("*Dload BZ on a 2-D mesh")
+                force[comp] = float(f[2])
+            else:
+                raise ValueError("*Dload type {} has not been supported (GRAV, BX, BY, BZ are)".format(f[1]))
+            body_force_info.append({"ele_set": ele_set, "force": force})
+        cload_info = []
+        for f in cloads:
+            if len(f) < 3:
+                raise ValueError("*Cload data line needs `nset-or-node, dof, value`: {}".format(", ".join(f)))
+            if f[0] in self.node_sets:
+                node_set = self.node_sets[f[0]]
+            else:
+                try:
+                    label = int(f[0])
+                except ValueError:
+                    raise ValueError("*Cload: {} is neither a node set nor a node label".format(f[0])) from None
+                lut = self._label_lut
+                if not (0 <= label < lut.size) or lut[label] < 0:
+                    raise ValueError("*Cload: no node with label {}".format(label))
+                node_set = np.array([lut[label]], dtype=np.int64)
+            dof = int(f[1]) - 1
+            if not 0 <= dof < dm:
+                raise ValueError("*Cload: degree of freedom {} on a {}-D mesh".format(f[1], dm))
+            cload_info.append({"node_set": node_set, "dof": dof, "val": float(f[2])})
+        return density, body_force_info, cload_info
 
     # ---------------------------------------------------------------------- step definition
     def read_geometric_nonlinear(self, fileName) -> bool:

@@ -14,7 +14,10 @@ REQUIRED = ("read_node_element",        # -> nodes f64[nn, dm], {abaqus_type: co
 class InpInfoBase:
     #: attributes a reader instance exposes after construction
     ATTRIBUTES = ("nodes", "eSets", "ELE", "node_sets", "ele_sets", "face_sets", "dirichlet_bc_info",
-                  "neumann_bc_info", "materials", "geometric_nonlinear", "time_incs")
+                  "neumann_bc_info", "materials", "geometric_nonlinear", "time_incs",
+                  # loads beyond the reference's *Dsload: *Density (float or None), *Dload GRAV / BX / BY / BZ as
+                  # [{"ele_set": index array or None, "force": f64[dm]}], *Cload as [{"node_set", "dof", "val"}]
+                  "density", "body_force_info", "cload_info")
 
     def __init_subclass__(cls, **kwargs):
         super().__init_subclass__(**kwargs)

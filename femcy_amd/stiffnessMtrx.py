@@ -5,8 +5,10 @@ Same constructor, same public attributes (`dof`, `rhs`, `nodal_force`, `residual
 `du`, `dof_old`, `F`, `cauchy_stress`, `dsdx`, `vol`, `ELE`, `body`, `dm`, ...) and the same
 control flow for the increment / modified-Newton / line-search drivers (`solve`, `advance_inc`),
 but every kernel is a call into libfemcy_hip.so and every field is a handle to HBM-resident data
-(`.to_numpy()` downloads it).  Nothing numerical runs on the CPU except the consistent Neumann
-loads (a per-facet loop in the reference too, stiffnessMtrx.py:369-411) and the user Dirichlet hook.
+(`.to_numpy()` downloads it).  Body forces (`*Dload` GRAV / BX / BY / BZ) and point loads (`*Cload`), which the
+reference does not have, are added to `rhs` after its `*Dsload` loop.  Nothing numerical runs on the CPU except
+the consistent Neumann loads (a per-facet loop in the reference too, stiffnessMtrx.py:369-411) and the user
+Dirichlet hook.
 
 Deliberate deviations, all outside the arithmetic of the path:
   * `solve_dof`: the reference switches to scipy's direct `spsolve` below 1e5 DOF
@@ -142,6 +144,7 @@ class System_of_equations:
         self.compiled = False
         self._dofsets = {}
         self._loadsets = {}
+        self._bodyloads = {}
         self.cg_log = []          # one entry per CG solve: iterations, max|r0|, max|r|, increment end time
         self.stats = {"assemblies": 0, "force_evals": 0, "linear_solves": 0, "cg_iterations": 0, "direct_solves": 0,
                       "direct_rejected": 0}
@@ -403,9 +406,34 @@ class System_of_equations:
         for i, ls in enumerate(self._loadset(load_facets)):
             self.ctx.loadset_neumann(ls, load_val, load_dir, be.VEC_RHS, add=i > 0)
 
+    def _bodyload(self, ele_set) -> int:
+        """device body load (nodal weights) of one element set, None = the whole mesh; built once per set, by content."""
+        ids = None if ele_set is None else np.ascontiguousarray(ele_set, dtype=np.int32).ravel()
+        key = None if ids is None else ids.tobytes()
+        if key not in self._bodyloads:
+            self._bodyloads[key] = self.ctx.bodyload(self.ELE, ids)
+        return self._bodyloads[key]
+
+    def bodyForce(self, ele_set, force):
+        """rhs += consistent nodal loads of a uniform force per unit volume on `ele_set` (*Dload GRAV / BX / BY / BZ):
+        a dead load on the undeformed volume, evaluated on the device."""
+        self.ctx.bodyload_apply(self._bodyload(ele_set), force, be.VEC_RHS, add=True)
+
+    def cload(self, nodeSet, dm_specified: int, val: float):
+        """rhs[node, dm_specified] += val for every node of the set (*Cload)."""
+        self.ctx.dofset_add(self._dofset(nodeSet, dm_specified), be.VEC_RHS, val)
+
     def impose_boundary_condition(self, boundary_conditions: dict):
         for nb in boundary_conditions["neumannBCs"]:
             self.neumannBC(nb["face_set"], load_val=nb["traction"], load_dir=nb.get("direction", np.array([])))
+        body_forces = boundary_conditions.get("bodyForces", ())
+        cloads = boundary_conditions.get("cloads", ())
+        if (body_forces or cloads) and not boundary_conditions["neumannBCs"]:
+            self.rhs.fill(0.0)              # no *Dsload refreshed rhs: the added loads start from zero
+        for bf in body_forces:
+            self.bodyForce(bf["ele_set"], bf["force"])
+        for cl in cloads:
+            self.cload(cl["node_set"], cl["dof"], cl["val"])
         for bc in boundary_conditions["dirichletBCs"]:
             if not self.geometric_nonlinear:
                 self.dirichletBC_linearEquations(bc["node_set"], bc["dof"], bc["val"])
@@ -423,6 +451,10 @@ class System_of_equations:
         for bc in dirichletBCs:
             bc["node_set"] = HostField(np.array([*bc["node_set"]]), dtype=np.int32)
         boundary_conditions = {"neumannBCs": neumannBCs, "dirichletBCs": dirichletBCs}
+        body_force_info, cload_info = getattr(inp, "body_force_info", None) or [], getattr(inp, "cload_info", None) or []
+        if body_force_info or cload_info:          # decks without *Dload / *Cload make the calls they always made
+            boundary_conditions["bodyForces"] = copy.deepcopy(body_force_info)
+            boundary_conditions["cloads"] = copy.deepcopy(cload_info)
         self.increments = []
         kinc = -1
         while self.time1 < max_time:
@@ -432,6 +464,10 @@ class System_of_equations:
             load_ratio = self.time1 / max_time
             for i, nb in enumerate(neumannBCs):
                 nb["traction"] = inp.neumann_bc_info[i]["traction"] * load_ratio
+            for i, bf in enumerate(boundary_conditions.get("bodyForces", ())):
+                bf["force"] = np.asarray(body_force_info[i]["force"], dtype=np.float64) * load_ratio
+            for i, cl in enumerate(boundary_conditions.get("cloads", ())):
+                cl["val"] = cload_info[i]["val"] * load_ratio
             for i, bc in enumerate(dirichletBCs):
                 bc["val"] = inp.dirichlet_bc_info[i]["val"] * load_ratio
             converged, newton_loop = self.advance_inc(inp, boundary_conditions, show_newton_steps, save2path)

@@ -258,7 +258,7 @@ int femcy_sync(femcy_ctx* ctx);                                   /* hipStreamSy
 
 /* ----------------------------------------------------------------------- problem definition */
 /* Body + System_of_equations.__init__ state (body.py:13-17, stiffnessMtrx.py:26-121).  Calling it again on a used
- * ctx starts over: element tables, material, pattern, DOF lists and load sets of the old mesh are dropped. */
+ * ctx starts over: element tables, material, pattern, DOF lists, load sets and body loads of the old mesh are dropped. */
 int femcy_set_mesh(femcy_ctx* ctx, int32_t nn, int32_t dm, const double* nodes /*[nn*dm]*/,
                    int32_t ne, int32_t npe, const int32_t* elems /*[ne*npe]*/);
 /* table-driven element plugin: ELE.gaussPoints/gaussWeights/dshape_dnat (element_zoo modules) */
@@ -319,6 +319,9 @@ int femcy_dofset_dirichlet_newton(femcy_ctx* ctx, int32_t id, int residual_vec);
 int femcy_dofset_dirichlet_linear(femcy_ctx* ctx, int32_t id, double value, int rhs_vec);
 int femcy_dofset_fill(femcy_ctx* ctx, int32_t id, int vec, double value);       /* dirichletBC_val */
 int femcy_dofset_scatter(femcy_ctx* ctx, int32_t id, int vec, const double* vals /*[k]*/);
+/* *Cload: vec[dof] += value over the set (the entries of a set are distinct DOFs).  Several ranks: no exchange -- the
+ * right-hand side holds the summed value on every rank that shares a node, so each rank adds the full value to its copy. */
+int femcy_dofset_add(femcy_ctx* ctx, int32_t id, int vec, double value);
 /* neumannBC (stiffnessMtrx.py:369-411) on the device.  A load set is the device-resident description of one
  * *Dsload surface: for each loaded facet its owning element (body.boundary[facet], body.py:197-216) and its
  * facet type = index into the element plugin's facet tables (facet_natural_coos / facet_point_weights /
@@ -346,6 +349,24 @@ int femcy_loadset_neumann(femcy_ctx* ctx, int32_t id, double traction, const dou
                           int rhs_vec);
 int femcy_loadset_neumann_add(femcy_ctx* ctx, int32_t id, double traction, const double* direction /*[dm] or NULL*/,
                               int rhs_vec);
+/* Body forces (*Dload GRAV / BX / BY / BZ; an extension, the reference has surface tractions only).  A body load is to a
+ * volume force what a load set is to a *Dsload surface: a device-resident description built once.
+ * femcy_bodyload_create computes, on the UNDEFORMED geometry, the nodal weights
+ *   m_a = sum over the selected elements e and their Gauss points g of N_a(xi_g) |det J_g| w_g
+ * with N [nGP][npe] = the plugin's shapeFunc at its Gauss points (dN and w are those of femcy_set_element); sel_elems =
+ * NULL selects every element, otherwise nsel distinct element ids.  After femcy_set_element and femcy_build_pattern.
+ * The consistent load vector of a uniform force b per unit volume is then exactly f[a*dm + i] = m_a * b[i]: a dead load on
+ * the reference volume, which is also the gravity load under nlgeom (mass is conserved), so nothing is re-evaluated per
+ * Newton step.  Element pass + owner-computes node sums in a fixed order: the same bits on every run.
+ * femcy_bodyload_weights downloads m [nn].
+ * femcy_bodyload_apply writes (add = 0) or adds (add != 0) m_a * b[i] to vec[rhs]; b [dm] is read during the call and
+ * travels in the kernel arguments (no copy, no stream synchronisation).  The product is rounded before it is added.
+ * Several ranks: each rank weighs its own elements; apply sums over the interface like femcy_loadset_neumann, and with
+ * add through vector TMP1, which must then not be vec[rhs] (collective calls). */
+int femcy_bodyload_create(femcy_ctx* ctx, const double* N /*[nGP][npe]*/, int32_t nsel,
+                          const int32_t* sel_elems /*[nsel], NULL = every element*/, int32_t* id_out);
+int femcy_bodyload_weights(femcy_ctx* ctx, int32_t id, double* out /*[nn]*/);
+int femcy_bodyload_apply(femcy_ctx* ctx, int32_t id, const double* b /*[dm]*/, int rhs_vec, int32_t add);
 /* compute_Ad (conjugateGradientSolver.py:53-58): vec[y] = K vec[x] */
 int femcy_spmv(femcy_ctx* ctx, int x_vec, int y_vec);
 /* ConjugateGradientSolver_rowMajor.re_init + solve (conjugateGradientSolver.py:32-51, 103-127):
