@@ -279,6 +279,10 @@ __global__ void __launch_bounds__(BS) k_recip(int64_t n, double* __restrict__ v)
 }
 
 // x = 0, r = b, d = M r, partials of (r.M.r, max|r|)   (re_init + r_d_init, :32-38, :60-65)
+// node order with n odd: n2 = (n + 1) / 2 and the last double2 holds entry n, one behind the vector.  Every operand is
+// padded there (femcy_set_mesh: n rounded up to 64 + 64 doubles, zero-filled; upload / download / the femcy_vec_* kernels
+// and the node-order product stop at n), so b[n] = 0 is read, r[n] = d[n] = x[n] = 0 are written back and stay 0 through
+// the iteration (r -= alpha Ad with Ad[n] = 0), and neither r.M.r nor max|r| sees the slot
 __global__ void __launch_bounds__(BS) k_pcg_init(int64_t n2, const double2* __restrict__ b, const double2* __restrict__ M,
                                                  double2* __restrict__ x, double2* __restrict__ r,
                                                  double2* __restrict__ d, const uint8_t* __restrict__ owner,
@@ -403,6 +407,9 @@ __global__ void __launch_bounds__(BS) k_update_xr(XcdRanges er, int np1, const d
     double2 av[VU], mv[VU], rv[VU];
 #pragma unroll
     for (int u = 0; u < VU; ++u) {
+        // an empty range (start == n2) reads element n2 itself, unused: for the last XCD that is the double2 behind the
+        // vector, which every operand owns -- femcy_set_mesh pads the femcy_vec vectors to n rounded up to 64 + 64 doubles
+        // and d_r / d_d / d_M / d_Ad to whole slices + 64, ensure_pos_vectors d_posb / d_posx likewise (all zero-filled)
         const int64_t i = max((int64_t)er.start[xk], min(base + u * stride, n2 - 1));
         av[u] = ld2<NT>(Ad + i);
         mv[u] = ld2<NT>(M + i);
@@ -491,6 +498,7 @@ __global__ void __launch_bounds__(BS) k_update_d(XcdRanges er, int np2, const do
     double2 rv[VU], mv[VU], dv[VU], xv[VU];
 #pragma unroll
     for (int u = 0; u < VU; ++u) {                  // first batch in flight while the scalars are reduced
+        // (an empty range reads element n2, inside the padding of every operand: see k_update_xr)
         const int64_t i = max((int64_t)er.start[xk], min(base + u * stride, n2 - 1));
         rv[u] = ld2<NT>(r + i);
         mv[u] = ld2<NT>(M + i);
