@@ -70,6 +70,7 @@ EXPORTS = [
     "femcy_assemble_K", "femcy_internal_force", "femcy_residual_and_K", "femcy_apply_dirichlet_linear", "femcy_apply_dirichlet_newton",
     "femcy_dofset_create", "femcy_dofset_dirichlet_newton", "femcy_dofset_dirichlet_linear", "femcy_dofset_fill",
     "femcy_dofset_scatter", "femcy_dofset_add", "femcy_bodyload_create", "femcy_bodyload_weights", "femcy_bodyload_apply",
+    "femcy_thermal_create", "femcy_thermal_force", "femcy_thermal_apply", "femcy_thermal_stress",
     "femcy_loadset_create", "femcy_loadset_neumann", "femcy_loadset_neumann_add", "femcy_spmv", "femcy_pcg", "femcy_compute_strain_stress", "femcy_elastic_energy", "femcy_extrapolate",
     "femcy_get_K_ell", "femcy_get_K_bsr", "femcy_get_gp_field", "femcy_timing",
     "femcy_timing_reset", "femcy_comm_unique_id", "femcy_comm_local_id", "femcy_comm_init", "femcy_comm_info", "femcy_comm_set_neighbours",
@@ -163,6 +164,8 @@ def _bind(lib, kind):
         "femcy_dofset_scatter": [p, i32, cint, p], "femcy_dofset_add": [p, i32, cint, f64],
         "femcy_bodyload_create": [p, p, i32, p, C.POINTER(i32)], "femcy_bodyload_weights": [p, i32, p],
         "femcy_bodyload_apply": [p, i32, p, cint, i32],
+        "femcy_thermal_create": [p, p, f64, p, C.POINTER(i32)], "femcy_thermal_force": [p, i32, p],
+        "femcy_thermal_apply": [p, i32, f64, cint, i32], "femcy_thermal_stress": [p, i32, f64],
         "femcy_loadset_create": [p, i32, i32, i32, p, p, p, p, p, i32, p, p, C.POINTER(i32)],
         "femcy_loadset_neumann": [p, i32, f64, p, cint],
         "femcy_loadset_neumann_add": [p, i32, f64, p, cint],
@@ -452,6 +455,33 @@ class Context:
         if b.size < self.dm:
             raise FemcyError(f"body force needs {self.dm} components")
         self._call("femcy_bodyload_apply", int(bl), _ptr(b), int(rhs_vec), 1 if add else 0)
+
+    # device-resident thermal loads (*Expansion + *Temperature)
+    def thermal(self, ELE, alpha: float, dT) -> int:
+        """consistent nodal load of the thermal strain alpha * dT I at scale 1, dT = nodal temperature changes [nn], on
+        the undeformed geometry with the material of this moment (linear materials only)."""
+        N = _f64(ELE.tables()["N"])
+        if N.shape != (self.nGP, self.npe):
+            raise FemcyError(f"shape-function table must be {self.nGP} x {self.npe}, got {N.shape}")
+        dT = _f64(dT).ravel()
+        if dT.size != self.nn:
+            raise FemcyError(f"temperature field needs {self.nn} nodal values, got {dT.size}")
+        out = C.c_int32()
+        self._call("femcy_thermal_create", _ptr(N), float(alpha), _ptr(dT), C.byref(out))
+        return out.value
+
+    def thermal_force(self, th: int) -> np.ndarray:
+        out = np.empty(self.n, dtype=np.float64)
+        self._call("femcy_thermal_force", int(th), _ptr(out))
+        return out
+
+    def thermal_apply(self, th: int, scale: float, rhs_vec: int = VEC_RHS, add: bool = False):
+        """rhs = scale * f_unit (add: rhs += it)."""
+        self._call("femcy_thermal_apply", int(th), float(scale), int(rhs_vec), 1 if add else 0)
+
+    def thermal_stress(self, th: int, scale: float):
+        """after compute_strain_stress(large=False): sigma -= scale * sigma_th, von Mises again."""
+        self._call("femcy_thermal_stress", int(th), float(scale))
 
     def spmv(self, x_vec: int, y_vec: int):
         self._call("femcy_spmv", int(x_vec), int(y_vec))

@@ -306,6 +306,14 @@ struct Ctx {
     struct BodyLoad { double* d_m; int32_t nsel; };
     std::vector<BodyLoad> bodyloads;
 
+    // ---- device-resident thermal loads (femcy_thermal_*): the load vector at scale 1 of one nodal temperature change,
+    // and what the stress correction reads again (the temperatures, the shape functions at the Gauss points, and the
+    // stress of full restraint per unit temperature change, alpha * C : eps_th, as a full row-major tensor)
+    struct ThermalStress { double s[9]; };
+    struct Thermal { double *d_f, *d_dT, *d_N; ThermalStress ts; };
+    std::vector<Thermal> thermals;
+    bool post_small = false;          // sigma / mises hold femcy_compute_strain_stress(large = 0), not yet corrected
+
     // ---- options / timing
     int opt_assembly = FEMCY_ASM_AUTO;
     int asm_used = -1;                // the mode the last assembly ran, AUTO resolved (femcy_get_assembly_used)
@@ -399,6 +407,9 @@ int launch_nodal_force(Ctx* c, double* d_f);
 int launch_neumann(Ctx* c, const Ctx::LoadSet& ls, double traction, bool along_normal, double* d_rhs, bool add);
 int launch_body_weights(Ctx* c, const double* d_N, const uint8_t* d_mask_or_null, double* d_we, double* d_m);
 int launch_body_apply(Ctx* c, const double* d_m, const double* b, bool add, double* d_f);
+int launch_thermal_force(Ctx* c, const Ctx::Thermal& th, double* d_fe);
+int launch_thermal_apply(Ctx* c, const double* d_funit, double scale, bool add, double* d_f);
+int launch_thermal_post(Ctx* c, const Ctx::Thermal& th, double scale);
 // pos_space: x and y are in STORAGE order (entry p * dm + c belongs to the node at storage position p = slice * 64 + lane;
 // the padding lanes of the last slice hold zeros) -- the form the three-kernel PCG runs in since round 4
 int launch_spmv(Ctx* c, const double* d_x, double* d_y, double* d_partials, int* nblocks_out, bool pos_space = false);

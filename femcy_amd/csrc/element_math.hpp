@@ -615,4 +615,110 @@ FEMCY_HD void body_weights_element(const double (&X)[NPE][DM], int32_t nGP, cons
     }
 }
 
+// ------------------------------------------------------------------------------------ thermal loads
+// *Expansion + *Temperature (small strain): the stress of full restraint at alpha * dT = 1, s = C : eps_th with the
+// isotropic thermal strain eps_th = k I and C exactly as femcy_set_material received it (no isotropy is assumed: an
+// anisotropic C gives shear entries).  3-D: Voigt order [xx,yy,zz,xy,zx,yz], k = 1.  Plane stress: [xx,yy,xy], k = 1.
+// Plane strain: eps_zz = 0 is enforced, the in-plane effective thermal strain is (1 + nu) alpha dT, so k = 1 + nu
+// (nu = p1, as post_point uses it) and s_xx = s_yy = E / (1 - 2 nu) for the isotropic C.
+template <int DM>
+FEMCY_HD void thermal_unit_stress(int kind, const double* __restrict__ C, double p1, double (&s)[DM][DM]);
+
+template <>
+FEMCY_HD void thermal_unit_stress<3>(int, const double* __restrict__ C, double, double (&s)[3][3]) {
+    double v[6];
+#pragma unroll
+    for (int p = 0; p < 6; ++p) v[p] = C[p * 6 + 0] + C[p * 6 + 1] + C[p * 6 + 2];
+    s[0][0] = v[0]; s[1][1] = v[1]; s[2][2] = v[2];
+    s[0][1] = s[1][0] = v[3];
+    s[0][2] = s[2][0] = v[4];
+    s[1][2] = s[2][1] = v[5];
+}
+
+template <>
+FEMCY_HD void thermal_unit_stress<2>(int kind, const double* __restrict__ C, double p1, double (&s)[2][2]) {
+    const double k = kind == FEMCY_MAT_PSTRAIN ? 1.0 + p1 : 1.0;
+    double v[3];
+#pragma unroll
+    for (int p = 0; p < 3; ++p) v[p] = k * (C[p * 3 + 0] + C[p * 3 + 1]);
+    s[0][0] = v[0]; s[1][1] = v[1];
+    s[0][1] = s[1][0] = v[2];
+}
+
+// one element of a thermal load: fe[a*DM + i] = sum_g dT_g |det J_g| w_g sum_j dN_a/dx_j s[i][j] on the UNDEFORMED
+// coordinates X, with dT_g = sum_a N_a(xi_g) dT[a] interpolated by the element's own shape functions and s the stress
+// of full restraint per unit temperature change (alpha x the unit stress above).  dN[g][a][:] and N[g][a] are the
+// plugin's tables at the Gauss points.
+template <int NPE, int DM>
+FEMCY_HD void thermal_force_element(const double (&X)[NPE][DM], const double (&dT)[NPE], int32_t nGP,
+                                    const double* __restrict__ dN, const double* __restrict__ N,
+                                    const double* __restrict__ w, const double (&s)[DM][DM], double (&fe)[NPE * DM]) {
+#pragma unroll
+    for (int q = 0; q < NPE * DM; ++q) fe[q] = 0.0;
+    for (int32_t g = 0; g < nGP; ++g) {
+        const double* __restrict__ dNg = dN + g * NPE * DM;
+        const double* __restrict__ Ng = N + g * NPE;
+        double J[DM][DM], inv[DM][DM];
+#pragma unroll
+        for (int i = 0; i < DM; ++i)
+#pragma unroll
+            for (int j = 0; j < DM; ++j) {
+                double acc = 0.0;
+#pragma unroll
+                for (int a = 0; a < NPE; ++a) acc += X[a][i] * dNg[a * DM + j];
+                J[i][j] = acc;
+            }
+        double tg = 0.0;
+#pragma unroll
+        for (int a = 0; a < NPE; ++a) tg += Ng[a] * dT[a];
+        const double vg = fabs(det_inv<DM>(J, inv)) * w[g] * tg;
+#pragma unroll
+        for (int a = 0; a < NPE; ++a) {
+            double ga[DM];
+#pragma unroll
+            for (int j = 0; j < DM; ++j) {
+                double acc = 0.0;
+#pragma unroll
+                for (int k = 0; k < DM; ++k) acc += dNg[a * DM + k] * inv[k][j];
+                ga[j] = acc;
+            }
+#pragma unroll
+            for (int i = 0; i < DM; ++i) {
+                double d = 0.0;
+#pragma unroll
+                for (int j = 0; j < DM; ++j) d += ga[j] * s[i][j];
+                fe[a * DM + i] += d * vg;
+            }
+        }
+    }
+}
+
+// one Gauss point of the stress correction: sigma -= th * s with th = scale * dT_g (s per unit temperature change), then the von Mises stress of
+// the corrected tensor by material kind as post_point forms it; plane strain: s_zz = nu (s_xx + s_yy) - E alpha dT_g with
+// E alpha dT_g = (1 - 2 nu) th s_xx, so that no further material parameter is needed.  The strain stays the total strain.
+template <int DM>
+FEMCY_HD void thermal_post_point(int kind, double p1, const double (&s)[DM][DM], double th,
+                                 double* __restrict__ sigma, double* __restrict__ mises) {
+    double s3[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+#pragma unroll
+    for (int i = 0; i < DM; ++i)
+#pragma unroll
+        for (int j = 0; j < DM; ++j) {
+            const double v = sigma[i * DM + j] - th * s[i][j];
+            sigma[i * DM + j] = v;
+            s3[i][j] = v;
+        }
+    if (kind == FEMCY_MAT_PSTRAIN) s3[2][2] = p1 * (s3[0][0] + s3[1][1]) - (1.0 - 2.0 * p1) * (th * s[0][0]);
+    const double tr = (s3[0][0] + s3[1][1] + s3[2][2]) / 3.0;
+    double ss = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const double dv = s3[i][j] - (i == j ? tr : 0.0);
+            ss += dv * dv;
+        }
+    *mises = sqrt(1.5 * ss);
+}
+
 }  // namespace femcy

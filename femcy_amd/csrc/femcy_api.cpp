@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstring>
 #include "ctx.hpp"
+#include "element_math.hpp"
 #include "direct.hpp"
 
 namespace femcy {
@@ -138,6 +139,7 @@ static int check_vec(Ctx* c, int v) {
 
 // element pass of a force evaluation: gradients + per-element nodal forces; F / sigma stay un-stored (gp_lazy)
 int force_pass(Ctx* c, const double* d_u) {
+    c->post_small = false;                           // sigma is about to be the stress of this evaluation (now or lazily)
     if (c->opt_tangent == 1) {                       // the consistent tangent reads F and sigma right away
         c->gp_lazy = false;
         return launch_geom(c, d_u, GEOM_DSDX | GEOM_F | GEOM_SIGMA | GEOM_FE);
@@ -288,6 +290,9 @@ int femcy_ctx_destroy(femcy_ctx* ctx) {
     }
     for (auto& bl : c->bodyloads)
         if (bl.d_m) (void)hipFree(bl.d_m);
+    for (auto& th : c->thermals)
+        for (void* q : {(void*)th.d_f, (void*)th.d_dT, (void*)th.d_N})
+            if (q) (void)hipFree(q);
     for (auto& p : c->ev_pool) {
         (void)hipEventDestroy(p.a);
         (void)hipEventDestroy(p.b);
@@ -514,6 +519,11 @@ int femcy_set_mesh(femcy_ctx* ctx, int32_t nn, int32_t dm, const double* nodes, 
     for (auto& bl : c->bodyloads)
         if (bl.d_m) (void)hipFree(bl.d_m);
     c->bodyloads.clear();
+    for (auto& th : c->thermals)
+        for (void* q : {(void*)th.d_f, (void*)th.d_dT, (void*)th.d_N})
+            if (q) (void)hipFree(q);
+    c->thermals.clear();
+    c->post_small = false;
     c->have_material = false;
     c->nn = nn; c->dm = dm; c->ne = ne; c->npe = npe;
     c->n = (int64_t)nn * dm;
@@ -576,6 +586,7 @@ int femcy_set_element(femcy_ctx* ctx, int32_t nGP, const double* dN, const doubl
         (rc = dev_alloc(&c->d_energy, ngp)))
         return rc;
     c->have_element = true;
+    c->post_small = false;
     c->gp_lazy = false;
     return FEMCY_OK;
 }
@@ -617,6 +628,7 @@ int femcy_set_material(femcy_ctx* ctx, int32_t kind, const double* C, const doub
     }
     for (int i = 0; i < 4; ++i) c->mat_params[i] = (i < nparams) ? params[i] : 0.0;
     c->have_material = true;
+    c->post_small = false;
     return FEMCY_OK;
 }
 
@@ -1096,6 +1108,98 @@ int femcy_bodyload_apply(femcy_ctx* ctx, int32_t id, const double* b, int rhs_ve
     return iface_sum(c, rhs);                  // multi-rank: each rank weighs its own elements
 }
 
+// --------------------------------------------------------------------------------- thermal loads
+static void thermal_free(Ctx::Thermal& th) {
+    for (void* q : {(void*)th.d_f, (void*)th.d_dT, (void*)th.d_N})
+        if (q) (void)hipFree(q);
+    th.d_f = th.d_dT = th.d_N = nullptr;
+}
+
+int femcy_thermal_create(femcy_ctx* ctx, const double* N, double alpha, const double* dT, int32_t* id_out) {
+    CTX_OR_FAIL(ctx);
+    FEMCY_REQUIRE(c->have_mesh && c->have_element && c->have_material && c->have_pattern,
+                  "femcy_thermal_create needs the mesh, the element tables, the material and the pattern (mesh=%d element=%d "
+                  "material=%d pattern=%d)", (int)c->have_mesh, (int)c->have_element, (int)c->have_material,
+                  (int)c->have_pattern);
+    FEMCY_REQUIRE(N && dT && id_out, "null shape-function table, temperature field or id_out");
+    FEMCY_REQUIRE(std::isfinite(alpha), "thermal load: the expansion coefficient is not finite");
+    FEMCY_REQUIRE(c->mat_kind != FEMCY_MAT_NEOHOOKE, "thermal load: a neo-Hookean material has no small-strain thermal "
+                  "stress (linear materials only)");
+    Ctx::Thermal th{nullptr, nullptr, nullptr, {}};
+    if (c->dm == 3) {
+        double s[3][3];
+        thermal_unit_stress<3>(c->mat_kind, c->h_C, c->mat_params[1], s);
+        for (int i = 0; i < 9; ++i) th.ts.s[i] = alpha * s[i / 3][i % 3];
+    } else {
+        double s[2][2];
+        thermal_unit_stress<2>(c->mat_kind, c->h_C, c->mat_params[1], s);
+        for (int i = 0; i < 4; ++i) th.ts.s[i] = alpha * s[i / 2][i % 2];
+    }
+    double* d_fe = nullptr;
+    int rc = to_device(&th.d_N, N, sizeof(double) * c->nGP * c->npe);
+    if (!rc) rc = to_device(&th.d_dT, dT, sizeof(double) * (size_t)c->nn);
+    if (!rc && dmalloc(&d_fe, sizeof(double) * (size_t)c->ne * c->npe * c->dm) != hipSuccess) rc = FEMCY_ENOMEM;
+    if (!rc && dmalloc(&th.d_f, sizeof(double) * (size_t)c->n) != hipSuccess) rc = FEMCY_ENOMEM;
+    if (!rc) rc = launch_thermal_force(c, th, d_fe);
+    // the element records are scratch of this call: wait for the two kernels, then release them
+    if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) {
+        set_error("thermal load: the force kernels failed");
+        rc = FEMCY_EHIP;
+    }
+    if (d_fe) (void)hipFree(d_fe);
+    if (rc) {
+        thermal_free(th);
+        if (rc == FEMCY_ENOMEM) set_error("out of device memory for a thermal load on %d elements", c->ne);
+        return rc;
+    }
+    c->thermals.push_back(th);
+    *id_out = (int32_t)c->thermals.size() - 1;
+    return FEMCY_OK;
+}
+
+#define THERMAL_OR_FAIL(id)                                                                            \
+    FEMCY_REQUIRE((id) >= 0 && (size_t)(id) < c->thermals.size(), "unknown thermal load %d", (int)(id)); \
+    const Ctx::Thermal& th = c->thermals[(id)]
+
+int femcy_thermal_force(femcy_ctx* ctx, int32_t id, double* out) {
+    CTX_OR_FAIL(ctx);
+    THERMAL_OR_FAIL(id);
+    FEMCY_REQUIRE(out, "null output");
+    FEMCY_HIP(hipMemcpyAsync(out, th.d_f, sizeof(double) * c->n, hipMemcpyDeviceToHost, c->stream));
+    FEMCY_HIP(hipStreamSynchronize(c->stream));
+    return FEMCY_OK;
+}
+
+int femcy_thermal_apply(femcy_ctx* ctx, int32_t id, double scale, int rhs_vec, int32_t add) {
+    CTX_OR_FAIL(ctx);
+    VEC_OR_FAIL(rhs_vec);
+    THERMAL_OR_FAIL(id);
+    FEMCY_REQUIRE(!add || !c->comm || rhs_vec != FEMCY_VEC_TMP1, "femcy_thermal_apply with add on several ranks sums the "
+                  "interface through vector TMP1: it cannot be the right-hand side");
+    double* rhs = c->d_vec[rhs_vec];
+    int rc;
+    if (add && c->comm) {   // multi-rank: only this load is summed over the interface, then added
+        double* tmp = c->d_vec[FEMCY_VEC_TMP1];
+        if ((rc = launch_thermal_apply(c, th.d_f, scale, false, tmp))) return rc;
+        if ((rc = iface_sum(c, tmp))) return rc;
+        return vec_axpy(c, rhs, rhs, 1.0, tmp);
+    }
+    if ((rc = launch_thermal_apply(c, th.d_f, scale, add != 0, rhs))) return rc;
+    if (add) return FEMCY_OK;
+    return iface_sum(c, rhs);                  // multi-rank: each rank evaluates its own elements
+}
+
+int femcy_thermal_stress(femcy_ctx* ctx, int32_t id, double scale) {
+    CTX_OR_FAIL(ctx);
+    THERMAL_OR_FAIL(id);
+    FEMCY_REQUIRE(c->mat_kind != FEMCY_MAT_NEOHOOKE, "thermal stress: a neo-Hookean material has no small-strain thermal "
+                  "stress (linear materials only)");
+    FEMCY_REQUIRE(c->post_small, "femcy_thermal_stress corrects the stress of femcy_compute_strain_stress(large = 0): call "
+                  "that first (the Gauss-point stress does not exist, is the nlgeom one, or has been corrected already)");
+    c->post_small = false;
+    return launch_thermal_post(c, th, scale);
+}
+
 int femcy_spmv(femcy_ctx* ctx, int x_vec, int y_vec) {
     CTX_OR_FAIL(ctx);
     FEMCY_REQUIRE(c->have_pattern, "pattern not built");
@@ -1151,7 +1255,10 @@ int femcy_compute_strain_stress(femcy_ctx* ctx, int u_vec, int large) {
     int rc = ensure_gp_stress(c);
     if (rc) return rc;
     if ((rc = launch_geom(c, c->d_vec[u_vec], GEOM_F))) return rc;
-    return launch_post(c, large ? 1 : 0);
+    c->post_small = false;
+    if ((rc = launch_post(c, large ? 1 : 0))) return rc;
+    c->post_small = !large;                    // what femcy_thermal_stress may correct, once
+    return FEMCY_OK;
 }
 
 int femcy_elastic_energy(femcy_ctx* ctx, int u_vec, double* total) {

@@ -1563,6 +1563,81 @@ __global__ void __launch_bounds__(256) k_body_apply(int64_t n, const double* __r
     f[i] = add ? __dadd_rn(f[i], v) : v;
 }
 
+// -------------------------------------------------------------------------------- thermal loads
+// *Expansion + *Temperature: the consistent nodal load of the thermal strain alpha dT I is linear in the temperature
+// change, so the element work is done once per load (femcy_thermal_create) and an increment only scales the stored
+// vector.  Element pass in the shape of k_body_weights: one thread per element, the tables dN / N / w wave-uniform, node
+// rows by load_row, the element's NPE nodal temperature changes by the same node ids, the stress of full restraint per
+// unit temperature change in the kernel arguments.  The record fe[e][a][0..DM) goes out as k_geom's per-element nodal
+// forces do: through block_store, or in chunks through block_store_strided when it is wider than 16 doubles.  It has the
+// layout k_nodal_force gathers, which does the node sum (no atomics, fixed order).
+template <int NPE, int DM>
+__global__ void __launch_bounds__(256) k_thermal_force(int32_t ne, int32_t nGP, const double* __restrict__ nodes,
+                                                       const int32_t* __restrict__ elems,
+                                                       const double* __restrict__ dN, const double* __restrict__ N,
+                                                       const double* __restrict__ w, const double* __restrict__ dT,
+                                                       Ctx::ThermalStress ts, double* __restrict__ fe_out) {
+    constexpr int WG = NPE * DM;
+    constexpr bool STAGE = WG <= 16;
+    constexpr int CHK = WG % 16 == 0 ? 16 : WG % 15 == 0 ? 15 : WG % 12 == 0 ? 12 : WG % 9 == 0 ? 9 : WG % 8 == 0 ? 8 :
+                        WG % 6 == 0 ? 6 : 1;
+    static_assert(STAGE || CHK > 1, "no chunk width for this record");
+    __shared__ double stage_lds[257 * (STAGE ? WG : CHK)];
+    const int32_t e0 = blockIdx.x * blockDim.x;
+    const int nvalid = min(256, ne - e0);
+    const bool valid = (int)threadIdx.x < nvalid;
+    const int32_t e = valid ? e0 + (int32_t)threadIdx.x : ne - 1;      // idle lanes recompute the last element, store nothing
+    double X[NPE][DM], T[NPE], s[DM][DM], Fe[WG];
+#pragma unroll
+    for (int a = 0; a < NPE; ++a) {
+        const int32_t nd = elems[(int64_t)e * NPE + a];
+        load_row<DM>(nodes + (int64_t)nd * DM, X[a]);
+        T[a] = dT[nd];
+    }
+#pragma unroll
+    for (int i = 0; i < DM; ++i)
+#pragma unroll
+        for (int j = 0; j < DM; ++j) s[i][j] = ts.s[i * DM + j];
+    thermal_force_element<NPE, DM>(X, T, nGP, dN, N, w, s, Fe);
+    if constexpr (STAGE) {
+        block_store<WG>(fe_out + (int64_t)e0 * WG, Fe, nvalid, stage_lds);
+    } else {
+#pragma unroll
+        for (int c = 0; c < WG / CHK; ++c)
+            block_store_strided<CHK>(fe_out + (int64_t)e0 * WG + c * CHK, Fe + c * CHK, nvalid, stage_lds, (int64_t)WG);
+    }
+}
+
+// f = scale * f_unit (add: f += that); scale travels in the kernel arguments.  The product is rounded before the sum (no
+// fused multiply-add), so that adding to a vector gives the bits of the two vectors added by the caller.
+__global__ void __launch_bounds__(256) k_thermal_apply(int64_t n, const double* __restrict__ funit, double scale, int add,
+                                                       double* __restrict__ f) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double v = __dmul_rn(scale, funit[i]);
+    f[i] = add ? __dadd_rn(f[i], v) : v;
+}
+
+// one thread per Gauss point, as k_post: dT_g from the element's nodal values, sigma -= scale dT_g s, von Mises again
+template <int DM>
+__global__ void __launch_bounds__(256) k_thermal_post(int64_t ngp, int32_t nGP, int32_t npe, int kind, double p1,
+                                                      const int32_t* __restrict__ elems, const double* __restrict__ N,
+                                                      const double* __restrict__ dT, Ctx::ThermalStress ts, double scale,
+                                                      double* __restrict__ sigma, double* __restrict__ mises) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= ngp) return;
+    const int64_t e = t / nGP;
+    const int g = (int)(t - e * nGP);
+    double tg = 0.0;
+    for (int a = 0; a < npe; ++a) tg += N[g * npe + a] * dT[elems[e * npe + a]];
+    double s[DM][DM];
+#pragma unroll
+    for (int i = 0; i < DM; ++i)
+#pragma unroll
+        for (int j = 0; j < DM; ++j) s[i][j] = ts.s[i * DM + j];
+    thermal_post_point<DM>(kind, p1, s, scale * tg, sigma + t * DM * DM, mises + t);
+}
+
 int launch_extrapolate(Ctx* c, const double* d_E, const double* d_field, int width, int comp, double* d_out) {
     const int64_t total = (int64_t)c->ne * c->npe;
     hipLaunchKernelGGL(k_extrapolate, dim3((int)((total + 255) / 256)), dim3(256), 0, c->stream, (int64_t)c->ne, c->npe,
@@ -1673,6 +1748,68 @@ int launch_body_apply(Ctx* c, const double* d_m, const double* b, bool add, doub
     else
         hipLaunchKernelGGL((k_body_apply<2>), dim3(grid), dim3(bs), 0, c->stream, c->n, d_m, b[0], b[1], 0.0,
                            add ? 1 : 0, d_f);
+    FEMCY_HIP(hipGetLastError());
+    return FEMCY_OK;
+}
+
+// load vector of a thermal load at scale 1: element pass into d_fe [ne][npe][dm] (scratch of the caller), node sums by
+// k_nodal_force into th.d_f [n]
+int launch_thermal_force(Ctx* c, const Ctx::Thermal& th, double* d_fe) {
+    const int bs = 256, grid = (c->ne + bs - 1) / bs;
+    bool launched = false;
+    size_t tm = timing_begin(c, T_GEOM);
+#define THERMAL_CALL                                                                                                \
+    hipLaunchKernelGGL((k_thermal_force<NPE, DM>), dim3(grid), dim3(bs), 0, c->stream, c->ne, c->nGP, c->d_nodes,   \
+                       c->d_elems, c->d_dN, th.d_N, c->d_w, th.d_dT, th.ts, d_fe)
+    FEMCY_DISPATCH_ELEMENT(3, 2, THERMAL_CALL)
+    FEMCY_DISPATCH_ELEMENT(4, 2, THERMAL_CALL)
+    FEMCY_DISPATCH_ELEMENT(6, 2, THERMAL_CALL)
+    FEMCY_DISPATCH_ELEMENT(8, 2, THERMAL_CALL)
+    FEMCY_DISPATCH_ELEMENT(4, 3, THERMAL_CALL)
+    FEMCY_DISPATCH_ELEMENT(10, 3, THERMAL_CALL)
+    FEMCY_DISPATCH_ELEMENT(8, 3, THERMAL_CALL)
+    FEMCY_DISPATCH_ELEMENT(6, 3, THERMAL_CALL)
+#undef THERMAL_CALL
+    if (launched) {
+        const int ngrid = (int)(((int64_t)c->nn * 32 + bs - 1) / bs);   // 32 lanes per node
+        if (c->dm == 3)
+            hipLaunchKernelGGL((k_nodal_force<3>), dim3(ngrid), dim3(bs), 0, c->stream, c->nn, c->d_ne_ptr, c->d_ne_idx,
+                               d_fe, th.d_f);
+        else
+            hipLaunchKernelGGL((k_nodal_force<2>), dim3(ngrid), dim3(bs), 0, c->stream, c->nn, c->d_ne_ptr, c->d_ne_idx,
+                               d_fe, th.d_f);
+    }
+    timing_end(c, tm);
+    if (!launched) {
+        set_error("no thermal-load kernel instantiated for npe=%d dm=%d", c->npe, c->dm);
+        return FEMCY_ENOKERNEL;
+    }
+    FEMCY_HIP(hipGetLastError());
+    return FEMCY_OK;
+}
+
+// d_f = scale * f_unit (add: d_f += that)
+int launch_thermal_apply(Ctx* c, const double* d_funit, double scale, bool add, double* d_f) {
+    const int bs = 256;
+    const unsigned grid = (unsigned)((c->n + bs - 1) / bs);
+    size_t tm = timing_begin(c, T_GEOM);          // events only under FEMCY_OPT_TIMING (tools/thermal_record.py)
+    hipLaunchKernelGGL(k_thermal_apply, dim3(grid), dim3(bs), 0, c->stream, c->n, d_funit, scale, add ? 1 : 0, d_f);
+    timing_end(c, tm);
+    FEMCY_HIP(hipGetLastError());
+    return FEMCY_OK;
+}
+
+int launch_thermal_post(Ctx* c, const Ctx::Thermal& th, double scale) {
+    const int64_t ngp = (int64_t)c->ne * c->nGP;
+    const int bs = 256, grid = (int)((ngp + bs - 1) / bs);
+    size_t tm = timing_begin(c, T_GEOM);
+    if (c->dm == 3)
+        hipLaunchKernelGGL((k_thermal_post<3>), dim3(grid), dim3(bs), 0, c->stream, ngp, c->nGP, c->npe, c->mat_kind,
+                           c->mat_params[1], c->d_elems, th.d_N, th.d_dT, th.ts, scale, c->d_sigma, c->d_mises);
+    else
+        hipLaunchKernelGGL((k_thermal_post<2>), dim3(grid), dim3(bs), 0, c->stream, ngp, c->nGP, c->npe, c->mat_kind,
+                           c->mat_params[1], c->d_elems, th.d_N, th.d_dT, th.ts, scale, c->d_sigma, c->d_mises);
+    timing_end(c, tm);
     FEMCY_HIP(hipGetLastError());
     return FEMCY_OK;
 }

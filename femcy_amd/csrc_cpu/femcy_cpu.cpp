@@ -65,6 +65,10 @@ struct LoadSet {
 struct BodyLoad {
     std::vector<double> m;   // [nn] nodal weights
 };
+struct Thermal {
+    std::vector<double> f, dT, N;   // [n] load at scale 1, [nn] temperature changes, [nGP][npe] shape functions
+    double s[9];                    // stress of full restraint per unit temperature change, row-major tensor
+};
 
 }  // namespace
 
@@ -90,6 +94,8 @@ struct femcy_ctx {
     std::vector<DofSet> dofsets;
     std::vector<LoadSet> loadsets;
     std::vector<BodyLoad> bodyloads;
+    std::vector<Thermal> thermals;
+    bool post_small = false;              // sigma / mises hold femcy_compute_strain_stress(large = 0), not yet corrected
     int opt_tangent = 0, opt_timing = 0;
     femcy_timing_t timing{};
     // femcy_direct_solve: band order of the current pattern (built on first use), storage limit
@@ -193,6 +199,7 @@ void geom_pass(femcy_ctx* c, const double* u, unsigned what) {
     }
 }
 void geom(femcy_ctx* c, const double* u, unsigned what) {
+    if (what & GEOM_SIGMA) c->post_small = false;
     const double t = c->opt_timing ? now_ms() : 0.0;
     if (c->dm == 3) geom_pass<3>(c, u, what); else geom_pass<2>(c, u, what);
     if (c->opt_timing) {
@@ -447,6 +454,8 @@ int femcy_set_mesh(femcy_ctx* ctx, int32_t nn, int32_t dm, const double* nodes, 
     c->dofsets.clear();
     c->loadsets.clear();
     c->bodyloads.clear();
+    c->thermals.clear();
+    c->post_small = false;
     c->nn = nn; c->dm = dm; c->ne = ne; c->npe = npe;
     c->n = (int64_t)nn * dm;
     c->nodes.assign(nodes, nodes + (size_t)nn * dm);
@@ -481,6 +490,7 @@ int femcy_set_element(femcy_ctx* ctx, int32_t nGP, const double* dN, const doubl
     c->energy.assign(ngp, 0.0);
     c->fe.assign((size_t)c->ne * c->npe * c->dm, 0.0);
     c->have_element = true;
+    c->post_small = false;
     return FEMCY_OK;
 }
 
@@ -509,6 +519,7 @@ int femcy_set_material(femcy_ctx* ctx, int32_t kind, const double* C, const doub
     }
     for (int i = 0; i < 4; ++i) c->params[i] = (i < nparams) ? params[i] : 0.0;
     c->have_material = true;
+    c->post_small = false;
     return FEMCY_OK;
 }
 
@@ -1013,6 +1024,132 @@ int femcy_bodyload_apply(femcy_ctx* ctx, int32_t id, const double* b, int rhs_ve
     return FEMCY_OK;
 }
 
+// --------------------------------------------------------------------------------- thermal loads
+}  // extern "C"
+namespace {
+// the element pass of the device's k_thermal_force (csrc/element_math.hpp: thermal_force_element), then the node sums in
+// ascending (element, local node) order
+template <int NPE, int DM>
+void thermal_force(femcy_ctx* c, Thermal& th) {
+    double s[DM][DM];
+    for (int i = 0; i < DM; ++i)
+        for (int j = 0; j < DM; ++j) s[i][j] = th.s[i * DM + j];
+    std::vector<double> fe((size_t)c->ne * NPE * DM, 0.0);
+#pragma omp parallel for schedule(static)
+    for (int32_t e = 0; e < c->ne; ++e) {
+        double X[NPE][DM], T[NPE], f_e[NPE * DM];
+        for (int a = 0; a < NPE; ++a) {
+            const int32_t nd = c->elems[(int64_t)e * NPE + a];
+            for (int i = 0; i < DM; ++i) X[a][i] = c->nodes[(int64_t)nd * DM + i];
+            T[a] = th.dT[nd];
+        }
+        thermal_force_element<NPE, DM>(X, T, c->nGP, c->dN.data(), th.N.data(), c->w.data(), s, f_e);
+        for (int q = 0; q < NPE * DM; ++q) fe[(size_t)e * NPE * DM + q] = f_e[q];
+    }
+    th.f.assign((size_t)c->n, 0.0);
+#pragma omp parallel for schedule(static)
+    for (int32_t a = 0; a < c->nn; ++a)
+        for (int i = 0; i < DM; ++i) {
+            double acc = 0.0;
+            for (int32_t k = c->ne_ptr[a]; k < c->ne_ptr[a + 1]; ++k) acc += fe[(size_t)c->ne_idx[k] * DM + i];
+            th.f[(size_t)a * DM + i] = acc;
+        }
+}
+}  // namespace
+extern "C" {
+
+int femcy_thermal_create(femcy_ctx* ctx, const double* N, double alpha, const double* dT, int32_t* id_out) {
+    CTX_OR_FAIL(ctx);
+    REQUIRE(c->have_mesh && c->have_element && c->have_material && c->have_pattern,
+            "femcy_thermal_create needs the mesh, the element tables, the material and the pattern (mesh=%d element=%d "
+            "material=%d pattern=%d)", (int)c->have_mesh, (int)c->have_element, (int)c->have_material, (int)c->have_pattern);
+    REQUIRE(N && dT && id_out, "null shape-function table, temperature field or id_out");
+    REQUIRE(std::isfinite(alpha), "thermal load: the expansion coefficient is not finite");
+    REQUIRE(c->mat_kind != FEMCY_MAT_NEOHOOKE, "thermal load: a neo-Hookean material has no small-strain thermal stress "
+            "(linear materials only)");
+    Thermal th;
+    th.N.assign(N, N + (size_t)c->nGP * c->npe);
+    th.dT.assign(dT, dT + (size_t)c->nn);
+    if (c->dm == 3) {
+        double s[3][3];
+        thermal_unit_stress<3>(c->mat_kind, c->C, c->params[1], s);
+        for (int i = 0; i < 9; ++i) th.s[i] = alpha * s[i / 3][i % 3];
+    } else {
+        double s[2][2];
+        thermal_unit_stress<2>(c->mat_kind, c->C, c->params[1], s);
+        for (int i = 0; i < 4; ++i) th.s[i] = alpha * s[i / 2][i % 2];
+    }
+    const int key = c->npe * 10 + c->dm;
+    switch (key) {
+        case 32: thermal_force<3, 2>(c, th); break;
+        case 42: thermal_force<4, 2>(c, th); break;
+        case 62: thermal_force<6, 2>(c, th); break;
+        case 82: thermal_force<8, 2>(c, th); break;
+        case 43: thermal_force<4, 3>(c, th); break;
+        case 103: thermal_force<10, 3>(c, th); break;
+        case 83: thermal_force<8, 3>(c, th); break;
+        case 63: thermal_force<6, 3>(c, th); break;
+        default:
+            set_error("no thermal-load kernel instantiated for npe=%d dm=%d", c->npe, c->dm);
+            return FEMCY_ENOKERNEL;
+    }
+    c->thermals.push_back(std::move(th));
+    *id_out = (int32_t)c->thermals.size() - 1;
+    return FEMCY_OK;
+}
+#define THERMAL_OR_FAIL(id)                                                                       \
+    REQUIRE((id) >= 0 && (size_t)(id) < c->thermals.size(), "unknown thermal load %d", (int)(id)); \
+    const Thermal& th = c->thermals[(id)]
+int femcy_thermal_force(femcy_ctx* ctx, int32_t id, double* out) {
+    CTX_OR_FAIL(ctx);
+    THERMAL_OR_FAIL(id);
+    REQUIRE(out, "null output");
+    std::copy(th.f.begin(), th.f.end(), out);
+    return FEMCY_OK;
+}
+int femcy_thermal_apply(femcy_ctx* ctx, int32_t id, double scale, int rhs_vec, int32_t add) {
+    CTX_OR_FAIL(ctx);
+    VEC_OR_FAIL(rhs_vec);
+    THERMAL_OR_FAIL(id);
+    double* rhs = c->vec[rhs_vec].data();
+    // the product is rounded before it is added (two passes: no fused multiply-add), as on the device
+    std::vector<double> f((size_t)c->n);
+    for (int64_t i = 0; i < c->n; ++i) f[i] = scale * th.f[i];
+    if (add)
+        for (int64_t i = 0; i < c->n; ++i) rhs[i] += f[i];
+    else
+        std::copy(f.begin(), f.end(), rhs);
+    return FEMCY_OK;
+}
+int femcy_thermal_stress(femcy_ctx* ctx, int32_t id, double scale) {
+    CTX_OR_FAIL(ctx);
+    THERMAL_OR_FAIL(id);
+    REQUIRE(c->mat_kind != FEMCY_MAT_NEOHOOKE, "thermal stress: a neo-Hookean material has no small-strain thermal stress "
+            "(linear materials only)");
+    REQUIRE(c->post_small, "femcy_thermal_stress corrects the stress of femcy_compute_strain_stress(large = 0): call that "
+            "first (the Gauss-point stress does not exist, is the nlgeom one, or has been corrected already)");
+    c->post_small = false;
+    const int64_t ngp = (int64_t)c->ne * c->nGP;
+    const int npe = c->npe, nGP = c->nGP, dm = c->dm, dd = dm * dm;
+#pragma omp parallel for schedule(static)
+    for (int64_t t = 0; t < ngp; ++t) {
+        const int64_t e = t / nGP;
+        const int g = (int)(t - e * nGP);
+        double tg = 0.0;
+        for (int a = 0; a < npe; ++a) tg += th.N[(size_t)g * npe + a] * th.dT[c->elems[e * npe + a]];
+        if (dm == 3) {
+            double s[3][3];
+            for (int i = 0; i < 9; ++i) s[i / 3][i % 3] = th.s[i];
+            thermal_post_point<3>(c->mat_kind, c->params[1], s, scale * tg, c->sigma.data() + t * dd, c->mises.data() + t);
+        } else {
+            double s[2][2];
+            for (int i = 0; i < 4; ++i) s[i / 2][i % 2] = th.s[i];
+            thermal_post_point<2>(c->mat_kind, c->params[1], s, scale * tg, c->sigma.data() + t * dd, c->mises.data() + t);
+        }
+    }
+    return FEMCY_OK;
+}
+
 int femcy_spmv(femcy_ctx* ctx, int x_vec, int y_vec) {
     CTX_OR_FAIL(ctx);
     REQUIRE(c->have_pattern, "pattern not built");
@@ -1245,6 +1382,7 @@ int femcy_compute_strain_stress(femcy_ctx* ctx, int u_vec, int large) {
             post_point<2>(large ? 1 : 0, c->mat_kind, c->C, c->params[0], c->params[1], c->F.data() + t * dd,
                           c->sigma.data() + t * dd, c->strain.data() + t * dd, c->mises.data() + t);
     }
+    c->post_small = !large;                    // what femcy_thermal_stress may correct, once
     return FEMCY_OK;
 }
 

@@ -35,7 +35,8 @@ def run(fileName: str, device: int = 0, verbose: bool = True, tangent: str = "re
     print(f"\033[40;33;1m system.dof = \n{system.dof.to_numpy()}, "
           f"time for finite element computing is {time1 - time0} s \033[0m")
     system.get_elasEng()
-    print(f"total elastic energy is {system.elsEng}")
+    print(f"total elastic energy is {system.elsEng}"
+          + (" (of the total strain: the thermal strain is not taken out)" if system._thermal is not None else ""))
     system.compute_strain_stress()
     stress = system.mises_stress.to_numpy()
     print(f"\033[35;1m max mises_stress at integration point is {stress.max()} MPa \033[0m", end="; ")

@@ -189,7 +189,7 @@ class LocalDeck:
     dropped), face sets keep the facets of elements this rank holds, as local sorted node tuples.  The element set of
     a body force becomes the local ids of the rank's own elements (None, the whole mesh, stays None; a set the rank
     holds nothing of becomes empty, so that every rank makes the same collective calls), a *Cload node set is handed
-    over like a Dirichlet node set."""
+    over like a Dirichlet node set, the nodal temperatures of a thermal load are those of the rank's nodes."""
 
     def __init__(self, inp, part: Part, body):
         self.time_incs = inp.time_incs
@@ -215,3 +215,7 @@ class LocalDeck:
                                 for bf in getattr(inp, "body_force_info", ())]
         self.cload_info = [dict(cl, node_set=part.localize_nodes(np.asarray(cl["node_set"])))
                            for cl in getattr(inp, "cload_info", ())]
+        self.expansion = getattr(inp, "expansion", None)
+        ti = getattr(inp, "temperature_info", None)
+        self.temperature_info = None if ti is None else {k: np.asarray(ti[k], dtype=np.float64)[part.l2g]
+                                                         for k in ("initial", "final")}

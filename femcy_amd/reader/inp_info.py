@@ -23,7 +23,8 @@ Reference behaviours that are kept on purpose:
 
 Beyond the reference (it reads `*Dsload` only and skips the rest): `*Density` inside a `*Material` block -> density,
 `*Dload` GRAV / BX / BY / BZ -> body_force_info, `*Cload` -> cload_info (read_loads).  Any other `*Dload` type is
-refused by name instead of being skipped.
+refused by name instead of being skipped.  `*Expansion` inside a `*Material` block -> expansion (isotropic, constant),
+`*Initial Conditions, type=TEMPERATURE` and `*Temperature` -> temperature_info (read_thermal).
 """
 import sys
 from typing import Dict, List
@@ -126,6 +127,7 @@ class InpInfo(InpInfoBase):
         self.dirichlet_bc_info, self.neumann_bc_info = self.get_boundary_condition(file)
         self.materials = self.read_material(file)
         self.density, self.body_force_info, self.cload_info = self.read_loads(file)
+        self.expansion, self.temperature_info = self.read_thermal(file)
         self.geometric_nonlinear = self.read_geometric_nonlinear(file)
         self.time_incs = self.read_time_inc(file)
 
@@ -274,6 +276,8 @@ class InpInfo(InpInfoBase):
                 expect_type = True
             elif line[0:8].lower() == "*density":             # Abaqus/CAE writes it first; it is not the material type
                 continue
+            elif line[0:10].lower() == "*expansion":          # neither is the expansion coefficient (read_thermal)
+                continue
             elif expect_type:
                 expect_type = False
                 data = [t for t in block if t]
@@ -371,6 +375,72 @@ class InpInfo(InpInfoBase):
                 raise ValueError("*Cload: degree of freedom {} on a {}-D mesh".format(f[1], dm))
             cload_info.append({"node_set": node_set, "dof": dof, "val": float(f[2])})
         return density, body_force_info, cload_info
+
+    # ------------------------------------------------------------------------- thermal loads
+    def _nodes_of(self, keyword, name):
+        """a node set by its name, or a bare node label through the label map of the connectivity (like `*Cload`)"""
+        if name in self.node_sets:
+            return self.node_sets[name]
+        try:
+            label = int(name)
+        except ValueError:
+            raise ValueError("{}: {} is neither a node set nor a node label".format(keyword, name)) from None
+        lut = self._label_lut
+        if not (0 <= label < lut.size) or lut[label] < 0:
+            raise ValueError("{}: no node with label {}".format(keyword, label))
+        return np.array([lut[label]], dtype=np.int64)
+
+    def read_thermal(self, fileName):
+        """-> expansion (float or None), temperature_info ({"initial": f64[nn], "final": f64[nn]} or None).
+        `*Expansion` (inside a `*Material` block, before or after the material type): one data line with one number, the
+        isotropic, constant coefficient alpha.  `zero=` is accepted: the reference temperature cancels for a constant
+        alpha.  `type=ORTHO` / `type=ANISO`, a second data line and a second column (temperature-dependent alpha) are
+        refused by name.
+        `*Initial Conditions, type=TEMPERATURE` and `*Temperature`: data lines `nset-or-node-label, T`.  A node that
+        `*Temperature` does not name keeps its initial value; a missing initial value is 0.  Any other
+        `*Initial Conditions` type is left alone.  `*Temperature` without `*Expansion` is an error."""
+        expansion, in_material = None, False
+        initial_lines, final_lines, seen = [], [], False
+        for line, block in _deck(fileName).keywords():
+            fields = [t.strip() for t in line.split(",")]
+            key = fields[0].lower()
+            params = {t.split("=")[0].strip().lower(): t.split("=")[1].strip() for t in fields[1:] if "=" in t}
+            if key == "*material":
+                in_material = True
+            elif key == "*expansion" and in_material:
+                kind = params.get("type", "ISO").upper()
+                if kind != "ISO":
+                    raise ValueError("*Expansion, type={} has not been supported (isotropic expansion is)".format(kind))
+                data = [t for t in block if t.strip()]
+                if not data:
+                    raise ValueError("*Expansion without a data line")
+                cols = [t for t in data[0].split(",") if t.strip()]
+                if len(data) > 1 or len(cols) > 1:
+                    raise ValueError("*Expansion: a temperature-dependent coefficient (more than one data line or a "
+                                     "second column) has not been supported")
+                expansion = float(cols[0])
+            elif key == "*initial conditions":
+                if params.get("type", "").upper() == "TEMPERATURE":
+                    seen = True
+                    initial_lines += [[t.strip() for t in d.split(",")] for d in block if d.strip()]
+            elif key == "*temperature":
+                seen = True
+                final_lines += [[t.strip() for t in d.split(",")] for d in block if d.strip()]
+        if not seen:
+            return expansion, None
+        if final_lines and expansion is None:
+            raise ValueError("*Temperature needs an *Expansion in the *Material block")
+        initial = np.zeros(len(self.nodes), dtype=np.float64)
+        for f in initial_lines:
+            if len(f) < 2 or not f[1]:
+                raise ValueError("*Initial Conditions, type=TEMPERATURE data line needs `nset-or-node, T`: {}".format(", ".join(f)))
+            initial[self._nodes_of("*Initial Conditions", f[0])] = float(f[1])
+        final = initial.copy()
+        for f in final_lines:
+            if len(f) < 2 or not f[1]:
+                raise ValueError("*Temperature data line needs `nset-or-node, T`: {}".format(", ".join(f)))
+            final[self._nodes_of("*Temperature", f[0])] = float(f[1])
+        return expansion, {"initial": initial, "final": final}
 
     # ---------------------------------------------------------------------- step definition
     def read_geometric_nonlinear(self, fileName) -> bool:

@@ -17,7 +17,10 @@ class InpInfoBase:
                   "neumann_bc_info", "materials", "geometric_nonlinear", "time_incs",
                   # loads beyond the reference's *Dsload: *Density (float or None), *Dload GRAV / BX / BY / BZ as
                   # [{"ele_set": index array or None, "force": f64[dm]}], *Cload as [{"node_set", "dof", "val"}]
-                  "density", "body_force_info", "cload_info")
+                  "density", "body_force_info", "cload_info",
+                  # thermal loads: *Expansion (float or None), *Initial Conditions, type=TEMPERATURE + *Temperature as
+                  # {"initial": f64[nn], "final": f64[nn]} or None
+                  "expansion", "temperature_info")
 
     def __init_subclass__(cls, **kwargs):
         super().__init_subclass__(**kwargs)

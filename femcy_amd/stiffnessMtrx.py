@@ -6,7 +6,8 @@ Same constructor, same public attributes (`dof`, `rhs`, `nodal_force`, `residual
 control flow for the increment / modified-Newton / line-search drivers (`solve`, `advance_inc`),
 but every kernel is a call into libfemcy_hip.so and every field is a handle to HBM-resident data
 (`.to_numpy()` downloads it).  Body forces (`*Dload` GRAV / BX / BY / BZ) and point loads (`*Cload`), which the
-reference does not have, are added to `rhs` after its `*Dsload` loop.  Nothing numerical runs on the CPU except
+reference does not have, are added to `rhs` after its `*Dsload` loop, and so is the load of a thermal strain
+(`*Expansion` + `*Temperature`, small strain only), whose stress `compute_strain_stress` then subtracts.  Nothing numerical runs on the CPU except
 the consistent Neumann loads (a per-facet loop in the reference too, stiffnessMtrx.py:369-411) and the user
 Dirichlet hook.
 
@@ -145,6 +146,7 @@ class System_of_equations:
         self._dofsets = {}
         self._loadsets = {}
         self._bodyloads = {}
+        self._thermal = None      # {"id", "scale"} of the thermal load that was applied last (compute_strain_stress)
         self.cg_log = []          # one entry per CG solve: iterations, max|r0|, max|r|, increment end time
         self.stats = {"assemblies": 0, "force_evals": 0, "linear_solves": 0, "cg_iterations": 0, "direct_solves": 0,
                       "direct_rejected": 0}
@@ -423,17 +425,26 @@ class System_of_equations:
         """rhs[node, dm_specified] += val for every node of the set (*Cload)."""
         self.ctx.dofset_add(self._dofset(nodeSet, dm_specified), be.VEC_RHS, val)
 
+    def thermalLoad(self, thermal: dict):
+        """rhs += scale x the consistent nodal load of the thermal strain alpha dT I (*Expansion + *Temperature), built
+        once on the undeformed geometry by `solve` (ctx.thermal)."""
+        self.ctx.thermal_apply(thermal["id"], thermal["scale"], be.VEC_RHS, add=True)
+        self._thermal = thermal
+
     def impose_boundary_condition(self, boundary_conditions: dict):
         for nb in boundary_conditions["neumannBCs"]:
             self.neumannBC(nb["face_set"], load_val=nb["traction"], load_dir=nb.get("direction", np.array([])))
         body_forces = boundary_conditions.get("bodyForces", ())
         cloads = boundary_conditions.get("cloads", ())
-        if (body_forces or cloads) and not boundary_conditions["neumannBCs"]:
+        thermal = boundary_conditions.get("thermal")
+        if (body_forces or cloads or thermal) and not boundary_conditions["neumannBCs"]:
             self.rhs.fill(0.0)              # no *Dsload refreshed rhs: the added loads start from zero
         for bf in body_forces:
             self.bodyForce(bf["ele_set"], bf["force"])
         for cl in cloads:
             self.cload(cl["node_set"], cl["dof"], cl["val"])
+        if thermal:
+            self.thermalLoad(thermal)
         for bc in boundary_conditions["dirichletBCs"]:
             if not self.geometric_nonlinear:
                 self.dirichletBC_linearEquations(bc["node_set"], bc["dof"], bc["val"])
@@ -455,6 +466,13 @@ class System_of_equations:
         if body_force_info or cload_info:          # decks without *Dload / *Cload make the calls they always made
             boundary_conditions["bodyForces"] = copy.deepcopy(body_force_info)
             boundary_conditions["cloads"] = copy.deepcopy(cload_info)
+        temperature_info, expansion = getattr(inp, "temperature_info", None), getattr(inp, "expansion", None)
+        if temperature_info is not None and expansion is not None:
+            if self.geometric_nonlinear or inp.geometric_nonlinear:
+                raise ValueError("a thermal load (*Expansion + *Temperature) with nlgeom has not been supported: the "
+                                 "thermal strain is a small-strain one")
+            dT = np.asarray(temperature_info["final"], dtype=np.float64) - np.asarray(temperature_info["initial"], dtype=np.float64)
+            boundary_conditions["thermal"] = {"id": self.ctx.thermal(self.ELE, expansion, dT), "scale": 0.0}
         self.increments = []
         kinc = -1
         while self.time1 < max_time:
@@ -468,6 +486,8 @@ class System_of_equations:
                 bf["force"] = np.asarray(body_force_info[i]["force"], dtype=np.float64) * load_ratio
             for i, cl in enumerate(boundary_conditions.get("cloads", ())):
                 cl["val"] = cload_info[i]["val"] * load_ratio
+            if "thermal" in boundary_conditions:     # the temperature ramps over the step like every other load
+                boundary_conditions["thermal"]["scale"] = load_ratio
             for i, bc in enumerate(dirichletBCs):
                 bc["val"] = inp.dirichlet_bc_info[i]["val"] * load_ratio
             converged, newton_loop = self.advance_inc(inp, boundary_conditions, show_newton_steps, save2path)
@@ -576,6 +596,8 @@ class System_of_equations:
         nlgeom: the stress of the last force evaluation) and von Mises stress per Gauss point, on the device
         (reference :436-501).  Results: .F, .strain, .cauchy_stress, .mises_stress (`.to_numpy()`)."""
         self.ctx.compute_strain_stress(be.VEC_DOF, large=self.geometric_nonlinear)
+        if self._thermal is not None:        # sigma = C : eps(u) - sigma_th at the temperature of the last increment
+            self.ctx.thermal_stress(self._thermal["id"], self._thermal["scale"])
 
     def get_elasEng(self):
         """total elastic energy = sum over Gauss points of elasticEnergyDensity(F) * vol (reference :592-606)."""

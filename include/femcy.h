@@ -258,7 +258,8 @@ int femcy_sync(femcy_ctx* ctx);                                   /* hipStreamSy
 
 /* ----------------------------------------------------------------------- problem definition */
 /* Body + System_of_equations.__init__ state (body.py:13-17, stiffnessMtrx.py:26-121).  Calling it again on a used
- * ctx starts over: element tables, material, pattern, DOF lists, load sets and body loads of the old mesh are dropped. */
+ * ctx starts over: element tables, material, pattern, DOF lists, load sets, body loads and thermal
+ * loads of the old mesh are dropped. */
 int femcy_set_mesh(femcy_ctx* ctx, int32_t nn, int32_t dm, const double* nodes /*[nn*dm]*/,
                    int32_t ne, int32_t npe, const int32_t* elems /*[ne*npe]*/);
 /* table-driven element plugin: ELE.gaussPoints/gaussWeights/dshape_dnat (element_zoo modules) */
@@ -367,6 +368,34 @@ int femcy_bodyload_create(femcy_ctx* ctx, const double* N /*[nGP][npe]*/, int32_
                           const int32_t* sel_elems /*[nsel], NULL = every element*/, int32_t* id_out);
 int femcy_bodyload_weights(femcy_ctx* ctx, int32_t id, double* out /*[nn]*/);
 int femcy_bodyload_apply(femcy_ctx* ctx, int32_t id, const double* b /*[dm]*/, int rhs_vec, int32_t add);
+/* Thermal loads (*Expansion + *Temperature; an extension, small strain only).  With nodal temperature changes dT_a the
+ * temperature change at a Gauss point is dT_g = sum_a N_a(xi_g) dT_a (the element's own shape functions, mid-side nodes
+ * included), the thermal strain is isotropic, eps_th = alpha dT_g I, and the stress of full restraint is
+ * sigma_th = C : eps_th with C as femcy_set_material received it:
+ *   FEMCY_MAT_LIN3D    eps_th = alpha dT (1,1,1,0,0,0)
+ *   FEMCY_MAT_PSTRESS  eps_th = alpha dT (1,1,0) against the plane-stress C
+ *   FEMCY_MAT_PSTRAIN  eps_zz = 0 is enforced: (1 + nu) alpha dT (1,1,0) against the plane-strain C, nu = params[1]
+ *   FEMCY_MAT_NEOHOOKE refused
+ * femcy_thermal_create evaluates, once, on the UNDEFORMED geometry, the consistent load at scale 1
+ *   f[a*dm + i] = sum over elements e and Gauss points g of sum_j dN_a/dx_j sigma_th[i][j] |det J_g| w_g
+ * with N [nGP][npe] = the plugin's shapeFunc at its Gauss points and dT [nn] (both are copied).  After
+ * femcy_set_element, femcy_set_material (the material of this moment is the one the load keeps) and femcy_build_pattern.
+ * Element pass + owner-computes node sums in a fixed order: the same bits on every run.  The load is linear in dT, so an
+ * increment only scales it.  femcy_thermal_force downloads f [n] (several ranks: the sum over the rank's own elements).
+ * femcy_thermal_apply writes (add = 0) or adds (add != 0) scale * f to vec[rhs]; scale travels in the kernel arguments (no
+ * copy, no stream synchronisation), the product is rounded before it is added.  Several ranks: apply sums over the
+ * interface like femcy_bodyload_apply, and with add through vector TMP1, which must then not be vec[rhs] (collective).
+ * femcy_thermal_stress corrects the result of femcy_compute_strain_stress(large = 0), once per such call:
+ * FEMCY_GP_SIGMA -= scale * sigma_th(dT_g) and FEMCY_GP_MISES is formed again by material kind (plane strain:
+ * sigma_zz = nu (sigma_xx + sigma_yy) - E alpha dT_g scale).  FEMCY_GP_STRAIN stays the total strain.
+ * Refused with FEMCY_EINVAL, the context stays usable: an unknown id, a neo-Hookean material, a null N or dT, a
+ * non-finite alpha, femcy_thermal_stress without a preceding femcy_compute_strain_stress(large = 0).
+ * Thermal loads are dropped where body loads are: femcy_set_mesh and femcy_ctx_destroy. */
+int femcy_thermal_create(femcy_ctx* ctx, const double* N /*[nGP][npe]*/, double alpha, const double* dT /*[nn]*/,
+                         int32_t* id_out);
+int femcy_thermal_force(femcy_ctx* ctx, int32_t id, double* out /*[n]*/);
+int femcy_thermal_apply(femcy_ctx* ctx, int32_t id, double scale, int rhs_vec, int32_t add);
+int femcy_thermal_stress(femcy_ctx* ctx, int32_t id, double scale);
 /* compute_Ad (conjugateGradientSolver.py:53-58): vec[y] = K vec[x] */
 int femcy_spmv(femcy_ctx* ctx, int x_vec, int y_vec);
 /* ConjugateGradientSolver_rowMajor.re_init + solve (conjugateGradientSolver.py:32-51, 103-127):
