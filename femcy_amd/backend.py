@@ -36,6 +36,7 @@ def default_backend() -> str:
 
 # enum femcy_vec
 VEC_DOF, VEC_RHS, VEC_RESIDUAL, VEC_FORCE, VEC_DU, VEC_DOF_OLD, VEC_X, VEC_TMP0, VEC_TMP1 = range(9)
+VEC_VEL, VEC_ACC = 9, 10     # implicit dynamics: nodal velocities and accelerations
 # enum femcy_gpfield
 GP_DSDX, GP_VOL, GP_F, GP_SIGMA, GP_STRAIN, GP_MISES, GP_ENERGY = range(7)
 # enum femcy_option
@@ -71,7 +72,9 @@ EXPORTS = [
     "femcy_dofset_create", "femcy_dofset_dirichlet_newton", "femcy_dofset_dirichlet_linear", "femcy_dofset_fill",
     "femcy_dofset_scatter", "femcy_dofset_add", "femcy_bodyload_create", "femcy_bodyload_weights", "femcy_bodyload_apply",
     "femcy_thermal_create", "femcy_thermal_force", "femcy_thermal_apply", "femcy_thermal_stress",
-    "femcy_loadset_create", "femcy_loadset_neumann", "femcy_loadset_neumann_add", "femcy_spmv", "femcy_pcg", "femcy_compute_strain_stress", "femcy_elastic_energy", "femcy_extrapolate",
+    "femcy_mass_create", "femcy_mass_get", "femcy_mass_apply", "femcy_mass_add_to_K", "femcy_mass_kinetic_energy",
+    "femcy_newmark_predict", "femcy_newmark_update",
+    "femcy_loadset_create", "femcy_loadset_neumann", "femcy_loadset_neumann_add", "femcy_spmv", "femcy_pcg", "femcy_compute_strain_stress", "femcy_elastic_energy", "femcy_elastic_energy_small", "femcy_extrapolate",
     "femcy_get_K_ell", "femcy_get_K_bsr", "femcy_get_gp_field", "femcy_timing",
     "femcy_timing_reset", "femcy_comm_unique_id", "femcy_comm_local_id", "femcy_comm_init", "femcy_comm_info", "femcy_comm_set_neighbours",
     "femcy_comm_tune", "femcy_iface_sum",
@@ -166,12 +169,18 @@ def _bind(lib, kind):
         "femcy_bodyload_apply": [p, i32, p, cint, i32],
         "femcy_thermal_create": [p, p, f64, p, C.POINTER(i32)], "femcy_thermal_force": [p, i32, p],
         "femcy_thermal_apply": [p, i32, f64, cint, i32], "femcy_thermal_stress": [p, i32, f64],
+        "femcy_mass_create": [p, i32, p, p, p, f64, C.POINTER(i32)], "femcy_mass_get": [p, i32, p],
+        "femcy_mass_apply": [p, i32, cint, cint, f64, i32], "femcy_mass_add_to_K": [p, i32, f64, i32],
+        "femcy_mass_kinetic_energy": [p, i32, cint, C.POINTER(f64)],
+        "femcy_newmark_predict": [p, cint, cint, cint, cint, f64, f64, f64],
+        "femcy_newmark_update": [p, cint, cint, cint, cint, f64, f64, f64],
         "femcy_loadset_create": [p, i32, i32, i32, p, p, p, p, p, i32, p, p, C.POINTER(i32)],
         "femcy_loadset_neumann": [p, i32, f64, p, cint],
         "femcy_loadset_neumann_add": [p, i32, f64, p, cint],
         "femcy_spmv": [p, cint, cint],
         "femcy_pcg": [p, cint, cint, f64, i32, C.POINTER(i32), C.POINTER(f64), C.POINTER(f64)],
         "femcy_compute_strain_stress": [p, cint, cint], "femcy_elastic_energy": [p, cint, C.POINTER(f64)],
+        "femcy_elastic_energy_small": [p, cint, C.POINTER(f64)],
         "femcy_extrapolate": [p, cint, cint, p, p],
         "femcy_get_K_ell": [p, p, p], "femcy_get_K_bsr": [p, p, p, p], "femcy_get_gp_field": [p, cint, p],
         "femcy_timing": [p, C.POINTER(Timing)], "femcy_timing_reset": [p],
@@ -483,6 +492,52 @@ class Context:
         """after compute_strain_stress(large=False): sigma -= scale * sigma_th, von Mises again."""
         self._call("femcy_thermal_stress", int(th), float(scale))
 
+    # device-resident consistent mass and the Newmark vector passes (*Dynamic)
+    def mass(self, ELE, rho: float) -> int:
+        """consistent mass M (x) I of the undeformed mesh at density rho, one scalar per stored block of K, integrated
+        with the plug-in's mass_rule()."""
+        t = ELE.mass_tables()
+        if t["Nq"].shape != (t["nq"], self.npe) or t["dNq"].shape != (t["nq"], self.npe, self.dm):
+            raise FemcyError(f"mass-rule tables do not match the mesh (npe={self.npe}, dm={self.dm})")
+        out = C.c_int32()
+        self._call("femcy_mass_create", int(t["nq"]), _ptr(t["Nq"]), _ptr(t["dNq"]), _ptr(t["wq"]), float(rho),
+                   C.byref(out))
+        return out.value
+
+    def mass_get(self, ms: int):
+        """scipy.sparse.csr_matrix [nn, nn] of the scalars m_ab (ascending columns, the block order of get_K_bsr)."""
+        import scipy.sparse as sp
+        info = self.pattern_info()
+        rowptr = np.empty(self.nn + 1, dtype=np.int32)
+        col = np.empty(info.nnzb, dtype=np.int32)
+        kv = np.empty((info.nnzb, self.dm, self.dm), dtype=np.float64)
+        self._call("femcy_get_K_bsr", _ptr(rowptr), _ptr(col), _ptr(kv))
+        vals = np.empty(info.nnzb, dtype=np.float64)
+        self._call("femcy_mass_get", int(ms), _ptr(vals))
+        return sp.csr_matrix((vals, col, rowptr), shape=(self.nn, self.nn))
+
+    def mass_apply(self, ms: int, x_vec: int, y_vec: int, scale: float = 1.0, add: bool = False):
+        """y = [y +] scale * (M (x) I) x"""
+        self._call("femcy_mass_apply", int(ms), int(x_vec), int(y_vec), float(scale), 1 if add else 0)
+
+    def mass_add_to_K(self, ms: int, c: float, overwrite: bool = False):
+        """K += c * M (x) I on the block diagonals (overwrite: K := c * M (x) I)"""
+        self._call("femcy_mass_add_to_K", int(ms), float(c), 1 if overwrite else 0)
+
+    def mass_kinetic_energy(self, ms: int, v_vec: int = VEC_VEL) -> float:
+        out = C.c_double()
+        self._call("femcy_mass_kinetic_energy", int(ms), int(v_vec), C.byref(out))
+        return out.value
+
+    def newmark_predict(self, u_vec: int, v_vec: int, a_vec: int, out_vec: int, c0: float, c1: float, c2: float):
+        """out = c0 u + c1 v + c2 a"""
+        self._call("femcy_newmark_predict", int(u_vec), int(v_vec), int(a_vec), int(out_vec), float(c0), float(c1), float(c2))
+
+    def newmark_update(self, u_new_vec: int, u_vec: int, v_vec: int, a_vec: int, beta: float, gamma: float, dt: float):
+        """a, v of t + dt in place of a, v, from the displacements u_new (t + dt) and u (t)"""
+        self._call("femcy_newmark_update", int(u_new_vec), int(u_vec), int(v_vec), int(a_vec), float(beta), float(gamma),
+                   float(dt))
+
     def spmv(self, x_vec: int, y_vec: int):
         self._call("femcy_spmv", int(x_vec), int(y_vec))
 
@@ -510,9 +565,11 @@ class Context:
     def compute_strain_stress(self, u_vec: int = VEC_DOF, large: bool = False):
         self._call("femcy_compute_strain_stress", int(u_vec), int(bool(large)))
 
-    def elastic_energy(self, u_vec: int = VEC_DOF) -> float:
+    def elastic_energy(self, u_vec: int = VEC_DOF, small: bool = False) -> float:
+        """small: the energy of the infinitesimal strain on the undeformed mesh (u.Ku / 2 of a linear analysis) instead of
+        the reference's energy of the Green strain"""
         out = C.c_double()
-        self._call("femcy_elastic_energy", int(u_vec), C.byref(out))
+        self._call("femcy_elastic_energy_small" if small else "femcy_elastic_energy", int(u_vec), C.byref(out))
         return out.value
 
     def extrapolate(self, gp_field: int, E: np.ndarray, comp: int = 0) -> np.ndarray:

@@ -312,6 +312,9 @@ struct Ctx {
     struct ThermalStress { double s[9]; };
     struct Thermal { double *d_f, *d_dT, *d_N; ThermalStress ts; };
     std::vector<Thermal> thermals;
+    // ---- device-resident consistent mass (femcy_mass_*): one scalar per stored block, in d_bcol's [block row][lane] layout
+    struct Mass { double* d_m; };
+    std::vector<Mass> masses;
     bool post_small = false;          // sigma / mises hold femcy_compute_strain_stress(large = 0), not yet corrected
 
     // ---- options / timing
@@ -400,6 +403,7 @@ int launch_geom(Ctx* c, const double* d_u, unsigned what);
 int ensure_gp_stress(Ctx* c);   // F / sigma of the last force evaluation, recomputed on demand (see Ctx::gp_lazy)
 int launch_post(Ctx* c, int large);
 int launch_energy(Ctx* c);
+int launch_energy_small(Ctx* c);   // d_energy = sigma : eps / 2 of the infinitesimal strain of d_F
 int launch_extrapolate(Ctx* c, const double* d_E, const double* d_field, int width, int comp, double* d_out);
 int launch_energy_sum(Ctx* c, double* total);
 int launch_assemble(Ctx* c);
@@ -410,6 +414,19 @@ int launch_body_apply(Ctx* c, const double* d_m, const double* b, bool add, doub
 int launch_thermal_force(Ctx* c, const Ctx::Thermal& th, double* d_fe);
 int launch_thermal_apply(Ctx* c, const double* d_funit, double scale, bool add, double* d_f);
 int launch_thermal_post(Ctx* c, const Ctx::Thermal& th, double scale);
+// consistent mass: element pass (rho |det J| w at the mass rule's points) into d_vq [ne][nq] (scratch of the caller), then one
+// scalar per stored block into d_m [stored_rows * 64]
+int launch_mass_blocks(Ctx* c, int32_t nq, const double* d_Nq, const double* d_dNq, const double* d_wq, double rho,
+                       double* d_vq, double* d_m);
+// d_y = [d_y +] scale (M (x) I) d_x (d_y may be null); d_partials != null: per-workgroup partials of x . (M x), count in *np
+int launch_mass_spmv(Ctx* c, const double* d_m, const double* d_x, double* d_y, double scale, bool add, double* d_partials,
+                     int* np);
+int launch_mass_add_to_K(Ctx* c, const double* d_m, double cc, bool overwrite);
+int launch_mass_energy(Ctx* c, const double* d_m, const double* d_v, double* out);
+int launch_newmark_predict(Ctx* c, const double* u, const double* v, const double* a, double* out, double c0, double c1,
+                           double c2);
+int launch_newmark_update(Ctx* c, const double* un, const double* u, double* v, double* a, double beta, double gamma,
+                          double dt);
 // pos_space: x and y are in STORAGE order (entry p * dm + c belongs to the node at storage position p = slice * 64 + lane;
 // the padding lanes of the last slice hold zeros) -- the form the three-kernel PCG runs in since round 4
 int launch_spmv(Ctx* c, const double* d_x, double* d_y, double* d_partials, int* nblocks_out, bool pos_space = false);

@@ -407,6 +407,23 @@ FEMCY_HD double energy_voigt3(const double (&F3)[3][3], const double (&C6)[6][6]
     return acc / 2.0;
 }
 
+// energy density of the INFINITESIMAL strain, sigma : eps / 2 with sigma = constitutiveOfSmallDeform(eps) and
+// eps = sym(F) - I: the quadratic form u.Ku / 2 per unit reference volume, which is what a linear (small-strain) analysis
+// stores and what the Newmark integrator conserves; energy_density below is the reference's energy of the GREEN strain and
+// differs from it by the order of the strain.  Linear materials only.
+template <int DM>
+FEMCY_HD double energy_density_small(int kind, const double* __restrict__ C, double p0, double p1,
+                                     const double (&F)[DM][DM]) {
+    double sig[DM][DM];
+    cauchy_small<DM>(kind, C, p0, p1, F, sig);
+    double acc = 0.0;
+#pragma unroll
+    for (int i = 0; i < DM; ++i)
+#pragma unroll
+        for (int j = 0; j < DM; ++j) acc += sig[i][j] * ((F[i][j] + F[j][i]) / 2.0 - (i == j ? 1.0 : 0.0));
+    return acc / 2.0;
+}
+
 template <int DM>
 FEMCY_HD double energy_density(int kind, const double* __restrict__ C, double p0, double p1,
                                                  const double (&F)[DM][DM]) {
@@ -719,6 +736,47 @@ FEMCY_HD void thermal_post_point(int kind, double p1, const double (&s)[DM][DM],
             ss += dv * dv;
         }
     *mises = sqrt(1.5 * ss);
+}
+
+// --------------------------------------------------------------------------------- implicit dynamics
+// one element of the consistent mass: vq[q * stride] = rho |det J_q| w_q at the nq points of the element's MASS rule, on
+// the UNDEFORMED coordinates X.  dNq[q][a][:] are the plugin's natural derivatives at those points (mass_rule(), not the
+// Gauss points of the stiffness).
+template <int NPE, int DM>
+FEMCY_HD void mass_points_element(const double (&X)[NPE][DM], int32_t nq, const double* __restrict__ dNq,
+                                  const double* __restrict__ wq, double rho, double* __restrict__ vq, int64_t stride) {
+    for (int32_t q = 0; q < nq; ++q) {
+        const double* __restrict__ dNg = dNq + q * NPE * DM;
+        double J[DM][DM], inv[DM][DM];
+#pragma unroll
+        for (int i = 0; i < DM; ++i)
+#pragma unroll
+            for (int j = 0; j < DM; ++j) {
+                double acc = 0.0;
+#pragma unroll
+                for (int a = 0; a < NPE; ++a) acc += X[a][i] * dNg[a * DM + j];
+                J[i][j] = acc;
+            }
+        vq[q * stride] = rho * (fabs(det_inv<DM>(J, inv)) * wq[q]);
+    }
+}
+
+// the contribution of one element to the mass block (a, b): sum_q (N_a N_b)(xi_q) vq[q].  The product N_a N_b is formed
+// first, so that (a, b) and (b, a) receive the same bits.
+FEMCY_HD double mass_pair(int32_t nq, int32_t npe, const double* __restrict__ Nq, int la, int lb,
+                          const double* __restrict__ vq) {
+    double acc = 0.0;
+    for (int32_t q = 0; q < nq; ++q) acc += (Nq[q * npe + la] * Nq[q * npe + lb]) * vq[q];
+    return acc;
+}
+
+// Newmark, one entry: a_new = b0 (u_new - u) - b1 v - b2 a with b0 = 1 / (beta dt^2), b1 = 1 / (beta dt),
+// b2 = 1 / (2 beta) - 1; v_new = v + dt ((1 - gamma) a + gamma a_new).  v and a are replaced.
+FEMCY_HD void newmark_update_entry(double un, double u, double& v, double& a, double b0, double b1, double b2, double dt,
+                                   double gamma) {
+    const double an = b0 * (un - u) - b1 * v - b2 * a;
+    v = v + dt * ((1.0 - gamma) * a + gamma * an);
+    a = an;
 }
 
 }  // namespace femcy

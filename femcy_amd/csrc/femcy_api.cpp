@@ -293,6 +293,8 @@ int femcy_ctx_destroy(femcy_ctx* ctx) {
     for (auto& th : c->thermals)
         for (void* q : {(void*)th.d_f, (void*)th.d_dT, (void*)th.d_N})
             if (q) (void)hipFree(q);
+    for (auto& ms : c->masses)
+        if (ms.d_m) (void)hipFree(ms.d_m);
     for (auto& p : c->ev_pool) {
         (void)hipEventDestroy(p.a);
         (void)hipEventDestroy(p.b);
@@ -523,6 +525,9 @@ int femcy_set_mesh(femcy_ctx* ctx, int32_t nn, int32_t dm, const double* nodes, 
         for (void* q : {(void*)th.d_f, (void*)th.d_dT, (void*)th.d_N})
             if (q) (void)hipFree(q);
     c->thermals.clear();
+    for (auto& ms : c->masses)
+        if (ms.d_m) (void)hipFree(ms.d_m);
+    c->masses.clear();
     c->post_small = false;
     c->have_material = false;
     c->nn = nn; c->dm = dm; c->ne = ne; c->npe = npe;
@@ -1200,6 +1205,123 @@ int femcy_thermal_stress(femcy_ctx* ctx, int32_t id, double scale) {
     return launch_thermal_post(c, th, scale);
 }
 
+// ------------------------------------------------------------------------------ implicit dynamics
+#define SINGLE_RANK_OR_FAIL(name) \
+    FEMCY_REQUIRE(!c->comm, name ": the consistent mass is not available on several ranks (femcy_comm_init has run)")
+
+int femcy_mass_create(femcy_ctx* ctx, int32_t nq, const double* Nq, const double* dNq, const double* wq, double rho,
+                      int32_t* id_out) {
+    CTX_OR_FAIL(ctx);
+    SINGLE_RANK_OR_FAIL("femcy_mass_create");
+    FEMCY_REQUIRE(c->have_mesh && c->have_element && c->have_pattern,
+                  "femcy_mass_create needs the mesh, the element tables and the pattern (mesh=%d element=%d pattern=%d)",
+                  (int)c->have_mesh, (int)c->have_element, (int)c->have_pattern);
+    FEMCY_REQUIRE(Nq && dNq && wq && id_out, "null mass-rule table or id_out");
+    FEMCY_REQUIRE(nq >= 1 && nq <= 64, "mass rule: %d points (1 .. 64 are supported)", nq);
+    FEMCY_REQUIRE(std::isfinite(rho) && rho > 0.0, "mass: the density must be finite and positive");
+    Ctx::Mass ms{nullptr};
+    double *d_Nq = nullptr, *d_dNq = nullptr, *d_wq = nullptr, *d_vq = nullptr;
+    const size_t npos = (size_t)c->stored_rows * SLICE;
+    int rc = to_device(&d_Nq, Nq, sizeof(double) * nq * c->npe);
+    if (!rc) rc = to_device(&d_dNq, dNq, sizeof(double) * nq * c->npe * c->dm);
+    if (!rc) rc = to_device(&d_wq, wq, sizeof(double) * nq);
+    if (!rc && dmalloc(&d_vq, sizeof(double) * (size_t)c->ne * nq) != hipSuccess) rc = FEMCY_ENOMEM;
+    if (!rc && dmalloc(&ms.d_m, std::max<size_t>(sizeof(double) * npos, 8)) != hipSuccess) rc = FEMCY_ENOMEM;
+    if (!rc) rc = launch_mass_blocks(c, nq, d_Nq, d_dNq, d_wq, rho, d_vq, ms.d_m);
+    // the tables and the element records are scratch of this call: wait for the two kernels, then release them
+    if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) {
+        set_error("mass: the assembly kernels failed");
+        rc = FEMCY_EHIP;
+    }
+    for (void* q : {(void*)d_Nq, (void*)d_dNq, (void*)d_wq, (void*)d_vq})
+        if (q) (void)hipFree(q);
+    if (rc) {
+        if (ms.d_m) (void)hipFree(ms.d_m);
+        if (rc == FEMCY_ENOMEM) set_error("out of device memory for a mass matrix on %d elements", c->ne);
+        return rc;
+    }
+    c->masses.push_back(ms);
+    *id_out = (int32_t)c->masses.size() - 1;
+    return FEMCY_OK;
+}
+
+#define MASS_OR_FAIL(id)                                                                          \
+    FEMCY_REQUIRE((id) >= 0 && (size_t)(id) < c->masses.size(), "unknown mass object %d", (int)(id)); \
+    const Ctx::Mass& ms = c->masses[(id)]
+
+int femcy_mass_get(femcy_ctx* ctx, int32_t id, double* vals) {
+    CTX_OR_FAIL(ctx);
+    SINGLE_RANK_OR_FAIL("femcy_mass_get");
+    MASS_OR_FAIL(id);
+    FEMCY_REQUIRE(vals, "null output");
+    std::vector<double> m((size_t)c->stored_rows * SLICE);
+    FEMCY_HIP(hipMemcpyAsync(m.data(), ms.d_m, sizeof(double) * m.size(), hipMemcpyDeviceToHost, c->stream));
+    FEMCY_HIP(hipStreamSynchronize(c->stream));
+    int64_t w = 0;
+    std::vector<std::pair<int32_t, int32_t>> order;
+    for (int32_t a = 0; a < c->nn; ++a) {       // the block order of femcy_get_K_bsr
+        const int64_t off = c->h_slice_off[c->h_pos[a] / SLICE];
+        const int lane = c->h_pos[a] % SLICE, L = c->h_rowlen[a];
+        order.clear();
+        for (int j = 0; j < L; ++j) order.push_back({c->h_bcol[(off + j) * SLICE + lane], j});
+        std::sort(order.begin(), order.end());
+        for (auto& pr : order) vals[w++] = m[(off + pr.second) * SLICE + lane];
+    }
+    return FEMCY_OK;
+}
+
+int femcy_mass_apply(femcy_ctx* ctx, int32_t id, int x_vec, int y_vec, double scale, int32_t add) {
+    CTX_OR_FAIL(ctx);
+    SINGLE_RANK_OR_FAIL("femcy_mass_apply");
+    VEC_OR_FAIL(x_vec);
+    VEC_OR_FAIL(y_vec);
+    MASS_OR_FAIL(id);
+    FEMCY_REQUIRE(x_vec != y_vec, "the mass product cannot run in place");
+    return launch_mass_spmv(c, ms.d_m, c->d_vec[x_vec], c->d_vec[y_vec], scale, add != 0, nullptr, nullptr);
+}
+
+int femcy_mass_add_to_K(femcy_ctx* ctx, int32_t id, double cc, int32_t overwrite) {
+    CTX_OR_FAIL(ctx);
+    SINGLE_RANK_OR_FAIL("femcy_mass_add_to_K");
+    MASS_OR_FAIL(id);
+    FEMCY_REQUIRE(std::isfinite(cc), "femcy_mass_add_to_K: the factor is not finite");
+    return launch_mass_add_to_K(c, ms.d_m, cc, overwrite != 0);
+}
+
+int femcy_mass_kinetic_energy(femcy_ctx* ctx, int32_t id, int v_vec, double* out) {
+    CTX_OR_FAIL(ctx);
+    SINGLE_RANK_OR_FAIL("femcy_mass_kinetic_energy");
+    VEC_OR_FAIL(v_vec);
+    MASS_OR_FAIL(id);
+    FEMCY_REQUIRE(out, "null output");
+    return launch_mass_energy(c, ms.d_m, c->d_vec[v_vec], out);
+}
+
+int femcy_newmark_predict(femcy_ctx* ctx, int u_vec, int v_vec, int a_vec, int out_vec, double c0, double c1, double c2) {
+    CTX_OR_FAIL(ctx);
+    VEC_OR_FAIL(u_vec);
+    VEC_OR_FAIL(v_vec);
+    VEC_OR_FAIL(a_vec);
+    VEC_OR_FAIL(out_vec);
+    FEMCY_REQUIRE(out_vec != u_vec && out_vec != v_vec && out_vec != a_vec,
+                  "femcy_newmark_predict: the output may not be one of the inputs");
+    return launch_newmark_predict(c, c->d_vec[u_vec], c->d_vec[v_vec], c->d_vec[a_vec], c->d_vec[out_vec], c0, c1, c2);
+}
+
+int femcy_newmark_update(femcy_ctx* ctx, int u_new_vec, int u_vec, int v_vec, int a_vec, double beta, double gamma,
+                         double dt) {
+    CTX_OR_FAIL(ctx);
+    VEC_OR_FAIL(u_new_vec);
+    VEC_OR_FAIL(u_vec);
+    VEC_OR_FAIL(v_vec);
+    VEC_OR_FAIL(a_vec);
+    FEMCY_REQUIRE(std::isfinite(beta) && beta > 0.0 && std::isfinite(gamma) && std::isfinite(dt) && dt > 0.0,
+                  "femcy_newmark_update: beta and dt must be positive, gamma finite");
+    FEMCY_REQUIRE(v_vec != a_vec && v_vec != u_vec && v_vec != u_new_vec && a_vec != u_vec && a_vec != u_new_vec,
+                  "femcy_newmark_update: velocity and acceleration are written in place and may alias nothing");
+    return launch_newmark_update(c, c->d_vec[u_new_vec], c->d_vec[u_vec], c->d_vec[v_vec], c->d_vec[a_vec], beta, gamma, dt);
+}
+
 int femcy_spmv(femcy_ctx* ctx, int x_vec, int y_vec) {
     CTX_OR_FAIL(ctx);
     FEMCY_REQUIRE(c->have_pattern, "pattern not built");
@@ -1269,6 +1391,21 @@ int femcy_elastic_energy(femcy_ctx* ctx, int u_vec, double* total) {
     if (rc) return rc;
     if ((rc = launch_geom(c, c->d_vec[u_vec], GEOM_F))) return rc;
     if ((rc = launch_energy(c))) return rc;
+    return launch_energy_sum(c, total);
+}
+
+int femcy_elastic_energy_small(femcy_ctx* ctx, int u_vec, double* total) {
+    CTX_OR_FAIL(ctx);
+    FEMCY_REQUIRE(c->have_mesh && c->have_element && c->have_material && total, "context not fully defined");
+    VEC_OR_FAIL(u_vec);
+    FEMCY_REQUIRE(c->mat_kind != FEMCY_MAT_NEOHOOKE, "femcy_elastic_energy_small: a neo-Hookean material has no small-strain "
+                  "energy (linear materials only)");
+    int rc = ensure_gp_stress(c);
+    if (rc) return rc;
+    if ((rc = launch_geom(c, c->d_vec[u_vec], GEOM_F))) return rc;
+    if ((rc = launch_energy_small(c))) return rc;
+    // the weights det J w of the UNDEFORMED mesh (the F pass left those of the displaced one)
+    if ((rc = launch_geom(c, nullptr, GEOM_DSDX))) return rc;
     return launch_energy_sum(c, total);
 }
 

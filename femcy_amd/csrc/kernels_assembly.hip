@@ -1388,6 +1388,21 @@ __global__ void __launch_bounds__(256) k_energy(int64_t ngp, int kind, const dou
     energy[t] = energy_density<DM>(kind, C, p0, p1, F);
 }
 
+// the same for the energy of the infinitesimal strain (femcy_elastic_energy_small)
+template <int DM>
+__global__ void __launch_bounds__(256) k_energy_small(int64_t ngp, int kind, const double* __restrict__ C, double p0,
+                                                      double p1, const double* __restrict__ Fin,
+                                                      double* __restrict__ energy) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= ngp) return;
+    double F[DM][DM];
+#pragma unroll
+    for (int i = 0; i < DM; ++i)
+#pragma unroll
+        for (int j = 0; j < DM; ++j) F[i][j] = Fin[t * DM * DM + i * DM + j];
+    energy[t] = energy_density_small<DM>(kind, C, p0, p1, F);
+}
+
 // ELE.extrapolate (element_zoo/*.py): nodal_vals[e][a] = sum_g E[a][g] * field[e][g][comp]
 __global__ void __launch_bounds__(256) k_extrapolate(int64_t ne, int npe, int nGP, int width, int comp,
                                                      const double* __restrict__ E, const double* __restrict__ field,
@@ -1435,6 +1450,19 @@ int launch_energy(Ctx* c) {
                            c->mat_params[0], c->mat_params[1], c->d_F, c->d_energy);
     else
         hipLaunchKernelGGL((k_energy<2>), dim3(grid), dim3(bs), 0, c->stream, ngp, c->mat_kind, c->d_C,
+                           c->mat_params[0], c->mat_params[1], c->d_F, c->d_energy);
+    FEMCY_HIP(hipGetLastError());
+    return FEMCY_OK;
+}
+
+int launch_energy_small(Ctx* c) {
+    const int64_t ngp = (int64_t)c->ne * c->nGP;
+    const int bs = 256, grid = (int)((ngp + bs - 1) / bs);
+    if (c->dm == 3)
+        hipLaunchKernelGGL((k_energy_small<3>), dim3(grid), dim3(bs), 0, c->stream, ngp, c->mat_kind, c->d_C,
+                           c->mat_params[0], c->mat_params[1], c->d_F, c->d_energy);
+    else
+        hipLaunchKernelGGL((k_energy_small<2>), dim3(grid), dim3(bs), 0, c->stream, ngp, c->mat_kind, c->d_C,
                            c->mat_params[0], c->mat_params[1], c->d_F, c->d_energy);
     FEMCY_HIP(hipGetLastError());
     return FEMCY_OK;
@@ -1638,6 +1666,49 @@ __global__ void __launch_bounds__(256) k_thermal_post(int64_t ngp, int32_t nGP, 
     thermal_post_point<DM>(kind, p1, s, scale * tg, sigma + t * DM * DM, mises + t);
 }
 
+// ------------------------------------------------------------------------------- consistent mass
+// *Dynamic: the mass matrix M (x) I_dm with m_ab = sum_e sum_q N_a N_b rho |det J_q| w_q on the undeformed mesh, one scalar
+// per stored block.  It is built once per run (femcy_mass_create), so neither pass is tuned beyond coalesced reads of the
+// contribution lists.  Element pass in the shape of k_body_weights: one thread per element, the tables dNq / wq of the MASS
+// rule wave-uniform, node rows by load_row; the nq values rho |det J_q| w_q of an element go to vq[e][0..nq).
+template <int NPE, int DM>
+__global__ void __launch_bounds__(256) k_mass_points(int32_t ne, int32_t nq, const double* __restrict__ nodes,
+                                                     const int32_t* __restrict__ elems, const double* __restrict__ dNq,
+                                                     const double* __restrict__ wq, double rho, double* __restrict__ vq) {
+    const int32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= ne) return;
+    double X[NPE][DM];
+#pragma unroll
+    for (int a = 0; a < NPE; ++a) load_row<DM>(nodes + (int64_t)elems[(int64_t)e * NPE + a] * DM, X[a]);
+    mass_points_element<NPE, DM>(X, nq, dNq, wq, rho, vq + (int64_t)e * nq, 1);
+}
+
+// owner-computes block pass: one lane per stored block p (bcol's layout), which walks its contributions ctr[ctr_ptr[p] ..
+// ctr_ptr[p+1]) -- codes (e * npe + la) * npe + lb in ascending order, the order of the stiffness assembly -- and sums
+// sum_q N_a N_b vq[e][q].  The shape-function table of the mass rule (up to 36 x 10 doubles) is staged once per workgroup
+// in LDS.  No atomics: the same bits on every run; a padding block has no contributions and holds 0.
+constexpr int MASS_TABLE_MAX = 64 * 10;
+__global__ void __launch_bounds__(256) k_mass_blocks(int64_t npos, int32_t nq, int32_t npe,
+                                                     const int32_t* __restrict__ ctr_ptr, const int32_t* __restrict__ ctr,
+                                                     const double* __restrict__ Nq, const double* __restrict__ vq,
+                                                     double* __restrict__ m) {
+    __shared__ double sN[MASS_TABLE_MAX];
+    for (int i = threadIdx.x; i < nq * npe; i += 256) sN[i] = Nq[i];
+    __syncthreads();
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= npos) return;
+    double acc = 0.0;
+    const int32_t k1 = ctr_ptr[p + 1];
+    for (int32_t k = ctr_ptr[p]; k < k1; ++k) {
+        const int32_t code = ctr[k];
+        const int lb = code % npe;
+        const int32_t t = code / npe;
+        const int la = t % npe;
+        acc += mass_pair(nq, npe, sN, la, lb, vq + (int64_t)(t / npe) * nq);
+    }
+    m[p] = acc;
+}
+
 int launch_extrapolate(Ctx* c, const double* d_E, const double* d_field, int width, int comp, double* d_out) {
     const int64_t total = (int64_t)c->ne * c->npe;
     hipLaunchKernelGGL(k_extrapolate, dim3((int)((total + 255) / 256)), dim3(256), 0, c->stream, (int64_t)c->ne, c->npe,
@@ -1810,6 +1881,41 @@ int launch_thermal_post(Ctx* c, const Ctx::Thermal& th, double scale) {
         hipLaunchKernelGGL((k_thermal_post<2>), dim3(grid), dim3(bs), 0, c->stream, ngp, c->nGP, c->npe, c->mat_kind,
                            c->mat_params[1], c->d_elems, th.d_N, th.d_dT, th.ts, scale, c->d_sigma, c->d_mises);
     timing_end(c, tm);
+    FEMCY_HIP(hipGetLastError());
+    return FEMCY_OK;
+}
+
+int launch_mass_blocks(Ctx* c, int32_t nq, const double* d_Nq, const double* d_dNq, const double* d_wq, double rho,
+                       double* d_vq, double* d_m) {
+    if (nq < 1 || nq * c->npe > MASS_TABLE_MAX) {
+        set_error("mass rule of %d points x %d nodes exceeds the staged table (%d entries)", nq, c->npe, MASS_TABLE_MAX);
+        return FEMCY_EINVAL;
+    }
+    const int bs = 256, grid = (c->ne + bs - 1) / bs;
+    bool launched = false;
+    size_t tm = timing_begin(c, T_GEOM);          // events only under FEMCY_OPT_TIMING (tools/dynamic_record.py)
+#define MASS_CALL                                                                                                   \
+    hipLaunchKernelGGL((k_mass_points<NPE, DM>), dim3(grid), dim3(bs), 0, c->stream, c->ne, nq, c->d_nodes, c->d_elems, \
+                       d_dNq, d_wq, rho, d_vq)
+    FEMCY_DISPATCH_ELEMENT(3, 2, MASS_CALL)
+    FEMCY_DISPATCH_ELEMENT(4, 2, MASS_CALL)
+    FEMCY_DISPATCH_ELEMENT(6, 2, MASS_CALL)
+    FEMCY_DISPATCH_ELEMENT(8, 2, MASS_CALL)
+    FEMCY_DISPATCH_ELEMENT(4, 3, MASS_CALL)
+    FEMCY_DISPATCH_ELEMENT(10, 3, MASS_CALL)
+    FEMCY_DISPATCH_ELEMENT(8, 3, MASS_CALL)
+    FEMCY_DISPATCH_ELEMENT(6, 3, MASS_CALL)
+#undef MASS_CALL
+    if (launched) {
+        const int64_t npos = c->stored_rows * SLICE;
+        hipLaunchKernelGGL(k_mass_blocks, dim3((unsigned)((npos + bs - 1) / bs)), dim3(bs), 0, c->stream, npos, nq, c->npe,
+                           c->d_ctr_ptr, c->d_ctr, d_Nq, d_vq, d_m);
+    }
+    timing_end(c, tm);
+    if (!launched) {
+        set_error("no mass kernel instantiated for npe=%d dm=%d", c->npe, c->dm);
+        return FEMCY_ENOKERNEL;
+    }
     FEMCY_HIP(hipGetLastError());
     return FEMCY_OK;
 }

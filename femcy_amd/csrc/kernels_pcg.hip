@@ -27,6 +27,7 @@
 #include <type_traits>
 #include <hip/hip_ext.h>
 #include "ctx.hpp"
+#include "element_math.hpp"
 #include "wave_reduce.hpp"
 
 namespace femcy {
@@ -1559,6 +1560,178 @@ int pcg_solve(Ctx* c, const double* d_b, double* d_x, double eps, int32_t maxit,
         set_error("PCG breakdown: NaN/Inf residual after %d iterations (r0 = %g)", c->h_state->iters, c->h_state->r0);
         return FEMCY_ENUMERIC;
     }
+    return FEMCY_OK;
+}
+
+// ------------------------------------------------------------------------------ implicit dynamics
+// y = [y +] scale (M (x) I_dm) x with the consistent mass stored as ONE scalar per block in bcol's layout (femcy_mass_create):
+// 12 bytes per stored block (column + scalar) where k_spmv streams 4 + 8 dm^2, the same gathers through gather_x.  Launch
+// shape and slice ranges are k_spmv's at one wave per slice: XCD k walks its contiguous range of c->xcd, four slices per
+// workgroup task, lane = node; the rounds are not rotated (the scalar rows are short).  y == nullptr: nothing is stored;
+// partials != nullptr: per-workgroup partials of x . (M x) in a fixed order (the kinetic energy).
+template <int DM>
+__global__ void __launch_bounds__(BS) k_mass_spmv(int32_t nn, XcdRanges xr, const int32_t* __restrict__ slice_len,
+                                                  const int64_t* __restrict__ slice_off,
+                                                  const int32_t* __restrict__ bcol, const int32_t* __restrict__ node_of,
+                                                  const double* __restrict__ mvals, const double* __restrict__ x,
+                                                  double* __restrict__ y, double scale, int add,
+                                                  double* __restrict__ partials) {
+    __shared__ double sm[BS / 64];
+    const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, (int)std::min<size_t>((size_t)nn * DM * sizeof(double), 0x7fffffffu), 0x00020000);
+    constexpr int SPB = BS / 64;
+    const int k = blockIdx.x % NXCD;
+    const int bpx = gridDim.x / NXCD;
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int s_end = xr.start[k + 1];
+    const int ntask = (s_end - xr.start[k] + SPB - 1) / SPB;
+    const int wgx = blockIdx.x / NXCD;
+    double dot = 0.0;
+    for (int rnd = 0; rnd * bpx < ntask; ++rnd) {
+        const int s = xr.start[k] + (rnd * bpx + wgx) * SPB + wave;
+        if (s >= s_end) continue;
+        const int32_t L = slice_len[s];
+        const int64_t off = slice_off[s];
+        const int32_t* __restrict__ bc = bcol + off * SLICE + lane;
+        const double* __restrict__ mp = mvals + off * SLICE + lane;
+        double acc[DM];
+#pragma unroll
+        for (int r = 0; r < DM; ++r) acc[r] = 0.0;
+#pragma unroll 2
+        for (int32_t j = 0; j < L; ++j) {
+            const int32_t col = bc[(int64_t)j * SLICE];
+            const double mj = mp[(int64_t)j * SLICE];
+            double xv[DM];
+            gather_x<DM>(xrsrc, col, xv);
+#pragma unroll
+            for (int r = 0; r < DM; ++r) acc[r] += mj * xv[r];
+        }
+        const int64_t a = node_of[(int64_t)s * SLICE + lane];      // -1 = padding lane
+        if (a >= 0) {
+#pragma unroll
+            for (int r = 0; r < DM; ++r) {
+                if (y) y[a * DM + r] = add ? y[a * DM + r] + scale * acc[r] : scale * acc[r];
+                if (partials) dot += x[a * DM + r] * acc[r];
+            }
+        }
+    }
+    if (partials) {
+        const double t = block_sum(dot, sm);
+        if (threadIdx.x == 0) partials[blockIdx.x] = t;
+    }
+}
+
+// K += c M (x) I: one lane per stored block p = row * 64 + lane, the dm diagonal entries of the block through kv_index; the
+// product is rounded before it is added.  overwrite: every entry of the block is written, K := c M (x) I.
+template <int DM>
+__global__ void __launch_bounds__(BS) k_mass_add_to_K(int64_t npos, const double* __restrict__ mvals, double cc,
+                                                      int overwrite, double* __restrict__ K) {
+    const int64_t p = (int64_t)blockIdx.x * BS + threadIdx.x;
+    if (p >= npos) return;
+    const int64_t row = p >> 6;
+    const int lane = (int)(p & 63);
+    const double v = __dmul_rn(cc, mvals[p]);
+    if (overwrite) {
+#pragma unroll
+        for (int q = 0; q < DM * DM; ++q) K[kv_index<DM>(row, q, lane)] = (q % (DM + 1) == 0) ? v : 0.0;
+    } else {
+#pragma unroll
+        for (int d = 0; d < DM; ++d) {
+            const int64_t i = kv_index<DM>(row, d * (DM + 1), lane);
+            K[i] = __dadd_rn(K[i], v);
+        }
+    }
+}
+
+// out = c0 u + c1 v + c2 a, one pass, two entries per lane (the vectors are padded with zeros past n)
+__global__ void __launch_bounds__(BS) k_newmark_predict(int64_t n2, const double2* __restrict__ u,
+                                                        const double2* __restrict__ v, const double2* __restrict__ a,
+                                                        double2* __restrict__ out, double c0, double c1, double c2) {
+    for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < n2; i += (int64_t)gridDim.x * BS) {
+        const double2 uu = u[i], vv = v[i], aa = a[i];
+        out[i] = make_double2(c0 * uu.x + c1 * vv.x + c2 * aa.x, c0 * uu.y + c1 * vv.y + c2 * aa.y);
+    }
+}
+// a_new, v_new in place of a, v (element_math.hpp: newmark_update_entry), one pass
+__global__ void __launch_bounds__(BS) k_newmark_update(int64_t n2, const double2* __restrict__ un,
+                                                       const double2* __restrict__ u, double2* __restrict__ v,
+                                                       double2* __restrict__ a, double b0, double b1, double b2, double dt,
+                                                       double gamma) {
+    for (int64_t i = (int64_t)blockIdx.x * BS + threadIdx.x; i < n2; i += (int64_t)gridDim.x * BS) {
+        const double2 nn = un[i], uu = u[i];
+        double2 vv = v[i], aa = a[i];
+        newmark_update_entry(nn.x, uu.x, vv.x, aa.x, b0, b1, b2, dt, gamma);
+        newmark_update_entry(nn.y, uu.y, vv.y, aa.y, b0, b1, b2, dt, gamma);
+        v[i] = vv;
+        a[i] = aa;
+    }
+}
+
+int launch_mass_spmv(Ctx* c, const double* d_m, const double* d_x, double* d_y, double scale, bool add, double* d_partials,
+                     int* np) {
+    const int grid = c->spmv_grid;
+    if (d_partials && grid > MAX_PARTIALS) {
+        set_error("mass product grid %d exceeds MAX_PARTIALS %d", grid, MAX_PARTIALS);
+        return FEMCY_EINVAL;
+    }
+    size_t tm = timing_begin(c, T_GEOM);          // events only under FEMCY_OPT_TIMING (tools/dynamic_record.py)
+#define MASS_SPMV_ARGS                                                                                            \
+    c->nn, c->xcd, (const int32_t*)c->d_slice_len, (const int64_t*)c->d_slice_off, (const int32_t*)c->d_bcol,     \
+        (const int32_t*)c->d_node_of, d_m, d_x, d_y, scale, add ? 1 : 0, d_partials
+    if (c->dm == 3) hipLaunchKernelGGL((k_mass_spmv<3>), dim3(grid), dim3(BS), 0, c->stream, MASS_SPMV_ARGS);
+    else hipLaunchKernelGGL((k_mass_spmv<2>), dim3(grid), dim3(BS), 0, c->stream, MASS_SPMV_ARGS);
+#undef MASS_SPMV_ARGS
+    timing_end(c, tm);
+    FEMCY_HIP(hipGetLastError());
+    if (np) *np = grid;
+    return FEMCY_OK;
+}
+
+int launch_mass_add_to_K(Ctx* c, const double* d_m, double cc, bool overwrite) {
+    const int64_t npos = c->stored_rows * SLICE;
+    const unsigned grid = (unsigned)((npos + BS - 1) / BS);
+    if (!grid) return FEMCY_OK;
+    size_t tm = timing_begin(c, T_GEOM);
+    if (c->dm == 3) hipLaunchKernelGGL((k_mass_add_to_K<3>), dim3(grid), dim3(BS), 0, c->stream, npos, d_m, cc, overwrite ? 1 : 0, c->d_Kvals);
+    else hipLaunchKernelGGL((k_mass_add_to_K<2>), dim3(grid), dim3(BS), 0, c->stream, npos, d_m, cc, overwrite ? 1 : 0, c->d_Kvals);
+    timing_end(c, tm);
+    FEMCY_HIP(hipGetLastError());
+    return FEMCY_OK;
+}
+
+// 1/2 v . (M v): the product's per-workgroup partials, re-reduced by one workgroup in a fixed order
+int launch_mass_energy(Ctx* c, const double* d_m, const double* d_v, double* out) {
+    int np = 0;
+    int rc = launch_mass_spmv(c, d_m, d_v, nullptr, 1.0, false, c->d_part1, &np);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_reduce_final, dim3(1), dim3(BS), 0, c->stream, np, c->d_part1, 0, c->d_part2);
+    FEMCY_HIP(hipGetLastError());
+    double s = 0.0;
+    if ((rc = scalar_across_ranks(c, c->d_part2, 0, &s))) return rc;
+    *out = 0.5 * s;
+    return FEMCY_OK;
+}
+
+int launch_newmark_predict(Ctx* c, const double* u, const double* v, const double* a, double* out, double c0, double c1,
+                           double c2) {
+    const int64_t n2 = (c->n + 1) / 2;
+    size_t tm = timing_begin(c, T_GEOM);
+    hipLaunchKernelGGL(k_newmark_predict, dim3(ew_grid(c, n2)), dim3(BS), 0, c->stream, n2, (const double2*)u,
+                       (const double2*)v, (const double2*)a, (double2*)out, c0, c1, c2);
+    timing_end(c, tm);
+    FEMCY_HIP(hipGetLastError());
+    return FEMCY_OK;
+}
+
+int launch_newmark_update(Ctx* c, const double* un, const double* u, double* v, double* a, double beta, double gamma,
+                          double dt) {
+    const int64_t n2 = (c->n + 1) / 2;
+    size_t tm = timing_begin(c, T_GEOM);
+    hipLaunchKernelGGL(k_newmark_update, dim3(ew_grid(c, n2)), dim3(BS), 0, c->stream, n2, (const double2*)un,
+                       (const double2*)u, (double2*)v, (double2*)a, 1.0 / (beta * dt * dt), 1.0 / (beta * dt),
+                       1.0 / (2.0 * beta) - 1.0, dt, gamma);
+    timing_end(c, tm);
+    FEMCY_HIP(hipGetLastError());
     return FEMCY_OK;
 }
 

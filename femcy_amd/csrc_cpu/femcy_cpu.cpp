@@ -65,6 +65,9 @@ struct LoadSet {
 struct BodyLoad {
     std::vector<double> m;   // [nn] nodal weights
 };
+struct Mass {
+    std::vector<double> m;   // [blocks of the block-CSR matrix] one scalar per block, K's block order
+};
 struct Thermal {
     std::vector<double> f, dT, N;   // [n] load at scale 1, [nn] temperature changes, [nGP][npe] shape functions
     double s[9];                    // stress of full restraint per unit temperature change, row-major tensor
@@ -95,6 +98,7 @@ struct femcy_ctx {
     std::vector<LoadSet> loadsets;
     std::vector<BodyLoad> bodyloads;
     std::vector<Thermal> thermals;
+    std::vector<Mass> masses;
     bool post_small = false;              // sigma / mises hold femcy_compute_strain_stress(large = 0), not yet corrected
     int opt_tangent = 0, opt_timing = 0;
     femcy_timing_t timing{};
@@ -455,6 +459,7 @@ int femcy_set_mesh(femcy_ctx* ctx, int32_t nn, int32_t dm, const double* nodes, 
     c->loadsets.clear();
     c->bodyloads.clear();
     c->thermals.clear();
+    c->masses.clear();
     c->post_small = false;
     c->nn = nn; c->dm = dm; c->ne = ne; c->npe = npe;
     c->n = (int64_t)nn * dm;
@@ -1150,6 +1155,189 @@ int femcy_thermal_stress(femcy_ctx* ctx, int32_t id, double scale) {
     return FEMCY_OK;
 }
 
+// ------------------------------------------------------------------------------ implicit dynamics
+}  // extern "C"
+namespace {
+// the two passes of the device's femcy_mass_create (csrc/element_math.hpp: mass_points_element, mass_pair): rho |det J| w at
+// the mass rule's points per element, then every block of a row from the row's incident elements in ascending order
+template <int NPE, int DM>
+void mass_blocks(femcy_ctx* c, int32_t nq, const double* Nq, const double* dNq, const double* wq, double rho,
+                 std::vector<double>& m) {
+    std::vector<double> vq((size_t)c->ne * nq, 0.0);
+#pragma omp parallel for schedule(static)
+    for (int32_t e = 0; e < c->ne; ++e) {
+        double X[NPE][DM];
+        for (int a = 0; a < NPE; ++a)
+            for (int i = 0; i < DM; ++i) X[a][i] = c->nodes[(int64_t)c->elems[(int64_t)e * NPE + a] * DM + i];
+        mass_points_element<NPE, DM>(X, nq, dNq, wq, rho, vq.data() + (size_t)e * nq, 1);
+    }
+    m.assign(c->col.size(), 0.0);
+#pragma omp parallel for schedule(static)
+    for (int32_t a = 0; a < c->nn; ++a)
+        for (int32_t k = c->ne_ptr[a]; k < c->ne_ptr[a + 1]; ++k) {
+            const int32_t code = c->ne_idx[k];
+            const int64_t e = code / NPE;
+            const int la = code - (int32_t)e * NPE;
+            for (int lb = 0; lb < NPE; ++lb)
+                m[c->eslot[((int64_t)e * NPE + la) * NPE + lb]] += mass_pair(nq, NPE, Nq, la, lb, vq.data() + (size_t)e * nq);
+        }
+}
+}  // namespace
+extern "C" {
+
+int femcy_mass_create(femcy_ctx* ctx, int32_t nq, const double* Nq, const double* dNq, const double* wq, double rho,
+                      int32_t* id_out) {
+    CTX_OR_FAIL(ctx);
+    REQUIRE(c->have_mesh && c->have_element && c->have_pattern,
+            "femcy_mass_create needs the mesh, the element tables and the pattern (mesh=%d element=%d pattern=%d)",
+            (int)c->have_mesh, (int)c->have_element, (int)c->have_pattern);
+    REQUIRE(Nq && dNq && wq && id_out, "null mass-rule table or id_out");
+    REQUIRE(nq >= 1 && nq <= 64, "mass rule: %d points (1 .. 64 are supported)", nq);
+    REQUIRE(std::isfinite(rho) && rho > 0.0, "mass: the density must be finite and positive");
+    Mass ms;
+    const int key = c->npe * 10 + c->dm;
+    switch (key) {
+        case 32: mass_blocks<3, 2>(c, nq, Nq, dNq, wq, rho, ms.m); break;
+        case 42: mass_blocks<4, 2>(c, nq, Nq, dNq, wq, rho, ms.m); break;
+        case 62: mass_blocks<6, 2>(c, nq, Nq, dNq, wq, rho, ms.m); break;
+        case 82: mass_blocks<8, 2>(c, nq, Nq, dNq, wq, rho, ms.m); break;
+        case 43: mass_blocks<4, 3>(c, nq, Nq, dNq, wq, rho, ms.m); break;
+        case 103: mass_blocks<10, 3>(c, nq, Nq, dNq, wq, rho, ms.m); break;
+        case 83: mass_blocks<8, 3>(c, nq, Nq, dNq, wq, rho, ms.m); break;
+        case 63: mass_blocks<6, 3>(c, nq, Nq, dNq, wq, rho, ms.m); break;
+        default:
+            set_error("no mass kernel instantiated for npe=%d dm=%d", c->npe, c->dm);
+            return FEMCY_ENOKERNEL;
+    }
+    c->masses.push_back(std::move(ms));
+    *id_out = (int32_t)c->masses.size() - 1;
+    return FEMCY_OK;
+}
+#define MASS_OR_FAIL(id)                                                                    \
+    REQUIRE((id) >= 0 && (size_t)(id) < c->masses.size(), "unknown mass object %d", (int)(id)); \
+    const Mass& ms = c->masses[(id)]
+
+int femcy_mass_get(femcy_ctx* ctx, int32_t id, double* vals) {
+    CTX_OR_FAIL(ctx);
+    MASS_OR_FAIL(id);
+    REQUIRE(vals, "null output");
+    int64_t w = 0;
+    std::vector<std::pair<int32_t, int64_t>> order;
+    for (int32_t a = 0; a < c->nn; ++a) {       // the block order of femcy_get_K_bsr
+        order.clear();
+        for (int64_t p = c->rowptr[a]; p < c->rowptr[a + 1]; ++p) order.push_back({c->col[p], p});
+        std::sort(order.begin(), order.end());
+        for (auto& pr : order) vals[w++] = ms.m[pr.second];
+    }
+    return FEMCY_OK;
+}
+
+int femcy_mass_apply(femcy_ctx* ctx, int32_t id, int x_vec, int y_vec, double scale, int32_t add) {
+    CTX_OR_FAIL(ctx);
+    VEC_OR_FAIL(x_vec);
+    VEC_OR_FAIL(y_vec);
+    MASS_OR_FAIL(id);
+    REQUIRE(x_vec != y_vec, "the mass product cannot run in place");
+    const double* x = c->vec[x_vec].data();
+    double* y = c->vec[y_vec].data();
+    const int dm = c->dm;
+#pragma omp parallel for schedule(static)
+    for (int32_t a = 0; a < c->nn; ++a) {
+        double acc[3] = {0.0, 0.0, 0.0};
+        for (int64_t p = c->rowptr[a]; p < c->rowptr[a + 1]; ++p) {
+            const double* xv = x + (int64_t)c->col[p] * dm;
+            for (int r = 0; r < dm; ++r) acc[r] += ms.m[p] * xv[r];
+        }
+        for (int r = 0; r < dm; ++r) {
+            double& dst = y[(int64_t)a * dm + r];
+            dst = add ? dst + scale * acc[r] : scale * acc[r];
+        }
+    }
+    return FEMCY_OK;
+}
+
+int femcy_mass_add_to_K(femcy_ctx* ctx, int32_t id, double cc, int32_t overwrite) {
+    CTX_OR_FAIL(ctx);
+    MASS_OR_FAIL(id);
+    REQUIRE(std::isfinite(cc), "femcy_mass_add_to_K: the factor is not finite");
+    const int dm = c->dm, dd = dm * dm;
+    // the product is rounded before it is added (two statements on a volatile: no fused multiply-add), as on the device
+#pragma omp parallel for schedule(static)
+    for (int64_t p = 0; p < (int64_t)c->col.size(); ++p) {
+        volatile double v = cc * ms.m[p];
+        double* blk = c->K.data() + p * dd;
+        if (overwrite) {
+            for (int q = 0; q < dd; ++q) blk[q] = (q % (dm + 1) == 0) ? v : 0.0;
+        } else {
+            for (int d = 0; d < dm; ++d) blk[d * (dm + 1)] += v;
+        }
+    }
+    return FEMCY_OK;
+}
+
+int femcy_mass_kinetic_energy(femcy_ctx* ctx, int32_t id, int v_vec, double* out) {
+    CTX_OR_FAIL(ctx);
+    VEC_OR_FAIL(v_vec);
+    MASS_OR_FAIL(id);
+    REQUIRE(out, "null output");
+    const double* x = c->vec[v_vec].data();
+    const int dm = c->dm;
+    const int64_t nchunk = (c->nn + NODE_CHUNK - 1) / NODE_CHUNK;
+    std::vector<double> part((size_t)nchunk, 0.0);      // sums of fixed chunks of rows, combined in order
+#pragma omp parallel for schedule(static)
+    for (int64_t ch = 0; ch < nchunk; ++ch) {
+        double pd = 0.0;
+        const int32_t a1 = (int32_t)std::min<int64_t>(c->nn, (ch + 1) * NODE_CHUNK);
+        for (int32_t a = (int32_t)(ch * NODE_CHUNK); a < a1; ++a) {
+            double acc[3] = {0.0, 0.0, 0.0};
+            for (int64_t p = c->rowptr[a]; p < c->rowptr[a + 1]; ++p) {
+                const double* xv = x + (int64_t)c->col[p] * dm;
+                for (int r = 0; r < dm; ++r) acc[r] += ms.m[p] * xv[r];
+            }
+            for (int r = 0; r < dm; ++r) pd += x[(int64_t)a * dm + r] * acc[r];
+        }
+        part[ch] = pd;
+    }
+    double sum = 0.0;
+    for (double v : part) sum += v;
+    *out = 0.5 * sum;
+    return FEMCY_OK;
+}
+
+int femcy_newmark_predict(femcy_ctx* ctx, int u_vec, int v_vec, int a_vec, int out_vec, double c0, double c1, double c2) {
+    CTX_OR_FAIL(ctx);
+    VEC_OR_FAIL(u_vec);
+    VEC_OR_FAIL(v_vec);
+    VEC_OR_FAIL(a_vec);
+    VEC_OR_FAIL(out_vec);
+    REQUIRE(out_vec != u_vec && out_vec != v_vec && out_vec != a_vec,
+            "femcy_newmark_predict: the output may not be one of the inputs");
+    const double *u = c->vec[u_vec].data(), *v = c->vec[v_vec].data(), *a = c->vec[a_vec].data();
+    double* out = c->vec[out_vec].data();
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < c->n; ++i) out[i] = c0 * u[i] + c1 * v[i] + c2 * a[i];
+    return FEMCY_OK;
+}
+
+int femcy_newmark_update(femcy_ctx* ctx, int u_new_vec, int u_vec, int v_vec, int a_vec, double beta, double gamma,
+                         double dt) {
+    CTX_OR_FAIL(ctx);
+    VEC_OR_FAIL(u_new_vec);
+    VEC_OR_FAIL(u_vec);
+    VEC_OR_FAIL(v_vec);
+    VEC_OR_FAIL(a_vec);
+    REQUIRE(std::isfinite(beta) && beta > 0.0 && std::isfinite(gamma) && std::isfinite(dt) && dt > 0.0,
+            "femcy_newmark_update: beta and dt must be positive, gamma finite");
+    REQUIRE(v_vec != a_vec && v_vec != u_vec && v_vec != u_new_vec && a_vec != u_vec && a_vec != u_new_vec,
+            "femcy_newmark_update: velocity and acceleration are written in place and may alias nothing");
+    const double *un = c->vec[u_new_vec].data(), *u = c->vec[u_vec].data();
+    double *v = c->vec[v_vec].data(), *a = c->vec[a_vec].data();
+    const double b0 = 1.0 / (beta * dt * dt), b1 = 1.0 / (beta * dt), b2 = 1.0 / (2.0 * beta) - 1.0;
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < c->n; ++i) newmark_update_entry(un[i], u[i], v[i], a[i], b0, b1, b2, dt, gamma);
+    return FEMCY_OK;
+}
+
 int femcy_spmv(femcy_ctx* ctx, int x_vec, int y_vec) {
     CTX_OR_FAIL(ctx);
     REQUIRE(c->have_pattern, "pattern not built");
@@ -1409,6 +1597,36 @@ int femcy_elastic_energy(femcy_ctx* ctx, int u_vec, double* total) {
     }
     double s = 0.0;
     for (int64_t t = 0; t < ngp; ++t) s += c->energy[t] * c->vol[t];   // get_elasEng_kernel (:597-606)
+    *total = s;
+    return FEMCY_OK;
+}
+
+int femcy_elastic_energy_small(femcy_ctx* ctx, int u_vec, double* total) {
+    CTX_OR_FAIL(ctx);
+    REQUIRE(c->have_mesh && c->have_element && c->have_material && total, "context not fully defined");
+    VEC_OR_FAIL(u_vec);
+    REQUIRE(c->mat_kind != FEMCY_MAT_NEOHOOKE, "femcy_elastic_energy_small: a neo-Hookean material has no small-strain energy "
+            "(linear materials only)");
+    geom(c, c->vec[u_vec].data(), GEOM_F);
+    geom(c, nullptr, GEOM_DSDX);                     // the weights det J w of the UNDEFORMED mesh
+    const int64_t ngp = (int64_t)c->ne * c->nGP;
+    const int dm = c->dm, dd = dm * dm;
+#pragma omp parallel for schedule(static)
+    for (int64_t t = 0; t < ngp; ++t) {
+        if (dm == 3) {
+            double F[3][3];
+            for (int i = 0; i < 3; ++i)
+                for (int j = 0; j < 3; ++j) F[i][j] = c->F[t * dd + i * 3 + j];
+            c->energy[t] = energy_density_small<3>(c->mat_kind, c->C, c->params[0], c->params[1], F);
+        } else {
+            double F[2][2];
+            for (int i = 0; i < 2; ++i)
+                for (int j = 0; j < 2; ++j) F[i][j] = c->F[t * dd + i * 2 + j];
+            c->energy[t] = energy_density_small<2>(c->mat_kind, c->C, c->params[0], c->params[1], F);
+        }
+    }
+    double s = 0.0;
+    for (int64_t t = 0; t < ngp; ++t) s += c->energy[t] * c->vol[t];
     *total = s;
     return FEMCY_OK;
 }

@@ -33,6 +33,8 @@ class ElementBase(abc.ABC):
     _tri_split: Sequence[Tuple[int, int, int]]      # visualisation triangles per element / per face
     _extrap_points = None                           # natural coords fed to _extrap_basis
     _extrap_matrix = None                           # or an explicit [npe, nGP] matrix
+    _parent_shape: str                              # "simplex" (unit triangle / tetrahedron), "cube" ([-1, 1]^dm), "wedge"
+    _order: int                                     # polynomial degree p of the shape functions (per direction on a cube)
 
     def __init__(self):
         self.gaussPoints = HostField(self._gauss_points)
@@ -65,6 +67,57 @@ class ElementBase(abc.ABC):
         return {"nGP": gp.shape[0], "npe": self.npe, "dm": self.dm, "dN": dN, "N": N,
                 "w": np.ascontiguousarray(self.gaussWeights, dtype=np.float64),
                 "voigt_kind": VOIGT_2D if self.dm == 2 else VOIGT_3D}
+
+    def mass_rule(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(points [nq, dm], weights [nq]) on the parent element for the consistent mass.  The integrand N_a N_b has
+        twice the degree of the shape functions, which the stiffness rule under-integrates (the four-point rule of C3D10
+        gives an element mass of rank 4), so the mass has a rule of its own, generated and not typed in: tensor
+        Gauss-Legendre of p + 1 points per direction on [-1, 1]^dm (exact to degree 2p per direction), and on the unit
+        triangle / tetrahedron the same rule collapsed by the Duffy map x = u, y = v (1 - u), z = w (1 - u)(1 - v), with
+        enough points per direction for the Jacobian (1 - u)^(dm-1) (1 - v)^(dm-2) on top of total degree 2p (C3D10:
+        4 x 3 x 3 = 36 points).  The wedge takes the triangle's rule times the line's.  All weights are positive."""
+        from numpy.polynomial.legendre import leggauss
+        p, dm = int(self._order), int(self.dm)
+
+        def unit(n):                                 # n-point Gauss-Legendre rule on [0, 1]
+            x, w = leggauss(n)
+            return 0.5 * (x + 1.0), 0.5 * w
+
+        def simplex(d, degree):                      # exact for total degree `degree` on the unit d-simplex
+            rules = [unit((degree + (d - 1 - i) + 2) // 2) for i in range(d)]      # 2n - 1 >= degree + (d - 1 - i)
+            pts, wts = [], []
+            for idx in np.ndindex(*[len(r[0]) for r in rules]):
+                t = [rules[i][0][k] for i, k in enumerate(idx)]
+                w = np.prod([rules[i][1][k] for i, k in enumerate(idx)])
+                x, shrink = [], 1.0
+                for i in range(d):
+                    x.append(t[i] * shrink)
+                    w *= (1.0 - t[i]) ** (d - 1 - i)
+                    shrink *= 1.0 - t[i]
+                pts.append(x)
+                wts.append(w)
+            return np.array(pts), np.array(wts)
+
+        if self._parent_shape == "cube":
+            x, w = leggauss(p + 1)
+            grids = np.meshgrid(*([x] * dm), indexing="ij")
+            wg = np.meshgrid(*([w] * dm), indexing="ij")
+            return np.column_stack([g.ravel() for g in grids]), np.prod([g.ravel() for g in wg], axis=0)
+        if self._parent_shape == "simplex":
+            return simplex(dm, 2 * p)
+        assert self._parent_shape == "wedge"
+        tp, tw = simplex(2, 2 * p)
+        z, wz = leggauss(p + 1)
+        pts = np.array([[a, b, c] for c in z for a, b in tp])
+        return pts, np.array([u * v for v in wz for u in tw])
+
+    def mass_tables(self) -> dict:
+        """what femcy_mass_create takes: the shape functions Nq [nq, npe], their natural derivatives dNq [nq, npe, dm] and
+        the weights wq [nq] at the points of mass_rule()"""
+        pts, w = self.mass_rule()
+        return {"nq": len(w), "Nq": np.ascontiguousarray([self.shapeFunc_pyscope(q) for q in pts], dtype=np.float64),
+                "dNq": np.ascontiguousarray([self.dshape_dnat_pyscope(q) for q in pts], dtype=np.float64),
+                "wq": np.ascontiguousarray(w, dtype=np.float64), "points": pts}
 
     def facet_arities(self) -> List[int]:
         """the node counts of the element's facets, ascending (the wedge has triangles and quadrilaterals)."""

@@ -35,6 +35,7 @@ def _normal(axis, side):
 
 class Element_linear_hexahedral(ElementBase):
     dm, npe = 3, 8
+    _parent_shape, _order = "cube", 1          # mass_rule()
     _gauss_points = (_CORNERS * _G).tolist()
     _gauss_weights = [1.] * 8
     facet_natural_coos = {tuple(sorted(f)): _face_points(ax, sd) for f, ax, sd in _FACES}

@@ -13,6 +13,7 @@ def bilinear(c):
 
 class Element_linear_quadrilateral(ElementBase):
     dm, npe = 2, 4
+    _parent_shape, _order = "cube", 1          # mass_rule()
     _gauss_points = (_CORNERS * _G).tolist()
     _gauss_weights = [1.] * 4
     facet_natural_coos = {(0, 1): [[-1., -1.], [1., -1.]], (1, 2): [[1., -1.], [1., 1.]],

@@ -18,6 +18,7 @@ TET_DBARY = np.array([[0., 0., 1.], [1., 0., 0.], [-1., -1., -1.], [0., 1., 0.]]
 
 class Element_linear_tetrahedral(ElementBase):
     dm, npe = 3, 4
+    _parent_shape, _order = "simplex", 1          # mass_rule()
     _gauss_points = [[0.25, 0.25, 0.25]]
     _gauss_weights = [1. / 6.]
     facet_natural_coos = {f: [_CENTROID[f]] for f in TET_FACES}

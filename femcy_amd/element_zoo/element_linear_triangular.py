@@ -8,6 +8,7 @@ _R = 2 ** 0.5 / 2.
 
 class Element_linear_triangular(ElementBase):
     dm, npe = 2, 3
+    _parent_shape, _order = "simplex", 1          # mass_rule()
     _gauss_points = [[1. / 3., 1. / 3.]]
     _gauss_weights = [0.5]
     facet_natural_coos = {(0, 1): [[0.5, 0.5]], (1, 2): [[0., 0.5]], (0, 2): [[0.5, 0.]]}

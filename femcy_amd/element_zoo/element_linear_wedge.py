@@ -48,6 +48,7 @@ _GP = [[a, b, z] for z in (-_G, _G) for a, b in _TRI]
 
 class Element_linear_wedge(ElementBase):
     dm, npe = 3, 6
+    _parent_shape, _order = "wedge", 1          # mass_rule()
     _gauss_points = _GP
     _gauss_weights = [1. / 6.] * 6
     facet_natural_coos = {tuple(sorted(f)): _face_points(i)[0] for i, (f, _) in enumerate(_FACES)}

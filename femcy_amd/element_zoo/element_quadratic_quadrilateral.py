@@ -10,6 +10,7 @@ _T = 3. ** 0.5
 
 class Element_quadratic_quadrilateral(ElementBase):
     dm, npe = 2, 8
+    _parent_shape, _order = "cube", 2          # mass_rule()
     _gauss_points = [[-_G, -_G], [_G, -_G], [_G, _G], [-_G, _G]]
     _gauss_weights = [1.] * 4
     # NB (0,7)/(3,7) carry the opposite corner's coordinate in the reference table (:40);

@@ -19,6 +19,7 @@ _c, _d, _x = (1. - _A) / (_A - _B), _B / (_A - _B), (0.5 - _B) / (_A - _B)
 
 class Element_quadratic_tetrahedral(ElementBase):
     dm, npe = 3, 10
+    _parent_shape, _order = "simplex", 2          # mass_rule()
     _gauss_points = [[_A, _B, _B], [_B, _A, _B], [_B, _B, _A], [_B, _B, _B]]
     _gauss_weights = [1. / 24.] * 4
     facet_natural_coos = _FACE_POINTS

@@ -15,6 +15,7 @@ def _area(c):
 
 class Element_quadratic_triangular(ElementBase):
     dm, npe = 2, 6
+    _parent_shape, _order = "simplex", 2          # mass_rule()
     _gauss_points = [[2. / 3., 1. / 6.], [1. / 6., 2. / 3.], [1. / 6., 1. / 6.]]
     _gauss_weights = [1. / 6.] * 3
     # each straight edge is two half-edges (corner, mid); points = [mid node, corner node]

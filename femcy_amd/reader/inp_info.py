@@ -16,7 +16,8 @@ Reference behaviours that are kept on purpose:
     "user" when the keyword line contains "user"; every block in the file counts (:218-244);
   * `*Dsload` with <= 3 columns is a pressure: traction = -value along the outward normal; with
     more columns traction = value and direction = columns 3..5 (:246-271);
-  * `nlgeom` comes from the last comma field of the first `*Step` line (:319-330);
+  * `nlgeom` comes from the last comma field of the first `*Step` line (:319-330); the `amplitude=` parameter added here
+    is skipped by that rule;
   * `*Static` data -> ini_inc, max_time, min_inc, max_inc with ini_inc clipped to max_inc (:333-350);
   * 2-D elements accept only `*Elastic`; C3D* accept `*Elastic` and `*Hyperelastic, neo hooke`
     with D1 = 1/value (:294-316).
@@ -25,6 +26,9 @@ Beyond the reference (it reads `*Dsload` only and skips the rest): `*Density` in
 `*Dload` GRAV / BX / BY / BZ -> body_force_info, `*Cload` -> cload_info (read_loads).  Any other `*Dload` type is
 refused by name instead of being skipped.  `*Expansion` inside a `*Material` block -> expansion (isotropic, constant),
 `*Initial Conditions, type=TEMPERATURE` and `*Temperature` -> temperature_info (read_thermal).
+`*Dynamic, direct[, beta=, gamma=]` with data `dt, T` -> procedure = "dynamic", dynamic = {"beta", "gamma"} and time_incs
+with fixed increments (read_procedure); `*Step, amplitude=RAMP|STEP` -> amplitude; `*Initial Conditions, type=VELOCITY` ->
+initial_velocity_info.  A deck with `*Static` has procedure = "static" and reads as before.
 """
 import sys
 from typing import Dict, List
@@ -129,7 +133,9 @@ class InpInfo(InpInfoBase):
         self.density, self.body_force_info, self.cload_info = self.read_loads(file)
         self.expansion, self.temperature_info = self.read_thermal(file)
         self.geometric_nonlinear = self.read_geometric_nonlinear(file)
+        self.procedure, self.dynamic, self.amplitude = self.read_procedure(file)
         self.time_incs = self.read_time_inc(file)
+        self.initial_velocity_info = self.read_initial_velocity(file)
 
     # ------------------------------------------------------------------ nodes and elements
     def read_node_element(self, fileName):
@@ -444,13 +450,89 @@ class InpInfo(InpInfoBase):
 
     # ---------------------------------------------------------------------- step definition
     def read_geometric_nonlinear(self, fileName) -> bool:
+        """the last comma field of the first `*Step` line, as the reference reads it (`nlgeom=NO, inc=100` is nlgeom: kept on
+        purpose, tests/test_host_logic.py::test_reader_quirks).  The `amplitude=` parameter, which this reader adds, is
+        transparent to that rule: `nlgeom=NO, amplitude=STEP` and `amplitude=STEP, nlgeom=NO` read alike."""
         for line, _ in _deck(fileName).keywords():
             if line[:5] == "*Step":
-                return line.split(",")[-1].split("nlgeom=")[-1] != "NO"
+                fields = [f for f in line.split(",") if not f.strip().lower().startswith("amplitude=")]
+                return fields[-1].split("nlgeom=")[-1].rstrip() != "NO" if len(fields) < len(line.split(",")) \
+                    else fields[-1].split("nlgeom=")[-1] != "NO"
         raise ValueError("no *Step keyword in {}".format(fileName))
+
+    def read_procedure(self, fileName):
+        """-> procedure ("static" | "dynamic"), dynamic ({"beta", "gamma"} or None), amplitude ("RAMP" | "STEP").
+        `*Dynamic` needs `direct` (fixed increments; automatic time incrementation is not built), takes the Newmark
+        parameters `beta=` / `gamma=` (default 1/4, 1/2: the trapezoidal rule, no numerical damping) and refuses
+        `alpha=` other than 0 (no HHT damping), beta <= 0, gamma < 1/2, a deck without `*Density`, and a non-zero
+        `*Boundary` value (prescribed motion).  `*Step, amplitude=` defaults to RAMP under `*Static` (every load grows
+        with t / T, as it always did) and to STEP under `*Dynamic` (loads in full from t = 0+)."""
+        procedure, dynamic, amplitude = "static", None, None
+        for line, block in _deck(fileName).keywords():
+            fields = [t.strip() for t in line.split(",")]
+            key = fields[0].lower()
+            params = {t.split("=")[0].strip().lower(): t.split("=")[1].strip() for t in fields[1:] if "=" in t}
+            flags = {t.lower() for t in fields[1:] if "=" not in t}
+            if key == "*step" and amplitude is None and "amplitude" in params:
+                amplitude = params["amplitude"].upper()
+                if amplitude not in ("RAMP", "STEP"):
+                    raise ValueError("*Step, amplitude={} has not been supported (RAMP and STEP are)".format(params["amplitude"]))
+            elif key == "*dynamic":
+                if "direct" not in flags:
+                    raise ValueError("*Dynamic without `direct` has not been supported: automatic time incrementation "
+                                     "is not built, give fixed increments with *Dynamic, direct")
+                if float(params.get("alpha", 0.0)) != 0.0:
+                    raise ValueError("*Dynamic, alpha={} has not been supported: the integrator is the undamped Newmark "
+                                     "scheme (alpha = 0)".format(params["alpha"]))
+                beta, gamma = float(params.get("beta", 0.25)), float(params.get("gamma", 0.5))
+                if not beta > 0.0 or not gamma >= 0.5:
+                    raise ValueError("*Dynamic: beta = {} and gamma = {} are refused (beta > 0 and gamma >= 1/2 are "
+                                     "needed)".format(beta, gamma))
+                procedure, dynamic = "dynamic", {"beta": beta, "gamma": gamma}
+                break
+            elif key == "*static":
+                break
+        if procedure == "dynamic":
+            if getattr(self, "density", None) is None:
+                raise ValueError("*Dynamic needs a *Density in the *Material block")
+            if any(bc["val"] != 0.0 for bc in self.dirichlet_bc_info):
+                raise ValueError("a non-zero *Boundary value in a *Dynamic step (prescribed motion) has not been supported")
+        return procedure, dynamic, amplitude or ("STEP" if procedure == "dynamic" else "RAMP")
+
+    def read_initial_velocity(self, fileName):
+        """`*Initial Conditions, type=VELOCITY` data lines `nset-or-node-label, dof, value` -> [{"node_set", "dof",
+        "val"}], resolved like `*Cload`"""
+        dm = int(self.ELE.dm)
+        out = []
+        for line, block in _deck(fileName).keywords():
+            fields = [t.strip() for t in line.split(",")]
+            if fields[0].lower() != "*initial conditions":
+                continue
+            params = {t.split("=")[0].strip().lower(): t.split("=")[1].strip() for t in fields[1:] if "=" in t}
+            if params.get("type", "").upper() != "VELOCITY":
+                continue
+            for d in block:
+                if not d.strip():
+                    continue
+                f = [t.strip() for t in d.split(",")]
+                if len(f) < 3 or not f[2]:
+                    raise ValueError("*Initial Conditions, type=VELOCITY data line needs `nset-or-node, dof, value`: {}".format(", ".join(f)))
+                dof = int(f[1]) - 1
+                if not 0 <= dof < dm:
+                    raise ValueError("*Initial Conditions, type=VELOCITY: degree of freedom {} on a {}-D mesh".format(f[1], dm))
+                out.append({"node_set": self._nodes_of("*Initial Conditions", f[0]), "dof": dof, "val": float(f[2])})
+        return out
 
     def read_time_inc(self, fileName):
         for line, block in _deck(fileName).keywords():
+            if line[:8].lower() == "*dynamic":
+                data = [t for t in block if t.strip()]
+                if not data or len([t for t in data[0].split(",") if t.strip()]) < 2:
+                    raise ValueError("*Dynamic needs the data line `dt, T`")
+                dt, tmax = [float(t) for t in data[0].split(",") if t.strip()][:2]
+                if not (dt > 0.0 and tmax > 0.0):
+                    raise ValueError("*Dynamic: dt and T must be positive")
+                return {"ini_inc": dt, "max_time": tmax, "min_inc": dt, "max_inc": dt}
             if line[:7] == "*Static":
                 data = [t for t in block if t]
                 if data:

@@ -20,7 +20,10 @@ class InpInfoBase:
                   "density", "body_force_info", "cload_info",
                   # thermal loads: *Expansion (float or None), *Initial Conditions, type=TEMPERATURE + *Temperature as
                   # {"initial": f64[nn], "final": f64[nn]} or None
-                  "expansion", "temperature_info")
+                  "expansion", "temperature_info",
+                  # the step's procedure: "static" | "dynamic" (*Dynamic, direct), its Newmark parameters {"beta", "gamma"}
+                  # or None, the load amplitude "RAMP" | "STEP", *Initial Conditions, type=VELOCITY as [{"node_set", "dof", "val"}]
+                  "procedure", "dynamic", "amplitude", "initial_velocity_info")
 
     def __init_subclass__(cls, **kwargs):
         super().__init_subclass__(**kwargs)

@@ -146,6 +146,7 @@ class System_of_equations:
         self._dofsets = {}
         self._loadsets = {}
         self._bodyloads = {}
+        self._linear_energy = False   # set by solve_dynamic: get_elasEng then reports u.Ku / 2 (femcy_elastic_energy_small)
         self._thermal = None      # {"id", "scale"} of the thermal load that was applied last (compute_strain_stress)
         self.cg_log = []          # one entry per CG solve: iterations, max|r0|, max|r|, increment end time
         self.stats = {"assemblies": 0, "force_evals": 0, "linear_solves": 0, "cg_iterations": 0, "direct_solves": 0,
@@ -453,7 +454,11 @@ class System_of_equations:
 
     # --------------------------------------------------------------------- time stepping
     def solve(self, inp, show_newton_steps: bool = False, save2path: str = None):
-        """multiple time increments with automatic cut-back (reference :647-711)."""
+        """multiple time increments with automatic cut-back (reference :647-711).  A `*Dynamic` step goes to
+        `solve_dynamic`; a deck without it makes the calls it always made."""
+        self._linear_energy = False      # get_elasEng: the reference's energy, unless solve_dynamic says otherwise
+        if getattr(inp, "procedure", "static") == "dynamic":
+            return self.solve_dynamic(inp)
         max_inc, min_inc = inp.time_incs["max_inc"], inp.time_incs["min_inc"]
         max_time = inp.time_incs["max_time"]
         self.dt = inp.time_incs["ini_inc"]
@@ -479,7 +484,7 @@ class System_of_equations:
             kinc += 1
             self.time1 = min(self.time0 + self.dt, max_time)
             self._say("\033[40;33;1m >>>>> kinc = {}, time0 = {}, dt = {} \033[0m".format(kinc, self.time0, self.dt))
-            load_ratio = self.time1 / max_time
+            load_ratio = 1.0 if getattr(inp, "amplitude", "RAMP") == "STEP" else self.time1 / max_time
             for i, nb in enumerate(neumannBCs):
                 nb["traction"] = inp.neumann_bc_info[i]["traction"] * load_ratio
             for i, bf in enumerate(boundary_conditions.get("bodyForces", ())):
@@ -507,6 +512,127 @@ class System_of_equations:
                 self.dt = min(self.dt * 1.5, max_inc)
             self.dof_old.copy_from(self.dof)
             self.time0 = self.time1
+
+    # ------------------------------------------------------------------- implicit dynamics
+    def solve_dynamic(self, inp):
+        """linear transient dynamics (`*Dynamic, direct`): undamped Newmark with the consistent mass, fixed increments.
+        u_0 = 0, v_0 from `*Initial Conditions, type=VELOCITY`, a_0 from M a_0 = f(0+); per step, with a0 = 1/(beta dt^2),
+            (K + a0 M) u_{n+1} = f(t_{n+1}) + M (a0 u_n + v_n / (beta dt) + (1/(2 beta) - 1) a_n),
+        then a_{n+1}, v_{n+1} by `femcy_newmark_update`.  K is the matrix of the undeformed mesh, rebuilt with the mass
+        every step (the last step is clipped to T); the Dirichlet rows take the value 0; every solve uses the tight
+        settings of the direct branch (band factorisation, or PCG with eps = direct_eps), whatever the size.  Each entry
+        of `increments` carries the kinetic and the strain energy (`get_elasEng`: u.Ku / 2 here) after the step,
+        `initial_energy` those of t = 0."""
+        from .material_zoo.mater_base import FEMCY_MAT_NEOHOOKE
+        if self.geometric_nonlinear or inp.geometric_nonlinear:
+            raise ValueError("a *Dynamic step with nlgeom=YES has not been supported: the integrator is linear "
+                             "(small strain)")
+        if getattr(self.material, "kind", None) == FEMCY_MAT_NEOHOOKE:
+            raise ValueError("a *Dynamic step with a neo-Hookean material has not been supported: the integrator is linear "
+                             "(small strain)")
+        if self.part is not None:
+            raise ValueError("a *Dynamic step on more than one rank has not been supported: the mass matrix is "
+                             "single-rank")
+        if getattr(inp, "density", None) is None:
+            raise ValueError("*Dynamic needs a *Density in the *Material block")
+        if any(bc["val"] != 0.0 for bc in inp.dirichlet_bc_info):
+            raise ValueError("a non-zero *Boundary value in a *Dynamic step (prescribed motion) has not been supported")
+        beta, gamma = inp.dynamic["beta"], inp.dynamic["gamma"]
+        dt, max_time = inp.time_incs["ini_inc"], inp.time_incs["max_time"]
+        ctx = self.ctx
+        neumannBCs = copy.deepcopy(inp.neumann_bc_info)
+        dirichletBCs = copy.deepcopy(inp.dirichlet_bc_info)
+        for bc in dirichletBCs:
+            bc["node_set"] = HostField(np.array([*bc["node_set"]]), dtype=np.int32)
+        loads = {"neumannBCs": neumannBCs, "dirichletBCs": []}        # Dirichlet rows are treated after the inertia term
+        body_force_info, cload_info = getattr(inp, "body_force_info", None) or [], getattr(inp, "cload_info", None) or []
+        if body_force_info or cload_info:
+            loads["bodyForces"] = copy.deepcopy(body_force_info)
+            loads["cloads"] = copy.deepcopy(cload_info)
+        temperature_info, expansion = getattr(inp, "temperature_info", None), getattr(inp, "expansion", None)
+        if temperature_info is not None and expansion is not None:
+            dT = np.asarray(temperature_info["final"], dtype=np.float64) - np.asarray(temperature_info["initial"], dtype=np.float64)
+            loads["thermal"] = {"id": ctx.thermal(self.ELE, expansion, dT), "scale": 0.0}
+        any_load = bool(neumannBCs or body_force_info or cload_info or "thermal" in loads)
+
+        def external_force(t):
+            """rhs = f(t) through impose_boundary_condition, load ratio = amplitude(t)"""
+            ratio = 1.0 if inp.amplitude == "STEP" else t / max_time
+            for i, nb in enumerate(neumannBCs):
+                nb["traction"] = inp.neumann_bc_info[i]["traction"] * ratio
+            for i, bf in enumerate(loads.get("bodyForces", ())):
+                bf["force"] = np.asarray(body_force_info[i]["force"], dtype=np.float64) * ratio
+            for i, cl in enumerate(loads.get("cloads", ())):
+                cl["val"] = cload_info[i]["val"] * ratio
+            if "thermal" in loads:
+                loads["thermal"]["scale"] = ratio
+            if not any_load:
+                self.rhs.fill(0.0)
+            self.impose_boundary_condition(loads)
+
+        def dirichlet_rows():
+            for bc in dirichletBCs:
+                self.dirichletBC_linearEquations(bc["node_set"], bc["dof"], 0.0)
+
+        def linear_solve():
+            if self.n_system < self.cg_branch_from:
+                return self.solve_by_scipy()
+            du = self.solve_by_CG(eps=self.direct_eps, maxit=int(min(10 * self.n_system, 2 ** 31 - 1)))
+            if not self.PCG.converged:
+                raise be.FemcyError("dynamic step: the PCG stopped at max|r| = {:.3e} > {:.1e} * {:.3e}".format(
+                    self.PCG.rmax, self.direct_eps, self.PCG.r0), status=be.FEMCY_ENUMERIC)
+            return du
+
+        vel, acc = ctx.vector(be.VEC_VEL), ctx.vector(be.VEC_ACC)
+        self.velocity, self.acceleration = vel, acc
+        self._linear_energy = True
+        self.mass = ctx.mass(self.ELE, inp.density)
+        # ---- t = 0: u_0 = 0, v_0 from the deck (0 where the body is held), M a_0 = f(0+) - K u_0
+        self.dof.fill(0.0)
+        self.dof_old.fill(0.0)
+        vel.fill(0.0)
+        for iv in getattr(inp, "initial_velocity_info", None) or []:
+            ctx.dofset_fill(self._dofset(iv["node_set"], iv["dof"]), be.VEC_VEL, iv["val"])
+        for bc in dirichletBCs:
+            ctx.dofset_fill(self._dofset(bc["node_set"], bc["dof"]), be.VEC_VEL, 0.0)
+        self.time0 = self.time1 = 0.0
+        external_force(0.0)
+        ctx.mass_add_to_K(self.mass, 1.0, overwrite=True)
+        dirichlet_rows()
+        linear_solve()
+        acc.copy_from(self.dof)
+        self.dof.fill(0.0)
+        self.initial_energy = {"kinetic": ctx.mass_kinetic_energy(self.mass, be.VEC_VEL), "strain_energy": self.get_elasEng()}
+        self.increments = []
+        kinc = 0
+        while self.time0 < max_time * (1.0 - 1.0e-12):
+            self.time1 = min((kinc + 1) * dt, max_time)               # the last step is clipped to T
+            if max_time - self.time1 < 1.0e-12 * max_time:
+                self.time1 = max_time
+            self.dt = h = self.time1 - self.time0
+            self._say("\033[40;33;1m >>>>> kinc = {}, time0 = {}, dt = {} \033[0m".format(kinc, self.time0, h))
+            t0 = time.time()
+            a0 = 1.0 / (beta * h * h)
+            ctx.assemble_K(-1)                                        # K of the undeformed mesh (small strain)
+            self.stats["assemblies"] += 1
+            if not self.compiled:
+                self.compiled = True
+                ctx.sync()
+                self._say("\033[35;1m first assembly took {:.4f} s\033[0m".format(time.time() - t0))
+            ctx.mass_add_to_K(self.mass, a0)
+            ctx.newmark_predict(be.VEC_DOF, be.VEC_VEL, be.VEC_ACC, be.VEC_RESIDUAL, a0, 1.0 / (beta * h),
+                                1.0 / (2.0 * beta) - 1.0)
+            external_force(self.time1)
+            ctx.mass_apply(self.mass, be.VEC_RESIDUAL, be.VEC_RHS, 1.0, add=True)
+            dirichlet_rows()
+            linear_solve()                                            # dof = u_{n+1}; dof_old still holds u_n
+            ctx.newmark_update(be.VEC_DOF, be.VEC_DOF_OLD, be.VEC_VEL, be.VEC_ACC, beta, gamma, h)
+            self.dof_old.copy_from(self.dof)
+            self.increments.append({"kinc": kinc, "time1": self.time1, "dt": h, "converged": True, "newton_loop": 0,
+                                    "kinetic": ctx.mass_kinetic_energy(self.mass, be.VEC_VEL),
+                                    "strain_energy": self.get_elasEng()})
+            self.time0 = self.time1
+            kinc += 1
 
     def _residual(self, dirichletBCs):
         """nodal force + K at the current dof, residual = f_int - rhs, Newton Dirichlet treatment,
@@ -600,6 +726,12 @@ class System_of_equations:
             self.ctx.thermal_stress(self._thermal["id"], self._thermal["scale"])
 
     def get_elasEng(self):
-        """total elastic energy = sum over Gauss points of elasticEnergyDensity(F) * vol (reference :592-606)."""
-        self.elsEng = self.ctx.elastic_energy(be.VEC_DOF)
+        """total elastic energy = sum over Gauss points of elasticEnergyDensity(F) * vol (reference :592-606).  In and
+        after a `*Dynamic` step it is the energy of the infinitesimal strain on the undeformed mesh, u.Ku / 2: the
+        analysis is linear there, and that is the energy its integrator exchanges with the kinetic one (the reference's
+        density is that of the Green strain, which is off by the order of the strain)."""
+        if self._linear_energy:
+            self.elsEng = self.ctx.elastic_energy(be.VEC_DOF, small=True)
+        else:
+            self.elsEng = self.ctx.elastic_energy(be.VEC_DOF)
         return self.elsEng

@@ -50,7 +50,9 @@ enum femcy_vec {
     FEMCY_VEC_X = 6,         /* ConjugateGradientSolver_rowMajor.x      */
     FEMCY_VEC_TMP0 = 7,
     FEMCY_VEC_TMP1 = 8,
-    FEMCY_VEC_COUNT = 9
+    FEMCY_VEC_VEL = 9,       /* implicit dynamics: nodal velocities      */
+    FEMCY_VEC_ACC = 10,      /* implicit dynamics: nodal accelerations   */
+    FEMCY_VEC_COUNT = 11
 };
 
 /* Voigt pattern of the strain matrix B (element_zoo: strainMtrx) */
@@ -236,7 +238,8 @@ typedef struct femcy_pattern_info {
 
 typedef struct femcy_timing_t {
     /* accumulated since the last femcy_timing_reset; *_ms from hipEvents on the ctx stream */
-    double geom_ms;      int64_t geom_launches;      /* get_dsdx_and_vol / F / sigma kernels  */
+    double geom_ms;      int64_t geom_launches;      /* get_dsdx_and_vol / F / sigma kernels; also the element and vector passes
+                                                        of the body-load, thermal, mass and Newmark calls */
     double assemble_ms;  int64_t assemble_launches;  /* K assembly kernel                     */
     double force_ms;     int64_t force_launches;     /* nodal-force gather                    */
     double spmv_ms;      int64_t spmv_launches;      /* compute_Ad                            */
@@ -258,7 +261,7 @@ int femcy_sync(femcy_ctx* ctx);                                   /* hipStreamSy
 
 /* ----------------------------------------------------------------------- problem definition */
 /* Body + System_of_equations.__init__ state (body.py:13-17, stiffnessMtrx.py:26-121).  Calling it again on a used
- * ctx starts over: element tables, material, pattern, DOF lists, load sets, body loads and thermal
+ * ctx starts over: element tables, material, pattern, DOF lists, load sets, body loads, mass objects and thermal
  * loads of the old mesh are dropped. */
 int femcy_set_mesh(femcy_ctx* ctx, int32_t nn, int32_t dm, const double* nodes /*[nn*dm]*/,
                    int32_t ne, int32_t npe, const int32_t* elems /*[ne*npe]*/);
@@ -396,6 +399,41 @@ int femcy_thermal_create(femcy_ctx* ctx, const double* N /*[nGP][npe]*/, double 
 int femcy_thermal_force(femcy_ctx* ctx, int32_t id, double* out /*[n]*/);
 int femcy_thermal_apply(femcy_ctx* ctx, int32_t id, double scale, int rhs_vec, int32_t add);
 int femcy_thermal_stress(femcy_ctx* ctx, int32_t id, double scale);
+/* Implicit dynamics (*Dynamic; an extension, small strain, single rank).  A mass object is the CONSISTENT mass matrix of
+ * the mesh in the matrix's own storage: one scalar per stored block,
+ *   m_ab = sum over elements e and mass-rule points q of N_a(xi_q) N_b(xi_q) rho |det J_q| w_q,
+ * in bcol's [block row][lane] layout (8 B where K has 8 dm^2; padding blocks hold 0); the matrix itself is M (x) I_dm.
+ * femcy_mass_create works on the UNDEFORMED mesh with a rule of its own (the stiffness rule under-integrates N_a N_b):
+ * Nq [nq][npe], dNq [nq][npe][dm], wq [nq] are the plugin's shape functions, natural derivatives and weights at the points
+ * of its mass_rule() (nq <= 64), rho > 0 the density.  An element pass evaluates rho |det J_q| w_q (it does not read the
+ * Gauss-point volumes of the stiffness rule), an owner-computes pass sums every stored block's contributions in ascending
+ * (element, local node) order: no atomics, the same bits on every run, and m_ab == m_ba bit for bit.
+ * After femcy_set_element and femcy_build_pattern.
+ * femcy_mass_get downloads the nnzb scalars in the block order of femcy_get_K_bsr (rows ascending, columns ascending).
+ * femcy_mass_apply: vec[y] = [vec[y] +] scale * (M (x) I) vec[x] (add != 0 adds); the launch shape and slice ranges are the
+ * stiffness product's, scale travels in the kernel arguments; x and y must differ.
+ * femcy_mass_add_to_K adds c * m_ab to the dm diagonal entries of every stored block of K (products rounded before they are
+ * added); overwrite != 0 sets K := c * M (x) I instead (the initial-acceleration solve).  K is the matrix of the last
+ * femcy_assemble_K, so the call belongs between the assembly and the Dirichlet treatment.
+ * femcy_mass_kinetic_energy: *out = 1/2 v^T (M (x) I) v, reduced in a fixed order.
+ * femcy_newmark_predict: vec[out] = c0 vec[u] + c1 vec[v] + c2 vec[a] in one pass; out may not be one of the three inputs
+ * (FEMCY_EINVAL), the inputs may coincide with each other.
+ * femcy_newmark_update: with u_new the solution at t + dt, in one pass and in place of vec[a] and vec[v],
+ *   a_new = (u_new - u) / (beta dt^2) - v / (beta dt) - (1 / (2 beta) - 1) a,   v_new = v + dt ((1 - gamma) a + gamma a_new).
+ * Refused with FEMCY_EINVAL, the context stays usable: an unknown id, a null table or output, nq outside 1 .. 64, a
+ * non-finite or non-positive rho, beta <= 0, dt <= 0, a call before the pattern exists, and every mass call once
+ * femcy_comm_init has run (several ranks are not supported; the host backend has one rank, its femcy_comm_init never
+ * succeeds, so it has no such check).  Mass objects are dropped where body loads are:
+ * femcy_set_mesh and femcy_ctx_destroy. */
+int femcy_mass_create(femcy_ctx* ctx, int32_t nq, const double* Nq /*[nq][npe]*/, const double* dNq /*[nq][npe][dm]*/,
+                      const double* wq /*[nq]*/, double rho, int32_t* id_out);
+int femcy_mass_get(femcy_ctx* ctx, int32_t id, double* vals /*[nnzb], in femcy_get_K_bsr's block order*/);
+int femcy_mass_apply(femcy_ctx* ctx, int32_t id, int x_vec, int y_vec, double scale, int32_t add);
+int femcy_mass_add_to_K(femcy_ctx* ctx, int32_t id, double c, int32_t overwrite);
+int femcy_mass_kinetic_energy(femcy_ctx* ctx, int32_t id, int v_vec, double* out);
+int femcy_newmark_predict(femcy_ctx* ctx, int u_vec, int v_vec, int a_vec, int out_vec, double c0, double c1, double c2);
+int femcy_newmark_update(femcy_ctx* ctx, int u_new_vec, int u_vec, int v_vec, int a_vec, double beta, double gamma,
+                         double dt);
 /* compute_Ad (conjugateGradientSolver.py:53-58): vec[y] = K vec[x] */
 int femcy_spmv(femcy_ctx* ctx, int x_vec, int y_vec);
 /* ConjugateGradientSolver_rowMajor.re_init + solve (conjugateGradientSolver.py:32-51, 103-127):
@@ -442,6 +480,13 @@ int femcy_compute_strain_stress(femcy_ctx* ctx, int u_vec, int large);
 /* get_elasEng (stiffnessMtrx.py:592-606): F at vec[u], elasticEnergyDensity, sum(density * vol) with the
  * vol left by the last geometry pass (reference behaviour) */
 int femcy_elastic_energy(femcy_ctx* ctx, int u_vec, double* total);
+/* The strain energy of a LINEAR (small-strain) analysis: sum over the Gauss points of sigma : eps / 2 with the infinitesimal
+ * strain eps = sym(F) - I at vec[u], sigma = constitutiveOfSmallDeform(eps), times det J w of the UNDEFORMED mesh, i.e.
+ * u^T K u / 2 with the K of femcy_assemble_K(ctx, -1) up to rounding.  This is the energy the Newmark integrator conserves;
+ * femcy_elastic_energy is the reference's energy of the Green strain and differs from it by the order of the strain.  The
+ * call leaves the gradients and weights of the undeformed mesh behind (what femcy_assemble_K(ctx, -1) leaves) and the
+ * density in FEMCY_GP_ENERGY.  A neo-Hookean material is refused with FEMCY_EINVAL. */
+int femcy_elastic_energy_small(femcy_ctx* ctx, int u_vec, double* total);
 /* ELE.extrapolate (element_zoo): out[e][a] = sum_g E[a][g] * field[e][g][comp]; E is npe x nGP */
 int femcy_extrapolate(femcy_ctx* ctx, int gp_field, int comp, const double* E, double* out /*[ne*npe]*/);
 
