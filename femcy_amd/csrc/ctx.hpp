@@ -77,6 +77,36 @@ inline hipError_t dmalloc(T** p, size_t bytes) {
     return dmalloc(reinterpret_cast<void**>(p), bytes);
 }
 
+// Move-only owner of one device allocation (through dmalloc): the members of the objects a context hands out by id (Ctx::
+// DofSet ... Mass) and the scratch of the calls that create them.  The memory is released when the owner goes, so whoever
+// drops one while kernels may still read it synchronises the stream first.
+template <class T>
+class DevBuf {
+    T* p_ = nullptr;
+
+public:
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            reset();
+            p_ = o.p_;
+            o.p_ = nullptr;
+        }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    void reset() {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr;
+    }
+    hipError_t alloc(size_t bytes) {
+        reset();
+        return dmalloc(&p_, bytes);
+    }
+    T* get() const { return p_; }
+};
+
 #define FEMCY_REQUIRE(cond, ...)                    \
     do {                                            \
         if (!(cond)) {                              \
@@ -291,29 +321,29 @@ struct Ctx {
     int ew_cap = 512;                 // FEMCY_OPT_EW_GRID
 
     // ---- device-resident DOF lists of *Boundary blocks
-    struct DofSet { int32_t* d_dofs; double* d_vals; int32_t k; };
+    struct DofSet { DevBuf<int32_t> d_dofs; DevBuf<double> d_vals; int32_t k = 0; };
     std::vector<DofSet> dofsets;
 
     // ---- device-resident *Dsload surfaces (femcy_loadset_*)
     struct LoadSet {
-        int32_t nft, nfn, nip, nload, nnode;
-        int32_t *d_ft_nodes, *d_elem, *d_ft, *d_node, *d_ptr, *d_slot;
-        double *d_N, *d_dN, *d_normal, *d_weight, *d_contrib, *d_dir;
+        int32_t nft = 0, nfn = 0, nip = 0, nload = 0, nnode = 0;
+        DevBuf<int32_t> d_ft_nodes, d_elem, d_ft, d_node, d_ptr, d_slot;
+        DevBuf<double> d_N, d_dN, d_normal, d_weight, d_contrib, d_dir;
     };
     std::vector<LoadSet> loadsets;
 
     // ---- device-resident body loads (femcy_bodyload_*): the nodal weights m_a of one element selection
-    struct BodyLoad { double* d_m; int32_t nsel; };
+    struct BodyLoad { DevBuf<double> d_m; int32_t nsel = 0; };
     std::vector<BodyLoad> bodyloads;
 
     // ---- device-resident thermal loads (femcy_thermal_*): the load vector at scale 1 of one nodal temperature change,
     // and what the stress correction reads again (the temperatures, the shape functions at the Gauss points, and the
     // stress of full restraint per unit temperature change, alpha * C : eps_th, as a full row-major tensor)
     struct ThermalStress { double s[9]; };
-    struct Thermal { double *d_f, *d_dT, *d_N; ThermalStress ts; };
+    struct Thermal { DevBuf<double> d_f, d_dT, d_N; ThermalStress ts{}; };
     std::vector<Thermal> thermals;
     // ---- device-resident consistent mass (femcy_mass_*): one scalar per stored block, in d_bcol's [block row][lane] layout
-    struct Mass { double* d_m; };
+    struct Mass { DevBuf<double> d_m; };
     std::vector<Mass> masses;
     bool post_small = false;          // sigma / mises hold femcy_compute_strain_stress(large = 0), not yet corrected
 

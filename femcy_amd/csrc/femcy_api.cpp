@@ -6,7 +6,9 @@
 #include <chrono>
 #include <cstdio>
 #include <cstring>
+#include <utility>
 #include "ctx.hpp"
+#include "element_dispatch.hpp"
 #include "element_math.hpp"
 #include "direct.hpp"
 
@@ -41,6 +43,43 @@ template <class T>
 static void dev_free(T** p) {
     if (*p) (void)hipFree(*p);
     *p = nullptr;
+}
+
+// a new device buffer holding `bytes` of host memory
+template <class T>
+static int to_device(DevBuf<T>& d, const void* h, size_t bytes) {
+    FEMCY_HIP(d.alloc(std::max<size_t>(bytes, 8)));
+    if (bytes) FEMCY_HIP(hipMemcpy(d.get(), h, bytes, hipMemcpyHostToDevice));
+    return FEMCY_OK;
+}
+
+// the objects a context hands out by id; their buffers go with them (DevBuf), so the streams are drained by the caller
+static void drop_objects(Ctx* c) {
+    c->dofsets.clear();
+    c->loadsets.clear();
+    c->bodyloads.clear();
+    c->thermals.clear();
+    c->masses.clear();
+}
+
+// Right-hand side of a stored load: apply(dst, add) writes this rank's share of it into dst (add: adds it) and is called
+// once.  Multi-rank: every rank evaluates its own elements, so the load is summed over the interface -- when it is added
+// to a vector, alone in TMP1 first.  `who` names the caller in the refusal.
+template <class Apply>
+static int apply_load(Ctx* c, const char* who, int rhs_vec, bool add, Apply&& apply) {
+    FEMCY_REQUIRE(!add || !c->comm || rhs_vec != FEMCY_VEC_TMP1, "%s on several ranks sums the interface through vector "
+                  "TMP1: it cannot be the right-hand side", who);
+    double* rhs = c->d_vec[rhs_vec];
+    int rc;
+    if (add && c->comm) {
+        double* tmp = c->d_vec[FEMCY_VEC_TMP1];
+        if ((rc = apply(tmp, false))) return rc;
+        if ((rc = iface_sum(c, tmp))) return rc;
+        return vec_axpy(c, rhs, rhs, 1.0, tmp);
+    }
+    if ((rc = apply(rhs, add))) return rc;
+    if (add) return FEMCY_OK;
+    return iface_sum(c, rhs);
 }
 
 int ensure_scratch(Ctx* c, int64_t k) {
@@ -278,23 +317,7 @@ int femcy_ctx_destroy(femcy_ctx* ctx) {
     if (c->h_state) (void)hipHostFree(c->h_state);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->h_scalar) (void)hipHostFree(c->h_scalar);
-    for (auto& ds : c->dofsets) {
-        if (ds.d_dofs) (void)hipFree(ds.d_dofs);
-        if (ds.d_vals) (void)hipFree(ds.d_vals);
-    }
-    for (auto& ls : c->loadsets) {
-        void* ptrs[] = {ls.d_ft_nodes, ls.d_elem, ls.d_ft, ls.d_node, ls.d_ptr, ls.d_slot,
-                        ls.d_N, ls.d_dN, ls.d_normal, ls.d_weight, ls.d_contrib, ls.d_dir};
-        for (void* q : ptrs)
-            if (q) (void)hipFree(q);
-    }
-    for (auto& bl : c->bodyloads)
-        if (bl.d_m) (void)hipFree(bl.d_m);
-    for (auto& th : c->thermals)
-        for (void* q : {(void*)th.d_f, (void*)th.d_dT, (void*)th.d_N})
-            if (q) (void)hipFree(q);
-    for (auto& ms : c->masses)
-        if (ms.d_m) (void)hipFree(ms.d_m);
+    drop_objects(c);       // here, with the device current and every stream drained: not left to `delete ctx`
     for (auto& p : c->ev_pool) {
         (void)hipEventDestroy(p.a);
         (void)hipEventDestroy(p.b);
@@ -496,8 +519,6 @@ int femcy_sync(femcy_ctx* ctx) {
 }
 
 // ------------------------------------------------------------------------- problem definition
-static void loadset_free(Ctx::LoadSet& ls);
-
 int femcy_set_mesh(femcy_ctx* ctx, int32_t nn, int32_t dm, const double* nodes, int32_t ne, int32_t npe,
                    const int32_t* elems) {
     CTX_OR_FAIL(ctx);
@@ -511,23 +532,7 @@ int femcy_set_mesh(femcy_ctx* ctx, int32_t nn, int32_t dm, const double* nodes, 
     FEMCY_REQUIRE(!c->comm, "the mesh of a context cannot change once a communicator is attached");
     FEMCY_HIP(hipStreamSynchronize(c->stream));
     // a new mesh invalidates everything that was defined on the old one
-    for (auto& ds : c->dofsets) {
-        if (ds.d_dofs) (void)hipFree(ds.d_dofs);
-        if (ds.d_vals) (void)hipFree(ds.d_vals);
-    }
-    c->dofsets.clear();
-    for (auto& ls : c->loadsets) loadset_free(ls);
-    c->loadsets.clear();
-    for (auto& bl : c->bodyloads)
-        if (bl.d_m) (void)hipFree(bl.d_m);
-    c->bodyloads.clear();
-    for (auto& th : c->thermals)
-        for (void* q : {(void*)th.d_f, (void*)th.d_dT, (void*)th.d_N})
-            if (q) (void)hipFree(q);
-    c->thermals.clear();
-    for (auto& ms : c->masses)
-        if (ms.d_m) (void)hipFree(ms.d_m);
-    c->masses.clear();
+    drop_objects(c);
     c->post_small = false;
     c->have_material = false;
     c->nn = nn; c->dm = dm; c->ne = ne; c->npe = npe;
@@ -865,11 +870,12 @@ int femcy_dofset_create(femcy_ctx* ctx, const int32_t* dofs, int32_t k, int32_t*
     CTX_OR_FAIL(ctx);
     FEMCY_REQUIRE(c->have_mesh && id_out && k >= 0 && (k == 0 || dofs), "bad dofset arguments");
     for (int32_t i = 0; i < k; ++i) FEMCY_REQUIRE(dofs[i] >= 0 && dofs[i] < c->n, "DOF %d out of range", dofs[i]);
-    Ctx::DofSet ds{nullptr, nullptr, k};
-    FEMCY_HIP(dmalloc(&ds.d_dofs, std::max<size_t>(k, 1) * sizeof(int32_t)));
-    FEMCY_HIP(dmalloc(&ds.d_vals, std::max<size_t>(k, 1) * sizeof(double)));
-    if (k) FEMCY_HIP(hipMemcpy(ds.d_dofs, dofs, sizeof(int32_t) * k, hipMemcpyHostToDevice));
-    c->dofsets.push_back(ds);
+    Ctx::DofSet ds;
+    ds.k = k;
+    FEMCY_HIP(ds.d_dofs.alloc(std::max<size_t>(k, 1) * sizeof(int32_t)));
+    FEMCY_HIP(ds.d_vals.alloc(std::max<size_t>(k, 1) * sizeof(double)));
+    if (k) FEMCY_HIP(hipMemcpy(ds.d_dofs.get(), dofs, sizeof(int32_t) * k, hipMemcpyHostToDevice));
+    c->dofsets.push_back(std::move(ds));
     *id_out = (int32_t)c->dofsets.size() - 1;
     return FEMCY_OK;
 }
@@ -883,21 +889,21 @@ int femcy_dofset_dirichlet_newton(femcy_ctx* ctx, int32_t id, int residual_vec) 
     READY_OR_FAIL();
     VEC_OR_FAIL(residual_vec);
     DOFSET_OR_FAIL(id);
-    return launch_dirichlet_zero(c, ds.d_dofs, ds.k, c->d_vec[residual_vec]);
+    return launch_dirichlet_zero(c, ds.d_dofs.get(), ds.k, c->d_vec[residual_vec]);
 }
 
 int femcy_dofset_fill(femcy_ctx* ctx, int32_t id, int vec, double value) {
     CTX_OR_FAIL(ctx);
     VEC_OR_FAIL(vec);
     DOFSET_OR_FAIL(id);
-    return vec_scatter_const(c, c->d_vec[vec], ds.d_dofs, value, ds.k);
+    return vec_scatter_const(c, c->d_vec[vec], ds.d_dofs.get(), value, ds.k);
 }
 
 int femcy_dofset_add(femcy_ctx* ctx, int32_t id, int vec, double value) {
     CTX_OR_FAIL(ctx);
     VEC_OR_FAIL(vec);
     DOFSET_OR_FAIL(id);
-    return vec_scatter_add(c, c->d_vec[vec], ds.d_dofs, value, ds.k);
+    return vec_scatter_add(c, c->d_vec[vec], ds.d_dofs.get(), value, ds.k);
 }
 
 int femcy_dofset_scatter(femcy_ctx* ctx, int32_t id, int vec, const double* vals) {
@@ -906,9 +912,9 @@ int femcy_dofset_scatter(femcy_ctx* ctx, int32_t id, int vec, const double* vals
     DOFSET_OR_FAIL(id);
     if (ds.k == 0) return FEMCY_OK;
     FEMCY_REQUIRE(vals, "null values");
-    int rc = stage_h2d(c, ds.d_vals, vals, sizeof(double) * ds.k);   // the host buffer is only borrowed for the call
+    int rc = stage_h2d(c, ds.d_vals.get(), vals, sizeof(double) * ds.k);   // the host buffer is only borrowed for the call
     if (rc) return rc;
-    return vec_scatter(c, c->d_vec[vec], ds.d_dofs, ds.d_vals, ds.k);
+    return vec_scatter(c, c->d_vec[vec], ds.d_dofs.get(), ds.d_vals.get(), ds.k);
 }
 
 int femcy_dofset_dirichlet_linear(femcy_ctx* ctx, int32_t id, double value, int rhs_vec) {
@@ -923,31 +929,16 @@ int femcy_dofset_dirichlet_linear(femcy_ctx* ctx, int32_t id, double value, int 
         double* s = c->d_vec[FEMCY_VEC_TMP0];
         double* Ks = c->d_vec[FEMCY_VEC_TMP1];
         if ((rc = vec_fill(c, s, 0.0, c->n))) return rc;
-        if ((rc = vec_scatter_const(c, s, ds.d_dofs, value, ds.k))) return rc;
+        if ((rc = vec_scatter_const(c, s, ds.d_dofs.get(), value, ds.k))) return rc;
         if ((rc = launch_spmv(c, s, Ks, nullptr, nullptr))) return rc;
         if ((rc = iface_sum(c, Ks))) return rc;
         if ((rc = vec_sub(c, c->d_vec[rhs_vec], c->d_vec[rhs_vec], Ks))) return rc;
     }
-    if ((rc = vec_scatter_const(c, c->d_vec[rhs_vec], ds.d_dofs, value, ds.k))) return rc;
-    return launch_dirichlet_zero(c, ds.d_dofs, ds.k, nullptr);
+    if ((rc = vec_scatter_const(c, c->d_vec[rhs_vec], ds.d_dofs.get(), value, ds.k))) return rc;
+    return launch_dirichlet_zero(c, ds.d_dofs.get(), ds.k, nullptr);
 }
 
 // ------------------------------------------------------------------------------- Neumann load sets
-static int to_device(void* dptr, const void* h, size_t bytes) {
-    void** d = (void**)dptr;
-    FEMCY_HIP(dmalloc(d, std::max<size_t>(bytes, 8)));
-    if (bytes) FEMCY_HIP(hipMemcpy(*d, h, bytes, hipMemcpyHostToDevice));
-    return FEMCY_OK;
-}
-
-static void loadset_free(Ctx::LoadSet& ls) {
-    void* ptrs[] = {ls.d_ft_nodes, ls.d_elem, ls.d_ft, ls.d_node, ls.d_ptr, ls.d_slot,
-                    ls.d_N, ls.d_dN, ls.d_normal, ls.d_weight, ls.d_contrib, ls.d_dir};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    ls = Ctx::LoadSet{};
-}
-
 int femcy_loadset_create(femcy_ctx* ctx, int32_t nft, int32_t nfn, int32_t nip, const int32_t* ft_nodes,
                          const double* ft_N, const double* ft_dN, const double* ft_normal, const double* ft_weight,
                          int32_t nload, const int32_t* load_elem, const int32_t* load_ft, int32_t* id_out) {
@@ -979,28 +970,27 @@ int femcy_loadset_create(femcy_ctx* ctx, int32_t nft, int32_t nfn, int32_t nip, 
     }
     ld_ptr.push_back((int32_t)nslot);
 
-    Ctx::LoadSet ls{};
+    Ctx::LoadSet ls;
     ls.nft = nft; ls.nfn = nfn; ls.nip = nip; ls.nload = nload; ls.nnode = (int32_t)ld_node.size();
     int rc = FEMCY_OK;
     const size_t tip = (size_t)nft * nip;
-    if (!rc) rc = to_device(&ls.d_ft_nodes, ft_nodes, sizeof(int32_t) * nft * nfn);
-    if (!rc) rc = to_device(&ls.d_N, ft_N, sizeof(double) * tip * c->npe);
-    if (!rc) rc = to_device(&ls.d_dN, ft_dN, sizeof(double) * tip * c->npe * c->dm);
-    if (!rc) rc = to_device(&ls.d_normal, ft_normal, sizeof(double) * tip * c->dm);
-    if (!rc) rc = to_device(&ls.d_weight, ft_weight, sizeof(double) * tip);
-    if (!rc) rc = to_device(&ls.d_elem, load_elem, sizeof(int32_t) * nload);
-    if (!rc) rc = to_device(&ls.d_ft, load_ft, sizeof(int32_t) * nload);
-    if (!rc) rc = to_device(&ls.d_node, ld_node.data(), sizeof(int32_t) * ld_node.size());
-    if (!rc) rc = to_device(&ls.d_ptr, ld_ptr.data(), sizeof(int32_t) * ld_ptr.size());
-    if (!rc) rc = to_device(&ls.d_slot, order.data(), sizeof(int32_t) * nslot);
-    if (!rc && dmalloc(&ls.d_contrib, std::max<size_t>(nslot, 1) * c->dm * sizeof(double)) != hipSuccess) rc = FEMCY_ENOMEM;
-    if (!rc && dmalloc(&ls.d_dir, 3 * sizeof(double)) != hipSuccess) rc = FEMCY_ENOMEM;
+    if (!rc) rc = to_device(ls.d_ft_nodes, ft_nodes, sizeof(int32_t) * nft * nfn);
+    if (!rc) rc = to_device(ls.d_N, ft_N, sizeof(double) * tip * c->npe);
+    if (!rc) rc = to_device(ls.d_dN, ft_dN, sizeof(double) * tip * c->npe * c->dm);
+    if (!rc) rc = to_device(ls.d_normal, ft_normal, sizeof(double) * tip * c->dm);
+    if (!rc) rc = to_device(ls.d_weight, ft_weight, sizeof(double) * tip);
+    if (!rc) rc = to_device(ls.d_elem, load_elem, sizeof(int32_t) * nload);
+    if (!rc) rc = to_device(ls.d_ft, load_ft, sizeof(int32_t) * nload);
+    if (!rc) rc = to_device(ls.d_node, ld_node.data(), sizeof(int32_t) * ld_node.size());
+    if (!rc) rc = to_device(ls.d_ptr, ld_ptr.data(), sizeof(int32_t) * ld_ptr.size());
+    if (!rc) rc = to_device(ls.d_slot, order.data(), sizeof(int32_t) * nslot);
+    if (!rc && ls.d_contrib.alloc(std::max<size_t>(nslot, 1) * c->dm * sizeof(double)) != hipSuccess) rc = FEMCY_ENOMEM;
+    if (!rc && ls.d_dir.alloc(3 * sizeof(double)) != hipSuccess) rc = FEMCY_ENOMEM;
     if (rc) {
-        loadset_free(ls);
         if (rc == FEMCY_ENOMEM) set_error("out of device memory for a load set of %d facets", nload);
         return rc;
     }
-    c->loadsets.push_back(ls);
+    c->loadsets.push_back(std::move(ls));
     *id_out = (int32_t)c->loadsets.size() - 1;
     return FEMCY_OK;
 }
@@ -1008,24 +998,14 @@ int femcy_loadset_create(femcy_ctx* ctx, int32_t nft, int32_t nfn, int32_t nip, 
 static int loadset_neumann(Ctx* c, int32_t id, double traction, const double* direction, int rhs_vec, bool add) {
     VEC_OR_FAIL(rhs_vec);
     FEMCY_REQUIRE(id >= 0 && (size_t)id < c->loadsets.size(), "unknown load set %d", (int)id);
-    FEMCY_REQUIRE(!add || !c->comm || rhs_vec != FEMCY_VEC_TMP1, "femcy_loadset_neumann_add on several ranks sums the "
-                  "interface through vector TMP1: it cannot be the right-hand side");
     const Ctx::LoadSet& ls = c->loadsets[id];
-    if (direction) {
-        FEMCY_HIP(hipMemcpyAsync(ls.d_dir, direction, sizeof(double) * c->dm, hipMemcpyHostToDevice, c->stream));
-        FEMCY_HIP(hipStreamSynchronize(c->stream));   // the host buffer is only borrowed for the call
-    }
-    double* rhs = c->d_vec[rhs_vec];
-    int rc;
-    if (add && c->comm) {   // multi-rank: only this set's loads are summed over the interface, then added
-        double* tmp = c->d_vec[FEMCY_VEC_TMP1];
-        if ((rc = launch_neumann(c, ls, traction, direction == nullptr, tmp, false))) return rc;
-        if ((rc = iface_sum(c, tmp))) return rc;
-        return vec_axpy(c, rhs, rhs, 1.0, tmp);
-    }
-    if ((rc = launch_neumann(c, ls, traction, direction == nullptr, rhs, add))) return rc;
-    if (add) return FEMCY_OK;
-    return iface_sum(c, rhs);                  // multi-rank: each rank loads the facets of its own elements
+    return apply_load(c, "femcy_loadset_neumann_add", rhs_vec, add, [&](double* dst, bool add_to) -> int {
+        if (direction) {
+            FEMCY_HIP(hipMemcpyAsync(ls.d_dir.get(), direction, sizeof(double) * c->dm, hipMemcpyHostToDevice, c->stream));
+            FEMCY_HIP(hipStreamSynchronize(c->stream));   // the host buffer is only borrowed for the call
+        }
+        return launch_neumann(c, ls, traction, direction == nullptr, dst, add_to);
+    });
 }
 
 int femcy_loadset_neumann(femcy_ctx* ctx, int32_t id, double traction, const double* direction, int rhs_vec) {
@@ -1055,27 +1035,25 @@ int femcy_bodyload_create(femcy_ctx* ctx, const double* N, int32_t nsel, const i
             mask[sel_elems[i]] = 1;
         }
     }
-    Ctx::BodyLoad bl{nullptr, sel_elems ? nsel : c->ne};
-    double *d_N = nullptr, *d_we = nullptr;
-    uint8_t* d_mask = nullptr;
-    int rc = to_device(&d_N, N, sizeof(double) * c->nGP * c->npe);
-    if (!rc && sel_elems) rc = to_device(&d_mask, mask.data(), mask.size());
-    if (!rc && dmalloc(&d_we, sizeof(double) * (size_t)c->ne * c->npe) != hipSuccess) rc = FEMCY_ENOMEM;
-    if (!rc && dmalloc(&bl.d_m, sizeof(double) * (size_t)c->nn) != hipSuccess) rc = FEMCY_ENOMEM;
-    if (!rc) rc = launch_body_weights(c, d_N, d_mask, d_we, bl.d_m);
-    // the tables and the element records are scratch of this call: wait for the two kernels, then release them
+    Ctx::BodyLoad bl;
+    bl.nsel = sel_elems ? nsel : c->ne;
+    DevBuf<double> d_N, d_we;      // the tables and the element records are scratch of this call
+    DevBuf<uint8_t> d_mask;
+    int rc = to_device(d_N, N, sizeof(double) * c->nGP * c->npe);
+    if (!rc && sel_elems) rc = to_device(d_mask, mask.data(), mask.size());
+    if (!rc && d_we.alloc(sizeof(double) * (size_t)c->ne * c->npe) != hipSuccess) rc = FEMCY_ENOMEM;
+    if (!rc && bl.d_m.alloc(sizeof(double) * (size_t)c->nn) != hipSuccess) rc = FEMCY_ENOMEM;
+    if (!rc) rc = launch_body_weights(c, d_N.get(), d_mask.get(), d_we.get(), bl.d_m.get());
+    // ... which the two kernels read: wait for them before the scratch is released at the end of the call
     if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) {
         set_error("body load: the weight kernels failed");
         rc = FEMCY_EHIP;
     }
-    for (void* q : {(void*)d_N, (void*)d_we, (void*)d_mask})
-        if (q) (void)hipFree(q);
     if (rc) {
-        if (bl.d_m) (void)hipFree(bl.d_m);
         if (rc == FEMCY_ENOMEM) set_error("out of device memory for a body load on %d elements", c->ne);
         return rc;
     }
-    c->bodyloads.push_back(bl);
+    c->bodyloads.push_back(std::move(bl));
     *id_out = (int32_t)c->bodyloads.size() - 1;
     return FEMCY_OK;
 }
@@ -1088,7 +1066,7 @@ int femcy_bodyload_weights(femcy_ctx* ctx, int32_t id, double* out) {
     CTX_OR_FAIL(ctx);
     BODYLOAD_OR_FAIL(id);
     FEMCY_REQUIRE(out, "null output");
-    FEMCY_HIP(hipMemcpyAsync(out, bl.d_m, sizeof(double) * c->nn, hipMemcpyDeviceToHost, c->stream));
+    FEMCY_HIP(hipMemcpyAsync(out, bl.d_m.get(), sizeof(double) * c->nn, hipMemcpyDeviceToHost, c->stream));
     FEMCY_HIP(hipStreamSynchronize(c->stream));
     return FEMCY_OK;
 }
@@ -1098,28 +1076,11 @@ int femcy_bodyload_apply(femcy_ctx* ctx, int32_t id, const double* b, int rhs_ve
     VEC_OR_FAIL(rhs_vec);
     BODYLOAD_OR_FAIL(id);
     FEMCY_REQUIRE(b, "null force");
-    FEMCY_REQUIRE(!add || !c->comm || rhs_vec != FEMCY_VEC_TMP1, "femcy_bodyload_apply with add on several ranks sums the "
-                  "interface through vector TMP1: it cannot be the right-hand side");
-    double* rhs = c->d_vec[rhs_vec];
-    int rc;
-    if (add && c->comm) {   // multi-rank: only this load is summed over the interface, then added
-        double* tmp = c->d_vec[FEMCY_VEC_TMP1];
-        if ((rc = launch_body_apply(c, bl.d_m, b, false, tmp))) return rc;
-        if ((rc = iface_sum(c, tmp))) return rc;
-        return vec_axpy(c, rhs, rhs, 1.0, tmp);
-    }
-    if ((rc = launch_body_apply(c, bl.d_m, b, add != 0, rhs))) return rc;
-    if (add) return FEMCY_OK;
-    return iface_sum(c, rhs);                  // multi-rank: each rank weighs its own elements
+    return apply_load(c, "femcy_bodyload_apply with add", rhs_vec, add != 0,
+                      [&](double* dst, bool add_to) { return launch_body_apply(c, bl.d_m.get(), b, add_to, dst); });
 }
 
 // --------------------------------------------------------------------------------- thermal loads
-static void thermal_free(Ctx::Thermal& th) {
-    for (void* q : {(void*)th.d_f, (void*)th.d_dT, (void*)th.d_N})
-        if (q) (void)hipFree(q);
-    th.d_f = th.d_dT = th.d_N = nullptr;
-}
-
 int femcy_thermal_create(femcy_ctx* ctx, const double* N, double alpha, const double* dT, int32_t* id_out) {
     CTX_OR_FAIL(ctx);
     FEMCY_REQUIRE(c->have_mesh && c->have_element && c->have_material && c->have_pattern,
@@ -1130,34 +1091,29 @@ int femcy_thermal_create(femcy_ctx* ctx, const double* N, double alpha, const do
     FEMCY_REQUIRE(std::isfinite(alpha), "thermal load: the expansion coefficient is not finite");
     FEMCY_REQUIRE(c->mat_kind != FEMCY_MAT_NEOHOOKE, "thermal load: a neo-Hookean material has no small-strain thermal "
                   "stress (linear materials only)");
-    Ctx::Thermal th{nullptr, nullptr, nullptr, {}};
-    if (c->dm == 3) {
-        double s[3][3];
-        thermal_unit_stress<3>(c->mat_kind, c->h_C, c->mat_params[1], s);
-        for (int i = 0; i < 9; ++i) th.ts.s[i] = alpha * s[i / 3][i % 3];
-    } else {
-        double s[2][2];
-        thermal_unit_stress<2>(c->mat_kind, c->h_C, c->mat_params[1], s);
-        for (int i = 0; i < 4; ++i) th.ts.s[i] = alpha * s[i / 2][i % 2];
-    }
-    double* d_fe = nullptr;
-    int rc = to_device(&th.d_N, N, sizeof(double) * c->nGP * c->npe);
-    if (!rc) rc = to_device(&th.d_dT, dT, sizeof(double) * (size_t)c->nn);
-    if (!rc && dmalloc(&d_fe, sizeof(double) * (size_t)c->ne * c->npe * c->dm) != hipSuccess) rc = FEMCY_ENOMEM;
-    if (!rc && dmalloc(&th.d_f, sizeof(double) * (size_t)c->n) != hipSuccess) rc = FEMCY_ENOMEM;
-    if (!rc) rc = launch_thermal_force(c, th, d_fe);
-    // the element records are scratch of this call: wait for the two kernels, then release them
+    Ctx::Thermal th;
+    dispatch_dm(c->dm, [&](auto dm) {
+        constexpr int DM = dm();
+        double s[DM][DM];
+        thermal_unit_stress<DM>(c->mat_kind, c->h_C, c->mat_params[1], s);
+        for (int i = 0; i < DM * DM; ++i) th.ts.s[i] = alpha * s[i / DM][i % DM];
+    });
+    DevBuf<double> d_fe;           // the element records are scratch of this call
+    int rc = to_device(th.d_N, N, sizeof(double) * c->nGP * c->npe);
+    if (!rc) rc = to_device(th.d_dT, dT, sizeof(double) * (size_t)c->nn);
+    if (!rc && d_fe.alloc(sizeof(double) * (size_t)c->ne * c->npe * c->dm) != hipSuccess) rc = FEMCY_ENOMEM;
+    if (!rc && th.d_f.alloc(sizeof(double) * (size_t)c->n) != hipSuccess) rc = FEMCY_ENOMEM;
+    if (!rc) rc = launch_thermal_force(c, th, d_fe.get());
+    // ... which the two kernels read: wait for them before the scratch is released at the end of the call
     if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) {
         set_error("thermal load: the force kernels failed");
         rc = FEMCY_EHIP;
     }
-    if (d_fe) (void)hipFree(d_fe);
     if (rc) {
-        thermal_free(th);
         if (rc == FEMCY_ENOMEM) set_error("out of device memory for a thermal load on %d elements", c->ne);
         return rc;
     }
-    c->thermals.push_back(th);
+    c->thermals.push_back(std::move(th));
     *id_out = (int32_t)c->thermals.size() - 1;
     return FEMCY_OK;
 }
@@ -1170,7 +1126,7 @@ int femcy_thermal_force(femcy_ctx* ctx, int32_t id, double* out) {
     CTX_OR_FAIL(ctx);
     THERMAL_OR_FAIL(id);
     FEMCY_REQUIRE(out, "null output");
-    FEMCY_HIP(hipMemcpyAsync(out, th.d_f, sizeof(double) * c->n, hipMemcpyDeviceToHost, c->stream));
+    FEMCY_HIP(hipMemcpyAsync(out, th.d_f.get(), sizeof(double) * c->n, hipMemcpyDeviceToHost, c->stream));
     FEMCY_HIP(hipStreamSynchronize(c->stream));
     return FEMCY_OK;
 }
@@ -1179,19 +1135,8 @@ int femcy_thermal_apply(femcy_ctx* ctx, int32_t id, double scale, int rhs_vec, i
     CTX_OR_FAIL(ctx);
     VEC_OR_FAIL(rhs_vec);
     THERMAL_OR_FAIL(id);
-    FEMCY_REQUIRE(!add || !c->comm || rhs_vec != FEMCY_VEC_TMP1, "femcy_thermal_apply with add on several ranks sums the "
-                  "interface through vector TMP1: it cannot be the right-hand side");
-    double* rhs = c->d_vec[rhs_vec];
-    int rc;
-    if (add && c->comm) {   // multi-rank: only this load is summed over the interface, then added
-        double* tmp = c->d_vec[FEMCY_VEC_TMP1];
-        if ((rc = launch_thermal_apply(c, th.d_f, scale, false, tmp))) return rc;
-        if ((rc = iface_sum(c, tmp))) return rc;
-        return vec_axpy(c, rhs, rhs, 1.0, tmp);
-    }
-    if ((rc = launch_thermal_apply(c, th.d_f, scale, add != 0, rhs))) return rc;
-    if (add) return FEMCY_OK;
-    return iface_sum(c, rhs);                  // multi-rank: each rank evaluates its own elements
+    return apply_load(c, "femcy_thermal_apply with add", rhs_vec, add != 0,
+                      [&](double* dst, bool add_to) { return launch_thermal_apply(c, th.d_f.get(), scale, add_to, dst); });
 }
 
 int femcy_thermal_stress(femcy_ctx* ctx, int32_t id, double scale) {
@@ -1219,28 +1164,25 @@ int femcy_mass_create(femcy_ctx* ctx, int32_t nq, const double* Nq, const double
     FEMCY_REQUIRE(Nq && dNq && wq && id_out, "null mass-rule table or id_out");
     FEMCY_REQUIRE(nq >= 1 && nq <= 64, "mass rule: %d points (1 .. 64 are supported)", nq);
     FEMCY_REQUIRE(std::isfinite(rho) && rho > 0.0, "mass: the density must be finite and positive");
-    Ctx::Mass ms{nullptr};
-    double *d_Nq = nullptr, *d_dNq = nullptr, *d_wq = nullptr, *d_vq = nullptr;
+    Ctx::Mass ms;
+    DevBuf<double> d_Nq, d_dNq, d_wq, d_vq;     // the tables and the element records are scratch of this call
     const size_t npos = (size_t)c->stored_rows * SLICE;
-    int rc = to_device(&d_Nq, Nq, sizeof(double) * nq * c->npe);
-    if (!rc) rc = to_device(&d_dNq, dNq, sizeof(double) * nq * c->npe * c->dm);
-    if (!rc) rc = to_device(&d_wq, wq, sizeof(double) * nq);
-    if (!rc && dmalloc(&d_vq, sizeof(double) * (size_t)c->ne * nq) != hipSuccess) rc = FEMCY_ENOMEM;
-    if (!rc && dmalloc(&ms.d_m, std::max<size_t>(sizeof(double) * npos, 8)) != hipSuccess) rc = FEMCY_ENOMEM;
-    if (!rc) rc = launch_mass_blocks(c, nq, d_Nq, d_dNq, d_wq, rho, d_vq, ms.d_m);
-    // the tables and the element records are scratch of this call: wait for the two kernels, then release them
+    int rc = to_device(d_Nq, Nq, sizeof(double) * nq * c->npe);
+    if (!rc) rc = to_device(d_dNq, dNq, sizeof(double) * nq * c->npe * c->dm);
+    if (!rc) rc = to_device(d_wq, wq, sizeof(double) * nq);
+    if (!rc && d_vq.alloc(sizeof(double) * (size_t)c->ne * nq) != hipSuccess) rc = FEMCY_ENOMEM;
+    if (!rc && ms.d_m.alloc(std::max<size_t>(sizeof(double) * npos, 8)) != hipSuccess) rc = FEMCY_ENOMEM;
+    if (!rc) rc = launch_mass_blocks(c, nq, d_Nq.get(), d_dNq.get(), d_wq.get(), rho, d_vq.get(), ms.d_m.get());
+    // ... which the two kernels read: wait for them before the scratch is released at the end of the call
     if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) {
         set_error("mass: the assembly kernels failed");
         rc = FEMCY_EHIP;
     }
-    for (void* q : {(void*)d_Nq, (void*)d_dNq, (void*)d_wq, (void*)d_vq})
-        if (q) (void)hipFree(q);
     if (rc) {
-        if (ms.d_m) (void)hipFree(ms.d_m);
         if (rc == FEMCY_ENOMEM) set_error("out of device memory for a mass matrix on %d elements", c->ne);
         return rc;
     }
-    c->masses.push_back(ms);
+    c->masses.push_back(std::move(ms));
     *id_out = (int32_t)c->masses.size() - 1;
     return FEMCY_OK;
 }
@@ -1255,7 +1197,7 @@ int femcy_mass_get(femcy_ctx* ctx, int32_t id, double* vals) {
     MASS_OR_FAIL(id);
     FEMCY_REQUIRE(vals, "null output");
     std::vector<double> m((size_t)c->stored_rows * SLICE);
-    FEMCY_HIP(hipMemcpyAsync(m.data(), ms.d_m, sizeof(double) * m.size(), hipMemcpyDeviceToHost, c->stream));
+    FEMCY_HIP(hipMemcpyAsync(m.data(), ms.d_m.get(), sizeof(double) * m.size(), hipMemcpyDeviceToHost, c->stream));
     FEMCY_HIP(hipStreamSynchronize(c->stream));
     int64_t w = 0;
     std::vector<std::pair<int32_t, int32_t>> order;
@@ -1277,7 +1219,7 @@ int femcy_mass_apply(femcy_ctx* ctx, int32_t id, int x_vec, int y_vec, double sc
     VEC_OR_FAIL(y_vec);
     MASS_OR_FAIL(id);
     FEMCY_REQUIRE(x_vec != y_vec, "the mass product cannot run in place");
-    return launch_mass_spmv(c, ms.d_m, c->d_vec[x_vec], c->d_vec[y_vec], scale, add != 0, nullptr, nullptr);
+    return launch_mass_spmv(c, ms.d_m.get(), c->d_vec[x_vec], c->d_vec[y_vec], scale, add != 0, nullptr, nullptr);
 }
 
 int femcy_mass_add_to_K(femcy_ctx* ctx, int32_t id, double cc, int32_t overwrite) {
@@ -1285,7 +1227,7 @@ int femcy_mass_add_to_K(femcy_ctx* ctx, int32_t id, double cc, int32_t overwrite
     SINGLE_RANK_OR_FAIL("femcy_mass_add_to_K");
     MASS_OR_FAIL(id);
     FEMCY_REQUIRE(std::isfinite(cc), "femcy_mass_add_to_K: the factor is not finite");
-    return launch_mass_add_to_K(c, ms.d_m, cc, overwrite != 0);
+    return launch_mass_add_to_K(c, ms.d_m.get(), cc, overwrite != 0);
 }
 
 int femcy_mass_kinetic_energy(femcy_ctx* ctx, int32_t id, int v_vec, double* out) {
@@ -1294,7 +1236,7 @@ int femcy_mass_kinetic_energy(femcy_ctx* ctx, int32_t id, int v_vec, double* out
     VEC_OR_FAIL(v_vec);
     MASS_OR_FAIL(id);
     FEMCY_REQUIRE(out, "null output");
-    return launch_mass_energy(c, ms.d_m, c->d_vec[v_vec], out);
+    return launch_mass_energy(c, ms.d_m.get(), c->d_vec[v_vec], out);
 }
 
 int femcy_newmark_predict(femcy_ctx* ctx, int u_vec, int v_vec, int a_vec, int out_vec, double c0, double c1, double c2) {

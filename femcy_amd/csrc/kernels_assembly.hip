@@ -31,6 +31,7 @@
 #include <algorithm>
 #include <vector>
 #include "ctx.hpp"
+#include "element_dispatch.hpp"
 #include "element_math.hpp"
 
 namespace femcy {
@@ -1432,12 +1433,10 @@ __global__ void __launch_bounds__(256) k_dot_partial(int64_t n, const double* __
 int launch_post(Ctx* c, int large) {
     const int64_t ngp = (int64_t)c->ne * c->nGP;
     const int bs = 256, grid = (int)((ngp + bs - 1) / bs);
-    if (c->dm == 3)
-        hipLaunchKernelGGL((k_post<3>), dim3(grid), dim3(bs), 0, c->stream, ngp, large, c->mat_kind, c->d_C,
+    dispatch_dm(c->dm, [&](auto dm) {
+        hipLaunchKernelGGL((k_post<dm()>), dim3(grid), dim3(bs), 0, c->stream, ngp, large, c->mat_kind, c->d_C,
                            c->mat_params[0], c->mat_params[1], c->d_F, c->d_sigma, c->d_strain, c->d_mises);
-    else
-        hipLaunchKernelGGL((k_post<2>), dim3(grid), dim3(bs), 0, c->stream, ngp, large, c->mat_kind, c->d_C,
-                           c->mat_params[0], c->mat_params[1], c->d_F, c->d_sigma, c->d_strain, c->d_mises);
+    });
     FEMCY_HIP(hipGetLastError());
     return FEMCY_OK;
 }
@@ -1445,12 +1444,10 @@ int launch_post(Ctx* c, int large) {
 int launch_energy(Ctx* c) {
     const int64_t ngp = (int64_t)c->ne * c->nGP;
     const int bs = 256, grid = (int)((ngp + bs - 1) / bs);
-    if (c->dm == 3)
-        hipLaunchKernelGGL((k_energy<3>), dim3(grid), dim3(bs), 0, c->stream, ngp, c->mat_kind, c->d_C,
+    dispatch_dm(c->dm, [&](auto dm) {
+        hipLaunchKernelGGL((k_energy<dm()>), dim3(grid), dim3(bs), 0, c->stream, ngp, c->mat_kind, c->d_C,
                            c->mat_params[0], c->mat_params[1], c->d_F, c->d_energy);
-    else
-        hipLaunchKernelGGL((k_energy<2>), dim3(grid), dim3(bs), 0, c->stream, ngp, c->mat_kind, c->d_C,
-                           c->mat_params[0], c->mat_params[1], c->d_F, c->d_energy);
+    });
     FEMCY_HIP(hipGetLastError());
     return FEMCY_OK;
 }
@@ -1458,12 +1455,10 @@ int launch_energy(Ctx* c) {
 int launch_energy_small(Ctx* c) {
     const int64_t ngp = (int64_t)c->ne * c->nGP;
     const int bs = 256, grid = (int)((ngp + bs - 1) / bs);
-    if (c->dm == 3)
-        hipLaunchKernelGGL((k_energy_small<3>), dim3(grid), dim3(bs), 0, c->stream, ngp, c->mat_kind, c->d_C,
+    dispatch_dm(c->dm, [&](auto dm) {
+        hipLaunchKernelGGL((k_energy_small<dm()>), dim3(grid), dim3(bs), 0, c->stream, ngp, c->mat_kind, c->d_C,
                            c->mat_params[0], c->mat_params[1], c->d_F, c->d_energy);
-    else
-        hipLaunchKernelGGL((k_energy_small<2>), dim3(grid), dim3(bs), 0, c->stream, ngp, c->mat_kind, c->d_C,
-                           c->mat_params[0], c->mat_params[1], c->d_F, c->d_energy);
+    });
     FEMCY_HIP(hipGetLastError());
     return FEMCY_OK;
 }
@@ -1514,17 +1509,15 @@ int launch_neumann(Ctx* c, const Ctx::LoadSet& ls, double traction, bool along_n
     if (!add) FEMCY_HIP(hipMemsetAsync(d_rhs, 0, sizeof(double) * c->n, c->stream));
     if (ls.nload == 0) return FEMCY_OK;
     const int bs = 128;
-    const double* dir = along_normal ? nullptr : ls.d_dir;
-    if (c->dm == 3)
-        hipLaunchKernelGGL((k_neumann_contrib<3>), dim3((ls.nload + bs - 1) / bs), dim3(bs), 0, c->stream, ls.nload,
-                           c->npe, ls.nfn, ls.nip, c->d_nodes, c->d_elems, ls.d_elem, ls.d_ft, ls.d_ft_nodes, ls.d_N,
-                           ls.d_dN, ls.d_normal, ls.d_weight, traction, dir, ls.d_contrib);
-    else
-        hipLaunchKernelGGL((k_neumann_contrib<2>), dim3((ls.nload + bs - 1) / bs), dim3(bs), 0, c->stream, ls.nload,
-                           c->npe, ls.nfn, ls.nip, c->d_nodes, c->d_elems, ls.d_elem, ls.d_ft, ls.d_ft_nodes, ls.d_N,
-                           ls.d_dN, ls.d_normal, ls.d_weight, traction, dir, ls.d_contrib);
+    const double* dir = along_normal ? nullptr : ls.d_dir.get();
+    dispatch_dm(c->dm, [&](auto dm) {
+        hipLaunchKernelGGL((k_neumann_contrib<dm()>), dim3((ls.nload + bs - 1) / bs), dim3(bs), 0, c->stream, ls.nload,
+                           c->npe, ls.nfn, ls.nip, c->d_nodes, c->d_elems, ls.d_elem.get(), ls.d_ft.get(),
+                           ls.d_ft_nodes.get(), ls.d_N.get(), ls.d_dN.get(), ls.d_normal.get(), ls.d_weight.get(), traction,
+                           dir, ls.d_contrib.get());
+    });
     hipLaunchKernelGGL(k_neumann_gather, dim3((ls.nnode + bs - 1) / bs), dim3(bs), 0, c->stream, ls.nnode, c->dm,
-                       ls.d_node, ls.d_ptr, ls.d_slot, ls.d_contrib, add ? 1 : 0, d_rhs);
+                       ls.d_node.get(), ls.d_ptr.get(), ls.d_slot.get(), ls.d_contrib.get(), add ? 1 : 0, d_rhs);
     FEMCY_HIP(hipGetLastError());
     return FEMCY_OK;
 }
@@ -1737,43 +1730,39 @@ int launch_energy_sum(Ctx* c, double* total) {
 }
 
 // ------------------------------------------------------------------------------- host launchers
-#define FEMCY_DISPATCH_ELEMENT(NPE_, DM_, CALL)                          \
-    if (c->npe == NPE_ && c->dm == DM_) {                                \
-        constexpr int NPE = NPE_, DM = DM_;                              \
-        CALL;                                                            \
-        launched = true;                                                 \
-    }
+// what an element pass answers for a mesh whose family dispatch_element does not list
+static int no_kernel(const Ctx* c, const char* what) {
+    set_error("no %s kernel instantiated for npe=%d dm=%d", what, c->npe, c->dm);
+    return FEMCY_ENOKERNEL;
+}
+
+// node sums of per-element nodal forces d_fe [ne][npe][dm] into d_f [n]
+static void launch_node_sums(Ctx* c, const double* d_fe, double* d_f) {
+    const int bs = 256;
+    const int grid = (int)(((int64_t)c->nn * 32 + bs - 1) / bs);   // 32 lanes per node
+    dispatch_dm(c->dm, [&](auto dm) {
+        hipLaunchKernelGGL((k_nodal_force<dm()>), dim3(grid), dim3(bs), 0, c->stream, c->nn, c->d_ne_ptr, c->d_ne_idx, d_fe,
+                           d_f);
+    });
+}
 
 int launch_geom(Ctx* c, const double* d_u, unsigned what) {
     const int bs = 256, grid = (c->ne + bs - 1) / bs;
-    bool launched = false;
     const bool with_stress = (what & (GEOM_F | GEOM_SIGMA | GEOM_FE)) != 0;
     size_t th = timing_begin(c, T_GEOM);
-#define GEOM_CALL                                                                                                   \
-    if (with_stress)                                                                                                \
-        hipLaunchKernelGGL((k_geom<NPE, DM, true>), dim3(grid), dim3(bs), 0, c->stream, c->ne, c->nGP, c->d_nodes,  \
-                           d_u, c->d_elems, c->d_dN, c->d_w, c->mat_kind, c->d_C, c->mat_params[0],                 \
-                           c->mat_params[1], (what & GEOM_DSDX) ? c->d_dsdx : nullptr, c->d_vol,                    \
-                           (what & GEOM_F) ? c->d_F : nullptr, (what & GEOM_SIGMA) ? c->d_sigma : nullptr,          \
-                           (what & GEOM_FE) ? c->d_fe : nullptr);                                                   \
-    else                                                                                                            \
-        hipLaunchKernelGGL((k_geom<NPE, DM, false>), dim3(grid), dim3(bs), 0, c->stream, c->ne, c->nGP, c->d_nodes, \
-                           d_u, c->d_elems, c->d_dN, c->d_w, c->mat_kind, c->d_C, c->mat_params[0],                 \
-                           c->mat_params[1], c->d_dsdx, c->d_vol, c->d_F, c->d_sigma, (double*)nullptr)
-    FEMCY_DISPATCH_ELEMENT(3, 2, GEOM_CALL)
-    FEMCY_DISPATCH_ELEMENT(4, 2, GEOM_CALL)
-    FEMCY_DISPATCH_ELEMENT(6, 2, GEOM_CALL)
-    FEMCY_DISPATCH_ELEMENT(8, 2, GEOM_CALL)
-    FEMCY_DISPATCH_ELEMENT(4, 3, GEOM_CALL)
-    FEMCY_DISPATCH_ELEMENT(10, 3, GEOM_CALL)
-    FEMCY_DISPATCH_ELEMENT(8, 3, GEOM_CALL)
-    FEMCY_DISPATCH_ELEMENT(6, 3, GEOM_CALL)
-#undef GEOM_CALL
+    const bool launched = dispatch_element(c->npe, c->dm, [&](auto npe, auto dm) {
+        if (with_stress)
+            hipLaunchKernelGGL((k_geom<npe(), dm(), true>), dim3(grid), dim3(bs), 0, c->stream, c->ne, c->nGP, c->d_nodes,
+                               d_u, c->d_elems, c->d_dN, c->d_w, c->mat_kind, c->d_C, c->mat_params[0], c->mat_params[1],
+                               (what & GEOM_DSDX) ? c->d_dsdx : nullptr, c->d_vol, (what & GEOM_F) ? c->d_F : nullptr,
+                               (what & GEOM_SIGMA) ? c->d_sigma : nullptr, (what & GEOM_FE) ? c->d_fe : nullptr);
+        else
+            hipLaunchKernelGGL((k_geom<npe(), dm(), false>), dim3(grid), dim3(bs), 0, c->stream, c->ne, c->nGP, c->d_nodes,
+                               d_u, c->d_elems, c->d_dN, c->d_w, c->mat_kind, c->d_C, c->mat_params[0], c->mat_params[1],
+                               c->d_dsdx, c->d_vol, c->d_F, c->d_sigma, (double*)nullptr);
+    });
     timing_end(c, th);
-    if (!launched) {
-        set_error("no geometry kernel instantiated for npe=%d dm=%d", c->npe, c->dm);
-        return FEMCY_ENOKERNEL;
-    }
+    if (!launched) return no_kernel(c, "geometry");
     FEMCY_HIP(hipGetLastError());
     return FEMCY_OK;
 }
@@ -1781,30 +1770,18 @@ int launch_geom(Ctx* c, const double* d_u, unsigned what) {
 // nodal weights of a body load: element pass into d_we [ne][npe] (scratch of the caller), node gather into d_m [nn]
 int launch_body_weights(Ctx* c, const double* d_N, const uint8_t* d_mask_or_null, double* d_we, double* d_m) {
     const int bs = 256, grid = (c->ne + bs - 1) / bs;
-    bool launched = false;
     size_t th = timing_begin(c, T_GEOM);
-#define BODY_CALL                                                                                                   \
-    hipLaunchKernelGGL((k_body_weights<NPE, DM>), dim3(grid), dim3(bs), 0, c->stream, c->ne, c->nGP, c->d_nodes,    \
-                       c->d_elems, c->d_dN, d_N, c->d_w, d_mask_or_null, d_we)
-    FEMCY_DISPATCH_ELEMENT(3, 2, BODY_CALL)
-    FEMCY_DISPATCH_ELEMENT(4, 2, BODY_CALL)
-    FEMCY_DISPATCH_ELEMENT(6, 2, BODY_CALL)
-    FEMCY_DISPATCH_ELEMENT(8, 2, BODY_CALL)
-    FEMCY_DISPATCH_ELEMENT(4, 3, BODY_CALL)
-    FEMCY_DISPATCH_ELEMENT(10, 3, BODY_CALL)
-    FEMCY_DISPATCH_ELEMENT(8, 3, BODY_CALL)
-    FEMCY_DISPATCH_ELEMENT(6, 3, BODY_CALL)
-#undef BODY_CALL
+    const bool launched = dispatch_element(c->npe, c->dm, [&](auto npe, auto dm) {
+        hipLaunchKernelGGL((k_body_weights<npe(), dm()>), dim3(grid), dim3(bs), 0, c->stream, c->ne, c->nGP, c->d_nodes,
+                           c->d_elems, c->d_dN, d_N, c->d_w, d_mask_or_null, d_we);
+    });
     if (launched) {
         const int64_t threads = (int64_t)c->nn * 32;
         hipLaunchKernelGGL(k_body_gather, dim3((unsigned)((threads + bs - 1) / bs)), dim3(bs), 0, c->stream, c->nn,
                            c->d_ne_ptr, c->d_ne_idx, d_we, d_m);
     }
     timing_end(c, th);
-    if (!launched) {
-        set_error("no body-load kernel instantiated for npe=%d dm=%d", c->npe, c->dm);
-        return FEMCY_ENOKERNEL;
-    }
+    if (!launched) return no_kernel(c, "body-load");
     FEMCY_HIP(hipGetLastError());
     return FEMCY_OK;
 }
@@ -1813,12 +1790,10 @@ int launch_body_weights(Ctx* c, const double* d_N, const uint8_t* d_mask_or_null
 int launch_body_apply(Ctx* c, const double* d_m, const double* b, bool add, double* d_f) {
     const int bs = 256;
     const unsigned grid = (unsigned)((c->n + bs - 1) / bs);
-    if (c->dm == 3)
-        hipLaunchKernelGGL((k_body_apply<3>), dim3(grid), dim3(bs), 0, c->stream, c->n, d_m, b[0], b[1], b[2],
-                           add ? 1 : 0, d_f);
-    else
-        hipLaunchKernelGGL((k_body_apply<2>), dim3(grid), dim3(bs), 0, c->stream, c->n, d_m, b[0], b[1], 0.0,
-                           add ? 1 : 0, d_f);
+    dispatch_dm(c->dm, [&](auto dm) {
+        hipLaunchKernelGGL((k_body_apply<dm()>), dim3(grid), dim3(bs), 0, c->stream, c->n, d_m, b[0], b[1],
+                           dm() == 3 ? b[2] : 0.0, add ? 1 : 0, d_f);
+    });
     FEMCY_HIP(hipGetLastError());
     return FEMCY_OK;
 }
@@ -1827,34 +1802,14 @@ int launch_body_apply(Ctx* c, const double* d_m, const double* b, bool add, doub
 // k_nodal_force into th.d_f [n]
 int launch_thermal_force(Ctx* c, const Ctx::Thermal& th, double* d_fe) {
     const int bs = 256, grid = (c->ne + bs - 1) / bs;
-    bool launched = false;
     size_t tm = timing_begin(c, T_GEOM);
-#define THERMAL_CALL                                                                                                \
-    hipLaunchKernelGGL((k_thermal_force<NPE, DM>), dim3(grid), dim3(bs), 0, c->stream, c->ne, c->nGP, c->d_nodes,   \
-                       c->d_elems, c->d_dN, th.d_N, c->d_w, th.d_dT, th.ts, d_fe)
-    FEMCY_DISPATCH_ELEMENT(3, 2, THERMAL_CALL)
-    FEMCY_DISPATCH_ELEMENT(4, 2, THERMAL_CALL)
-    FEMCY_DISPATCH_ELEMENT(6, 2, THERMAL_CALL)
-    FEMCY_DISPATCH_ELEMENT(8, 2, THERMAL_CALL)
-    FEMCY_DISPATCH_ELEMENT(4, 3, THERMAL_CALL)
-    FEMCY_DISPATCH_ELEMENT(10, 3, THERMAL_CALL)
-    FEMCY_DISPATCH_ELEMENT(8, 3, THERMAL_CALL)
-    FEMCY_DISPATCH_ELEMENT(6, 3, THERMAL_CALL)
-#undef THERMAL_CALL
-    if (launched) {
-        const int ngrid = (int)(((int64_t)c->nn * 32 + bs - 1) / bs);   // 32 lanes per node
-        if (c->dm == 3)
-            hipLaunchKernelGGL((k_nodal_force<3>), dim3(ngrid), dim3(bs), 0, c->stream, c->nn, c->d_ne_ptr, c->d_ne_idx,
-                               d_fe, th.d_f);
-        else
-            hipLaunchKernelGGL((k_nodal_force<2>), dim3(ngrid), dim3(bs), 0, c->stream, c->nn, c->d_ne_ptr, c->d_ne_idx,
-                               d_fe, th.d_f);
-    }
+    const bool launched = dispatch_element(c->npe, c->dm, [&](auto npe, auto dm) {
+        hipLaunchKernelGGL((k_thermal_force<npe(), dm()>), dim3(grid), dim3(bs), 0, c->stream, c->ne, c->nGP, c->d_nodes,
+                           c->d_elems, c->d_dN, th.d_N.get(), c->d_w, th.d_dT.get(), th.ts, d_fe);
+    });
+    if (launched) launch_node_sums(c, d_fe, th.d_f.get());
     timing_end(c, tm);
-    if (!launched) {
-        set_error("no thermal-load kernel instantiated for npe=%d dm=%d", c->npe, c->dm);
-        return FEMCY_ENOKERNEL;
-    }
+    if (!launched) return no_kernel(c, "thermal-load");
     FEMCY_HIP(hipGetLastError());
     return FEMCY_OK;
 }
@@ -1874,12 +1829,11 @@ int launch_thermal_post(Ctx* c, const Ctx::Thermal& th, double scale) {
     const int64_t ngp = (int64_t)c->ne * c->nGP;
     const int bs = 256, grid = (int)((ngp + bs - 1) / bs);
     size_t tm = timing_begin(c, T_GEOM);
-    if (c->dm == 3)
-        hipLaunchKernelGGL((k_thermal_post<3>), dim3(grid), dim3(bs), 0, c->stream, ngp, c->nGP, c->npe, c->mat_kind,
-                           c->mat_params[1], c->d_elems, th.d_N, th.d_dT, th.ts, scale, c->d_sigma, c->d_mises);
-    else
-        hipLaunchKernelGGL((k_thermal_post<2>), dim3(grid), dim3(bs), 0, c->stream, ngp, c->nGP, c->npe, c->mat_kind,
-                           c->mat_params[1], c->d_elems, th.d_N, th.d_dT, th.ts, scale, c->d_sigma, c->d_mises);
+    dispatch_dm(c->dm, [&](auto dm) {
+        hipLaunchKernelGGL((k_thermal_post<dm()>), dim3(grid), dim3(bs), 0, c->stream, ngp, c->nGP, c->npe, c->mat_kind,
+                           c->mat_params[1], c->d_elems, th.d_N.get(), th.d_dT.get(), th.ts, scale, c->d_sigma,
+                           c->d_mises);
+    });
     timing_end(c, tm);
     FEMCY_HIP(hipGetLastError());
     return FEMCY_OK;
@@ -1892,30 +1846,18 @@ int launch_mass_blocks(Ctx* c, int32_t nq, const double* d_Nq, const double* d_d
         return FEMCY_EINVAL;
     }
     const int bs = 256, grid = (c->ne + bs - 1) / bs;
-    bool launched = false;
     size_t tm = timing_begin(c, T_GEOM);          // events only under FEMCY_OPT_TIMING (tools/dynamic_record.py)
-#define MASS_CALL                                                                                                   \
-    hipLaunchKernelGGL((k_mass_points<NPE, DM>), dim3(grid), dim3(bs), 0, c->stream, c->ne, nq, c->d_nodes, c->d_elems, \
-                       d_dNq, d_wq, rho, d_vq)
-    FEMCY_DISPATCH_ELEMENT(3, 2, MASS_CALL)
-    FEMCY_DISPATCH_ELEMENT(4, 2, MASS_CALL)
-    FEMCY_DISPATCH_ELEMENT(6, 2, MASS_CALL)
-    FEMCY_DISPATCH_ELEMENT(8, 2, MASS_CALL)
-    FEMCY_DISPATCH_ELEMENT(4, 3, MASS_CALL)
-    FEMCY_DISPATCH_ELEMENT(10, 3, MASS_CALL)
-    FEMCY_DISPATCH_ELEMENT(8, 3, MASS_CALL)
-    FEMCY_DISPATCH_ELEMENT(6, 3, MASS_CALL)
-#undef MASS_CALL
+    const bool launched = dispatch_element(c->npe, c->dm, [&](auto npe, auto dm) {
+        hipLaunchKernelGGL((k_mass_points<npe(), dm()>), dim3(grid), dim3(bs), 0, c->stream, c->ne, nq, c->d_nodes,
+                           c->d_elems, d_dNq, d_wq, rho, d_vq);
+    });
     if (launched) {
         const int64_t npos = c->stored_rows * SLICE;
         hipLaunchKernelGGL(k_mass_blocks, dim3((unsigned)((npos + bs - 1) / bs)), dim3(bs), 0, c->stream, npos, nq, c->npe,
                            c->d_ctr_ptr, c->d_ctr, d_Nq, d_vq, d_m);
     }
     timing_end(c, tm);
-    if (!launched) {
-        set_error("no mass kernel instantiated for npe=%d dm=%d", c->npe, c->dm);
-        return FEMCY_ENOKERNEL;
-    }
+    if (!launched) return no_kernel(c, "mass");
     FEMCY_HIP(hipGetLastError());
     return FEMCY_OK;
 }
@@ -2021,12 +1963,10 @@ static int assembly_mode(const Ctx* c, int* out) {
 // K_aa = -sum_{b != a} K_ab (FEMCY_ASM_GATHER_SYM_ROWSUM and the consistent tangent)
 static void launch_diag_from_rowsum(Ctx* c, int bs) {
     const int gd = (int)(((int64_t)c->nslices * SLICE + bs - 1) / bs);
-    if (c->dm == 3)
-        hipLaunchKernelGGL((k_diag_from_rowsum<3>), dim3(gd), dim3(bs), 0, c->stream, c->nslices, c->d_node_of,
+    dispatch_dm(c->dm, [&](auto dm) {
+        hipLaunchKernelGGL((k_diag_from_rowsum<dm()>), dim3(gd), dim3(bs), 0, c->stream, c->nslices, c->d_node_of,
                            c->d_rowlen, c->d_slice_off, c->d_Kvals);
-    else
-        hipLaunchKernelGGL((k_diag_from_rowsum<2>), dim3(gd), dim3(bs), 0, c->stream, c->nslices, c->d_node_of,
-                           c->d_rowlen, c->d_slice_off, c->d_Kvals);
+    });
 }
 
 int launch_assemble(Ctx* c) {
@@ -2040,14 +1980,11 @@ int launch_assemble(Ctx* c) {
         const int64_t npos = c->stored_rows * SLICE;
         const int grid = (int)((npos + bs - 1) / bs);
         const int skip = c->dN_sums_to_zero ? 1 : 0;
-        if (c->dm == 3)
-            hipLaunchKernelGGL((k_assemble_gather_consistent<3>), dim3(grid), dim3(bs), 0, c->stream, npos, c->npe, c->nGP,
-                               c->d_ctr_ptr, c->d_ctr, c->d_dsdx, c->d_vol, c->d_F, c->d_sigma, neo, lam, mu,
+        dispatch_dm(c->dm, [&](auto dm) {
+            hipLaunchKernelGGL((k_assemble_gather_consistent<dm()>), dim3(grid), dim3(bs), 0, c->stream, npos, c->npe,
+                               c->nGP, c->d_ctr_ptr, c->d_ctr, c->d_dsdx, c->d_vol, c->d_F, c->d_sigma, neo, lam, mu,
                                c->mat_params[0], c->mat_params[1], c->d_tpos, skip, c->d_Kvals);
-        else
-            hipLaunchKernelGGL((k_assemble_gather_consistent<2>), dim3(grid), dim3(bs), 0, c->stream, npos, c->npe, c->nGP,
-                               c->d_ctr_ptr, c->d_ctr, c->d_dsdx, c->d_vol, c->d_F, c->d_sigma, neo, lam, mu,
-                               c->mat_params[0], c->mat_params[1], c->d_tpos, skip, c->d_Kvals);
+        });
         if (skip) launch_diag_from_rowsum(c, bs);
         timing_end(c, th);
         FEMCY_HIP(hipGetLastError());
@@ -2130,14 +2067,13 @@ int launch_assemble(Ctx* c) {
         case FEMCY_ASM_ROWS: {
             const int grid = std::min((c->nn + 3) / 4, 256 * 16);
             const size_t lds = rows_lds(c);
-            if (c->dm == 3)
-                FEMCY_LDS_LAUNCH((k_assemble_rows<3>), grid, lds, c->nn, c->npe, c->nGP, c->max_row_blocks, c->d_ne_ptr,
+            rc = dispatch_dm(c->dm, [&](auto dm) -> int {     // (FEMCY_LDS_LAUNCH returns on a HIP error)
+                FEMCY_LDS_LAUNCH((k_assemble_rows<dm()>), grid, lds, c->nn, c->npe, c->nGP, c->max_row_blocks, c->d_ne_ptr,
                                  c->d_ne_idx, c->d_slotj, c->d_rowlen, c->d_pos, c->d_slice_off, c->d_dsdx, c->d_vol, c->d_C,
                                  c->d_Kvals);
-            else
-                FEMCY_LDS_LAUNCH((k_assemble_rows<2>), grid, lds, c->nn, c->npe, c->nGP, c->max_row_blocks, c->d_ne_ptr,
-                                 c->d_ne_idx, c->d_slotj, c->d_rowlen, c->d_pos, c->d_slice_off, c->d_dsdx, c->d_vol, c->d_C,
-                                 c->d_Kvals);
+                return FEMCY_OK;
+            });
+            if (rc) return rc;
             break;
         }
         case FEMCY_ASM_ATOMIC: {
@@ -2145,12 +2081,10 @@ int launch_assemble(Ctx* c) {
                                      c->stream));
             const int64_t npair = (int64_t)c->ne * c->npe * c->npe;
             const int grid = (int)((npair + bs - 1) / bs);
-            if (c->dm == 3)
-                hipLaunchKernelGGL((k_assemble_atomic<3>), dim3(grid), dim3(bs), 0, c->stream, npair, c->npe, c->nGP,
+            dispatch_dm(c->dm, [&](auto dm) {
+                hipLaunchKernelGGL((k_assemble_atomic<dm()>), dim3(grid), dim3(bs), 0, c->stream, npair, c->npe, c->nGP,
                                    c->d_elems, c->d_slotj, c->d_pos, c->d_slice_off, c->d_dsdx, c->d_vol, c->d_C, c->d_Kvals);
-            else
-                hipLaunchKernelGGL((k_assemble_atomic<2>), dim3(grid), dim3(bs), 0, c->stream, npair, c->npe, c->nGP,
-                                   c->d_elems, c->d_slotj, c->d_pos, c->d_slice_off, c->d_dsdx, c->d_vol, c->d_C, c->d_Kvals);
+            });
             break;
         }
         default: {   // FEMCY_ASM_GATHER, FEMCY_ASM_GATHER_SYM, FEMCY_ASM_GATHER_SYM_ROWSUM
@@ -2178,15 +2112,8 @@ int launch_assemble(Ctx* c) {
 }
 
 int launch_nodal_force(Ctx* c, double* d_f) {
-    const int bs = 256;
-    const int grid = (int)(((int64_t)c->nn * 32 + bs - 1) / bs);   // 32 lanes per node
     size_t th = timing_begin(c, T_FORCE);
-    if (c->dm == 3)
-        hipLaunchKernelGGL((k_nodal_force<3>), dim3(grid), dim3(bs), 0, c->stream, c->nn, c->d_ne_ptr, c->d_ne_idx,
-                           c->d_fe, d_f);
-    else
-        hipLaunchKernelGGL((k_nodal_force<2>), dim3(grid), dim3(bs), 0, c->stream, c->nn, c->d_ne_ptr, c->d_ne_idx,
-                           c->d_fe, d_f);
+    launch_node_sums(c, c->d_fe, d_f);
     timing_end(c, th);
     FEMCY_HIP(hipGetLastError());
     return FEMCY_OK;
@@ -2198,12 +2125,10 @@ int launch_dirichlet_zero(Ctx* c, const int32_t* d_dofs, int32_t k, double* d_re
     const int64_t total = (int64_t)k * c->max_row_blocks;
     const int grid = (int)((total + bs - 1) / bs);
     const uint8_t* owner = c->comm ? c->d_owner : nullptr;
-    if (c->dm == 3)
-        hipLaunchKernelGGL((k_dirichlet_zero<3>), dim3(grid), dim3(bs), 0, c->stream, k, c->max_row_blocks, d_dofs,
+    dispatch_dm(c->dm, [&](auto dm) {
+        hipLaunchKernelGGL((k_dirichlet_zero<dm()>), dim3(grid), dim3(bs), 0, c->stream, k, c->max_row_blocks, d_dofs,
                            c->d_slice_off, c->d_rowlen, c->d_pos, c->d_bcol, c->d_Kvals, d_resid, owner);
-    else
-        hipLaunchKernelGGL((k_dirichlet_zero<2>), dim3(grid), dim3(bs), 0, c->stream, k, c->max_row_blocks, d_dofs,
-                           c->d_slice_off, c->d_rowlen, c->d_pos, c->d_bcol, c->d_Kvals, d_resid, owner);
+    });
     FEMCY_HIP(hipGetLastError());
     return FEMCY_OK;
 }

@@ -26,6 +26,7 @@
 #include <vector>
 #include "../../include/femcy.h"
 #include "../csrc/band_order.hpp"
+#include "../csrc/element_dispatch.hpp"
 #include "../csrc/element_math.hpp"
 
 using namespace femcy;
@@ -111,6 +112,12 @@ struct femcy_ctx {
 namespace {
 
 enum : unsigned { GEOM_DSDX = 1, GEOM_F = 2, GEOM_SIGMA = 4, GEOM_FE = 8 };
+
+// what an element pass answers for a mesh whose family dispatch_element (csrc/element_dispatch.hpp) does not list
+int no_kernel(const femcy_ctx* c, const char* what) {
+    set_error("no %s kernel instantiated for npe=%d dm=%d", what, c->npe, c->dm);
+    return FEMCY_ENOKERNEL;
+}
 
 // get_dsdx_and_vol (stiffnessMtrx.py:132-150), get_deformation_gradient (:532-556), constitutiveOfLargeDeform and the
 // per-element nodal forces of assemble_nodal_force_GN (:620-644): the element pass of the device's k_geom
@@ -983,20 +990,8 @@ int femcy_bodyload_create(femcy_ctx* ctx, const double* N, int32_t nsel, const i
     }
     const uint8_t* mk = sel_elems ? mask.data() : nullptr;
     BodyLoad bl;
-    const int key = c->npe * 10 + c->dm;
-    switch (key) {
-        case 32: body_weights<3, 2>(c, N, mk, bl.m); break;
-        case 42: body_weights<4, 2>(c, N, mk, bl.m); break;
-        case 62: body_weights<6, 2>(c, N, mk, bl.m); break;
-        case 82: body_weights<8, 2>(c, N, mk, bl.m); break;
-        case 43: body_weights<4, 3>(c, N, mk, bl.m); break;
-        case 103: body_weights<10, 3>(c, N, mk, bl.m); break;
-        case 83: body_weights<8, 3>(c, N, mk, bl.m); break;
-        case 63: body_weights<6, 3>(c, N, mk, bl.m); break;
-        default:
-            set_error("no body-load kernel instantiated for npe=%d dm=%d", c->npe, c->dm);
-            return FEMCY_ENOKERNEL;
-    }
+    if (!dispatch_element(c->npe, c->dm, [&](auto npe, auto dm) { body_weights<npe(), dm()>(c, N, mk, bl.m); }))
+        return no_kernel(c, "body-load");
     c->bodyloads.push_back(std::move(bl));
     *id_out = (int32_t)c->bodyloads.size() - 1;
     return FEMCY_OK;
@@ -1075,29 +1070,14 @@ int femcy_thermal_create(femcy_ctx* ctx, const double* N, double alpha, const do
     Thermal th;
     th.N.assign(N, N + (size_t)c->nGP * c->npe);
     th.dT.assign(dT, dT + (size_t)c->nn);
-    if (c->dm == 3) {
-        double s[3][3];
-        thermal_unit_stress<3>(c->mat_kind, c->C, c->params[1], s);
-        for (int i = 0; i < 9; ++i) th.s[i] = alpha * s[i / 3][i % 3];
-    } else {
-        double s[2][2];
-        thermal_unit_stress<2>(c->mat_kind, c->C, c->params[1], s);
-        for (int i = 0; i < 4; ++i) th.s[i] = alpha * s[i / 2][i % 2];
-    }
-    const int key = c->npe * 10 + c->dm;
-    switch (key) {
-        case 32: thermal_force<3, 2>(c, th); break;
-        case 42: thermal_force<4, 2>(c, th); break;
-        case 62: thermal_force<6, 2>(c, th); break;
-        case 82: thermal_force<8, 2>(c, th); break;
-        case 43: thermal_force<4, 3>(c, th); break;
-        case 103: thermal_force<10, 3>(c, th); break;
-        case 83: thermal_force<8, 3>(c, th); break;
-        case 63: thermal_force<6, 3>(c, th); break;
-        default:
-            set_error("no thermal-load kernel instantiated for npe=%d dm=%d", c->npe, c->dm);
-            return FEMCY_ENOKERNEL;
-    }
+    dispatch_dm(c->dm, [&](auto dm) {
+        constexpr int DM = dm();
+        double s[DM][DM];
+        thermal_unit_stress<DM>(c->mat_kind, c->C, c->params[1], s);
+        for (int i = 0; i < DM * DM; ++i) th.s[i] = alpha * s[i / DM][i % DM];
+    });
+    if (!dispatch_element(c->npe, c->dm, [&](auto npe, auto dm) { thermal_force<npe(), dm()>(c, th); }))
+        return no_kernel(c, "thermal-load");
     c->thermals.push_back(std::move(th));
     *id_out = (int32_t)c->thermals.size() - 1;
     return FEMCY_OK;
@@ -1135,23 +1115,21 @@ int femcy_thermal_stress(femcy_ctx* ctx, int32_t id, double scale) {
             "first (the Gauss-point stress does not exist, is the nlgeom one, or has been corrected already)");
     c->post_small = false;
     const int64_t ngp = (int64_t)c->ne * c->nGP;
-    const int npe = c->npe, nGP = c->nGP, dm = c->dm, dd = dm * dm;
+    const int npe = c->npe, nGP = c->nGP;
+    dispatch_dm(c->dm, [&](auto dm) {
+        constexpr int DM = dm();
+        double s[DM][DM];
+        for (int i = 0; i < DM * DM; ++i) s[i / DM][i % DM] = th.s[i];
 #pragma omp parallel for schedule(static)
-    for (int64_t t = 0; t < ngp; ++t) {
-        const int64_t e = t / nGP;
-        const int g = (int)(t - e * nGP);
-        double tg = 0.0;
-        for (int a = 0; a < npe; ++a) tg += th.N[(size_t)g * npe + a] * th.dT[c->elems[e * npe + a]];
-        if (dm == 3) {
-            double s[3][3];
-            for (int i = 0; i < 9; ++i) s[i / 3][i % 3] = th.s[i];
-            thermal_post_point<3>(c->mat_kind, c->params[1], s, scale * tg, c->sigma.data() + t * dd, c->mises.data() + t);
-        } else {
-            double s[2][2];
-            for (int i = 0; i < 4; ++i) s[i / 2][i % 2] = th.s[i];
-            thermal_post_point<2>(c->mat_kind, c->params[1], s, scale * tg, c->sigma.data() + t * dd, c->mises.data() + t);
+        for (int64_t t = 0; t < ngp; ++t) {
+            const int64_t e = t / nGP;
+            const int g = (int)(t - e * nGP);
+            double tg = 0.0;
+            for (int a = 0; a < npe; ++a) tg += th.N[(size_t)g * npe + a] * th.dT[c->elems[e * npe + a]];
+            thermal_post_point<DM>(c->mat_kind, c->params[1], s, scale * tg, c->sigma.data() + t * DM * DM,
+                                   c->mises.data() + t);
         }
-    }
+    });
     return FEMCY_OK;
 }
 
@@ -1195,20 +1173,9 @@ int femcy_mass_create(femcy_ctx* ctx, int32_t nq, const double* Nq, const double
     REQUIRE(nq >= 1 && nq <= 64, "mass rule: %d points (1 .. 64 are supported)", nq);
     REQUIRE(std::isfinite(rho) && rho > 0.0, "mass: the density must be finite and positive");
     Mass ms;
-    const int key = c->npe * 10 + c->dm;
-    switch (key) {
-        case 32: mass_blocks<3, 2>(c, nq, Nq, dNq, wq, rho, ms.m); break;
-        case 42: mass_blocks<4, 2>(c, nq, Nq, dNq, wq, rho, ms.m); break;
-        case 62: mass_blocks<6, 2>(c, nq, Nq, dNq, wq, rho, ms.m); break;
-        case 82: mass_blocks<8, 2>(c, nq, Nq, dNq, wq, rho, ms.m); break;
-        case 43: mass_blocks<4, 3>(c, nq, Nq, dNq, wq, rho, ms.m); break;
-        case 103: mass_blocks<10, 3>(c, nq, Nq, dNq, wq, rho, ms.m); break;
-        case 83: mass_blocks<8, 3>(c, nq, Nq, dNq, wq, rho, ms.m); break;
-        case 63: mass_blocks<6, 3>(c, nq, Nq, dNq, wq, rho, ms.m); break;
-        default:
-            set_error("no mass kernel instantiated for npe=%d dm=%d", c->npe, c->dm);
-            return FEMCY_ENOKERNEL;
-    }
+    if (!dispatch_element(c->npe, c->dm,
+                          [&](auto npe, auto dm) { mass_blocks<npe(), dm()>(c, nq, Nq, dNq, wq, rho, ms.m); }))
+        return no_kernel(c, "mass");
     c->masses.push_back(std::move(ms));
     *id_out = (int32_t)c->masses.size() - 1;
     return FEMCY_OK;

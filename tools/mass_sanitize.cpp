@@ -1,5 +1,5 @@
-// Stand-alone sanitizer check of the host backend's mass / Newmark / small-strain-energy calls on a 65-node CPS4 mesh (12 x 4
-// cells): no Python, no GPU.  Build and run from the repository root:
+// Stand-alone sanitizer check of the host backend's mass / Newmark / small-strain-energy / body-load / thermal-load calls on
+// a 65-node CPS4 mesh (12 x 4 cells): no Python, no GPU.  Build and run from the repository root:
 //   g++ -O1 -g -std=c++17 -fopenmp -fsanitize=address,undefined -fno-omit-frame-pointer tools/mass_sanitize.cpp \
 //       femcy_amd/csrc_cpu/femcy_cpu.cpp -o /tmp/mass_sanitize && /tmp/mass_sanitize
 // It prints one line and returns 0 when every call succeeded; the sanitizers abort on a finding.
@@ -47,7 +47,22 @@ int main() {
     double es = 0;
     rc |= femcy_elastic_energy_small(h, FEMCY_VEC_VEL, &es);
     int bad = femcy_mass_apply(h, 5, FEMCY_VEC_VEL, FEMCY_VEC_RHS, 1.0, 0);
-    printf("rc=%d nn=%d total mass=%.6g (area 6 x rho = %.6g) ke=%.6g refused=%d\n", rc, nn, total, 6 * 7.85e-3, ke, bad);
+    // the other two element passes that go through dispatch_element: a body load and a thermal load, created and applied
+    int32_t bl = -1, th = -1;
+    const double grav[2] = {0.0, -9.81 * 7.85e-3};
+    std::vector<double> wts(nn), dT(nn), fth(nn * 2);
+    for (int a = 0; a < nn; ++a) dT[a] = 20.0 + 5.0 * nodes[2 * a];
+    rc |= femcy_bodyload_create(h, N, 0, nullptr, &bl);
+    rc |= femcy_bodyload_weights(h, bl, wts.data());
+    rc |= femcy_bodyload_apply(h, bl, grav, FEMCY_VEC_RHS, 0);
+    rc |= femcy_thermal_create(h, N, 1.2e-5, dT.data(), &th);
+    rc |= femcy_thermal_force(h, th, fth.data());
+    rc |= femcy_thermal_apply(h, th, 1.0, FEMCY_VEC_RHS, 1);
+    rc |= femcy_compute_strain_stress(h, FEMCY_VEC_DOF, 0);
+    rc |= femcy_thermal_stress(h, th, 1.0);
+    double area = 0; for (double v : wts) area += v;
+    printf("rc=%d nn=%d total mass=%.6g (area 6 x rho = %.6g) ke=%.6g refused=%d body-load weights=%.6g (area 6)\n", rc, nn,
+           total, 6 * 7.85e-3, ke, bad, area);
     femcy_ctx_destroy(h);
     return rc;
 }
