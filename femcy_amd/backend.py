@@ -74,6 +74,8 @@ EXPORTS = [
     "femcy_thermal_create", "femcy_thermal_force", "femcy_thermal_apply", "femcy_thermal_stress",
     "femcy_mass_create", "femcy_mass_get", "femcy_mass_apply", "femcy_mass_add_to_K", "femcy_mass_kinetic_energy",
     "femcy_newmark_predict", "femcy_newmark_update",
+    "femcy_lumped_mass_create", "femcy_lumped_mass_get", "femcy_explicit_create", "femcy_explicit_start",
+    "femcy_explicit_advance", "femcy_explicit_kinetic_energy", "femcy_explicit_stable_dt",
     "femcy_loadset_create", "femcy_loadset_neumann", "femcy_loadset_neumann_add", "femcy_spmv", "femcy_pcg", "femcy_compute_strain_stress", "femcy_elastic_energy", "femcy_elastic_energy_small", "femcy_extrapolate",
     "femcy_get_K_ell", "femcy_get_K_bsr", "femcy_get_gp_field", "femcy_timing",
     "femcy_timing_reset", "femcy_comm_unique_id", "femcy_comm_local_id", "femcy_comm_init", "femcy_comm_info", "femcy_comm_set_neighbours",
@@ -174,6 +176,11 @@ def _bind(lib, kind):
         "femcy_mass_kinetic_energy": [p, i32, cint, C.POINTER(f64)],
         "femcy_newmark_predict": [p, cint, cint, cint, cint, f64, f64, f64],
         "femcy_newmark_update": [p, cint, cint, cint, cint, f64, f64, f64],
+        "femcy_lumped_mass_create": [p, i32, p, p, p, f64, C.POINTER(i32)], "femcy_lumped_mass_get": [p, i32, p],
+        "femcy_explicit_create": [p, i32, i32, p, C.POINTER(i32)], "femcy_explicit_start": [p, i32, cint, f64],
+        "femcy_explicit_advance": [p, i32, cint, i32, f64, f64, f64],
+        "femcy_explicit_kinetic_energy": [p, i32, cint, C.POINTER(f64)],
+        "femcy_explicit_stable_dt": [p, i32, C.POINTER(f64), C.POINTER(f64)],
         "femcy_loadset_create": [p, i32, i32, i32, p, p, p, p, p, i32, p, p, C.POINTER(i32)],
         "femcy_loadset_neumann": [p, i32, f64, p, cint],
         "femcy_loadset_neumann_add": [p, i32, f64, p, cint],
@@ -537,6 +544,49 @@ class Context:
         """a, v of t + dt in place of a, v, from the displacements u_new (t + dt) and u (t)"""
         self._call("femcy_newmark_update", int(u_new_vec), int(u_vec), int(v_vec), int(a_vec), float(beta), float(gamma),
                    float(dt))
+
+    # lumped mass and the explicit integrator (*Dynamic, explicit)
+    def lumped_mass(self, ELE, rho: float) -> int:
+        """HRZ-lumped nodal masses of the undeformed mesh at density rho, integrated with the plug-in's mass_rule()."""
+        t = ELE.mass_tables()
+        if t["Nq"].shape != (t["nq"], self.npe) or t["dNq"].shape != (t["nq"], self.npe, self.dm):
+            raise FemcyError(f"mass-rule tables do not match the mesh (npe={self.npe}, dm={self.dm})")
+        out = C.c_int32()
+        self._call("femcy_lumped_mass_create", int(t["nq"]), _ptr(t["Nq"]), _ptr(t["dNq"]), _ptr(t["wq"]), float(rho),
+                   C.byref(out))
+        return out.value
+
+    def lumped_mass_get(self, lm: int) -> np.ndarray:
+        out = np.empty(self.nn, dtype=np.float64)
+        self._call("femcy_lumped_mass_get", int(lm), _ptr(out))
+        return out
+
+    def explicit(self, lm: int, dofsets=()) -> int:
+        """an explicit integrator on the lumped mass lm; the DOFs of the given DOF sets are held (inverse mass 0)."""
+        ids = np.ascontiguousarray(list(dofsets), dtype=np.int32)
+        out = C.c_int32()
+        self._call("femcy_explicit_create", int(lm), int(ids.size), _ptr(ids) if ids.size else None, C.byref(out))
+        return out.value
+
+    def explicit_start(self, ex: int, rhs_vec: int = VEC_RHS, scale: float = 1.0):
+        """ACC = a_0 = minv (scale f - f_int(DOF))"""
+        self._call("femcy_explicit_start", int(ex), int(rhs_vec), float(scale))
+
+    def explicit_advance(self, ex: int, nsteps: int, dt: float, rhs_vec: int = VEC_RHS, scale0: float = 1.0,
+                         dscale: float = 0.0):
+        """nsteps velocity-Verlet steps on DOF, VEL, ACC; the k-th new state is loaded with (scale0 + k dscale) f"""
+        self._call("femcy_explicit_advance", int(ex), int(rhs_vec), int(nsteps), float(dt), float(scale0), float(dscale))
+
+    def explicit_kinetic_energy(self, ex: int, v_vec: int = VEC_VEL) -> float:
+        out = C.c_double()
+        self._call("femcy_explicit_kinetic_energy", int(ex), int(v_vec), C.byref(out))
+        return out.value
+
+    def explicit_stable_dt(self, ex: int):
+        """-> (dt, omega_bound): Gershgorin's bound on M_L^-1 K of the last assemble_K, and 2 / that bound"""
+        dt, om = C.c_double(), C.c_double()
+        self._call("femcy_explicit_stable_dt", int(ex), C.byref(dt), C.byref(om))
+        return dt.value, om.value
 
     def spmv(self, x_vec: int, y_vec: int):
         self._call("femcy_spmv", int(x_vec), int(y_vec))

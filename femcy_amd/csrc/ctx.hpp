@@ -345,7 +345,14 @@ struct Ctx {
     // ---- device-resident consistent mass (femcy_mass_*): one scalar per stored block, in d_bcol's [block row][lane] layout
     struct Mass { DevBuf<double> d_m; };
     std::vector<Mass> masses;
-    bool post_small = false;          // sigma / mises hold femcy_compute_strain_stress(large = 0), not yet corrected
+    // ---- explicit dynamics (femcy_lumped_mass_*, femcy_explicit_*): the HRZ-lumped nodal masses [nn], and an integrator =
+    // the inverse mass per scalar DOF [n] with 0 on the constrained DOFs + the lumped mass it was made from
+    struct LumpedMass { DevBuf<double> d_m; };
+    std::vector<LumpedMass> lumped_masses;
+    struct Explicit { DevBuf<double> d_minv; int32_t lumped = -1; };
+    std::vector<Explicit> explicits;
+    int64_t K_serial = -1;            // pattern_serial of the last successful assembly: K holds a matrix when they agree
+    bool post_small = false;         // sigma / mises hold femcy_compute_strain_stress(large = 0), not yet corrected
 
     // ---- options / timing
     int opt_assembly = FEMCY_ASM_AUTO;
@@ -457,6 +464,19 @@ int launch_newmark_predict(Ctx* c, const double* u, const double* v, const doubl
                            double c2);
 int launch_newmark_update(Ctx* c, const double* un, const double* u, double* v, double* a, double beta, double gamma,
                           double dt);
+// explicit dynamics (kernels_explicit.hip).  Lumped mass: element pass into d_me [ne][npe] (scratch of the caller), node sums
+// into d_m [nn].  launch_explicit_minv: d_minv [n] = 1 / m of the DOF's node.  launch_explicit_start / _node follow an element
+// pass that left d_fe (launch_geom with GEOM_FE): a_0, or one kick (+ the drift to the next state when drift is set) with the
+// node sums of d_fe never stored.  launch_explicit_drift: the first drift of a call.  All of them only enqueue.
+int launch_lumped_mass(Ctx* c, int32_t nq, const double* d_Nq, const double* d_dNq, const double* d_wq, double rho,
+                       double* d_me, double* d_m);
+int launch_explicit_minv(Ctx* c, const double* d_m, double* d_minv);
+int launch_explicit_start(Ctx* c, const double* d_minv, const double* d_f, double scale);
+int launch_explicit_drift(Ctx* c, double h);
+int launch_explicit_node(Ctx* c, const double* d_minv, const double* d_f, double scale, double h, bool drift);
+int launch_explicit_energy(Ctx* c, const double* d_m, const double* d_v, double* out);   // 1/2 sum m v^2, fixed order
+// max over the rows i with minv_i != 0 of minv_i sum_j |K_ij| (Gershgorin bound on the spectrum of M_L^-1 K)
+int launch_rowabs_bound(Ctx* c, const double* d_minv, double* out);
 // pos_space: x and y are in STORAGE order (entry p * dm + c belongs to the node at storage position p = slice * 64 + lane;
 // the padding lanes of the last slice hold zeros) -- the form the three-kernel PCG runs in since round 4
 int launch_spmv(Ctx* c, const double* d_x, double* d_y, double* d_partials, int* nblocks_out, bool pos_space = false);

@@ -779,4 +779,50 @@ FEMCY_HD void newmark_update_entry(double un, double u, double& v, double& a, do
     a = an;
 }
 
+// --------------------------------------------------------------------------------- explicit dynamics
+// one element of the LUMPED mass by HRZ lumping (Hinton, Rock, Zienkiewicz): with vq = rho |det J_q| w_q at the nq points of
+// the element's mass rule, on the UNDEFORMED coordinates X,
+//   m_e = sum_q vq,   d_a = sum_q N_a(xi_q)^2 vq,   me[a] = d_a m_e / sum_b d_b
+// i.e. the diagonal of the consistent element mass scaled to the element's mass: strictly positive for every family (the row
+// sums are negative at the corners of C3D10 / CPS6 / CPS8), m_e / NPE on CPS3 / C3D4.
+template <int NPE, int DM>
+FEMCY_HD void lumped_element(const double (&X)[NPE][DM], int32_t nq, const double* __restrict__ Nq,
+                             const double* __restrict__ dNq, const double* __restrict__ wq, double rho, double (&me)[NPE]) {
+    double mass = 0.0;
+#pragma unroll
+    for (int a = 0; a < NPE; ++a) me[a] = 0.0;
+    for (int32_t q = 0; q < nq; ++q) {
+        double vq;
+        mass_points_element<NPE, DM>(X, 1, dNq + q * NPE * DM, wq + q, rho, &vq, 1);
+        mass += vq;
+#pragma unroll
+        for (int a = 0; a < NPE; ++a) me[a] += (Nq[q * NPE + a] * Nq[q * NPE + a]) * vq;
+    }
+    double diag = 0.0;
+#pragma unroll
+    for (int a = 0; a < NPE; ++a) diag += me[a];
+#pragma unroll
+    for (int a = 0; a < NPE; ++a) me[a] = me[a] * mass / diag;
+}
+
+// Velocity Verlet (central differences with all state at whole steps), one scalar DOF.  The fused multiply-adds are written
+// out, so that the node kernel, the vector kernel of a call's first drift and the host backend round alike: a run split into
+// several calls gives the bits of one call.
+//   kick:  a_new = minv (s f - f_int),  v_new = v + (h / 2)(a + a_new)      hh = h / 2
+//   drift: u_new = u + h v + (h^2 / 2) a                                    h2h = h^2 / 2
+FEMCY_HD void explicit_kick(double minv, double s, double f, double fint, double hh, double& v, double& a) {
+    const double an = minv * fma(s, f, -fint);
+    v = fma(hh, a + an, v);
+    a = an;
+}
+FEMCY_HD double explicit_drift(double u, double v, double a, double h, double h2h) { return fma(h2h, a, fma(h, v, u)); }
+
+// sum of 32 partial sums by the xor tree of half a wavefront, as lane 0 of k_nodal_force ends up with it: what the host
+// backend runs so that a node sum has the device's summation order
+inline double half_wave_tree(double (&p)[32]) {
+    for (int o = 16; o > 0; o >>= 1)
+        for (int l = 0; l < o; ++l) p[l] += p[l + o];
+    return p[0];
+}
+
 }  // namespace femcy

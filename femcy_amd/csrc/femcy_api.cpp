@@ -60,6 +60,8 @@ static void drop_objects(Ctx* c) {
     c->bodyloads.clear();
     c->thermals.clear();
     c->masses.clear();
+    c->lumped_masses.clear();
+    c->explicits.clear();
 }
 
 // Right-hand side of a stored load: apply(dst, add) writes this rank's share of it into dst (add: adds it) and is called
@@ -780,7 +782,9 @@ int femcy_assemble_K(femcy_ctx* ctx, int u_vec) {
     if (c->opt_tangent == 1) c->gp_lazy = false;
     int rc = launch_geom(c, du, c->opt_tangent == 1 ? (GEOM_DSDX | GEOM_F | GEOM_SIGMA) : GEOM_DSDX);
     if (rc) return rc;
-    return launch_assemble(c);
+    if ((rc = launch_assemble(c))) return rc;
+    c->K_serial = c->pattern_serial;
+    return FEMCY_OK;
 }
 
 int femcy_internal_force(femcy_ctx* ctx, int u_vec, int f_vec) {
@@ -806,7 +810,9 @@ int femcy_residual_and_K(femcy_ctx* ctx, int u_vec, int f_vec) {
     if (rc) return rc;
     if ((rc = launch_nodal_force(c, c->d_vec[f_vec]))) return rc;
     if ((rc = iface_sum(c, c->d_vec[f_vec]))) return rc;
-    return launch_assemble(c);
+    if ((rc = launch_assemble(c))) return rc;
+    c->K_serial = c->pattern_serial;
+    return FEMCY_OK;
 }
 
 static int stage_dofs(Ctx* c, const int32_t* dofs, const double* vals, int32_t k) {
@@ -1262,6 +1268,150 @@ int femcy_newmark_update(femcy_ctx* ctx, int u_new_vec, int u_vec, int v_vec, in
     FEMCY_REQUIRE(v_vec != a_vec && v_vec != u_vec && v_vec != u_new_vec && a_vec != u_vec && a_vec != u_new_vec,
                   "femcy_newmark_update: velocity and acceleration are written in place and may alias nothing");
     return launch_newmark_update(c, c->d_vec[u_new_vec], c->d_vec[u_vec], c->d_vec[v_vec], c->d_vec[a_vec], beta, gamma, dt);
+}
+
+// ------------------------------------------------------------------------------ explicit dynamics
+#define EXPLICIT_SINGLE_RANK_OR_FAIL(name) \
+    FEMCY_REQUIRE(!c->comm, name ": explicit dynamics is not available on several ranks (femcy_comm_init has run)")
+
+int femcy_lumped_mass_create(femcy_ctx* ctx, int32_t nq, const double* Nq, const double* dNq, const double* wq, double rho,
+                             int32_t* id_out) {
+    CTX_OR_FAIL(ctx);
+    EXPLICIT_SINGLE_RANK_OR_FAIL("femcy_lumped_mass_create");
+    FEMCY_REQUIRE(c->have_mesh && c->have_element && c->have_pattern,
+                  "femcy_lumped_mass_create needs the mesh, the element tables and the pattern (mesh=%d element=%d "
+                  "pattern=%d)", (int)c->have_mesh, (int)c->have_element, (int)c->have_pattern);
+    FEMCY_REQUIRE(Nq && dNq && wq && id_out, "null mass-rule table or id_out");
+    FEMCY_REQUIRE(nq >= 1 && nq <= 64, "mass rule: %d points (1 .. 64 are supported)", nq);
+    FEMCY_REQUIRE(std::isfinite(rho) && rho > 0.0, "mass: the density must be finite and positive");
+    Ctx::LumpedMass lm;
+    DevBuf<double> d_Nq, d_dNq, d_wq, d_me;     // the tables and the element records are scratch of this call
+    int rc = to_device(d_Nq, Nq, sizeof(double) * nq * c->npe);
+    if (!rc) rc = to_device(d_dNq, dNq, sizeof(double) * nq * c->npe * c->dm);
+    if (!rc) rc = to_device(d_wq, wq, sizeof(double) * nq);
+    if (!rc && d_me.alloc(sizeof(double) * (size_t)c->ne * c->npe) != hipSuccess) rc = FEMCY_ENOMEM;
+    if (!rc && lm.d_m.alloc(sizeof(double) * (size_t)c->nn) != hipSuccess) rc = FEMCY_ENOMEM;
+    if (!rc) rc = launch_lumped_mass(c, nq, d_Nq.get(), d_dNq.get(), d_wq.get(), rho, d_me.get(), lm.d_m.get());
+    // ... which the two kernels read: wait for them before the scratch is released at the end of the call
+    if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) {
+        set_error("lumped mass: the kernels failed");
+        rc = FEMCY_EHIP;
+    }
+    if (rc) {
+        if (rc == FEMCY_ENOMEM) set_error("out of device memory for a lumped mass on %d elements", c->ne);
+        return rc;
+    }
+    c->lumped_masses.push_back(std::move(lm));
+    *id_out = (int32_t)c->lumped_masses.size() - 1;
+    return FEMCY_OK;
+}
+
+#define LUMPED_OR_FAIL(id)                                                                                        \
+    FEMCY_REQUIRE((id) >= 0 && (size_t)(id) < c->lumped_masses.size(), "unknown lumped mass %d", (int)(id)); \
+    const Ctx::LumpedMass& lm = c->lumped_masses[(id)]
+
+int femcy_lumped_mass_get(femcy_ctx* ctx, int32_t id, double* out) {
+    CTX_OR_FAIL(ctx);
+    EXPLICIT_SINGLE_RANK_OR_FAIL("femcy_lumped_mass_get");
+    LUMPED_OR_FAIL(id);
+    FEMCY_REQUIRE(out, "null output");
+    FEMCY_HIP(hipMemcpyAsync(out, lm.d_m.get(), sizeof(double) * c->nn, hipMemcpyDeviceToHost, c->stream));
+    FEMCY_HIP(hipStreamSynchronize(c->stream));
+    return FEMCY_OK;
+}
+
+int femcy_explicit_create(femcy_ctx* ctx, int32_t lumped_id, int32_t ndofsets, const int32_t* dofset_ids, int32_t* id_out) {
+    CTX_OR_FAIL(ctx);
+    EXPLICIT_SINGLE_RANK_OR_FAIL("femcy_explicit_create");
+    LUMPED_OR_FAIL(lumped_id);
+    FEMCY_REQUIRE(id_out && ndofsets >= 0 && (ndofsets == 0 || dofset_ids), "femcy_explicit_create: null id_out or DOF-set list");
+    for (int32_t k = 0; k < ndofsets; ++k)
+        FEMCY_REQUIRE(dofset_ids[k] >= 0 && (size_t)dofset_ids[k] < c->dofsets.size(), "unknown DOF set %d", dofset_ids[k]);
+    Ctx::Explicit ex;
+    ex.lumped = lumped_id;
+    if (ex.d_minv.alloc(sizeof(double) * (size_t)c->n) != hipSuccess) {
+        set_error("out of device memory for the inverse mass of %lld DOF", (long long)c->n);
+        return FEMCY_ENOMEM;
+    }
+    int rc = launch_explicit_minv(c, lm.d_m.get(), ex.d_minv.get());
+    for (int32_t k = 0; !rc && k < ndofsets; ++k) {
+        const Ctx::DofSet& ds = c->dofsets[dofset_ids[k]];
+        rc = vec_scatter_const(c, ex.d_minv.get(), ds.d_dofs.get(), 0.0, ds.k);
+    }
+    if (rc) {
+        (void)hipStreamSynchronize(c->stream);      // ex goes: nothing may still write its buffer
+        return rc;
+    }
+    c->explicits.push_back(std::move(ex));
+    *id_out = (int32_t)c->explicits.size() - 1;
+    return FEMCY_OK;
+}
+
+// the argument checks the stepping calls share: the integrator, and a load vector that is none of the three state vectors
+#define EXPLICIT_OR_FAIL(name, id)                                                                                \
+    EXPLICIT_SINGLE_RANK_OR_FAIL(name);                                                                           \
+    FEMCY_REQUIRE((id) >= 0 && (size_t)(id) < c->explicits.size(), "unknown explicit integrator %d", (int)(id));   \
+    const Ctx::Explicit& ex = c->explicits[(id)]
+#define EXPLICIT_RHS_OR_FAIL(name, rhs_vec)                                                                        \
+    VEC_OR_FAIL(rhs_vec);                                                                                          \
+    FEMCY_REQUIRE((rhs_vec) != FEMCY_VEC_DOF && (rhs_vec) != FEMCY_VEC_VEL && (rhs_vec) != FEMCY_VEC_ACC,         \
+                  name ": the load vector may not be one of the state vectors DOF, VEL, ACC")
+
+int femcy_explicit_start(femcy_ctx* ctx, int32_t id, int rhs_vec, double scale) {
+    CTX_OR_FAIL(ctx);
+    READY_OR_FAIL();
+    EXPLICIT_OR_FAIL("femcy_explicit_start", id);
+    EXPLICIT_RHS_OR_FAIL("femcy_explicit_start", rhs_vec);
+    FEMCY_REQUIRE(std::isfinite(scale), "femcy_explicit_start: the load scale is not finite");
+    int rc = force_pass(c, c->d_vec[FEMCY_VEC_DOF]);
+    if (rc) return rc;
+    return launch_explicit_start(c, ex.d_minv.get(), c->d_vec[rhs_vec], scale);
+}
+
+int femcy_explicit_advance(femcy_ctx* ctx, int32_t id, int rhs_vec, int32_t nsteps, double dt, double scale0, double dscale) {
+    CTX_OR_FAIL(ctx);
+    READY_OR_FAIL();
+    EXPLICIT_OR_FAIL("femcy_explicit_advance", id);
+    EXPLICIT_RHS_OR_FAIL("femcy_explicit_advance", rhs_vec);
+    FEMCY_REQUIRE(nsteps >= 0, "femcy_explicit_advance: %d steps", nsteps);
+    FEMCY_REQUIRE(std::isfinite(dt) && dt > 0.0, "femcy_explicit_advance: the increment must be finite and positive");
+    FEMCY_REQUIRE(std::isfinite(scale0) && std::isfinite(dscale), "femcy_explicit_advance: the load scale is not finite");
+    if (nsteps == 0) return FEMCY_OK;
+    double* u = c->d_vec[FEMCY_VEC_DOF];
+    int rc = launch_explicit_drift(c, dt);
+    for (int32_t k = 1; !rc && k <= nsteps; ++k) {
+        // the element pass of force_pass without its per-call copy of u: the lazy state is set once, below
+        if ((rc = launch_geom(c, u, GEOM_DSDX | GEOM_FE))) break;
+        rc = launch_explicit_node(c, ex.d_minv.get(), c->d_vec[rhs_vec], scale0 + k * dscale, dt, k < nsteps);
+    }
+    if (rc) return rc;
+    // post-processing reads "the stress of the last force evaluation": that of the last state (the last step did not drift)
+    FEMCY_HIP(hipMemcpyAsync(c->d_u_lazy, u, sizeof(double) * c->n, hipMemcpyDeviceToDevice, c->stream));
+    c->gp_lazy = true;
+    c->post_small = false;
+    return FEMCY_OK;
+}
+
+int femcy_explicit_kinetic_energy(femcy_ctx* ctx, int32_t id, int v_vec, double* out) {
+    CTX_OR_FAIL(ctx);
+    EXPLICIT_OR_FAIL("femcy_explicit_kinetic_energy", id);
+    VEC_OR_FAIL(v_vec);
+    FEMCY_REQUIRE(out, "null output");
+    return launch_explicit_energy(c, c->lumped_masses[ex.lumped].d_m.get(), c->d_vec[v_vec], out);
+}
+
+int femcy_explicit_stable_dt(femcy_ctx* ctx, int32_t id, double* dt, double* omega_bound) {
+    CTX_OR_FAIL(ctx);
+    EXPLICIT_OR_FAIL("femcy_explicit_stable_dt", id);
+    FEMCY_REQUIRE(dt && omega_bound, "null output");
+    FEMCY_REQUIRE(c->have_pattern && c->K_serial == c->pattern_serial,
+                  "femcy_explicit_stable_dt bounds the matrix of the last femcy_assemble_K: assemble first");
+    double w2 = 0.0;
+    int rc = launch_rowabs_bound(c, ex.d_minv.get(), &w2);
+    if (rc) return rc;
+    *omega_bound = std::sqrt(w2);
+    *dt = 2.0 / *omega_bound;
+    return FEMCY_OK;
 }
 
 int femcy_spmv(femcy_ctx* ctx, int x_vec, int y_vec) {

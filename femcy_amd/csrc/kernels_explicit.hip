@@ -1,0 +1,305 @@
+// Explicit dynamics for gfx950 (*Dynamic, explicit): HRZ-lumped mass, the fused node pass of a velocity-Verlet step, the
+// kinetic energy and the Gershgorin bound behind the stable increment.  The reference has no dynamics; the element pass of a
+// step is k_geom<..., true> of kernels_assembly.hip (launch_geom with GEOM_DSDX | GEOM_FE), which leaves fe[e][a][:].
+//
+// A step is two launches: that element pass and k_explicit_node, which does what femcy_internal_force's node gather and four
+// vector kernels would do in five launches -- the node sums of fe are never stored, and f, minv, a, v, u are read and a, v, u
+// written once per step, dm contiguous doubles per node each.
+#include <algorithm>
+#include <cmath>
+#include "ctx.hpp"
+#include "element_dispatch.hpp"
+#include "element_math.hpp"
+#include "load_row.hpp"
+
+namespace femcy {
+
+constexpr int XBS = 256;
+
+// ----------------------------------------------------------------------------------- lumped mass
+// element pass in the shape of k_mass_points: one thread per element, the mass rule's tables Nq / dNq / wq wave-uniform, node
+// rows by load_row; the element's NPE lumped masses (element_math.hpp: lumped_element) go to me[e][0..NPE).  Built once per
+// run, so the stores are left strided.
+template <int NPE, int DM>
+__global__ void __launch_bounds__(XBS) k_lumped_elem(int32_t ne, int32_t nq, const double* __restrict__ nodes,
+                                                     const int32_t* __restrict__ elems, const double* __restrict__ Nq,
+                                                     const double* __restrict__ dNq, const double* __restrict__ wq,
+                                                     double rho, double* __restrict__ me_out) {
+    const int32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= ne) return;
+    double X[NPE][DM], me[NPE];
+#pragma unroll
+    for (int a = 0; a < NPE; ++a) load_row<DM>(nodes + (int64_t)elems[(int64_t)e * NPE + a] * DM, X[a]);
+    lumped_element<NPE, DM>(X, nq, Nq, dNq, wq, rho, me);
+#pragma unroll
+    for (int a = 0; a < NPE; ++a) me_out[(int64_t)e * NPE + a] = me[a];
+}
+
+// one-component node sum in the shape of k_nodal_force: half a wavefront per node, its lanes take the node's incident
+// elements (ne_idx = e * npe + la is the position in me) with stride 32 in ascending order, fixed xor tree, lane 0 stores
+__global__ void __launch_bounds__(XBS) k_lumped_gather(int32_t nn, const int32_t* __restrict__ ne_ptr,
+                                                       const int32_t* __restrict__ ne_idx,
+                                                       const double* __restrict__ me, double* __restrict__ m) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int32_t a = (int32_t)(t >> 5);
+    const int sub = (int)(t & 31);
+    double acc = 0.0;
+    if (a < nn) {
+        const int32_t k1 = ne_ptr[a + 1];
+        for (int32_t k = ne_ptr[a] + sub; k < k1; k += 32) acc += me[ne_idx[k]];
+    }
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 32);
+    if (a < nn && sub == 0) m[a] = acc;
+}
+
+// minv[a * DM + i] = 1 / m[a]; the constrained DOFs are zeroed afterwards by the DOF sets' own scatter
+template <int DM>
+__global__ void __launch_bounds__(XBS) k_explicit_minv(int64_t n, const double* __restrict__ m, double* __restrict__ minv) {
+    const int64_t i = (int64_t)blockIdx.x * XBS + threadIdx.x;
+    if (i < n) minv[i] = 1.0 / m[i / DM];
+}
+
+// ------------------------------------------------------------------------------------ node pass
+// Launch shape and gather of k_nodal_force: half a wavefront (32 lanes) owns a node, the lanes are its incident rows of fe
+// (one load_row each, stride 32 in ascending order), the dm partial sums are combined by the fixed xor tree.  The tree leaves
+// the same bits in all 32 lanes (every level adds the same two values in both lanes of a pair), so lane i < DM takes
+// component i: its f, minv, a, v, u are requested before the gather and DM neighbouring lanes read and write DM contiguous
+// doubles.  mode 0: a_0 = minv (s f - f_int), nothing else is touched (femcy_explicit_start); 1: kick, a and v are replaced;
+// 2: kick, then u drifts to the next state with the new a and v still in registers.  The arithmetic is explicit_kick /
+// explicit_drift of element_math.hpp, the functions k_explicit_drift and the host backend call.
+enum { XN_START = 0, XN_KICK = 1, XN_KICK_DRIFT = 2 };
+template <int DM>
+__global__ void __launch_bounds__(XBS) k_explicit_node(int32_t nn, const int32_t* __restrict__ ne_ptr,
+                                                       const int32_t* __restrict__ ne_idx,
+                                                       const double* __restrict__ fe, const double* __restrict__ f,
+                                                       const double* __restrict__ minv, double s, double h, double hh,
+                                                       double h2h, int mode, double* __restrict__ u,
+                                                       double* __restrict__ v, double* __restrict__ acc_vec) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int32_t a = (int32_t)(t >> 5);
+    const int sub = (int)(t & 31);
+    const bool mine = a < nn && sub < DM;
+    const int64_t i = (int64_t)a * DM + sub;
+    double fi = 0.0, mi = 0.0, ai = 0.0, vi = 0.0, ui = 0.0;
+    if (mine) {
+        fi = f[i];
+        mi = minv[i];
+        if (mode != XN_START) {
+            ai = acc_vec[i];
+            vi = v[i];
+        }
+        if (mode == XN_KICK_DRIFT) ui = u[i];
+    }
+    double acc[DM];
+#pragma unroll
+    for (int c = 0; c < DM; ++c) acc[c] = 0.0;
+    if (a < nn) {
+        const int32_t k1 = ne_ptr[a + 1];
+        for (int32_t k = ne_ptr[a] + sub; k < k1; k += 32) {
+            double rv[DM];
+            load_row<DM>(fe + (int64_t)ne_idx[k] * DM, rv);                     // ne_idx = e*npe + la: the row of fe
+#pragma unroll
+            for (int c = 0; c < DM; ++c) acc[c] += rv[c];
+        }
+    }
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1)
+#pragma unroll
+        for (int c = 0; c < DM; ++c) acc[c] += __shfl_xor(acc[c], o, 32);
+    if (!mine) return;
+    const double fint = sub == 0 ? acc[0] : (sub == 1 ? acc[1] : acc[DM - 1]);
+    explicit_kick(mi, s, fi, fint, hh, vi, ai);
+    acc_vec[i] = ai;
+    if (mode == XN_START) return;
+    v[i] = vi;
+    if (mode == XN_KICK_DRIFT) u[i] = explicit_drift(ui, vi, ai, h, h2h);
+}
+
+// the first drift of a call: u += h v + (h^2 / 2) a from memory, by the function the node pass applies to its registers
+__global__ void __launch_bounds__(XBS) k_explicit_drift(int64_t n, double h, double h2h, const double* __restrict__ v,
+                                                        const double* __restrict__ a, double* __restrict__ u) {
+    const int64_t i = (int64_t)blockIdx.x * XBS + threadIdx.x;
+    if (i < n) u[i] = explicit_drift(u[i], v[i], a[i], h, h2h);
+}
+
+// ------------------------------------------------------------------------------------ reductions
+// a workgroup's 256 values -> one, in a fixed order: xor tree inside each wavefront, then the four wave results in ascending
+// order by thread 0 (MAX: the maximum instead of the sum)
+template <bool MAX>
+__device__ __forceinline__ double block_reduce(double x, double* sm) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double y = __shfl_xor(x, o, 64);
+        x = MAX ? fmax(x, y) : x + y;
+    }
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = x;
+    __syncthreads();
+    double r = sm[0];
+#pragma unroll
+    for (int w = 1; w < XBS / 64; ++w) r = MAX ? fmax(r, sm[w]) : r + sm[w];
+    __syncthreads();
+    return r;
+}
+
+// partial sums of m_a |v_a|^2: thread t of workgroup b takes the nodes b * 256 + t + k * (workgroups * 256), k ascending
+template <int DM>
+__global__ void __launch_bounds__(XBS) k_explicit_energy(int32_t nn, const double* __restrict__ m,
+                                                         const double* __restrict__ v, double* __restrict__ part) {
+    __shared__ double sm[XBS / 64];
+    double acc = 0.0;
+    for (int64_t a = (int64_t)blockIdx.x * XBS + threadIdx.x; a < nn; a += (int64_t)gridDim.x * XBS) {
+        double vv = v[a * DM] * v[a * DM];
+#pragma unroll
+        for (int c = 1; c < DM; ++c) vv = fma(v[a * DM + c], v[a * DM + c], vv);
+        acc = fma(m[a], vv, acc);
+    }
+    const double r = block_reduce<false>(acc, sm);
+    if (threadIdx.x == 0) part[blockIdx.x] = r;
+}
+
+// one workgroup: thread t takes the partials t, t + 256, ... in ascending order, then the same tree
+template <bool MAX>
+__global__ void __launch_bounds__(XBS) k_explicit_final(int np, const double* __restrict__ part, double* __restrict__ out) {
+    __shared__ double sm[XBS / 64];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < np; i += XBS) acc = MAX ? fmax(acc, part[i]) : acc + part[i];
+    const double r = block_reduce<MAX>(acc, sm);
+    if (threadIdx.x == 0) *out = r;
+}
+
+// Gershgorin pass over the SELL storage: one lane per stored row position p = slice * 64 + lane (node_of[p] < 0: padding),
+// the node's blocks j = 0 .. rowlen - 1 in storage order, the DM entries of each of its DM scalar rows through kv_index in
+// ascending column order; a scalar row counts with sum_j |K_ij| minv_i unless minv_i = 0 (constrained).  A NaN counts as
+// infinity, so that a broken matrix gives no increment.  Then the maximum reduction above.
+template <int DM>
+__global__ void __launch_bounds__(XBS) k_rowabs_bound(int64_t npos, const int32_t* __restrict__ node_of,
+                                                      const int32_t* __restrict__ rowlen,
+                                                      const int64_t* __restrict__ slice_off,
+                                                      const double* __restrict__ K, const double* __restrict__ minv,
+                                                      double* __restrict__ part) {
+    __shared__ double sm[XBS / 64];
+    double best = 0.0;
+    for (int64_t p = (int64_t)blockIdx.x * XBS + threadIdx.x; p < npos; p += (int64_t)gridDim.x * XBS) {
+        const int32_t a = node_of[p];
+        if (a < 0) continue;
+        const int lane = (int)(p & 63);
+        const int64_t off = slice_off[p >> 6];
+        const int32_t L = rowlen[a];
+        double sum[DM];
+#pragma unroll
+        for (int r = 0; r < DM; ++r) sum[r] = 0.0;
+        for (int32_t j = 0; j < L; ++j)
+#pragma unroll
+            for (int k = 0; k < DM * DM; ++k) sum[k / DM] += fabs(K[kv_index<DM>(off + j, k, lane)]);
+#pragma unroll
+        for (int r = 0; r < DM; ++r) {
+            const double mi = minv[(int64_t)a * DM + r];
+            const double b = sum[r] * mi;
+            if (mi != 0.0) best = fmax(best, b != b ? INFINITY : b);
+        }
+    }
+    const double r = block_reduce<true>(best, sm);
+    if (threadIdx.x == 0) part[blockIdx.x] = r;
+}
+
+// ------------------------------------------------------------------------------- host launchers
+static int reduction_grid(int64_t items) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>((items + XBS - 1) / XBS, 1024));   // <= MAX_PARTIALS partials
+}
+
+int launch_lumped_mass(Ctx* c, int32_t nq, const double* d_Nq, const double* d_dNq, const double* d_wq, double rho,
+                       double* d_me, double* d_m) {
+    const int grid = (c->ne + XBS - 1) / XBS;
+    size_t tm = timing_begin(c, T_GEOM);
+    const bool launched = dispatch_element(c->npe, c->dm, [&](auto npe, auto dm) {
+        hipLaunchKernelGGL((k_lumped_elem<npe(), dm()>), dim3(grid), dim3(XBS), 0, c->stream, c->ne, nq, c->d_nodes,
+                           c->d_elems, d_Nq, d_dNq, d_wq, rho, d_me);
+    });
+    if (launched) {
+        const int64_t threads = (int64_t)c->nn * 32;
+        hipLaunchKernelGGL(k_lumped_gather, dim3((unsigned)((threads + XBS - 1) / XBS)), dim3(XBS), 0, c->stream, c->nn,
+                           c->d_ne_ptr, c->d_ne_idx, d_me, d_m);
+    }
+    timing_end(c, tm);
+    if (!launched) {
+        set_error("no lumped-mass kernel instantiated for npe=%d dm=%d", c->npe, c->dm);
+        return FEMCY_ENOKERNEL;
+    }
+    FEMCY_HIP(hipGetLastError());
+    return FEMCY_OK;
+}
+
+int launch_explicit_minv(Ctx* c, const double* d_m, double* d_minv) {
+    const unsigned grid = (unsigned)((c->n + XBS - 1) / XBS);
+    dispatch_dm(c->dm, [&](auto dm) {
+        hipLaunchKernelGGL((k_explicit_minv<dm()>), dim3(grid), dim3(XBS), 0, c->stream, c->n, d_m, d_minv);
+    });
+    FEMCY_HIP(hipGetLastError());
+    return FEMCY_OK;
+}
+
+static int launch_node(Ctx* c, const double* d_minv, const double* d_f, double scale, double h, int mode) {
+    const unsigned grid = (unsigned)(((int64_t)c->nn * 32 + XBS - 1) / XBS);   // 32 lanes per node
+    size_t tm = timing_begin(c, T_FORCE);
+    dispatch_dm(c->dm, [&](auto dm) {
+        hipLaunchKernelGGL((k_explicit_node<dm()>), dim3(grid), dim3(XBS), 0, c->stream, c->nn, c->d_ne_ptr, c->d_ne_idx,
+                           c->d_fe, d_f, d_minv, scale, h, 0.5 * h, 0.5 * h * h, mode, c->d_vec[FEMCY_VEC_DOF],
+                           c->d_vec[FEMCY_VEC_VEL], c->d_vec[FEMCY_VEC_ACC]);
+    });
+    timing_end(c, tm);
+    FEMCY_HIP(hipGetLastError());
+    return FEMCY_OK;
+}
+
+int launch_explicit_start(Ctx* c, const double* d_minv, const double* d_f, double scale) {
+    return launch_node(c, d_minv, d_f, scale, 0.0, XN_START);
+}
+
+int launch_explicit_node(Ctx* c, const double* d_minv, const double* d_f, double scale, double h, bool drift) {
+    return launch_node(c, d_minv, d_f, scale, h, drift ? XN_KICK_DRIFT : XN_KICK);
+}
+
+int launch_explicit_drift(Ctx* c, double h) {
+    const unsigned grid = (unsigned)((c->n + XBS - 1) / XBS);
+    size_t tm = timing_begin(c, T_FORCE);
+    hipLaunchKernelGGL(k_explicit_drift, dim3(grid), dim3(XBS), 0, c->stream, c->n, h, 0.5 * h * h,
+                       c->d_vec[FEMCY_VEC_VEL], c->d_vec[FEMCY_VEC_ACC], c->d_vec[FEMCY_VEC_DOF]);
+    timing_end(c, tm);
+    FEMCY_HIP(hipGetLastError());
+    return FEMCY_OK;
+}
+
+static int fetch_scalar(Ctx* c, const double* d_val, double* out) {
+    FEMCY_HIP(hipMemcpyAsync(c->h_scalar, d_val, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    FEMCY_HIP(hipStreamSynchronize(c->stream));
+    *out = c->h_scalar[0];
+    return FEMCY_OK;
+}
+
+int launch_explicit_energy(Ctx* c, const double* d_m, const double* d_v, double* out) {
+    const int g = reduction_grid(c->nn);
+    dispatch_dm(c->dm, [&](auto dm) {
+        hipLaunchKernelGGL((k_explicit_energy<dm()>), dim3(g), dim3(XBS), 0, c->stream, c->nn, d_m, d_v, c->d_part1);
+    });
+    hipLaunchKernelGGL((k_explicit_final<false>), dim3(1), dim3(XBS), 0, c->stream, g, c->d_part1, c->d_part2);
+    FEMCY_HIP(hipGetLastError());
+    double s = 0.0;
+    int rc = fetch_scalar(c, c->d_part2, &s);
+    *out = 0.5 * s;
+    return rc;
+}
+
+int launch_rowabs_bound(Ctx* c, const double* d_minv, double* out) {
+    const int64_t npos = (int64_t)c->nslices * SLICE;
+    const int g = reduction_grid(npos);
+    dispatch_dm(c->dm, [&](auto dm) {
+        hipLaunchKernelGGL((k_rowabs_bound<dm()>), dim3(g), dim3(XBS), 0, c->stream, npos, c->d_node_of, c->d_rowlen,
+                           c->d_slice_off, c->d_Kvals, d_minv, c->d_part1);
+    });
+    hipLaunchKernelGGL((k_explicit_final<true>), dim3(1), dim3(XBS), 0, c->stream, g, c->d_part1, c->d_part2);
+    FEMCY_HIP(hipGetLastError());
+    return fetch_scalar(c, c->d_part2, out);
+}
+
+}  // namespace femcy

@@ -69,8 +69,15 @@ struct BodyLoad {
 struct Mass {
     std::vector<double> m;   // [blocks of the block-CSR matrix] one scalar per block, K's block order
 };
+struct LumpedMass {
+    std::vector<double> m;   // [nn] HRZ-lumped nodal masses
+};
+struct Explicit {
+    std::vector<double> minv;   // [n] inverse mass per scalar DOF, 0 on the constrained DOFs
+    int32_t lumped;
+};
 struct Thermal {
-    std::vector<double> f, dT, N;   // [n] load at scale 1, [nn] temperature changes, [nGP][npe] shape functions
+    std::vector<double> f, dT, N;  // [n] load at scale 1, [nn] temperature changes, [nGP][npe] shape functions
     double s[9];                    // stress of full restraint per unit temperature change, row-major tensor
 };
 
@@ -100,7 +107,10 @@ struct femcy_ctx {
     std::vector<BodyLoad> bodyloads;
     std::vector<Thermal> thermals;
     std::vector<Mass> masses;
-    bool post_small = false;              // sigma / mises hold femcy_compute_strain_stress(large = 0), not yet corrected
+    std::vector<LumpedMass> lumped_masses;
+    std::vector<Explicit> explicits;
+    bool have_K = false;                  // K holds an assembled matrix of the current pattern (femcy_explicit_stable_dt)
+    bool post_small = false;             // sigma / mises hold femcy_compute_strain_stress(large = 0), not yet corrected
     int opt_tangent = 0, opt_timing = 0;
     femcy_timing_t timing{};
     // femcy_direct_solve: band order of the current pattern (built on first use), storage limit
@@ -282,7 +292,7 @@ int assemble_K(femcy_ctx* c) {
     }
     const double t = c->opt_timing ? now_ms() : 0.0;
     if (c->dm == 3) assemble<3>(c); else assemble<2>(c);
-    c->asm_ran = true;
+    c->asm_ran = c->have_K = true;
     if (c->opt_timing) {
         c->timing.assemble_ms += now_ms() - t;
         c->timing.assemble_launches++;
@@ -467,6 +477,9 @@ int femcy_set_mesh(femcy_ctx* ctx, int32_t nn, int32_t dm, const double* nodes, 
     c->bodyloads.clear();
     c->thermals.clear();
     c->masses.clear();
+    c->lumped_masses.clear();
+    c->explicits.clear();
+    c->have_K = false;
     c->post_small = false;
     c->nn = nn; c->dm = dm; c->ne = ne; c->npe = npe;
     c->n = (int64_t)nn * dm;
@@ -603,6 +616,7 @@ int femcy_build_pattern(femcy_ctx* ctx) {
         }
     c->have_pattern = true;
     c->have_band_order = false;
+    c->have_K = false;
     return FEMCY_OK;
 }
 
@@ -1302,6 +1316,214 @@ int femcy_newmark_update(femcy_ctx* ctx, int u_new_vec, int u_vec, int v_vec, in
     const double b0 = 1.0 / (beta * dt * dt), b1 = 1.0 / (beta * dt), b2 = 1.0 / (2.0 * beta) - 1.0;
 #pragma omp parallel for schedule(static)
     for (int64_t i = 0; i < c->n; ++i) newmark_update_entry(un[i], u[i], v[i], a[i], b0, b1, b2, dt, gamma);
+    return FEMCY_OK;
+}
+
+// ------------------------------------------------------------------------------ explicit dynamics
+}  // extern "C"
+namespace {
+// the two passes of the device's femcy_lumped_mass_create (csrc/element_math.hpp: lumped_element), the node sums in the
+// order of its half-wavefront gather: partial sums of every 32nd incident element, combined by half_wave_tree
+template <int NPE, int DM>
+void lumped_mass(femcy_ctx* c, int32_t nq, const double* Nq, const double* dNq, const double* wq, double rho,
+                 std::vector<double>& m) {
+    std::vector<double> me((size_t)c->ne * NPE, 0.0);
+#pragma omp parallel for schedule(static)
+    for (int32_t e = 0; e < c->ne; ++e) {
+        double X[NPE][DM], w[NPE];
+        for (int a = 0; a < NPE; ++a)
+            for (int i = 0; i < DM; ++i) X[a][i] = c->nodes[(int64_t)c->elems[(int64_t)e * NPE + a] * DM + i];
+        lumped_element<NPE, DM>(X, nq, Nq, dNq, wq, rho, w);
+        for (int a = 0; a < NPE; ++a) me[(size_t)e * NPE + a] = w[a];
+    }
+    m.assign((size_t)c->nn, 0.0);
+#pragma omp parallel for schedule(static)
+    for (int32_t a = 0; a < c->nn; ++a) {
+        double p[32] = {0.0};
+        for (int32_t k = c->ne_ptr[a]; k < c->ne_ptr[a + 1]; ++k) p[(k - c->ne_ptr[a]) & 31] += me[c->ne_idx[k]];
+        m[a] = half_wave_tree(p);
+    }
+}
+
+// the device's k_explicit_node on the host: node sums of fe in the order of its gather, then explicit_kick / explicit_drift
+// (csrc/element_math.hpp).  mode 0: a_0 only; 1: kick; 2: kick + drift
+void explicit_node(femcy_ctx* c, const Explicit& ex, const double* f, double s, double h, int mode) {
+    const int dm = c->dm;
+    double *u = c->vec[FEMCY_VEC_DOF].data(), *v = c->vec[FEMCY_VEC_VEL].data(), *acc = c->vec[FEMCY_VEC_ACC].data();
+    const double hh = 0.5 * h, h2h = 0.5 * h * h;
+#pragma omp parallel for schedule(static)
+    for (int32_t a = 0; a < c->nn; ++a) {
+        double p[3][32] = {{0.0}};
+        for (int32_t k = c->ne_ptr[a]; k < c->ne_ptr[a + 1]; ++k)
+            for (int i = 0; i < dm; ++i) p[i][(k - c->ne_ptr[a]) & 31] += c->fe[(int64_t)c->ne_idx[k] * dm + i];
+        for (int i = 0; i < dm; ++i) {
+            const int64_t q = (int64_t)a * dm + i;
+            const double fint = half_wave_tree(p[i]);
+            double vi = mode ? v[q] : 0.0, ai = mode ? acc[q] : 0.0;
+            explicit_kick(ex.minv[q], s, f[q], fint, hh, vi, ai);
+            acc[q] = ai;
+            if (!mode) continue;
+            v[q] = vi;
+            if (mode == 2) u[q] = explicit_drift(u[q], vi, ai, h, h2h);
+        }
+    }
+}
+
+// a workgroup's 256 values -> one, in the order of the device's block_reduce (kernels_explicit.hip): xor tree inside each
+// wavefront of 64, then the four wave results in ascending order
+double block_reduce_sum(double (&x)[256]) {
+    double r = 0.0;
+    for (int w = 0; w < 4; ++w) {
+        double* y = x + w * 64;
+        for (int o = 32; o > 0; o >>= 1)
+            for (int l = 0; l < o; ++l) y[l] += y[l + o];
+        r = w ? r + y[0] : y[0];
+    }
+    return r;
+}
+}  // namespace
+extern "C" {
+
+int femcy_lumped_mass_create(femcy_ctx* ctx, int32_t nq, const double* Nq, const double* dNq, const double* wq, double rho,
+                             int32_t* id_out) {
+    CTX_OR_FAIL(ctx);
+    REQUIRE(c->have_mesh && c->have_element && c->have_pattern,
+            "femcy_lumped_mass_create needs the mesh, the element tables and the pattern (mesh=%d element=%d pattern=%d)",
+            (int)c->have_mesh, (int)c->have_element, (int)c->have_pattern);
+    REQUIRE(Nq && dNq && wq && id_out, "null mass-rule table or id_out");
+    REQUIRE(nq >= 1 && nq <= 64, "mass rule: %d points (1 .. 64 are supported)", nq);
+    REQUIRE(std::isfinite(rho) && rho > 0.0, "mass: the density must be finite and positive");
+    LumpedMass lm;
+    if (!dispatch_element(c->npe, c->dm,
+                          [&](auto npe, auto dm) { lumped_mass<npe(), dm()>(c, nq, Nq, dNq, wq, rho, lm.m); }))
+        return no_kernel(c, "lumped-mass");
+    c->lumped_masses.push_back(std::move(lm));
+    *id_out = (int32_t)c->lumped_masses.size() - 1;
+    return FEMCY_OK;
+}
+#define LUMPED_OR_FAIL(id)                                                                                  \
+    REQUIRE((id) >= 0 && (size_t)(id) < c->lumped_masses.size(), "unknown lumped mass %d", (int)(id)); \
+    const LumpedMass& lm = c->lumped_masses[(id)]
+
+int femcy_lumped_mass_get(femcy_ctx* ctx, int32_t id, double* out) {
+    CTX_OR_FAIL(ctx);
+    LUMPED_OR_FAIL(id);
+    REQUIRE(out, "null output");
+    std::copy(lm.m.begin(), lm.m.end(), out);
+    return FEMCY_OK;
+}
+
+int femcy_explicit_create(femcy_ctx* ctx, int32_t lumped_id, int32_t ndofsets, const int32_t* dofset_ids, int32_t* id_out) {
+    CTX_OR_FAIL(ctx);
+    LUMPED_OR_FAIL(lumped_id);
+    REQUIRE(id_out && ndofsets >= 0 && (ndofsets == 0 || dofset_ids), "femcy_explicit_create: null id_out or DOF-set list");
+    for (int32_t k = 0; k < ndofsets; ++k)
+        REQUIRE(dofset_ids[k] >= 0 && (size_t)dofset_ids[k] < c->dofsets.size(), "unknown DOF set %d", dofset_ids[k]);
+    Explicit ex;
+    ex.lumped = lumped_id;
+    ex.minv.resize((size_t)c->n);
+    for (int64_t i = 0; i < c->n; ++i) ex.minv[i] = 1.0 / lm.m[i / c->dm];
+    for (int32_t k = 0; k < ndofsets; ++k)
+        for (int32_t dof : c->dofsets[dofset_ids[k]].dofs) ex.minv[dof] = 0.0;
+    c->explicits.push_back(std::move(ex));
+    *id_out = (int32_t)c->explicits.size() - 1;
+    return FEMCY_OK;
+}
+#define EXPLICIT_OR_FAIL(id)                                                                                    \
+    REQUIRE((id) >= 0 && (size_t)(id) < c->explicits.size(), "unknown explicit integrator %d", (int)(id)); \
+    const Explicit& ex = c->explicits[(id)]
+#define EXPLICIT_RHS_OR_FAIL(name, rhs_vec)                                                                 \
+    VEC_OR_FAIL(rhs_vec);                                                                                   \
+    REQUIRE((rhs_vec) != FEMCY_VEC_DOF && (rhs_vec) != FEMCY_VEC_VEL && (rhs_vec) != FEMCY_VEC_ACC,        \
+            name ": the load vector may not be one of the state vectors DOF, VEL, ACC")
+
+int femcy_explicit_start(femcy_ctx* ctx, int32_t id, int rhs_vec, double scale) {
+    CTX_OR_FAIL(ctx);
+    READY_OR_FAIL();
+    EXPLICIT_OR_FAIL(id);
+    EXPLICIT_RHS_OR_FAIL("femcy_explicit_start", rhs_vec);
+    REQUIRE(std::isfinite(scale), "femcy_explicit_start: the load scale is not finite");
+    geom(c, c->vec[FEMCY_VEC_DOF].data(), GEOM_DSDX | GEOM_F | GEOM_SIGMA | GEOM_FE);
+    explicit_node(c, ex, c->vec[rhs_vec].data(), scale, 0.0, 0);
+    return FEMCY_OK;
+}
+
+int femcy_explicit_advance(femcy_ctx* ctx, int32_t id, int rhs_vec, int32_t nsteps, double dt, double scale0, double dscale) {
+    CTX_OR_FAIL(ctx);
+    READY_OR_FAIL();
+    EXPLICIT_OR_FAIL(id);
+    EXPLICIT_RHS_OR_FAIL("femcy_explicit_advance", rhs_vec);
+    REQUIRE(nsteps >= 0, "femcy_explicit_advance: %d steps", nsteps);
+    REQUIRE(std::isfinite(dt) && dt > 0.0, "femcy_explicit_advance: the increment must be finite and positive");
+    REQUIRE(std::isfinite(scale0) && std::isfinite(dscale), "femcy_explicit_advance: the load scale is not finite");
+    if (nsteps == 0) return FEMCY_OK;
+    double* u = c->vec[FEMCY_VEC_DOF].data();
+    const double *v = c->vec[FEMCY_VEC_VEL].data(), *a = c->vec[FEMCY_VEC_ACC].data();
+    const double h2h = 0.5 * dt * dt;
+#pragma omp parallel for schedule(static)
+    for (int64_t i = 0; i < c->n; ++i) u[i] = explicit_drift(u[i], v[i], a[i], dt, h2h);
+    for (int32_t k = 1; k <= nsteps; ++k) {
+        const bool last = k == nsteps;      // F and sigma of the last state stay behind for post-processing
+        geom(c, u, last ? (GEOM_DSDX | GEOM_F | GEOM_SIGMA | GEOM_FE) : (GEOM_DSDX | GEOM_FE));
+        explicit_node(c, ex, c->vec[rhs_vec].data(), scale0 + k * dscale, dt, last ? 1 : 2);
+    }
+    return FEMCY_OK;
+}
+
+int femcy_explicit_kinetic_energy(femcy_ctx* ctx, int32_t id, int v_vec, double* out) {
+    CTX_OR_FAIL(ctx);
+    EXPLICIT_OR_FAIL(id);
+    VEC_OR_FAIL(v_vec);
+    REQUIRE(out, "null output");
+    const double* m = c->lumped_masses[ex.lumped].m.data();
+    const double* v = c->vec[v_vec].data();
+    const int dm = c->dm;
+    // the device's two reductions: 256 strided partial sums per workgroup, at most 1024 workgroups, then one workgroup
+    const int64_t g = std::max<int64_t>(1, std::min<int64_t>(((int64_t)c->nn + 255) / 256, 1024));
+    std::vector<double> part((size_t)g);
+#pragma omp parallel for schedule(static)
+    for (int64_t b = 0; b < g; ++b) {
+        double x[256];
+        for (int t = 0; t < 256; ++t) {
+            double acc = 0.0;
+            for (int64_t a = b * 256 + t; a < c->nn; a += g * 256) {
+                double vv = v[a * dm] * v[a * dm];
+                for (int i = 1; i < dm; ++i) vv = std::fma(v[a * dm + i], v[a * dm + i], vv);
+                acc = std::fma(m[a], vv, acc);
+            }
+            x[t] = acc;
+        }
+        part[(size_t)b] = block_reduce_sum(x);
+    }
+    double x[256];
+    for (int t = 0; t < 256; ++t) {
+        double acc = 0.0;
+        for (int64_t i = t; i < g; i += 256) acc += part[(size_t)i];
+        x[t] = acc;
+    }
+    *out = 0.5 * block_reduce_sum(x);
+    return FEMCY_OK;
+}
+
+int femcy_explicit_stable_dt(femcy_ctx* ctx, int32_t id, double* dt, double* omega_bound) {
+    CTX_OR_FAIL(ctx);
+    EXPLICIT_OR_FAIL(id);
+    REQUIRE(dt && omega_bound, "null output");
+    REQUIRE(c->have_pattern && c->have_K,
+            "femcy_explicit_stable_dt bounds the matrix of the last femcy_assemble_K: assemble first");
+    const int dm = c->dm, dd = dm * dm;
+    double best = 0.0;
+    for (int32_t a = 0; a < c->nn; ++a) {      // blocks in storage order, entries of a scalar row in ascending column order
+        double sum[3] = {0.0, 0.0, 0.0};
+        for (int64_t p = c->rowptr[a]; p < c->rowptr[a + 1]; ++p)
+            for (int k = 0; k < dd; ++k) sum[k / dm] += std::fabs(c->K[p * dd + k]);
+        for (int r = 0; r < dm; ++r) {
+            const double mi = ex.minv[(int64_t)a * dm + r];
+            if (mi != 0.0) best = std::fmax(best, nan_to_inf_abs(sum[r] * mi));
+        }
+    }
+    *omega_bound = std::sqrt(best);
+    *dt = 2.0 / *omega_bound;
     return FEMCY_OK;
 }
 

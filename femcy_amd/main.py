@@ -23,7 +23,7 @@ def run(fileName: str, device: int = 0, verbose: bool = True, tangent: str = "re
     inp = InpInfo(fileName, allow_2d_hyperelastic=allow_2d_hyperelastic)
     nodes, eSets = inp.nodes, inp.eSets
     material = list(inp.materials.values())[0]
-    if inp.procedure == "dynamic" and distributed.wanted():
+    if inp.procedure in ("dynamic", "explicit") and distributed.wanted():
         raise ValueError("a *Dynamic step on more than one rank has not been supported: the mass matrix is single-rank")
     if distributed.wanted():       # launched by torch.distributed.run: one rank per GPU, one element partition each
         return run_partitioned(inp, material, verbose, tangent)

@@ -28,7 +28,10 @@ refused by name instead of being skipped.  `*Expansion` inside a `*Material` blo
 `*Initial Conditions, type=TEMPERATURE` and `*Temperature` -> temperature_info (read_thermal).
 `*Dynamic, direct[, beta=, gamma=]` with data `dt, T` -> procedure = "dynamic", dynamic = {"beta", "gamma"} and time_incs
 with fixed increments (read_procedure); `*Step, amplitude=RAMP|STEP` -> amplitude; `*Initial Conditions, type=VELOCITY` ->
-initial_velocity_info.  A deck with `*Static` has procedure = "static" and reads as before.
+initial_velocity_info.  `*Dynamic, explicit[, direct user control][, scale factor=][, output_every=]` with data `, T` (`dt, T`
+under direct user control) -> procedure = "explicit", dynamic = {"direct_user_control", "scale_factor", "output_every"} and
+time_incs whose increments are None until the driver has estimated one.  A deck with `*Static` has procedure = "static" and
+reads as before.
 """
 import sys
 from typing import Dict, List
@@ -466,7 +469,11 @@ class InpInfo(InpInfoBase):
         parameters `beta=` / `gamma=` (default 1/4, 1/2: the trapezoidal rule, no numerical damping) and refuses
         `alpha=` other than 0 (no HHT damping), beta <= 0, gamma < 1/2, a deck without `*Density`, and a non-zero
         `*Boundary` value (prescribed motion).  `*Step, amplitude=` defaults to RAMP under `*Static` (every load grows
-        with t / T, as it always did) and to STEP under `*Dynamic` (loads in full from t = 0+)."""
+        with t / T, as it always did) and to STEP under `*Dynamic` (loads in full from t = 0+).
+        `*Dynamic, explicit[, direct user control][, scale factor=][, output_every=]` -> procedure "explicit" and dynamic =
+        {"direct_user_control", "scale_factor", "output_every"}: central differences with a lumped mass (`solve_explicit`).
+        It refuses `beta=` / `gamma=` / `alpha=`, a deck without `*Density`, a non-zero `*Boundary` value and
+        `*Temperature`."""
         procedure, dynamic, amplitude = "static", None, None
         for line, block in _deck(fileName).keywords():
             fields = [t.strip() for t in line.split(",")]
@@ -477,6 +484,19 @@ class InpInfo(InpInfoBase):
                 amplitude = params["amplitude"].upper()
                 if amplitude not in ("RAMP", "STEP"):
                     raise ValueError("*Step, amplitude={} has not been supported (RAMP and STEP are)".format(params["amplitude"]))
+            elif key == "*dynamic" and "explicit" in flags:
+                for name in ("beta", "gamma", "alpha"):
+                    if name in params:
+                        raise ValueError("*Dynamic, explicit, {}= has not been supported: central differences have no "
+                                         "Newmark or HHT parameter".format(name))
+                scale_factor, output_every = float(params.get("scale factor", 1.0)), int(params.get("output_every", 64))
+                if not scale_factor > 0.0 or output_every < 1:
+                    raise ValueError("*Dynamic, explicit: scale factor = {} and output_every = {} are refused (both must "
+                                     "be positive)".format(scale_factor, output_every))
+                procedure = "explicit"
+                dynamic = {"direct_user_control": "direct user control" in flags, "scale_factor": scale_factor,
+                           "output_every": output_every}
+                break
             elif key == "*dynamic":
                 if "direct" not in flags:
                     raise ValueError("*Dynamic without `direct` has not been supported: automatic time incrementation "
@@ -492,12 +512,15 @@ class InpInfo(InpInfoBase):
                 break
             elif key == "*static":
                 break
-        if procedure == "dynamic":
+        if procedure in ("dynamic", "explicit"):
             if getattr(self, "density", None) is None:
                 raise ValueError("*Dynamic needs a *Density in the *Material block")
             if any(bc["val"] != 0.0 for bc in self.dirichlet_bc_info):
                 raise ValueError("a non-zero *Boundary value in a *Dynamic step (prescribed motion) has not been supported")
-        return procedure, dynamic, amplitude or ("STEP" if procedure == "dynamic" else "RAMP")
+        if procedure == "explicit" and getattr(self, "temperature_info", None) is not None:
+            raise ValueError("*Temperature in a *Dynamic, explicit step has not been supported: thermal loads are small "
+                             "strain, an explicit step is not")
+        return procedure, dynamic, amplitude or ("RAMP" if procedure == "static" else "STEP")
 
     def read_initial_velocity(self, fileName):
         """`*Initial Conditions, type=VELOCITY` data lines `nset-or-node-label, dof, value` -> [{"node_set", "dof",
@@ -525,6 +548,17 @@ class InpInfo(InpInfoBase):
 
     def read_time_inc(self, fileName):
         for line, block in _deck(fileName).keywords():
+            if line[:8].lower() == "*dynamic" and "explicit" in [t.strip().lower() for t in line.split(",")[1:]]:
+                # `dt, T` under `direct user control`, else `, T`: the increment is then estimated by the driver (ini_inc None)
+                data = [t for t in block if t.strip()]
+                cols = [t.strip() for t in data[0].split(",")] if data else []
+                fixed = "direct user control" in [t.strip().lower() for t in line.split(",")[1:]]
+                if len(cols) < 2 or not cols[1] or (fixed and not cols[0]):
+                    raise ValueError("*Dynamic, explicit needs the data line `, T` (`dt, T` with direct user control)")
+                dt, tmax = (float(cols[0]) if fixed else None), float(cols[1])
+                if not tmax > 0.0 or (fixed and not dt > 0.0):
+                    raise ValueError("*Dynamic, explicit: dt and T must be positive")
+                return {"ini_inc": dt, "max_time": tmax, "min_inc": dt, "max_inc": dt}
             if line[:8].lower() == "*dynamic":
                 data = [t for t in block if t.strip()]
                 if not data or len([t for t in data[0].split(",") if t.strip()]) < 2:

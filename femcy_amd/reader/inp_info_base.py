@@ -21,8 +21,8 @@ class InpInfoBase:
                   # thermal loads: *Expansion (float or None), *Initial Conditions, type=TEMPERATURE + *Temperature as
                   # {"initial": f64[nn], "final": f64[nn]} or None
                   "expansion", "temperature_info",
-                  # the step's procedure: "static" | "dynamic" (*Dynamic, direct), its Newmark parameters {"beta", "gamma"}
-                  # or None, the load amplitude "RAMP" | "STEP", *Initial Conditions, type=VELOCITY as [{"node_set", "dof", "val"}]
+                  # the step's procedure: "static" | "dynamic" (*Dynamic, direct) | "explicit" (*Dynamic, explicit), its
+                  # parameters ({"beta", "gamma"}; {"direct_user_control", "scale_factor", "output_every"}) or None, the load amplitude "RAMP" | "STEP", *Initial Conditions, type=VELOCITY as [{"node_set", "dof", "val"}]
                   "procedure", "dynamic", "amplitude", "initial_velocity_info")
 
     def __init_subclass__(cls, **kwargs):

@@ -459,6 +459,8 @@ class System_of_equations:
         self._linear_energy = False      # get_elasEng: the reference's energy, unless solve_dynamic says otherwise
         if getattr(inp, "procedure", "static") == "dynamic":
             return self.solve_dynamic(inp)
+        if getattr(inp, "procedure", "static") == "explicit":
+            return self.solve_explicit(inp)
         max_inc, min_inc = inp.time_incs["max_inc"], inp.time_incs["min_inc"]
         max_time = inp.time_incs["max_time"]
         self.dt = inp.time_incs["ini_inc"]
@@ -633,6 +635,85 @@ class System_of_equations:
                                     "strain_energy": self.get_elasEng()})
             self.time0 = self.time1
             kinc += 1
+
+    # ------------------------------------------------------------------- explicit dynamics
+    def solve_explicit(self, inp):
+        """transient dynamics at large deformation (`*Dynamic, explicit`): central differences with the HRZ-lumped mass, as
+        velocity Verlet (`femcy_explicit_*`); no matrix is solved.  The internal force is the large-deformation one for
+        every material, whatever the `*Step` line says about nlgeom.  u_0 = 0, v_0 from `*Initial Conditions,
+        type=VELOCITY`; tractions, body forces and `*Cload` are dead loads, evaluated once at scale 1 and scaled by the
+        amplitude (STEP: 1, RAMP: t / T); constrained DOFs have no inverse mass and stay at rest.
+        The increment is the deck's under `direct user control`, else `scale factor` x the stable increment estimated ONCE,
+        on the undeformed mesh with its matrix (`femcy_explicit_stable_dt`); either is then adjusted DOWN so that T is a
+        whole number of steps, and the run ends at T exactly.  Steps run in batches of `output_every` (default 64) per
+        `femcy_explicit_advance`, the last one clipped; after each batch `increments` gains {"kinc" (steps done), "time1",
+        "dt", "kinetic", "strain_energy"} (`get_elasEng`, the reference's large-strain energy), `initial_energy` holds those
+        of t = 0.  A displacement that is not finite -- an unstable increment -- raises FemcyError(FEMCY_ENUMERIC)."""
+        if self.part is not None:
+            raise ValueError("a *Dynamic, explicit step on more than one rank has not been supported: the lumped mass is "
+                             "single-rank")
+        if getattr(inp, "density", None) is None:
+            raise ValueError("*Dynamic needs a *Density in the *Material block")
+        if any(bc["val"] != 0.0 for bc in inp.dirichlet_bc_info):
+            raise ValueError("a non-zero *Boundary value in a *Dynamic step (prescribed motion) has not been supported")
+        if getattr(inp, "temperature_info", None) is not None:
+            raise ValueError("*Temperature in a *Dynamic, explicit step has not been supported: thermal loads are small "
+                             "strain, an explicit step is not")
+        ctx = self.ctx
+        self.geometric_nonlinear = True                               # post-processing: Green strain, the stress of f_int
+        max_time = inp.time_incs["max_time"]
+        loads = {"neumannBCs": copy.deepcopy(inp.neumann_bc_info), "dirichletBCs": []}
+        body_force_info, cload_info = getattr(inp, "body_force_info", None) or [], getattr(inp, "cload_info", None) or []
+        if body_force_info or cload_info:
+            loads["bodyForces"] = copy.deepcopy(body_force_info)
+            loads["cloads"] = copy.deepcopy(cload_info)
+        if not (loads["neumannBCs"] or body_force_info or cload_info):
+            self.rhs.fill(0.0)
+        self.impose_boundary_condition(loads)                         # rhs = f at scale 1, once
+        held = [self._dofset(np.array([*bc["node_set"]]), bc["dof"]) for bc in inp.dirichlet_bc_info]
+        self.lumped_mass = ctx.lumped_mass(self.ELE, inp.density)
+        self.explicit = ex = ctx.explicit(self.lumped_mass, held)
+        if inp.dynamic["direct_user_control"]:
+            dt = inp.time_incs["ini_inc"]
+        else:
+            ctx.assemble_K(-1)                                        # the matrix of the undeformed mesh, for the estimate only
+            self.stats["assemblies"] += 1
+            self.stable_dt, self.omega_bound = ctx.explicit_stable_dt(ex)
+            dt = inp.dynamic["scale_factor"] * self.stable_dt
+        if not (np.isfinite(dt) and dt > 0.0):
+            raise be.FemcyError("explicit step: no usable increment (dt = {})".format(dt), status=be.FEMCY_ENUMERIC)
+        nsteps = max(1, int(np.ceil(max_time / dt * (1.0 - 1.0e-12))))
+        self.dt = h = max_time / nsteps                               # <= dt: T is a whole number of steps
+        ramp = inp.amplitude == "RAMP"
+        dscale = h / max_time if ramp else 0.0
+        vel, acc = ctx.vector(be.VEC_VEL), ctx.vector(be.VEC_ACC)
+        self.velocity, self.acceleration = vel, acc
+        self.dof.fill(0.0)
+        self.dof_old.fill(0.0)
+        vel.fill(0.0)
+        for iv in getattr(inp, "initial_velocity_info", None) or []:
+            ctx.dofset_fill(self._dofset(iv["node_set"], iv["dof"]), be.VEC_VEL, iv["val"])
+        for ds in held:
+            ctx.dofset_fill(ds, be.VEC_VEL, 0.0)
+        self.time0 = self.time1 = 0.0
+        ctx.explicit_start(ex, be.VEC_RHS, 0.0 if ramp else 1.0)
+        self.initial_energy = {"kinetic": ctx.explicit_kinetic_energy(ex, be.VEC_VEL), "strain_energy": self.get_elasEng()}
+        self.increments = []
+        done, batch = 0, inp.dynamic["output_every"]
+        while done < nsteps:
+            k = min(batch, nsteps - done)                             # the last batch is clipped
+            self._say("\033[40;33;1m >>>>> steps {} .. {} of {}, dt = {} \033[0m".format(done + 1, done + k, nsteps, h))
+            ctx.explicit_advance(ex, k, h, be.VEC_RHS, (done * dscale) if ramp else 1.0, dscale)
+            self.stats["force_evals"] += k
+            done += k
+            self.time0, self.time1 = self.time1, max_time if done == nsteps else done * h
+            if not np.isfinite(ctx.vec_absmax(be.VEC_DOF)):
+                raise be.FemcyError("explicit step: the displacements are not finite after {} steps of dt = {} (an unstable "
+                                    "increment)".format(done, h), status=be.FEMCY_ENUMERIC)
+            self.increments.append({"kinc": done, "time1": self.time1, "dt": h, "converged": True, "newton_loop": 0,
+                                    "kinetic": ctx.explicit_kinetic_energy(ex, be.VEC_VEL),
+                                    "strain_energy": self.get_elasEng()})
+        self.dof_old.copy_from(self.dof)
 
     def _residual(self, dirichletBCs):
         """nodal force + K at the current dof, residual = f_int - rhs, Newton Dirichlet treatment,

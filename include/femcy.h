@@ -50,8 +50,8 @@ enum femcy_vec {
     FEMCY_VEC_X = 6,         /* ConjugateGradientSolver_rowMajor.x      */
     FEMCY_VEC_TMP0 = 7,
     FEMCY_VEC_TMP1 = 8,
-    FEMCY_VEC_VEL = 9,       /* implicit dynamics: nodal velocities      */
-    FEMCY_VEC_ACC = 10,      /* implicit dynamics: nodal accelerations   */
+    FEMCY_VEC_VEL = 9,       /* dynamics: nodal velocities               */
+    FEMCY_VEC_ACC = 10,      /* dynamics: nodal accelerations            */
     FEMCY_VEC_COUNT = 11
 };
 
@@ -261,8 +261,8 @@ int femcy_sync(femcy_ctx* ctx);                                   /* hipStreamSy
 
 /* ----------------------------------------------------------------------- problem definition */
 /* Body + System_of_equations.__init__ state (body.py:13-17, stiffnessMtrx.py:26-121).  Calling it again on a used
- * ctx starts over: element tables, material, pattern, DOF lists, load sets, body loads, mass objects and thermal
- * loads of the old mesh are dropped. */
+ * ctx starts over: element tables, material, pattern, DOF lists, load sets, body loads, mass objects, lumped masses,
+ * explicit integrators and thermal loads of the old mesh are dropped. */
 int femcy_set_mesh(femcy_ctx* ctx, int32_t nn, int32_t dm, const double* nodes /*[nn*dm]*/,
                    int32_t ne, int32_t npe, const int32_t* elems /*[ne*npe]*/);
 /* table-driven element plugin: ELE.gaussPoints/gaussWeights/dshape_dnat (element_zoo modules) */
@@ -434,6 +434,51 @@ int femcy_mass_kinetic_energy(femcy_ctx* ctx, int32_t id, int v_vec, double* out
 int femcy_newmark_predict(femcy_ctx* ctx, int u_vec, int v_vec, int a_vec, int out_vec, double c0, double c1, double c2);
 int femcy_newmark_update(femcy_ctx* ctx, int u_new_vec, int u_vec, int v_vec, int a_vec, double beta, double gamma,
                          double dt);
+/* Explicit dynamics (*Dynamic, explicit; an extension, large deformation, single rank).  Central differences with a diagonal
+ * mass, written as velocity Verlet so that u, v and a all belong to whole steps: with minv the inverse lumped mass per scalar
+ * DOF (0 on constrained DOFs, which therefore keep u = v = a = 0), f the load vector at scale 1 and s_n the load scale,
+ *   a_0     = minv o (s_0 f - f_int(u_0))
+ *   u_{n+1} = u_n + h v_n + (h^2 / 2) a_n
+ *   a_{n+1} = minv o (s_{n+1} f - f_int(u_{n+1}))
+ *   v_{n+1} = v_n + (h / 2)(a_n + a_{n+1})
+ * with f_int what femcy_internal_force computes (F, sigma(F), gradients of the current configuration, all four stress laws):
+ * an explicit step is geometrically non-linear whatever the deck's nlgeom says.  No matrix, no solve.
+ * femcy_lumped_mass_create: the nodal masses of the UNDEFORMED mesh by HRZ lumping over the plug-in's mass_rule() (the tables
+ * femcy_mass_create takes, nq <= 64).  Per element, with vq = rho |det J_q| w_q:
+ *   m_e = sum_q vq,   d_a = sum_q N_a(xi_q)^2 vq,   m_a^e = d_a m_e / sum_b d_b,
+ * strictly positive for every family (row sums are negative at the corners of C3D10 / CPS6 / CPS8), m_e / npe on CPS3 /
+ * C3D4.  Element pass + owner-computes node sums in ascending (element, local node) order: no atomics, the same bits on
+ * every run.  After femcy_set_element and femcy_build_pattern.  femcy_lumped_mass_get downloads m [nn].
+ * femcy_explicit_create: an integrator = minv [n] from a lumped mass, 0 on every DOF of the given DOF sets
+ * (femcy_dofset_create ids).
+ * The stepping calls work on vec[DOF] = u, vec[VEL] = v, vec[ACC] = a; vec[rhs] = f is only read and may be none of them.
+ * femcy_explicit_start: vec[ACC] = a_0 from vec[DOF], at load scale `scale`.
+ * femcy_explicit_advance: nsteps steps of size dt, the k-th new state (k = 1 .. nsteps) at load scale scale0 + k dscale.  A
+ * step is two launches -- the element pass of femcy_internal_force and one node pass that sums the element forces, forms
+ * a_new and v_new and moves u on to the next state, the node sums never reaching memory; the first move of a call is a vector
+ * pass of its own and the last step of a call leaves u alone, so that u, v, a leave the call at the same time.  All launches
+ * are enqueued without a host synchronisation and the scalars travel in the kernel arguments.  A run split into several
+ * calls gives the bits of one call (provided the caller's scales agree bit for bit).  nsteps = 0 does nothing.  Afterwards
+ * post-processing sees the last state as after femcy_internal_force.
+ * femcy_explicit_kinetic_energy: *out = 1/2 sum_a m_a |v_a|^2, reduced in a fixed order.
+ * femcy_explicit_stable_dt: Gershgorin's bound on the largest eigenvalue of M_L^-1 K for the K of the last femcy_assemble_K,
+ *   omega_bound^2 = max over the unconstrained scalar rows i of minv_i sum_j |K_ij|   (one pass over the SELL storage + a
+ * maximum reduction), and *dt = 2 / omega_bound, the stability limit of central differences for a linear system with that
+ * spectrum.
+ * Refused with FEMCY_EINVAL, the context stays usable: an unknown id, the refusals of femcy_mass_create, nsteps < 0, dt <= 0
+ * or not finite, a scale that is not finite, rhs_vec one of DOF / VEL / ACC, femcy_explicit_stable_dt before an assembly on
+ * the current pattern, and every one of these calls once femcy_comm_init has run (several ranks are not supported; the host
+ * backend has one rank, its femcy_comm_init never succeeds, so it has no such check).  Lumped masses and integrators are
+ * dropped where mass objects are: femcy_set_mesh and femcy_ctx_destroy. */
+int femcy_lumped_mass_create(femcy_ctx* ctx, int32_t nq, const double* Nq /*[nq][npe]*/, const double* dNq /*[nq][npe][dm]*/,
+                             const double* wq /*[nq]*/, double rho, int32_t* id_out);
+int femcy_lumped_mass_get(femcy_ctx* ctx, int32_t id, double* out /*[nn]*/);
+int femcy_explicit_create(femcy_ctx* ctx, int32_t lumped_id, int32_t ndofsets, const int32_t* dofset_ids /*[ndofsets]*/,
+                          int32_t* id_out);
+int femcy_explicit_start(femcy_ctx* ctx, int32_t id, int rhs_vec, double scale);
+int femcy_explicit_advance(femcy_ctx* ctx, int32_t id, int rhs_vec, int32_t nsteps, double dt, double scale0, double dscale);
+int femcy_explicit_kinetic_energy(femcy_ctx* ctx, int32_t id, int v_vec, double* out);
+int femcy_explicit_stable_dt(femcy_ctx* ctx, int32_t id, double* dt, double* omega_bound);
 /* compute_Ad (conjugateGradientSolver.py:53-58): vec[y] = K vec[x] */
 int femcy_spmv(femcy_ctx* ctx, int x_vec, int y_vec);
 /* ConjugateGradientSolver_rowMajor.re_init + solve (conjugateGradientSolver.py:32-51, 103-127):
