@@ -76,6 +76,7 @@ EXPORTS = [
     "femcy_newmark_predict", "femcy_newmark_update",
     "femcy_lumped_mass_create", "femcy_lumped_mass_get", "femcy_explicit_create", "femcy_explicit_start",
     "femcy_explicit_advance", "femcy_explicit_kinetic_energy", "femcy_explicit_stable_dt",
+    "femcy_explicit_element_bound", "femcy_explicit_auto_begin", "femcy_explicit_auto_advance", "femcy_explicit_auto_state",
     "femcy_loadset_create", "femcy_loadset_neumann", "femcy_loadset_neumann_add", "femcy_spmv", "femcy_pcg", "femcy_compute_strain_stress", "femcy_elastic_energy", "femcy_elastic_energy_small", "femcy_extrapolate",
     "femcy_get_K_ell", "femcy_get_K_bsr", "femcy_get_gp_field", "femcy_timing",
     "femcy_timing_reset", "femcy_comm_unique_id", "femcy_comm_local_id", "femcy_comm_init", "femcy_comm_info", "femcy_comm_set_neighbours",
@@ -181,6 +182,10 @@ def _bind(lib, kind):
         "femcy_explicit_advance": [p, i32, cint, i32, f64, f64, f64],
         "femcy_explicit_kinetic_energy": [p, i32, cint, C.POINTER(f64)],
         "femcy_explicit_stable_dt": [p, i32, C.POINTER(f64), C.POINTER(f64)],
+        "femcy_explicit_element_bound": [p, i32, cint, f64, C.POINTER(f64)],
+        "femcy_explicit_auto_begin": [p, i32, cint, f64, f64, f64, i32],
+        "femcy_explicit_auto_advance": [p, i32, cint, i32],
+        "femcy_explicit_auto_state": [p, i32, C.POINTER(f64), C.POINTER(f64), C.POINTER(f64), C.POINTER(C.c_int64)],
         "femcy_loadset_create": [p, i32, i32, i32, p, p, p, p, p, i32, p, p, C.POINTER(i32)],
         "femcy_loadset_neumann": [p, i32, f64, p, cint],
         "femcy_loadset_neumann_add": [p, i32, f64, p, cint],
@@ -587,6 +592,27 @@ class Context:
         dt, om = C.c_double(), C.c_double()
         self._call("femcy_explicit_stable_dt", int(ex), C.byref(dt), C.byref(om))
         return dt.value, om.value
+
+    def explicit_element_bound(self, ex: int, s_C: float, u_vec: int = VEC_DOF) -> float:
+        """omega of the element-by-element estimate at vec[u_vec] (no matrix): the stable increment is 2 / omega"""
+        om = C.c_double()
+        self._call("femcy_explicit_element_bound", int(ex), int(u_vec), float(s_C), C.byref(om))
+        return om.value
+
+    def explicit_auto_begin(self, ex: int, s_C: float, scale_factor: float, T: float, ramp: bool = False,
+                            rhs_vec: int = VEC_RHS):
+        """t = 0 on the device, vec[ACC] = a_0 and the first increment of an element-by-element run up to T"""
+        self._call("femcy_explicit_auto_begin", int(ex), int(rhs_vec), float(s_C), float(scale_factor), float(T), int(bool(ramp)))
+
+    def explicit_auto_advance(self, ex: int, nsteps: int, rhs_vec: int = VEC_RHS):
+        """nsteps steps with the increment re-estimated on the device in each; steps past T are no-ops; only enqueues"""
+        self._call("femcy_explicit_auto_advance", int(ex), int(rhs_vec), int(nsteps))
+
+    def explicit_auto_state(self, ex: int):
+        """-> (t, h_last, h_min, steps_done): the synchronising read-back of the device clock"""
+        t, hl, hm, k = C.c_double(), C.c_double(), C.c_double(), C.c_int64()
+        self._call("femcy_explicit_auto_state", int(ex), C.byref(t), C.byref(hl), C.byref(hm), C.byref(k))
+        return t.value, hl.value, hm.value, int(k.value)
 
     def spmv(self, x_vec: int, y_vec: int):
         self._call("femcy_spmv", int(x_vec), int(y_vec))

@@ -11,6 +11,7 @@
 namespace femcy {
 
 void set_error(const char* fmt, ...);
+struct ExplicitClock;   // element_math.hpp
 
 #define FEMCY_HIP(call)                                                                         \
     do {                                                                                        \
@@ -347,9 +348,18 @@ struct Ctx {
     std::vector<Mass> masses;
     // ---- explicit dynamics (femcy_lumped_mass_*, femcy_explicit_*): the HRZ-lumped nodal masses [nn], and an integrator =
     // the inverse mass per scalar DOF [n] with 0 on the constrained DOFs + the lumped mass it was made from
-    struct LumpedMass { DevBuf<double> d_m; };
+    // An automatic run (femcy_explicit_auto_*) also reads the element shares me [ne][npe] the nodal masses were summed from,
+    // and keeps its clock (element_math.hpp: ExplicitClock) and the partial maxima of the bound kernel [ceil(ne / 256)] on
+    // the device; both are allocated by the first call that needs them.
+    struct LumpedMass { DevBuf<double> d_m, d_me; };
     std::vector<LumpedMass> lumped_masses;
-    struct Explicit { DevBuf<double> d_minv; int32_t lumped = -1; };
+    struct Explicit {
+        DevBuf<double> d_minv, d_bpart;
+        DevBuf<ExplicitClock> d_clock;
+        int32_t lumped = -1;
+        bool auto_begun = false;
+        double s_C = 0.0;
+    };
     std::vector<Explicit> explicits;
     int64_t K_serial = -1;            // pattern_serial of the last successful assembly: K holds a matrix when they agree
     bool post_small = false;         // sigma / mises hold femcy_compute_strain_stress(large = 0), not yet corrected
@@ -477,6 +487,16 @@ int launch_explicit_node(Ctx* c, const double* d_minv, const double* d_f, double
 int launch_explicit_energy(Ctx* c, const double* d_m, const double* d_v, double* out);   // 1/2 sum m v^2, fixed order
 // max over the rows i with minv_i != 0 of minv_i sum_j |K_ij| (Gershgorin bound on the spectrum of M_L^-1 K)
 int launch_rowabs_bound(Ctx* c, const double* d_minv, double* out);
+// element-by-element increment.  launch_explicit_bound: the workgroup maxima of omega_e^2 at d_u into d_part
+// [explicit_bound_partials(c)], recomputed from the mesh.  _bound_max: their maximum, fetched (synchronises).  _clock: their maximum + one tick of the device
+// clock.  _node_auto (mode 0 = a_0, 1 = kick, 2 = kick + drift) / _drift_auto: launch_explicit_node / _drift with the
+// increments and the load scale read from the clock.  All but _bound_max only enqueue.
+int explicit_bound_partials(const Ctx* c);
+int launch_explicit_bound(Ctx* c, const double* d_u, const double* d_me, double s_C, double* d_part);
+int launch_explicit_bound_max(Ctx* c, const double* d_part, double* out);
+int launch_explicit_clock(Ctx* c, const double* d_part, ExplicitClock* d_clk);
+int launch_explicit_node_auto(Ctx* c, const double* d_minv, const double* d_f, const ExplicitClock* d_clk, int mode);
+int launch_explicit_drift_auto(Ctx* c, const ExplicitClock* d_clk);
 // pos_space: x and y are in STORAGE order (entry p * dm + c belongs to the node at storage position p = slice * 64 + lane;
 // the padding lanes of the last slice hold zeros) -- the form the three-kernel PCG runs in since round 4
 int launch_spmv(Ctx* c, const double* d_x, double* d_y, double* d_partials, int* nblocks_out, bool pos_space = false);

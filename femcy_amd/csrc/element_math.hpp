@@ -817,6 +817,125 @@ FEMCY_HD void explicit_kick(double minv, double s, double f, double fint, double
 }
 FEMCY_HD double explicit_drift(double u, double v, double a, double h, double h2h) { return fma(h2h, a, fma(h, v, u)); }
 
+// The element-by-element estimate of the highest frequency (*Dynamic, explicit, element by element), at the CURRENT
+// configuration x = X + u.  With m_a^e the element's own HRZ share of the lumped mass (lumped_element), v_q = |det J_x| w_q at
+// the stiffness rule's Gauss points, sigma_q = cauchy_large(F_q) and s_C = max eps:C:eps / eps:eps of the small-strain matrix,
+//   g_e       = sum_q v_q sum_a |grad_x N_a|^2 / m_a^e
+//   omega_e^2 = sum_q v_q (s_C + |sigma_q|_F) sum_a |grad_x N_a|^2 / m_a^e,      omega = sqrt(max_e omega_e^2).
+// At u = 0 with a linear material this is a proof: Cauchy-Schwarz gives |grad u|_F^2 <= (sum_a |grad N_a|^2 / m_a)(x^T M_e x),
+// hence lambda_max(M_e^-1 K_e) <= s_C g_e, and lambda_max(M^-1 K) <= max_e lambda_max(M_e^-1 K_e) because M and K are sums
+// over the elements; the |sigma|_F term bounds the geometric stiffness the same way.  At finite strain the material part is
+// an ESTIMATE: the spatial tangent is not C.  The user's `scale factor` is the margin there.
+// One Gauss point: G = grad_x N [NPE][DM], v = |det J_x| w, sig [DM][DM], rme[a] = 1 / m_a^e.
+template <int NPE, int DM>
+FEMCY_HD void explicit_bound_point(const double* __restrict__ G, double v, const double* __restrict__ sig,
+                                   const double (&rme)[NPE], double s_C, double& g, double& w2) {
+    double q = 0.0;
+#pragma unroll
+    for (int a = 0; a < NPE; ++a) {
+        double gg = 0.0;
+#pragma unroll
+        for (int j = 0; j < DM; ++j) gg += G[a * DM + j] * G[a * DM + j];
+        q += gg * rme[a];
+    }
+    double ss = 0.0;
+#pragma unroll
+    for (int k = 0; k < DM * DM; ++k) ss += sig[k] * sig[k];
+    const double qv = q * v;
+    g += qv;
+    w2 += (s_C + sqrt(ss)) * qv;
+}
+
+// the whole element from its coordinates X, displacements U and masses me: gradients, F and sigma as the element pass of the
+// internal force forms them (dN[g][a][:], w[g]: the plug-in's tables at the Gauss points)
+template <int NPE, int DM>
+FEMCY_HD void explicit_bound_element(const double (&X)[NPE][DM], const double (&U)[NPE][DM], int32_t nGP,
+                                     const double* __restrict__ dN, const double* __restrict__ w, int kind,
+                                     const double* __restrict__ C, double p0, double p1, const double (&me)[NPE], double s_C,
+                                     double& g, double& w2) {
+    double rme[NPE];
+#pragma unroll
+    for (int a = 0; a < NPE; ++a) rme[a] = 1.0 / me[a];
+    g = 0.0;
+    w2 = 0.0;
+    for (int32_t q = 0; q < nGP; ++q) {
+        const double* __restrict__ dNg = dN + q * NPE * DM;
+        double J[DM][DM], inv[DM][DM], J0[DM][DM], inv0[DM][DM], F[DM][DM], sig[DM][DM], G[NPE * DM], sl[DM * DM];
+#pragma unroll
+        for (int i = 0; i < DM; ++i)
+#pragma unroll
+            for (int j = 0; j < DM; ++j) {
+                double acc = 0.0, acc0 = 0.0;
+#pragma unroll
+                for (int a = 0; a < NPE; ++a) {
+                    acc += (X[a][i] + U[a][i]) * dNg[a * DM + j];
+                    acc0 += X[a][i] * dNg[a * DM + j];
+                }
+                J[i][j] = acc;
+                J0[i][j] = acc0;
+                F[i][j] = i == j ? 1.0 : 0.0;
+            }
+        const double det = det_inv<DM>(J, inv);
+        det_inv<DM>(J0, inv0);
+#pragma unroll
+        for (int a = 0; a < NPE; ++a) {
+#pragma unroll
+            for (int j = 0; j < DM; ++j) {
+                double acc = 0.0, acc0 = 0.0;
+#pragma unroll
+                for (int k = 0; k < DM; ++k) {
+                    acc += dNg[a * DM + k] * inv[k][j];
+                    acc0 += dNg[a * DM + k] * inv0[k][j];
+                }
+                G[a * DM + j] = acc;
+#pragma unroll
+                for (int i = 0; i < DM; ++i) F[i][j] += U[a][i] * acc0;
+            }
+        }
+        cauchy_large<DM>(kind, C, p0, p1, F, sig);
+#pragma unroll
+        for (int i = 0; i < DM; ++i)
+#pragma unroll
+            for (int j = 0; j < DM; ++j) sl[i * DM + j] = sig[i][j];
+        explicit_bound_point<NPE, DM>(G, fabs(det) * w[q], sl, rme, s_C, g, w2);
+    }
+}
+
+// the clock of an automatic run, advanced once per step on whichever backend: t is the time of the state the element pass
+// has just seen, h_next the increment of the next drift, t_next the time that drift reaches.
+struct ExplicitClock {
+    double t, t_next, T, sf, s_C, h_prev, h_next, h_last, h_min, omega;
+    int32_t steps, ramp;
+};
+// one tick: the drift by h_next has happened (a real step when h_next > 0), omega2 is the estimate at the new state.
+//   h_next = min(sf 2 / omega, T - t), exactly 0 once t >= T or when omega is not finite; the step that takes the remainder
+//   sets the clock to T itself.
+FEMCY_HD void explicit_clock_tick(ExplicitClock& r, double omega2) {
+    const double t = r.t_next, hp = r.h_next;
+    if (hp > 0.0) {
+        r.steps += 1;
+        r.h_last = hp;
+        r.h_min = hp < r.h_min ? hp : r.h_min;
+    }
+    const double omega = sqrt(omega2);
+    double h = 0.0, tn = t;
+    if (t < r.T && omega == omega && omega <= 1.79769313486231570815e308) {
+        const double rem = r.T - t, hs = r.sf * (2.0 / omega);
+        if (hs >= rem) {
+            h = rem;
+            tn = r.T;
+        } else {
+            h = hs;
+            tn = t + hs < r.T ? t + hs : r.T;
+        }
+    }
+    r.t = t;
+    r.t_next = tn;
+    r.h_prev = hp;
+    r.h_next = h;
+    r.omega = omega;
+}
+
 // sum of 32 partial sums by the xor tree of half a wavefront, as lane 0 of k_nodal_force ends up with it: what the host
 // backend runs so that a node sum has the device's summation order
 inline double half_wave_tree(double (&p)[32]) {

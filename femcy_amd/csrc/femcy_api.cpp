@@ -1285,7 +1285,8 @@ int femcy_lumped_mass_create(femcy_ctx* ctx, int32_t nq, const double* Nq, const
     FEMCY_REQUIRE(nq >= 1 && nq <= 64, "mass rule: %d points (1 .. 64 are supported)", nq);
     FEMCY_REQUIRE(std::isfinite(rho) && rho > 0.0, "mass: the density must be finite and positive");
     Ctx::LumpedMass lm;
-    DevBuf<double> d_Nq, d_dNq, d_wq, d_me;     // the tables and the element records are scratch of this call
+    DevBuf<double> d_Nq, d_dNq, d_wq;           // the tables are scratch of this call
+    DevBuf<double>& d_me = lm.d_me;             // the element shares stay: the element-by-element increment divides by them
     int rc = to_device(d_Nq, Nq, sizeof(double) * nq * c->npe);
     if (!rc) rc = to_device(d_dNq, dNq, sizeof(double) * nq * c->npe * c->dm);
     if (!rc) rc = to_device(d_wq, wq, sizeof(double) * nq);
@@ -1411,6 +1412,109 @@ int femcy_explicit_stable_dt(femcy_ctx* ctx, int32_t id, double* dt, double* ome
     if (rc) return rc;
     *omega_bound = std::sqrt(w2);
     *dt = 2.0 / *omega_bound;
+    return FEMCY_OK;
+}
+
+// ---- element-by-element increment (*Dynamic, explicit, element by element)
+#define POSITIVE_FINITE(x) (std::isfinite(x) && (x) > 0.0)
+
+// the buffers an integrator allocates on first use: the partial maxima of the bound kernel, the clock
+static int explicit_auto_buffers(Ctx* c, Ctx::Explicit& ex) {
+    if (!ex.d_bpart.get() && ex.d_bpart.alloc(sizeof(double) * (size_t)explicit_bound_partials(c)) != hipSuccess) {
+        set_error("out of device memory for the element bound of %d elements", c->ne);
+        return FEMCY_ENOMEM;
+    }
+    if (!ex.d_clock.get() && ex.d_clock.alloc(sizeof(ExplicitClock)) != hipSuccess) {
+        set_error("out of device memory for the clock of an explicit integrator");
+        return FEMCY_ENOMEM;
+    }
+    return FEMCY_OK;
+}
+
+int femcy_explicit_element_bound(femcy_ctx* ctx, int32_t id, int u_vec, double s_C, double* omega) {
+    CTX_OR_FAIL(ctx);
+    READY_OR_FAIL();
+    EXPLICIT_OR_FAIL("femcy_explicit_element_bound", id);
+    VEC_OR_FAIL(u_vec);
+    FEMCY_REQUIRE(omega, "null output");
+    FEMCY_REQUIRE(POSITIVE_FINITE(s_C), "femcy_explicit_element_bound: the material stiffness s_C must be finite and positive");
+    Ctx::Explicit& exm = c->explicits[id];
+    int rc = explicit_auto_buffers(c, exm);
+    if (rc) return rc;
+    rc = launch_explicit_bound(c, c->d_vec[u_vec], c->lumped_masses[ex.lumped].d_me.get(), s_C, exm.d_bpart.get());
+    if (rc) return rc;
+    double w2 = 0.0;
+    if ((rc = launch_explicit_bound_max(c, exm.d_bpart.get(), &w2))) return rc;
+    *omega = std::sqrt(w2);
+    return FEMCY_OK;
+}
+
+int femcy_explicit_auto_begin(femcy_ctx* ctx, int32_t id, int rhs_vec, double s_C, double scale_factor, double T,
+                              int32_t ramp) {
+    CTX_OR_FAIL(ctx);
+    READY_OR_FAIL();
+    EXPLICIT_OR_FAIL("femcy_explicit_auto_begin", id);
+    EXPLICIT_RHS_OR_FAIL("femcy_explicit_auto_begin", rhs_vec);
+    FEMCY_REQUIRE(POSITIVE_FINITE(s_C) && POSITIVE_FINITE(scale_factor) && POSITIVE_FINITE(T),
+                  "femcy_explicit_auto_begin: s_C, the scale factor and T must be finite and positive");
+    Ctx::Explicit& exm = c->explicits[id];
+    int rc = explicit_auto_buffers(c, exm);
+    if (rc) return rc;
+    ExplicitClock clk{};
+    clk.T = T;
+    clk.sf = scale_factor;
+    clk.s_C = s_C;
+    clk.h_min = INFINITY;
+    clk.ramp = ramp ? 1 : 0;
+    if ((rc = stage_h2d(c, exm.d_clock.get(), &clk, sizeof(clk)))) return rc;
+    const double* u = c->d_vec[FEMCY_VEC_DOF];
+    if ((rc = force_pass(c, u))) return rc;
+    if ((rc = launch_explicit_bound(c, u, c->lumped_masses[ex.lumped].d_me.get(), s_C, exm.d_bpart.get()))) return rc;
+    if ((rc = launch_explicit_clock(c, exm.d_bpart.get(), exm.d_clock.get()))) return rc;   // t = 0, the first h
+    if ((rc = launch_explicit_node_auto(c, ex.d_minv.get(), c->d_vec[rhs_vec], exm.d_clock.get(), 0))) return rc;
+    exm.auto_begun = true;
+    exm.s_C = s_C;
+    return FEMCY_OK;
+}
+
+int femcy_explicit_auto_advance(femcy_ctx* ctx, int32_t id, int rhs_vec, int32_t nsteps) {
+    CTX_OR_FAIL(ctx);
+    READY_OR_FAIL();
+    EXPLICIT_OR_FAIL("femcy_explicit_auto_advance", id);
+    EXPLICIT_RHS_OR_FAIL("femcy_explicit_auto_advance", rhs_vec);
+    FEMCY_REQUIRE(nsteps >= 0, "femcy_explicit_auto_advance: %d steps", nsteps);
+    FEMCY_REQUIRE(ex.auto_begun, "femcy_explicit_auto_advance before femcy_explicit_auto_begin");
+    if (nsteps == 0) return FEMCY_OK;
+    double* u = c->d_vec[FEMCY_VEC_DOF];
+    ExplicitClock* clk = ex.d_clock.get();
+    const double* me = c->lumped_masses[ex.lumped].d_me.get();
+    const double s_C = ex.s_C;
+    int rc = launch_explicit_drift_auto(c, clk);
+    for (int32_t k = 1; !rc && k <= nsteps; ++k) {
+        if ((rc = launch_geom(c, u, GEOM_DSDX | GEOM_FE))) break;
+        if ((rc = launch_explicit_bound(c, u, me, s_C, ex.d_bpart.get()))) break;
+        if ((rc = launch_explicit_clock(c, ex.d_bpart.get(), clk))) break;
+        rc = launch_explicit_node_auto(c, ex.d_minv.get(), c->d_vec[rhs_vec], clk, k < nsteps ? 2 : 1);
+    }
+    if (rc) return rc;
+    FEMCY_HIP(hipMemcpyAsync(c->d_u_lazy, u, sizeof(double) * c->n, hipMemcpyDeviceToDevice, c->stream));
+    c->gp_lazy = true;
+    c->post_small = false;
+    return FEMCY_OK;
+}
+
+int femcy_explicit_auto_state(femcy_ctx* ctx, int32_t id, double* t, double* h_last, double* h_min, int64_t* steps_done) {
+    CTX_OR_FAIL(ctx);
+    EXPLICIT_OR_FAIL("femcy_explicit_auto_state", id);
+    FEMCY_REQUIRE(t && h_last && h_min && steps_done, "null output");
+    FEMCY_REQUIRE(ex.auto_begun, "femcy_explicit_auto_state before femcy_explicit_auto_begin");
+    ExplicitClock clk;
+    FEMCY_HIP(hipMemcpyAsync(&clk, ex.d_clock.get(), sizeof(clk), hipMemcpyDeviceToHost, c->stream));
+    FEMCY_HIP(hipStreamSynchronize(c->stream));
+    *t = clk.t;
+    *h_last = clk.h_last;
+    *h_min = clk.steps ? clk.h_min : 0.0;
+    *steps_done = clk.steps;
     return FEMCY_OK;
 }
 

@@ -203,6 +203,121 @@ __global__ void __launch_bounds__(XBS) k_rowabs_bound(int64_t npos, const int32_
     if (threadIdx.x == 0) part[blockIdx.x] = r;
 }
 
+// ---------------------------------------------------------------------- element-by-element increment
+// omega_e^2 of element_math.hpp (explicit_bound_element), one thread per element, recomputed from nodes, u, elems and the
+// element's own lumped masses me[e][0..NPE): the launch shape of k_lumped_elem.  (Reading the records of an element pass that
+// also stores sigma was measured against this: 218.3 against 181.5 us per step on the 1 M C3D4 plate, the fixed step at
+// 149.2 -- the extra 72 B per element the element pass then writes cost more than the gathers here;
+// profiles/explicit_auto.json.)  The workgroup's maximum goes to
+// part[blockIdx.x] (ceil(ne / 256) partials, no grid-stride loop: k_explicit_clock loops over any number of them).  A NaN
+// counts as infinity, as in k_rowabs_bound, so that a broken element gives no increment.
+template <int NPE, int DM>
+__global__ void __launch_bounds__(XBS) k_explicit_bound(int32_t ne, int32_t nGP, const double* __restrict__ nodes,
+                                                        const double* __restrict__ u, const int32_t* __restrict__ elems,
+                                                        const double* __restrict__ dN, const double* __restrict__ w,
+                                                        int mat_kind, const double* __restrict__ C, double p0, double p1,
+                                                        const double* __restrict__ me_in, double s_C,
+                                                        double* __restrict__ part) {
+    __shared__ double sm[XBS / 64];
+    const int32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    double best = 0.0;
+    if (e < ne) {
+        double X[NPE][DM], U[NPE][DM], me[NPE], g, w2;
+#pragma unroll
+        for (int a = 0; a < NPE; ++a) {
+            const int32_t nd = elems[(int64_t)e * NPE + a];
+            load_row<DM>(nodes + (int64_t)nd * DM, X[a]);
+            load_row<DM>(u + (int64_t)nd * DM, U[a]);
+            me[a] = me_in[(int64_t)e * NPE + a];
+        }
+        explicit_bound_element<NPE, DM>(X, U, nGP, dN, w, mat_kind, C, p0, p1, me, s_C, g, w2);
+        best = w2 != w2 ? INFINITY : w2;
+    }
+    const double r = block_reduce<true>(best, sm);
+    if (threadIdx.x == 0) part[blockIdx.x] = r;
+}
+
+// one workgroup: the maximum of the np partials (thread t takes t, t + 256, ... in ascending order, then the tree), and one
+// tick of the clock by thread 0 (element_math.hpp: explicit_clock_tick)
+__global__ void __launch_bounds__(XBS) k_explicit_clock(int np, const double* __restrict__ part, ExplicitClock* __restrict__ clk) {
+    __shared__ double sm[XBS / 64];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < np; i += XBS) acc = fmax(acc, part[i]);
+    const double r = block_reduce<true>(acc, sm);
+    if (threadIdx.x == 0) {
+        ExplicitClock c = *clk;
+        explicit_clock_tick(c, r);
+        *clk = c;
+    }
+}
+
+// k_explicit_node with h, h / 2, h^2 / 2 and the load scale read from the device clock instead of the kernel arguments: the
+// kick uses h_prev (the increment that led to the state being kicked), the drift h_next; the scale is 1 (STEP) or t / T
+// (RAMP) at the time t of the state being kicked.  With h_prev = h_next = 0 (mode != XN_START) nothing is written: the steps
+// of a batch that overshoots T leave u, v, a bit for bit alone.  The drift is skipped when h_next = 0.
+template <int DM>
+__global__ void __launch_bounds__(XBS) k_explicit_node_auto(int32_t nn, const int32_t* __restrict__ ne_ptr,
+                                                            const int32_t* __restrict__ ne_idx,
+                                                            const double* __restrict__ fe, const double* __restrict__ f,
+                                                            const double* __restrict__ minv,
+                                                            const ExplicitClock* __restrict__ clk, int mode,
+                                                            double* __restrict__ u, double* __restrict__ v,
+                                                            double* __restrict__ acc_vec) {
+    const double hp = clk->h_prev, h = clk->h_next;
+    if (mode != XN_START && hp == 0.0 && h == 0.0) return;
+    const double s = clk->ramp ? clk->t / clk->T : 1.0;
+    const double hh = 0.5 * hp, h2h = 0.5 * h * h;
+    const bool drift = mode == XN_KICK_DRIFT && h != 0.0;
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int32_t a = (int32_t)(t >> 5);
+    const int sub = (int)(t & 31);
+    const bool mine = a < nn && sub < DM;
+    const int64_t i = (int64_t)a * DM + sub;
+    double fi = 0.0, mi = 0.0, ai = 0.0, vi = 0.0, ui = 0.0;
+    if (mine) {
+        fi = f[i];
+        mi = minv[i];
+        if (mode != XN_START) {
+            ai = acc_vec[i];
+            vi = v[i];
+        }
+        if (drift) ui = u[i];
+    }
+    double acc[DM];
+#pragma unroll
+    for (int c = 0; c < DM; ++c) acc[c] = 0.0;
+    if (a < nn) {
+        const int32_t k1 = ne_ptr[a + 1];
+        for (int32_t k = ne_ptr[a] + sub; k < k1; k += 32) {
+            double rv[DM];
+            load_row<DM>(fe + (int64_t)ne_idx[k] * DM, rv);
+#pragma unroll
+            for (int c = 0; c < DM; ++c) acc[c] += rv[c];
+        }
+    }
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1)
+#pragma unroll
+        for (int c = 0; c < DM; ++c) acc[c] += __shfl_xor(acc[c], o, 32);
+    if (!mine) return;
+    const double fint = sub == 0 ? acc[0] : (sub == 1 ? acc[1] : acc[DM - 1]);
+    explicit_kick(mi, s, fi, fint, hh, vi, ai);
+    acc_vec[i] = ai;
+    if (mode == XN_START) return;
+    v[i] = vi;
+    if (drift) u[i] = explicit_drift(ui, vi, ai, h, h2h);
+}
+
+// the first drift of an automatic call, by h_next of the device clock; h_next = 0 writes nothing
+__global__ void __launch_bounds__(XBS) k_explicit_drift_auto(int64_t n, const ExplicitClock* __restrict__ clk,
+                                                             const double* __restrict__ v, const double* __restrict__ a,
+                                                             double* __restrict__ u) {
+    const double h = clk->h_next;
+    if (h == 0.0) return;
+    const int64_t i = (int64_t)blockIdx.x * XBS + threadIdx.x;
+    if (i < n) u[i] = explicit_drift(u[i], v[i], a[i], h, 0.5 * h * h);
+}
+
 // ------------------------------------------------------------------------------- host launchers
 static int reduction_grid(int64_t items) {
     return (int)std::max<int64_t>(1, std::min<int64_t>((items + XBS - 1) / XBS, 1024));   // <= MAX_PARTIALS partials
@@ -300,6 +415,61 @@ int launch_rowabs_bound(Ctx* c, const double* d_minv, double* out) {
     hipLaunchKernelGGL((k_explicit_final<true>), dim3(1), dim3(XBS), 0, c->stream, g, c->d_part1, c->d_part2);
     FEMCY_HIP(hipGetLastError());
     return fetch_scalar(c, c->d_part2, out);
+}
+
+int explicit_bound_partials(const Ctx* c) { return (c->ne + XBS - 1) / XBS; }
+
+int launch_explicit_bound(Ctx* c, const double* d_u, const double* d_me, double s_C, double* d_part) {
+    const int grid = explicit_bound_partials(c);
+    size_t tm = timing_begin(c, T_GEOM);
+    const bool launched = dispatch_element(c->npe, c->dm, [&](auto npe, auto dm) {
+        hipLaunchKernelGGL((k_explicit_bound<npe(), dm()>), dim3(grid), dim3(XBS), 0, c->stream, c->ne, c->nGP, c->d_nodes, d_u,
+                           c->d_elems, c->d_dN, c->d_w, c->mat_kind, c->d_C, c->mat_params[0], c->mat_params[1], d_me, s_C,
+                           d_part);
+    });
+    timing_end(c, tm);
+    if (!launched) {
+        set_error("no element-bound kernel instantiated for npe=%d dm=%d", c->npe, c->dm);
+        return FEMCY_ENOKERNEL;
+    }
+    FEMCY_HIP(hipGetLastError());
+    return FEMCY_OK;
+}
+
+int launch_explicit_bound_max(Ctx* c, const double* d_part, double* out) {
+    hipLaunchKernelGGL((k_explicit_final<true>), dim3(1), dim3(XBS), 0, c->stream, explicit_bound_partials(c), d_part,
+                       c->d_part2);
+    FEMCY_HIP(hipGetLastError());
+    return fetch_scalar(c, c->d_part2, out);
+}
+
+int launch_explicit_clock(Ctx* c, const double* d_part, ExplicitClock* d_clk) {
+    hipLaunchKernelGGL(k_explicit_clock, dim3(1), dim3(XBS), 0, c->stream, explicit_bound_partials(c), d_part, d_clk);
+    FEMCY_HIP(hipGetLastError());
+    return FEMCY_OK;
+}
+
+int launch_explicit_node_auto(Ctx* c, const double* d_minv, const double* d_f, const ExplicitClock* d_clk, int mode) {
+    const unsigned grid = (unsigned)(((int64_t)c->nn * 32 + XBS - 1) / XBS);   // 32 lanes per node
+    size_t tm = timing_begin(c, T_FORCE);
+    dispatch_dm(c->dm, [&](auto dm) {
+        hipLaunchKernelGGL((k_explicit_node_auto<dm()>), dim3(grid), dim3(XBS), 0, c->stream, c->nn, c->d_ne_ptr,
+                           c->d_ne_idx, c->d_fe, d_f, d_minv, d_clk, mode, c->d_vec[FEMCY_VEC_DOF], c->d_vec[FEMCY_VEC_VEL],
+                           c->d_vec[FEMCY_VEC_ACC]);
+    });
+    timing_end(c, tm);
+    FEMCY_HIP(hipGetLastError());
+    return FEMCY_OK;
+}
+
+int launch_explicit_drift_auto(Ctx* c, const ExplicitClock* d_clk) {
+    const unsigned grid = (unsigned)((c->n + XBS - 1) / XBS);
+    size_t tm = timing_begin(c, T_FORCE);
+    hipLaunchKernelGGL(k_explicit_drift_auto, dim3(grid), dim3(XBS), 0, c->stream, c->n, d_clk, c->d_vec[FEMCY_VEC_VEL],
+                       c->d_vec[FEMCY_VEC_ACC], c->d_vec[FEMCY_VEC_DOF]);
+    timing_end(c, tm);
+    FEMCY_HIP(hipGetLastError());
+    return FEMCY_OK;
 }
 
 }  // namespace femcy

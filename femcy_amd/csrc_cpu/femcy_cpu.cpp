@@ -71,10 +71,13 @@ struct Mass {
 };
 struct LumpedMass {
     std::vector<double> m;   // [nn] HRZ-lumped nodal masses
+    std::vector<double> me;  // [ne][npe] the element shares they were summed from (the element-by-element increment)
 };
 struct Explicit {
     std::vector<double> minv;   // [n] inverse mass per scalar DOF, 0 on the constrained DOFs
     int32_t lumped;
+    femcy::ExplicitClock clock{};   // femcy_explicit_auto_*
+    bool auto_begun = false;
 };
 struct Thermal {
     std::vector<double> f, dT, N;  // [n] load at scale 1, [nn] temperature changes, [nGP][npe] shape functions
@@ -1326,8 +1329,8 @@ namespace {
 // order of its half-wavefront gather: partial sums of every 32nd incident element, combined by half_wave_tree
 template <int NPE, int DM>
 void lumped_mass(femcy_ctx* c, int32_t nq, const double* Nq, const double* dNq, const double* wq, double rho,
-                 std::vector<double>& m) {
-    std::vector<double> me((size_t)c->ne * NPE, 0.0);
+                 std::vector<double>& m, std::vector<double>& me) {
+    me.assign((size_t)c->ne * NPE, 0.0);
 #pragma omp parallel for schedule(static)
     for (int32_t e = 0; e < c->ne; ++e) {
         double X[NPE][DM], w[NPE];
@@ -1369,6 +1372,61 @@ void explicit_node(femcy_ctx* c, const Explicit& ex, const double* f, double s, 
     }
 }
 
+// the device's k_explicit_node_auto: the increments and the load scale come from the clock; h_prev = h_next = 0 writes nothing
+void explicit_node_auto(femcy_ctx* c, const Explicit& ex, const double* f, int mode) {
+    const ExplicitClock& k = ex.clock;
+    if (mode && k.h_prev == 0.0 && k.h_next == 0.0) return;
+    const int dm = c->dm;
+    double *u = c->vec[FEMCY_VEC_DOF].data(), *v = c->vec[FEMCY_VEC_VEL].data(), *acc = c->vec[FEMCY_VEC_ACC].data();
+    const double s = k.ramp ? k.t / k.T : 1.0, h = k.h_next, hh = 0.5 * k.h_prev, h2h = 0.5 * h * h;
+    const bool drift = mode == 2 && h != 0.0;
+#pragma omp parallel for schedule(static)
+    for (int32_t a = 0; a < c->nn; ++a) {
+        double p[3][32] = {{0.0}};
+        for (int32_t q = c->ne_ptr[a]; q < c->ne_ptr[a + 1]; ++q)
+            for (int i = 0; i < dm; ++i) p[i][(q - c->ne_ptr[a]) & 31] += c->fe[(int64_t)c->ne_idx[q] * dm + i];
+        for (int i = 0; i < dm; ++i) {
+            const int64_t q = (int64_t)a * dm + i;
+            const double fint = half_wave_tree(p[i]);
+            double vi = mode ? v[q] : 0.0, ai = mode ? acc[q] : 0.0;
+            explicit_kick(ex.minv[q], s, f[q], fint, hh, vi, ai);
+            acc[q] = ai;
+            if (!mode) continue;
+            v[q] = vi;
+            if (drift) u[q] = explicit_drift(u[q], vi, ai, h, h2h);
+        }
+    }
+}
+
+// max_e omega_e^2 at u (csrc/element_math.hpp: explicit_bound_element); a NaN counts as infinity
+template <int NPE, int DM>
+void element_bound(femcy_ctx* c, const double* u, const double* me_all, double s_C, double& out) {
+    double best = 0.0;
+#pragma omp parallel for schedule(static) reduction(max : best)
+    for (int32_t e = 0; e < c->ne; ++e) {
+        double X[NPE][DM], U[NPE][DM], me[NPE], g, w2;
+        for (int a = 0; a < NPE; ++a) {
+            const int32_t nd = c->elems[(int64_t)e * NPE + a];
+            for (int i = 0; i < DM; ++i) {
+                X[a][i] = c->nodes[(int64_t)nd * DM + i];
+                U[a][i] = u[(int64_t)nd * DM + i];
+            }
+            me[a] = me_all[(int64_t)e * NPE + a];
+        }
+        explicit_bound_element<NPE, DM>(X, U, c->nGP, c->dN.data(), c->w.data(), c->mat_kind, c->C, c->params[0],
+                                        c->params[1], me, s_C, g, w2);
+        if (w2 != w2) w2 = INFINITY;
+        best = std::fmax(best, w2);
+    }
+    out = best;
+}
+int element_bound_any(femcy_ctx* c, const Explicit& ex, const double* u, double s_C, double* w2) {
+    const double* me = c->lumped_masses[ex.lumped].me.data();
+    if (!dispatch_element(c->npe, c->dm, [&](auto npe, auto dm) { element_bound<npe(), dm()>(c, u, me, s_C, *w2); }))
+        return no_kernel(c, "element-bound");
+    return FEMCY_OK;
+}
+
 // a workgroup's 256 values -> one, in the order of the device's block_reduce (kernels_explicit.hip): xor tree inside each
 // wavefront of 64, then the four wave results in ascending order
 double block_reduce_sum(double (&x)[256]) {
@@ -1395,7 +1453,7 @@ int femcy_lumped_mass_create(femcy_ctx* ctx, int32_t nq, const double* Nq, const
     REQUIRE(std::isfinite(rho) && rho > 0.0, "mass: the density must be finite and positive");
     LumpedMass lm;
     if (!dispatch_element(c->npe, c->dm,
-                          [&](auto npe, auto dm) { lumped_mass<npe(), dm()>(c, nq, Nq, dNq, wq, rho, lm.m); }))
+                          [&](auto npe, auto dm) { lumped_mass<npe(), dm()>(c, nq, Nq, dNq, wq, rho, lm.m, lm.me); }))
         return no_kernel(c, "lumped-mass");
     c->lumped_masses.push_back(std::move(lm));
     *id_out = (int32_t)c->lumped_masses.size() - 1;
@@ -1524,6 +1582,88 @@ int femcy_explicit_stable_dt(femcy_ctx* ctx, int32_t id, double* dt, double* ome
     }
     *omega_bound = std::sqrt(best);
     *dt = 2.0 / *omega_bound;
+    return FEMCY_OK;
+}
+
+#define POSITIVE_FINITE(x) (std::isfinite(x) && (x) > 0.0)
+
+int femcy_explicit_element_bound(femcy_ctx* ctx, int32_t id, int u_vec, double s_C, double* omega) {
+    CTX_OR_FAIL(ctx);
+    READY_OR_FAIL();
+    EXPLICIT_OR_FAIL(id);
+    VEC_OR_FAIL(u_vec);
+    REQUIRE(omega, "null output");
+    REQUIRE(POSITIVE_FINITE(s_C), "femcy_explicit_element_bound: the material stiffness s_C must be finite and positive");
+    double w2 = 0.0;
+    int rc = element_bound_any(c, ex, c->vec[u_vec].data(), s_C, &w2);
+    if (rc) return rc;
+    *omega = std::sqrt(w2);
+    return FEMCY_OK;
+}
+
+int femcy_explicit_auto_begin(femcy_ctx* ctx, int32_t id, int rhs_vec, double s_C, double scale_factor, double T,
+                              int32_t ramp) {
+    CTX_OR_FAIL(ctx);
+    READY_OR_FAIL();
+    EXPLICIT_OR_FAIL(id);
+    EXPLICIT_RHS_OR_FAIL("femcy_explicit_auto_begin", rhs_vec);
+    REQUIRE(POSITIVE_FINITE(s_C) && POSITIVE_FINITE(scale_factor) && POSITIVE_FINITE(T),
+            "femcy_explicit_auto_begin: s_C, the scale factor and T must be finite and positive");
+    Explicit& exm = c->explicits[id];
+    const double* u = c->vec[FEMCY_VEC_DOF].data();
+    double w2 = 0.0;
+    int rc = element_bound_any(c, ex, u, s_C, &w2);
+    if (rc) return rc;
+    exm.clock = ExplicitClock{};
+    exm.clock.T = T;
+    exm.clock.sf = scale_factor;
+    exm.clock.s_C = s_C;
+    exm.clock.h_min = INFINITY;
+    exm.clock.ramp = ramp ? 1 : 0;
+    geom(c, u, GEOM_DSDX | GEOM_F | GEOM_SIGMA | GEOM_FE);
+    explicit_clock_tick(exm.clock, w2);                        // t = 0, the first h
+    explicit_node_auto(c, exm, c->vec[rhs_vec].data(), 0);
+    exm.auto_begun = true;
+    return FEMCY_OK;
+}
+
+int femcy_explicit_auto_advance(femcy_ctx* ctx, int32_t id, int rhs_vec, int32_t nsteps) {
+    CTX_OR_FAIL(ctx);
+    READY_OR_FAIL();
+    EXPLICIT_OR_FAIL(id);
+    EXPLICIT_RHS_OR_FAIL("femcy_explicit_auto_advance", rhs_vec);
+    REQUIRE(nsteps >= 0, "femcy_explicit_auto_advance: %d steps", nsteps);
+    REQUIRE(ex.auto_begun, "femcy_explicit_auto_advance before femcy_explicit_auto_begin");
+    if (nsteps == 0) return FEMCY_OK;
+    Explicit& exm = c->explicits[id];
+    double* u = c->vec[FEMCY_VEC_DOF].data();
+    const double *v = c->vec[FEMCY_VEC_VEL].data(), *a = c->vec[FEMCY_VEC_ACC].data();
+    if (const double h = exm.clock.h_next; h != 0.0) {
+        const double h2h = 0.5 * h * h;
+#pragma omp parallel for schedule(static)
+        for (int64_t i = 0; i < c->n; ++i) u[i] = explicit_drift(u[i], v[i], a[i], h, h2h);
+    }
+    for (int32_t k = 1; k <= nsteps; ++k) {
+        const bool last = k == nsteps;      // F and sigma of the last state stay behind for post-processing
+        geom(c, u, last ? (GEOM_DSDX | GEOM_F | GEOM_SIGMA | GEOM_FE) : (GEOM_DSDX | GEOM_FE));
+        double w2 = 0.0;
+        int rc = element_bound_any(c, exm, u, exm.clock.s_C, &w2);
+        if (rc) return rc;
+        explicit_clock_tick(exm.clock, w2);
+        explicit_node_auto(c, exm, c->vec[rhs_vec].data(), last ? 1 : 2);
+    }
+    return FEMCY_OK;
+}
+
+int femcy_explicit_auto_state(femcy_ctx* ctx, int32_t id, double* t, double* h_last, double* h_min, int64_t* steps_done) {
+    CTX_OR_FAIL(ctx);
+    EXPLICIT_OR_FAIL(id);
+    REQUIRE(t && h_last && h_min && steps_done, "null output");
+    REQUIRE(ex.auto_begun, "femcy_explicit_auto_state before femcy_explicit_auto_begin");
+    *t = ex.clock.t;
+    *h_last = ex.clock.h_last;
+    *h_min = ex.clock.steps ? ex.clock.h_min : 0.0;
+    *steps_done = ex.clock.steps;
     return FEMCY_OK;
 }
 

@@ -30,7 +30,8 @@ refused by name instead of being skipped.  `*Expansion` inside a `*Material` blo
 with fixed increments (read_procedure); `*Step, amplitude=RAMP|STEP` -> amplitude; `*Initial Conditions, type=VELOCITY` ->
 initial_velocity_info.  `*Dynamic, explicit[, direct user control][, scale factor=][, output_every=]` with data `, T` (`dt, T`
 under direct user control) -> procedure = "explicit", dynamic = {"direct_user_control", "scale_factor", "output_every"} and
-time_incs whose increments are None until the driver has estimated one.  A deck with `*Static` has procedure = "static" and
+time_incs whose increments are None until the driver has estimated one; `element by element` in place of `direct user
+control` -> dynamic_auto = True: the driver re-estimates the increment in every step.  A deck with `*Static` has procedure = "static" and
 reads as before.
 """
 import sys
@@ -473,8 +474,11 @@ class InpInfo(InpInfoBase):
         `*Dynamic, explicit[, direct user control][, scale factor=][, output_every=]` -> procedure "explicit" and dynamic =
         {"direct_user_control", "scale_factor", "output_every"}: central differences with a lumped mass (`solve_explicit`).
         It refuses `beta=` / `gamma=` / `alpha=`, a deck without `*Density`, a non-zero `*Boundary` value and
-        `*Temperature`."""
+        `*Temperature`.  `element by element` on `*Dynamic, explicit` asks for the increment to be re-estimated from the
+        current configuration in every step; it is refused together with `direct user control` and on any other
+        `*Dynamic`.  The flag is kept beside the dictionary, as `self.dynamic_auto` (False for every other deck)."""
         procedure, dynamic, amplitude = "static", None, None
+        self.dynamic_auto = False
         for line, block in _deck(fileName).keywords():
             fields = [t.strip() for t in line.split(",")]
             key = fields[0].lower()
@@ -493,11 +497,18 @@ class InpInfo(InpInfoBase):
                 if not scale_factor > 0.0 or output_every < 1:
                     raise ValueError("*Dynamic, explicit: scale factor = {} and output_every = {} are refused (both must "
                                      "be positive)".format(scale_factor, output_every))
+                if "element by element" in flags and "direct user control" in flags:
+                    raise ValueError("*Dynamic, explicit: `element by element` estimates the increment in every step and "
+                                     "`direct user control` fixes it; give one of them")
+                self.dynamic_auto = "element by element" in flags
                 procedure = "explicit"
                 dynamic = {"direct_user_control": "direct user control" in flags, "scale_factor": scale_factor,
                            "output_every": output_every}
                 break
             elif key == "*dynamic":
+                if "element by element" in flags:
+                    raise ValueError("*Dynamic, element by element has not been supported without `explicit`: the "
+                                     "implicit integrator takes fixed increments")
                 if "direct" not in flags:
                     raise ValueError("*Dynamic without `direct` has not been supported: automatic time incrementation "
                                      "is not built, give fixed increments with *Dynamic, direct")

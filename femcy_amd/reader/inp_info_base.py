@@ -23,7 +23,8 @@ class InpInfoBase:
                   "expansion", "temperature_info",
                   # the step's procedure: "static" | "dynamic" (*Dynamic, direct) | "explicit" (*Dynamic, explicit), its
                   # parameters ({"beta", "gamma"}; {"direct_user_control", "scale_factor", "output_every"}) or None, the load amplitude "RAMP" | "STEP", *Initial Conditions, type=VELOCITY as [{"node_set", "dof", "val"}]
-                  "procedure", "dynamic", "amplitude", "initial_velocity_info")
+                  # dynamic_auto: `element by element` on *Dynamic, explicit (bool; kept beside the dictionary)
+                  "procedure", "dynamic", "amplitude", "initial_velocity_info", "dynamic_auto")
 
     def __init_subclass__(cls, **kwargs):
         super().__init_subclass__(**kwargs)

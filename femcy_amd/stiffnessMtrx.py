@@ -648,7 +648,13 @@ class System_of_equations:
         whole number of steps, and the run ends at T exactly.  Steps run in batches of `output_every` (default 64) per
         `femcy_explicit_advance`, the last one clipped; after each batch `increments` gains {"kinc" (steps done), "time1",
         "dt", "kinetic", "strain_energy"} (`get_elasEng`, the reference's large-strain energy), `initial_energy` holds those
-        of t = 0.  A displacement that is not finite -- an unstable increment -- raises FemcyError(FEMCY_ENUMERIC)."""
+        of t = 0.  A displacement that is not finite -- an unstable increment -- raises FemcyError(FEMCY_ENUMERIC).
+        With `element by element` (`inp.dynamic_auto`) no matrix is assembled: the increment is `scale factor` x 2 / omega of
+        the element-by-element estimate at the CURRENT configuration, re-estimated on the device in every step
+        (`femcy_explicit_auto_*`), and the last step takes what is left of T.  Batches of `output_every` steps run until the
+        clock read back after a batch says t == T (the steps of the last batch past T are no-ops); the records carry "kinc"
+        (real steps so far), "time1" (the device clock), "dt" (the last increment) and "dt_min"; `stable_dt` is the first
+        estimate, `dt` the last increment.  An increment that collapses to 0 before T raises the same error."""
         if self.part is not None:
             raise ValueError("a *Dynamic, explicit step on more than one rank has not been supported: the lumped mass is "
                              "single-rank")
@@ -673,6 +679,8 @@ class System_of_equations:
         held = [self._dofset(np.array([*bc["node_set"]]), bc["dof"]) for bc in inp.dirichlet_bc_info]
         self.lumped_mass = ctx.lumped_mass(self.ELE, inp.density)
         self.explicit = ex = ctx.explicit(self.lumped_mass, held)
+        if getattr(inp, "dynamic_auto", False):
+            return self._solve_explicit_auto(inp, ex, held, max_time)
         if inp.dynamic["direct_user_control"]:
             dt = inp.time_incs["ini_inc"]
         else:
@@ -712,6 +720,58 @@ class System_of_equations:
                                     "increment)".format(done, h), status=be.FEMCY_ENUMERIC)
             self.increments.append({"kinc": done, "time1": self.time1, "dt": h, "converged": True, "newton_loop": 0,
                                     "kinetic": ctx.explicit_kinetic_energy(ex, be.VEC_VEL),
+                                    "strain_energy": self.get_elasEng()})
+        self.dof_old.copy_from(self.dof)
+
+    def material_stiffness(self):
+        """s_C = max eps:C:eps / eps:eps over symmetric strains of the material's small-strain matrix C (Voigt, engineering
+        shear): the largest eigenvalue of D C D with D = diag(1 on the normal, sqrt 2 on the shear components).  Isotropic:
+        3 lambda + 2 mu in 3-D, 2 lambda + 2 mu in plane strain, E / (1 - nu) in plane stress; neo-Hookean: the same with
+        mu = 2 C1 and lambda = 2 D1 of its constant tangent."""
+        C = np.asarray(self.material.C, dtype=np.float64)
+        d = np.where(np.arange(len(C)) < self.dm, 1.0, np.sqrt(2.0))
+        return float(np.linalg.eigvalsh(d[:, None] * C * d[None, :]).max())
+
+    def _solve_explicit_auto(self, inp, ex, held, max_time):
+        """the `element by element` branch of solve_explicit, from the integrator on"""
+        ctx = self.ctx
+        ramp = inp.amplitude == "RAMP"
+        s_C, sf, batch = self.material_stiffness(), inp.dynamic["scale_factor"], inp.dynamic["output_every"]
+        vel, acc = ctx.vector(be.VEC_VEL), ctx.vector(be.VEC_ACC)
+        self.velocity, self.acceleration = vel, acc
+        self.dof.fill(0.0)
+        self.dof_old.fill(0.0)
+        vel.fill(0.0)
+        for iv in getattr(inp, "initial_velocity_info", None) or []:
+            ctx.dofset_fill(self._dofset(iv["node_set"], iv["dof"]), be.VEC_VEL, iv["val"])
+        for ds in held:
+            ctx.dofset_fill(ds, be.VEC_VEL, 0.0)
+        self.time0 = self.time1 = 0.0
+        self.omega_bound = ctx.explicit_element_bound(ex, s_C, be.VEC_DOF)
+        self.stable_dt = 2.0 / self.omega_bound if self.omega_bound > 0.0 else np.inf
+        if not np.isfinite(self.omega_bound):
+            raise be.FemcyError("explicit step: no usable increment (omega = {})".format(self.omega_bound),
+                                status=be.FEMCY_ENUMERIC)
+        ctx.explicit_auto_begin(ex, s_C, sf, max_time, ramp, be.VEC_RHS)
+        self.stats["force_evals"] += 1
+        self.initial_energy = {"kinetic": ctx.explicit_kinetic_energy(ex, be.VEC_VEL), "strain_energy": self.get_elasEng()}
+        self.increments = []
+        done, t = 0, 0.0
+        while t < max_time:
+            self._say("\033[40;33;1m >>>>> steps {} .., t = {} of {} \033[0m".format(done + 1, t, max_time))
+            ctx.explicit_auto_advance(ex, batch, be.VEC_RHS)
+            self.stats["force_evals"] += batch
+            t, h_last, h_min, steps = ctx.explicit_auto_state(ex)
+            self.time0, self.time1, self.dt = self.time1, t, h_last
+            if not np.isfinite(ctx.vec_absmax(be.VEC_DOF)):
+                raise be.FemcyError("explicit step: the displacements are not finite after {} steps, the last of dt = {} (an "
+                                    "unstable increment)".format(steps, h_last), status=be.FEMCY_ENUMERIC)
+            if steps == done and t < max_time:
+                raise be.FemcyError("explicit step: the increment collapsed to 0 at t = {} of {} after {} steps (an unstable "
+                                    "increment)".format(t, max_time, steps), status=be.FEMCY_ENUMERIC)
+            done = steps
+            self.increments.append({"kinc": done, "time1": t, "dt": h_last, "dt_min": h_min, "converged": True,
+                                    "newton_loop": 0, "kinetic": ctx.explicit_kinetic_energy(ex, be.VEC_VEL),
                                     "strain_energy": self.get_elasEng()})
         self.dof_old.copy_from(self.dof)
 

@@ -479,6 +479,34 @@ int femcy_explicit_start(femcy_ctx* ctx, int32_t id, int rhs_vec, double scale);
 int femcy_explicit_advance(femcy_ctx* ctx, int32_t id, int rhs_vec, int32_t nsteps, double dt, double scale0, double dscale);
 int femcy_explicit_kinetic_energy(femcy_ctx* ctx, int32_t id, int v_vec, double* out);
 int femcy_explicit_stable_dt(femcy_ctx* ctx, int32_t id, double* dt, double* omega_bound);
+/* The element-by-element increment (*Dynamic, explicit, element by element): the highest frequency is estimated from the
+ * CURRENT configuration x = X + u in every step, element by element, and the increment and the clock stay on the device, so
+ * that a batch of steps needs no host synchronisation and no matrix is ever assembled.  With m_a^e the element's own HRZ
+ * share of the lumped mass, v_q = |det J_x(xi_q)| w_q at the stiffness rule's Gauss points, sigma_q the Cauchy stress of the
+ * internal force at F_q and s_C = max eps:C:eps / eps:eps of the material's small-strain matrix (3 lambda + 2 mu in 3-D,
+ * 2 lambda + 2 mu in plane strain, E / (1 - nu) in plane stress; neo-Hookean: the same with mu = 2 C1, kappa = 2 / D1),
+ *   omega_e^2 = sum_q v_q (s_C + |sigma_q|_F) sum_a |grad_x N_a(xi_q)|^2 / m_a^e,   omega = sqrt(max_e omega_e^2),
+ *   dt_stable = 2 / omega.
+ * At u = 0 with a linear material omega >= the largest eigenfrequency of M_L^-1 K, by Cauchy-Schwarz on every element and
+ * because M and K are sums over the elements; the |sigma|_F term bounds the geometric stiffness in the same way.  At finite
+ * strain the material part is an ESTIMATE, not a proof -- the spatial tangent is not C -- and scale_factor is the margin.
+ * femcy_explicit_element_bound: *omega at vec[u_vec], stand-alone (synchronises, like femcy_explicit_stable_dt).
+ * femcy_explicit_auto_begin: t = 0 on the device, vec[ACC] = a_0 from vec[DOF] at load scale 1 (ramp = 0) or 0 (ramp = 1:
+ * the scale is t / T throughout), and the first increment h_0 = min(scale_factor 2 / omega(u_0), T).
+ * femcy_explicit_auto_advance: nsteps steps, enqueued without a host synchronisation.  A step is the element pass at the
+ * new state, the element bound + one tick of the clock (h_{n+1} = min(scale_factor 2 / omega, T - t), exactly 0 once t >= T
+ * or when omega is not finite; the step that takes the remainder sets t = T itself), and the node pass, which kicks with h_n
+ * and drifts with h_{n+1}.  A step with h = 0 writes nothing: a batch that overshoots T ends in no-ops, bit for bit.  A run
+ * split into several calls gives the bits of one call.
+ * femcy_explicit_auto_state: the one synchronising read-back: the clock t, the last and the smallest non-zero increment
+ * taken (0 before the first) and the number of real steps.
+ * Refused with FEMCY_EINVAL as above; also s_C, scale_factor or T not finite and positive, and _advance / _state before
+ * _begin. */
+int femcy_explicit_element_bound(femcy_ctx* ctx, int32_t id, int u_vec, double s_C, double* omega);
+int femcy_explicit_auto_begin(femcy_ctx* ctx, int32_t id, int rhs_vec, double s_C, double scale_factor, double T,
+                              int32_t ramp);
+int femcy_explicit_auto_advance(femcy_ctx* ctx, int32_t id, int rhs_vec, int32_t nsteps);
+int femcy_explicit_auto_state(femcy_ctx* ctx, int32_t id, double* t, double* h_last, double* h_min, int64_t* steps_done);
 /* compute_Ad (conjugateGradientSolver.py:53-58): vec[y] = K vec[x] */
 int femcy_spmv(femcy_ctx* ctx, int x_vec, int y_vec);
 /* ConjugateGradientSolver_rowMajor.re_init + solve (conjugateGradientSolver.py:32-51, 103-127):

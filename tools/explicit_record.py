@@ -11,6 +11,11 @@ thousandth of the run):
                        and write what the update reads and writes.  The ABI has no element-wise product, so a scalar stands
                        in for the inverse mass: the composition is a traffic and launch count, not the same numbers.
   force_eval_us        femcy_internal_force alone, the same way
+  auto_us_per_step     femcy_explicit_auto_advance(steps): the element pass, the element bound + the clock tick and
+                       k_explicit_node_auto per step (`*Dynamic, explicit, element by element`), T far away so that every
+                       step is a real one; auto_over_fixed_us = that minus fused_us_per_step of the same build
+  element_bound_us     femcy_explicit_element_bound alone, the same way (the bound kernel, the maximum and the read-back
+                       that synchronises every call)
 The increment is a tenth of the estimated stable one and the loads are zero, so the state stays at rest and every step does
 the same work.  No gate hangs on these numbers: the correctness tests decide, the record states what the fusion gained."""
 import argparse
@@ -80,13 +85,31 @@ def record(k, steps, reps, rho=7.85e-3):
         for _ in range(steps):
             ctx.internal_force(be.VEC_DOF, be.VEC_FORCE)
 
+    lam, mu = m["elastic"][0] * m["elastic"][1] / (1 + m["elastic"][1]) / (1 - 2 * m["elastic"][1]), m["elastic"][0] / 2 / (1 + m["elastic"][1])
+    s_C = 3 * lam + 2 * mu
+
+    def auto():
+        ctx.explicit_auto_advance(ex, steps, be.VEC_RHS)
+
+    def element_bound():
+        for _ in range(steps):
+            ctx.explicit_element_bound(ex, s_C, be.VEC_DOF)
+
     out = {"mesh": "C3D4 k=%d" % k, "elements": int(ctx.ne), "nodes": int(ctx.nn), "steps": steps, "reps": reps,
            "stable_dt": dt_stable, "omega_bound": omega, "dt": h}
-    for name, run in (("fused", fused), ("unfused", unfused), ("force_eval", force)):
+    for name, run in (("fused", fused), ("unfused", unfused), ("force_eval", force), ("auto", auto), ("element_bound", element_bound)):
+        if name == "auto":
+            ctx.explicit_auto_begin(ex, s_C, 0.1, 1.0e9 * dt_stable, False, be.VEC_RHS)
         us = _runs_us(ctx, run, steps, reps)
-        key = name + ("_us" if name == "force_eval" else "_us_per_step")
+        key = name + ("_us" if name in ("force_eval", "element_bound") else "_us_per_step")
         out[key], out[name + "_runs_us"] = float(np.median(us)), [round(x, 3) for x in us]
+        if name == "auto":
+            t, h_last, h_min, done = ctx.explicit_auto_state(ex)
+            out["auto_steps_done"], out["auto_dt"] = done, h_last
+            assert done == steps * (reps + 1) and h_last == h_min, (done, h_last, h_min)
     out["unfused_over_fused"] = out["unfused_us_per_step"] / out["fused_us_per_step"]
+    out["auto_over_fixed_us"] = out["auto_us_per_step"] - out["fused_us_per_step"]
+    out["element_stable_dt"] = 2.0 / ctx.explicit_element_bound(ex, s_C, be.VEC_DOF)
     out["state_at_rest"] = bool(ctx.vec_absmax(be.VEC_DOF) == 0.0)
     ctx.close()
     return out
