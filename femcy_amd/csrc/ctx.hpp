@@ -456,6 +456,7 @@ int launch_energy_sum(Ctx* c, double* total);
 int launch_assemble(Ctx* c);
 int launch_nodal_force(Ctx* c, double* d_f);
 int launch_neumann(Ctx* c, const Ctx::LoadSet& ls, double traction, bool along_normal, double* d_rhs, bool add);
+void launch_node_sum(Ctx* c, const double* d_src, double* d_m);   // d_m [nn] = node sums of d_src [ne][npe]; only enqueues
 int launch_body_weights(Ctx* c, const double* d_N, const uint8_t* d_mask_or_null, double* d_we, double* d_m);
 int launch_body_apply(Ctx* c, const double* d_m, const double* b, bool add, double* d_f);
 int launch_thermal_force(Ctx* c, const Ctx::Thermal& th, double* d_fe);
@@ -475,28 +476,27 @@ int launch_newmark_predict(Ctx* c, const double* u, const double* v, const doubl
 int launch_newmark_update(Ctx* c, const double* un, const double* u, double* v, double* a, double beta, double gamma,
                           double dt);
 // explicit dynamics (kernels_explicit.hip).  Lumped mass: element pass into d_me [ne][npe] (scratch of the caller), node sums
-// into d_m [nn].  launch_explicit_minv: d_minv [n] = 1 / m of the DOF's node.  launch_explicit_start / _node follow an element
-// pass that left d_fe (launch_geom with GEOM_FE): a_0, or one kick (+ the drift to the next state when drift is set) with the
-// node sums of d_fe never stored.  launch_explicit_drift: the first drift of a call.  All of them only enqueue.
+// into d_m [nn].  launch_explicit_minv: d_minv [n] = 1 / m of the DOF's node.  launch_explicit_node follows an element pass
+// that left d_fe (launch_geom with GEOM_FE): mode XN_START = a_0, XN_KICK = one kick, XN_KICK_DRIFT = kick + the drift to the
+// next state (element_math.hpp), with the node sums of d_fe never stored.  launch_explicit_drift: the first drift of a call.
+// Both take the increment h and the load scale from the arguments when d_clk is null (a fixed step), and from the device
+// clock of an automatic run otherwise (scale and h are then ignored).  All of them only enqueue.
 int launch_lumped_mass(Ctx* c, int32_t nq, const double* d_Nq, const double* d_dNq, const double* d_wq, double rho,
                        double* d_me, double* d_m);
 int launch_explicit_minv(Ctx* c, const double* d_m, double* d_minv);
-int launch_explicit_start(Ctx* c, const double* d_minv, const double* d_f, double scale);
-int launch_explicit_drift(Ctx* c, double h);
-int launch_explicit_node(Ctx* c, const double* d_minv, const double* d_f, double scale, double h, bool drift);
+int launch_explicit_drift(Ctx* c, const ExplicitClock* d_clk, double h);
+int launch_explicit_node(Ctx* c, const double* d_minv, const double* d_f, const ExplicitClock* d_clk, double scale, double h,
+                         int mode);
 int launch_explicit_energy(Ctx* c, const double* d_m, const double* d_v, double* out);   // 1/2 sum m v^2, fixed order
 // max over the rows i with minv_i != 0 of minv_i sum_j |K_ij| (Gershgorin bound on the spectrum of M_L^-1 K)
 int launch_rowabs_bound(Ctx* c, const double* d_minv, double* out);
 // element-by-element increment.  launch_explicit_bound: the workgroup maxima of omega_e^2 at d_u into d_part
-// [explicit_bound_partials(c)], recomputed from the mesh.  _bound_max: their maximum, fetched (synchronises).  _clock: their maximum + one tick of the device
-// clock.  _node_auto (mode 0 = a_0, 1 = kick, 2 = kick + drift) / _drift_auto: launch_explicit_node / _drift with the
-// increments and the load scale read from the clock.  All but _bound_max only enqueue.
+// [explicit_bound_partials(c)], recomputed from the mesh.  _bound_max: their maximum, fetched (synchronises).  _clock: their
+// maximum + one tick of the device clock.  All but _bound_max only enqueue.
 int explicit_bound_partials(const Ctx* c);
 int launch_explicit_bound(Ctx* c, const double* d_u, const double* d_me, double s_C, double* d_part);
 int launch_explicit_bound_max(Ctx* c, const double* d_part, double* out);
 int launch_explicit_clock(Ctx* c, const double* d_part, ExplicitClock* d_clk);
-int launch_explicit_node_auto(Ctx* c, const double* d_minv, const double* d_f, const ExplicitClock* d_clk, int mode);
-int launch_explicit_drift_auto(Ctx* c, const ExplicitClock* d_clk);
 // pos_space: x and y are in STORAGE order (entry p * dm + c belongs to the node at storage position p = slice * 64 + lane;
 // the padding lanes of the last slice hold zeros) -- the form the three-kernel PCG runs in since round 4
 int launch_spmv(Ctx* c, const double* d_x, double* d_y, double* d_partials, int* nblocks_out, bool pos_space = false);

@@ -936,6 +936,29 @@ FEMCY_HD void explicit_clock_tick(ExplicitClock& r, double omega2) {
     r.omega = omega;
 }
 
+// What the node pass of a step does: XN_START a_0 = minv (s f - f_int), nothing else is touched; XN_KICK the kick, a and v
+// are replaced; XN_KICK_DRIFT the kick, then u drifts to the next state with the new a and v.  Its numbers: the load scale
+// s, hh = half the increment of the kick, h and h2h = h^2 / 2 of the drift.
+enum { XN_START = 0, XN_KICK = 1, XN_KICK_DRIFT = 2 };
+struct ExplicitStep {
+    double s, hh, h, h2h;
+    bool drift;
+};
+// a fixed increment h: kick and drift by the same h (h > 0 in a step, 0 with XN_START)
+FEMCY_HD ExplicitStep explicit_step_fixed(double s, double h, int mode) {
+    return {s, 0.5 * h, h, 0.5 * h * h, mode == XN_KICK_DRIFT && h != 0.0};
+}
+// from the clock of an automatic run: the kick uses h_prev (the increment that led to the state being kicked), the drift
+// h_next and is skipped when that is 0; the scale is 1 (STEP) or t / T (RAMP) at the time t of the state being kicked.
+// false: h_prev = h_next = 0 in a step, nothing may be written -- the steps of a batch that overshoots T leave u, v, a bit
+// for bit alone.
+FEMCY_HD bool explicit_step_clock(const ExplicitClock& k, int mode, ExplicitStep& st) {
+    const double hp = k.h_prev, h = k.h_next;
+    if (mode != XN_START && hp == 0.0 && h == 0.0) return false;
+    st = {k.ramp ? k.t / k.T : 1.0, 0.5 * hp, h, 0.5 * h * h, mode == XN_KICK_DRIFT && h != 0.0};
+    return true;
+}
+
 // sum of 32 partial sums by the xor tree of half a wavefront, as lane 0 of k_nodal_force ends up with it: what the host
 // backend runs so that a node sum has the device's summation order
 inline double half_wave_tree(double (&p)[32]) {

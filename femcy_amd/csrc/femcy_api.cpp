@@ -1366,7 +1366,35 @@ int femcy_explicit_start(femcy_ctx* ctx, int32_t id, int rhs_vec, double scale) 
     FEMCY_REQUIRE(std::isfinite(scale), "femcy_explicit_start: the load scale is not finite");
     int rc = force_pass(c, c->d_vec[FEMCY_VEC_DOF]);
     if (rc) return rc;
-    return launch_explicit_start(c, ex.d_minv.get(), c->d_vec[rhs_vec], scale);
+    return launch_explicit_node(c, ex.d_minv.get(), c->d_vec[rhs_vec], nullptr, scale, 0.0, XN_START);
+}
+
+// nsteps steps from a started state: the first drift, then per step the element pass and the node pass (kick, and the drift
+// to the next state unless it is the last).  A fixed run (clk null) takes the increment dt and the load scale
+// scale0 + k dscale from the caller; an automatic one bounds the element frequencies and ticks its device clock between the
+// two passes, and the node pass reads both from the clock.
+static int explicit_steps(Ctx* c, const Ctx::Explicit& ex, ExplicitClock* clk, int rhs_vec, int32_t nsteps, double dt,
+                          double scale0, double dscale) {
+    if (nsteps == 0) return FEMCY_OK;
+    double* u = c->d_vec[FEMCY_VEC_DOF];
+    const double* me = c->lumped_masses[ex.lumped].d_me.get();
+    int rc = launch_explicit_drift(c, clk, dt);
+    for (int32_t k = 1; !rc && k <= nsteps; ++k) {
+        // the element pass of force_pass without its per-call copy of u: the lazy state is set once, below
+        if ((rc = launch_geom(c, u, GEOM_DSDX | GEOM_FE))) break;
+        if (clk) {
+            if ((rc = launch_explicit_bound(c, u, me, ex.s_C, ex.d_bpart.get()))) break;
+            if ((rc = launch_explicit_clock(c, ex.d_bpart.get(), clk))) break;
+        }
+        rc = launch_explicit_node(c, ex.d_minv.get(), c->d_vec[rhs_vec], clk, scale0 + k * dscale, dt,
+                                  k < nsteps ? XN_KICK_DRIFT : XN_KICK);
+    }
+    if (rc) return rc;
+    // post-processing reads "the stress of the last force evaluation": that of the last state (the last step did not drift)
+    FEMCY_HIP(hipMemcpyAsync(c->d_u_lazy, u, sizeof(double) * c->n, hipMemcpyDeviceToDevice, c->stream));
+    c->gp_lazy = true;
+    c->post_small = false;
+    return FEMCY_OK;
 }
 
 int femcy_explicit_advance(femcy_ctx* ctx, int32_t id, int rhs_vec, int32_t nsteps, double dt, double scale0, double dscale) {
@@ -1377,20 +1405,7 @@ int femcy_explicit_advance(femcy_ctx* ctx, int32_t id, int rhs_vec, int32_t nste
     FEMCY_REQUIRE(nsteps >= 0, "femcy_explicit_advance: %d steps", nsteps);
     FEMCY_REQUIRE(std::isfinite(dt) && dt > 0.0, "femcy_explicit_advance: the increment must be finite and positive");
     FEMCY_REQUIRE(std::isfinite(scale0) && std::isfinite(dscale), "femcy_explicit_advance: the load scale is not finite");
-    if (nsteps == 0) return FEMCY_OK;
-    double* u = c->d_vec[FEMCY_VEC_DOF];
-    int rc = launch_explicit_drift(c, dt);
-    for (int32_t k = 1; !rc && k <= nsteps; ++k) {
-        // the element pass of force_pass without its per-call copy of u: the lazy state is set once, below
-        if ((rc = launch_geom(c, u, GEOM_DSDX | GEOM_FE))) break;
-        rc = launch_explicit_node(c, ex.d_minv.get(), c->d_vec[rhs_vec], scale0 + k * dscale, dt, k < nsteps);
-    }
-    if (rc) return rc;
-    // post-processing reads "the stress of the last force evaluation": that of the last state (the last step did not drift)
-    FEMCY_HIP(hipMemcpyAsync(c->d_u_lazy, u, sizeof(double) * c->n, hipMemcpyDeviceToDevice, c->stream));
-    c->gp_lazy = true;
-    c->post_small = false;
-    return FEMCY_OK;
+    return explicit_steps(c, ex, nullptr, rhs_vec, nsteps, dt, scale0, dscale);
 }
 
 int femcy_explicit_kinetic_energy(femcy_ctx* ctx, int32_t id, int v_vec, double* out) {
@@ -1471,7 +1486,7 @@ int femcy_explicit_auto_begin(femcy_ctx* ctx, int32_t id, int rhs_vec, double s_
     if ((rc = force_pass(c, u))) return rc;
     if ((rc = launch_explicit_bound(c, u, c->lumped_masses[ex.lumped].d_me.get(), s_C, exm.d_bpart.get()))) return rc;
     if ((rc = launch_explicit_clock(c, exm.d_bpart.get(), exm.d_clock.get()))) return rc;   // t = 0, the first h
-    if ((rc = launch_explicit_node_auto(c, ex.d_minv.get(), c->d_vec[rhs_vec], exm.d_clock.get(), 0))) return rc;
+    if ((rc = launch_explicit_node(c, ex.d_minv.get(), c->d_vec[rhs_vec], exm.d_clock.get(), 0.0, 0.0, XN_START))) return rc;
     exm.auto_begun = true;
     exm.s_C = s_C;
     return FEMCY_OK;
@@ -1484,23 +1499,7 @@ int femcy_explicit_auto_advance(femcy_ctx* ctx, int32_t id, int rhs_vec, int32_t
     EXPLICIT_RHS_OR_FAIL("femcy_explicit_auto_advance", rhs_vec);
     FEMCY_REQUIRE(nsteps >= 0, "femcy_explicit_auto_advance: %d steps", nsteps);
     FEMCY_REQUIRE(ex.auto_begun, "femcy_explicit_auto_advance before femcy_explicit_auto_begin");
-    if (nsteps == 0) return FEMCY_OK;
-    double* u = c->d_vec[FEMCY_VEC_DOF];
-    ExplicitClock* clk = ex.d_clock.get();
-    const double* me = c->lumped_masses[ex.lumped].d_me.get();
-    const double s_C = ex.s_C;
-    int rc = launch_explicit_drift_auto(c, clk);
-    for (int32_t k = 1; !rc && k <= nsteps; ++k) {
-        if ((rc = launch_geom(c, u, GEOM_DSDX | GEOM_FE))) break;
-        if ((rc = launch_explicit_bound(c, u, me, s_C, ex.d_bpart.get()))) break;
-        if ((rc = launch_explicit_clock(c, ex.d_bpart.get(), clk))) break;
-        rc = launch_explicit_node_auto(c, ex.d_minv.get(), c->d_vec[rhs_vec], clk, k < nsteps ? 2 : 1);
-    }
-    if (rc) return rc;
-    FEMCY_HIP(hipMemcpyAsync(c->d_u_lazy, u, sizeof(double) * c->n, hipMemcpyDeviceToDevice, c->stream));
-    c->gp_lazy = true;
-    c->post_small = false;
-    return FEMCY_OK;
+    return explicit_steps(c, ex, ex.d_clock.get(), rhs_vec, nsteps, 0.0, 0.0, 0.0);
 }
 
 int femcy_explicit_auto_state(femcy_ctx* ctx, int32_t id, double* t, double* h_last, double* h_min, int64_t* steps_done) {

@@ -34,6 +34,7 @@
 #include "element_dispatch.hpp"
 #include "element_math.hpp"
 #include "load_row.hpp"
+#include "node_gather.hpp"
 
 namespace femcy {
 
@@ -1277,7 +1278,8 @@ __global__ void __launch_bounds__(256) k_assemble_pairs(int32_t nunits, int32_t 
 // nodeEles row that reads a gradient row, a stress tensor and a weight per (element, Gauss point).  Here the element
 // pass (k_geom) leaves fe[e][a][:] = sum_g gradN_a . sigma * vol, half a wavefront (32 lanes) owns a node and the lanes
 // are its incident elements: one dm-double load each, side by side instead of ~24 dependent load chains one after
-// the other; the dm partial sums are combined by a fixed xor-shuffle tree (deterministic) and lane 0 stores.
+// the other; the dm partial sums are combined by a fixed xor-shuffle tree (deterministic) and lane 0 stores.  The sum
+// itself is node_gather (node_gather.hpp), which the node pass of explicit dynamics runs too.
 template <int DM>
 __global__ void __launch_bounds__(256) k_nodal_force(int32_t nn, const int32_t* __restrict__ ne_ptr,
                                                      const int32_t* __restrict__ ne_idx,
@@ -1286,26 +1288,24 @@ __global__ void __launch_bounds__(256) k_nodal_force(int32_t nn, const int32_t* 
     const int32_t a = (int32_t)(t >> 5);
     const int sub = (int)(t & 31);
     double acc[DM];
-#pragma unroll
-    for (int i = 0; i < DM; ++i) acc[i] = 0.0;
-    if (a < nn) {
-        const int32_t k1 = ne_ptr[a + 1];
-        for (int32_t k = ne_ptr[a] + sub; k < k1; k += 32) {
-            const double* __restrict__ row = fe + (int64_t)ne_idx[k] * DM;      // ne_idx = e*npe + la: the row of fe
-            double rv[DM];
-            load_row<DM>(row, rv);
-#pragma unroll
-            for (int i = 0; i < DM; ++i) acc[i] += rv[i];
-        }
-    }
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1)
-#pragma unroll
-        for (int i = 0; i < DM; ++i) acc[i] += __shfl_xor(acc[i], o, 32);
+    node_gather<DM>(a, sub, nn, ne_ptr, ne_idx, fe, acc);
     if (a < nn && sub == 0) {
 #pragma unroll
         for (int i = 0; i < DM; ++i) f[(int64_t)a * DM + i] = acc[i];
     }
+}
+
+// the same node sum of a one-component record (ne_idx = e*npe + la is the position in src): the nodal weights of a body
+// load from k_body_weights' we, the lumped mass from k_lumped_elem's me
+__global__ void __launch_bounds__(256) k_node_sum(int32_t nn, const int32_t* __restrict__ ne_ptr,
+                                                  const int32_t* __restrict__ ne_idx, const double* __restrict__ src,
+                                                  double* __restrict__ m) {
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int32_t a = (int32_t)(t >> 5);
+    const int sub = (int)(t & 31);
+    double acc[1];
+    node_gather<1>(a, sub, nn, ne_ptr, ne_idx, src, acc);
+    if (a < nn && sub == 0) m[a] = acc[0];
 }
 
 // ------------------------------------------------------------------ Dirichlet 0/1 on the matrix
@@ -1543,25 +1543,6 @@ __global__ void __launch_bounds__(256) k_body_weights(int32_t ne, int32_t nGP, c
     block_store<NPE>(we_out + (int64_t)e0 * NPE, we, nvalid, stage_lds);
 }
 
-// owner-computes node sum in the style of k_nodal_force: half a wavefront per node, its lanes take the node's incident
-// elements (ne_idx = e*npe + la is the position in we) with stride 32, fixed xor tree, lane 0 stores: no atomics, the
-// same bits on every run
-__global__ void __launch_bounds__(256) k_body_gather(int32_t nn, const int32_t* __restrict__ ne_ptr,
-                                                     const int32_t* __restrict__ ne_idx,
-                                                     const double* __restrict__ we, double* __restrict__ m) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int32_t a = (int32_t)(t >> 5);
-    const int sub = (int)(t & 31);
-    double acc = 0.0;
-    if (a < nn) {
-        const int32_t k1 = ne_ptr[a + 1];
-        for (int32_t k = ne_ptr[a] + sub; k < k1; k += 32) acc += we[ne_idx[k]];
-    }
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 32);
-    if (a < nn && sub == 0) m[a] = acc;
-}
-
 // f[a*dm + i] = m[a] * b[i] (add: f += that); b travels in the kernel arguments.  The product is rounded before the
 // sum (no fused multiply-add), so that adding to a vector gives the bits of the two vectors added by the caller.
 template <int DM>
@@ -1730,11 +1711,17 @@ static int no_kernel(const Ctx* c, const char* what) {
 // node sums of per-element nodal forces d_fe [ne][npe][dm] into d_f [n]
 static void launch_node_sums(Ctx* c, const double* d_fe, double* d_f) {
     const int bs = 256;
-    const int grid = (int)(((int64_t)c->nn * 32 + bs - 1) / bs);   // 32 lanes per node
     dispatch_dm(c->dm, [&](auto dm) {
-        hipLaunchKernelGGL((k_nodal_force<dm()>), dim3(grid), dim3(bs), 0, c->stream, c->nn, c->d_ne_ptr, c->d_ne_idx, d_fe,
-                           d_f);
+        hipLaunchKernelGGL((k_nodal_force<dm()>), dim3(node_gather_grid(c->nn, bs)), dim3(bs), 0, c->stream, c->nn,
+                           c->d_ne_ptr, c->d_ne_idx, d_fe, d_f);
     });
+}
+
+// node sums of a one-component per-element record d_src [ne][npe] into d_m [nn]; only enqueues
+void launch_node_sum(Ctx* c, const double* d_src, double* d_m) {
+    const int bs = 256;
+    hipLaunchKernelGGL(k_node_sum, dim3(node_gather_grid(c->nn, bs)), dim3(bs), 0, c->stream, c->nn, c->d_ne_ptr,
+                       c->d_ne_idx, d_src, d_m);
 }
 
 int launch_geom(Ctx* c, const double* d_u, unsigned what) {
@@ -1766,11 +1753,7 @@ int launch_body_weights(Ctx* c, const double* d_N, const uint8_t* d_mask_or_null
         hipLaunchKernelGGL((k_body_weights<npe(), dm()>), dim3(grid), dim3(bs), 0, c->stream, c->ne, c->nGP, c->d_nodes,
                            c->d_elems, c->d_dN, d_N, c->d_w, d_mask_or_null, d_we);
     });
-    if (launched) {
-        const int64_t threads = (int64_t)c->nn * 32;
-        hipLaunchKernelGGL(k_body_gather, dim3((unsigned)((threads + bs - 1) / bs)), dim3(bs), 0, c->stream, c->nn,
-                           c->d_ne_ptr, c->d_ne_idx, d_we, d_m);
-    }
+    if (launched) launch_node_sum(c, d_we, d_m);
     timing_end(c, th);
     if (!launched) return no_kernel(c, "body-load");
     FEMCY_HIP(hipGetLastError());

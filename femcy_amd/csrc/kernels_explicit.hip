@@ -2,15 +2,19 @@
 // kinetic energy and the Gershgorin bound behind the stable increment.  The reference has no dynamics; the element pass of a
 // step is k_geom<..., true> of kernels_assembly.hip (launch_geom with GEOM_DSDX | GEOM_FE), which leaves fe[e][a][:].
 //
-// A step is two launches: that element pass and k_explicit_node, which does what femcy_internal_force's node gather and four
-// vector kernels would do in five launches -- the node sums of fe are never stored, and f, minv, a, v, u are read and a, v, u
-// written once per step, dm contiguous doubles per node each.
+// A step is two launches: that element pass and the node pass (explicit_node_pass), which does what femcy_internal_force's
+// node gather and four vector kernels would do in five launches -- the node sums of fe are never stored, and f, minv, a, v, u
+// are read and a, v, u written once per step, dm contiguous doubles per node each.  The node pass has two entry points that
+// differ only in where the step's numbers (ExplicitStep, element_math.hpp) come from: k_explicit_node takes them from the
+// host, k_explicit_node_auto from the device clock of an element-by-element run; k_explicit_drift / _auto likewise.  The
+// node sums of the lumped mass are k_node_sum of kernels_assembly.hip (launch_node_sum).
 #include <algorithm>
 #include <cmath>
 #include "ctx.hpp"
 #include "element_dispatch.hpp"
 #include "element_math.hpp"
 #include "load_row.hpp"
+#include "node_gather.hpp"
 
 namespace femcy {
 
@@ -35,24 +39,6 @@ __global__ void __launch_bounds__(XBS) k_lumped_elem(int32_t ne, int32_t nq, con
     for (int a = 0; a < NPE; ++a) me_out[(int64_t)e * NPE + a] = me[a];
 }
 
-// one-component node sum in the shape of k_nodal_force: half a wavefront per node, its lanes take the node's incident
-// elements (ne_idx = e * npe + la is the position in me) with stride 32 in ascending order, fixed xor tree, lane 0 stores
-__global__ void __launch_bounds__(XBS) k_lumped_gather(int32_t nn, const int32_t* __restrict__ ne_ptr,
-                                                       const int32_t* __restrict__ ne_idx,
-                                                       const double* __restrict__ me, double* __restrict__ m) {
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int32_t a = (int32_t)(t >> 5);
-    const int sub = (int)(t & 31);
-    double acc = 0.0;
-    if (a < nn) {
-        const int32_t k1 = ne_ptr[a + 1];
-        for (int32_t k = ne_ptr[a] + sub; k < k1; k += 32) acc += me[ne_idx[k]];
-    }
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 32);
-    if (a < nn && sub == 0) m[a] = acc;
-}
-
 // minv[a * DM + i] = 1 / m[a]; the constrained DOFs are zeroed afterwards by the DOF sets' own scatter
 template <int DM>
 __global__ void __launch_bounds__(XBS) k_explicit_minv(int64_t n, const double* __restrict__ m, double* __restrict__ minv) {
@@ -61,21 +47,17 @@ __global__ void __launch_bounds__(XBS) k_explicit_minv(int64_t n, const double* 
 }
 
 // ------------------------------------------------------------------------------------ node pass
-// Launch shape and gather of k_nodal_force: half a wavefront (32 lanes) owns a node, the lanes are its incident rows of fe
-// (one load_row each, stride 32 in ascending order), the dm partial sums are combined by the fixed xor tree.  The tree leaves
-// the same bits in all 32 lanes (every level adds the same two values in both lanes of a pair), so lane i < DM takes
-// component i: its f, minv, a, v, u are requested before the gather and DM neighbouring lanes read and write DM contiguous
-// doubles.  mode 0: a_0 = minv (s f - f_int), nothing else is touched (femcy_explicit_start); 1: kick, a and v are replaced;
-// 2: kick, then u drifts to the next state with the new a and v still in registers.  The arithmetic is explicit_kick /
-// explicit_drift of element_math.hpp, the functions k_explicit_drift and the host backend call.
-enum { XN_START = 0, XN_KICK = 1, XN_KICK_DRIFT = 2 };
+// Launch shape and gather of k_nodal_force (node_gather.hpp): half a wavefront (32 lanes) owns a node and sums its incident
+// rows of fe.  The tree leaves the same bits in all 32 lanes, so lane i < DM takes component i: its f, minv, a, v, u are
+// requested before the gather and DM neighbouring lanes read and write DM contiguous doubles.  What mode and st say is with
+// ExplicitStep in element_math.hpp; the arithmetic is explicit_kick / explicit_drift there, the functions the first drift
+// below and the host backend call.
 template <int DM>
-__global__ void __launch_bounds__(XBS) k_explicit_node(int32_t nn, const int32_t* __restrict__ ne_ptr,
-                                                       const int32_t* __restrict__ ne_idx,
-                                                       const double* __restrict__ fe, const double* __restrict__ f,
-                                                       const double* __restrict__ minv, double s, double h, double hh,
-                                                       double h2h, int mode, double* __restrict__ u,
-                                                       double* __restrict__ v, double* __restrict__ acc_vec) {
+__device__ __forceinline__ void explicit_node_pass(int32_t nn, const int32_t* __restrict__ ne_ptr,
+                                                   const int32_t* __restrict__ ne_idx, const double* __restrict__ fe,
+                                                   const double* __restrict__ f, const double* __restrict__ minv,
+                                                   const ExplicitStep& st, int mode, double* __restrict__ u,
+                                                   double* __restrict__ v, double* __restrict__ acc_vec) {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int32_t a = (int32_t)(t >> 5);
     const int sub = (int)(t & 31);
@@ -89,38 +71,60 @@ __global__ void __launch_bounds__(XBS) k_explicit_node(int32_t nn, const int32_t
             ai = acc_vec[i];
             vi = v[i];
         }
-        if (mode == XN_KICK_DRIFT) ui = u[i];
+        if (st.drift) ui = u[i];
     }
     double acc[DM];
-#pragma unroll
-    for (int c = 0; c < DM; ++c) acc[c] = 0.0;
-    if (a < nn) {
-        const int32_t k1 = ne_ptr[a + 1];
-        for (int32_t k = ne_ptr[a] + sub; k < k1; k += 32) {
-            double rv[DM];
-            load_row<DM>(fe + (int64_t)ne_idx[k] * DM, rv);                     // ne_idx = e*npe + la: the row of fe
-#pragma unroll
-            for (int c = 0; c < DM; ++c) acc[c] += rv[c];
-        }
-    }
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1)
-#pragma unroll
-        for (int c = 0; c < DM; ++c) acc[c] += __shfl_xor(acc[c], o, 32);
+    node_gather<DM>(a, sub, nn, ne_ptr, ne_idx, fe, acc);
     if (!mine) return;
     const double fint = sub == 0 ? acc[0] : (sub == 1 ? acc[1] : acc[DM - 1]);
-    explicit_kick(mi, s, fi, fint, hh, vi, ai);
+    explicit_kick(mi, st.s, fi, fint, st.hh, vi, ai);
     acc_vec[i] = ai;
     if (mode == XN_START) return;
     v[i] = vi;
-    if (mode == XN_KICK_DRIFT) u[i] = explicit_drift(ui, vi, ai, h, h2h);
+    if (st.drift) u[i] = explicit_drift(ui, vi, ai, st.h, st.h2h);
+}
+
+// a fixed step: the host filled st (explicit_step_fixed)
+template <int DM>
+__global__ void __launch_bounds__(XBS) k_explicit_node(int32_t nn, const int32_t* __restrict__ ne_ptr,
+                                                       const int32_t* __restrict__ ne_idx,
+                                                       const double* __restrict__ fe, const double* __restrict__ f,
+                                                       const double* __restrict__ minv, ExplicitStep st, int mode,
+                                                       double* __restrict__ u, double* __restrict__ v,
+                                                       double* __restrict__ acc_vec) {
+    explicit_node_pass<DM>(nn, ne_ptr, ne_idx, fe, f, minv, st, mode, u, v, acc_vec);
+}
+
+// a step of an automatic run: st from the device clock, which may say that nothing is written (explicit_step_clock)
+template <int DM>
+__global__ void __launch_bounds__(XBS) k_explicit_node_auto(int32_t nn, const int32_t* __restrict__ ne_ptr,
+                                                            const int32_t* __restrict__ ne_idx,
+                                                            const double* __restrict__ fe, const double* __restrict__ f,
+                                                            const double* __restrict__ minv,
+                                                            const ExplicitClock* __restrict__ clk, int mode,
+                                                            double* __restrict__ u, double* __restrict__ v,
+                                                            double* __restrict__ acc_vec) {
+    ExplicitStep st;
+    if (!explicit_step_clock(*clk, mode, st)) return;
+    explicit_node_pass<DM>(nn, ne_ptr, ne_idx, fe, f, minv, st, mode, u, v, acc_vec);
 }
 
 // the first drift of a call: u += h v + (h^2 / 2) a from memory, by the function the node pass applies to its registers
-__global__ void __launch_bounds__(XBS) k_explicit_drift(int64_t n, double h, double h2h, const double* __restrict__ v,
-                                                        const double* __restrict__ a, double* __restrict__ u) {
+__device__ __forceinline__ void explicit_first_drift(int64_t n, double h, double h2h, const double* __restrict__ v,
+                                                     const double* __restrict__ a, double* __restrict__ u) {
     const int64_t i = (int64_t)blockIdx.x * XBS + threadIdx.x;
     if (i < n) u[i] = explicit_drift(u[i], v[i], a[i], h, h2h);
+}
+__global__ void __launch_bounds__(XBS) k_explicit_drift(int64_t n, double h, double h2h, const double* __restrict__ v,
+                                                        const double* __restrict__ a, double* __restrict__ u) {
+    explicit_first_drift(n, h, h2h, v, a, u);
+}
+// by h_next of the device clock; h_next = 0 writes nothing
+__global__ void __launch_bounds__(XBS) k_explicit_drift_auto(int64_t n, const ExplicitClock* __restrict__ clk,
+                                                             const double* __restrict__ v, const double* __restrict__ a,
+                                                             double* __restrict__ u) {
+    const double h = clk->h_next;
+    if (h != 0.0) explicit_first_drift(n, h, 0.5 * h * h, v, a, u);
 }
 
 // ------------------------------------------------------------------------------------ reductions
@@ -158,13 +162,18 @@ __global__ void __launch_bounds__(XBS) k_explicit_energy(int32_t nn, const doubl
     if (threadIdx.x == 0) part[blockIdx.x] = r;
 }
 
-// one workgroup: thread t takes the partials t, t + 256, ... in ascending order, then the same tree
+// np partials -> one, by one workgroup: thread t takes the partials t, t + 256, ... in ascending order, then the same tree
+template <bool MAX>
+__device__ __forceinline__ double reduce_partials(int np, const double* __restrict__ part, double* sm) {
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < np; i += XBS) acc = MAX ? fmax(acc, part[i]) : acc + part[i];
+    return block_reduce<MAX>(acc, sm);
+}
+
 template <bool MAX>
 __global__ void __launch_bounds__(XBS) k_explicit_final(int np, const double* __restrict__ part, double* __restrict__ out) {
     __shared__ double sm[XBS / 64];
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < np; i += XBS) acc = MAX ? fmax(acc, part[i]) : acc + part[i];
-    const double r = block_reduce<MAX>(acc, sm);
+    const double r = reduce_partials<MAX>(np, part, sm);
     if (threadIdx.x == 0) *out = r;
 }
 
@@ -237,85 +246,16 @@ __global__ void __launch_bounds__(XBS) k_explicit_bound(int32_t ne, int32_t nGP,
     if (threadIdx.x == 0) part[blockIdx.x] = r;
 }
 
-// one workgroup: the maximum of the np partials (thread t takes t, t + 256, ... in ascending order, then the tree), and one
-// tick of the clock by thread 0 (element_math.hpp: explicit_clock_tick)
+// one workgroup: the maximum of the np partials (reduce_partials), and one tick of the clock by thread 0 (element_math.hpp:
+// explicit_clock_tick)
 __global__ void __launch_bounds__(XBS) k_explicit_clock(int np, const double* __restrict__ part, ExplicitClock* __restrict__ clk) {
     __shared__ double sm[XBS / 64];
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < np; i += XBS) acc = fmax(acc, part[i]);
-    const double r = block_reduce<true>(acc, sm);
+    const double r = reduce_partials<true>(np, part, sm);
     if (threadIdx.x == 0) {
         ExplicitClock c = *clk;
         explicit_clock_tick(c, r);
         *clk = c;
     }
-}
-
-// k_explicit_node with h, h / 2, h^2 / 2 and the load scale read from the device clock instead of the kernel arguments: the
-// kick uses h_prev (the increment that led to the state being kicked), the drift h_next; the scale is 1 (STEP) or t / T
-// (RAMP) at the time t of the state being kicked.  With h_prev = h_next = 0 (mode != XN_START) nothing is written: the steps
-// of a batch that overshoots T leave u, v, a bit for bit alone.  The drift is skipped when h_next = 0.
-template <int DM>
-__global__ void __launch_bounds__(XBS) k_explicit_node_auto(int32_t nn, const int32_t* __restrict__ ne_ptr,
-                                                            const int32_t* __restrict__ ne_idx,
-                                                            const double* __restrict__ fe, const double* __restrict__ f,
-                                                            const double* __restrict__ minv,
-                                                            const ExplicitClock* __restrict__ clk, int mode,
-                                                            double* __restrict__ u, double* __restrict__ v,
-                                                            double* __restrict__ acc_vec) {
-    const double hp = clk->h_prev, h = clk->h_next;
-    if (mode != XN_START && hp == 0.0 && h == 0.0) return;
-    const double s = clk->ramp ? clk->t / clk->T : 1.0;
-    const double hh = 0.5 * hp, h2h = 0.5 * h * h;
-    const bool drift = mode == XN_KICK_DRIFT && h != 0.0;
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int32_t a = (int32_t)(t >> 5);
-    const int sub = (int)(t & 31);
-    const bool mine = a < nn && sub < DM;
-    const int64_t i = (int64_t)a * DM + sub;
-    double fi = 0.0, mi = 0.0, ai = 0.0, vi = 0.0, ui = 0.0;
-    if (mine) {
-        fi = f[i];
-        mi = minv[i];
-        if (mode != XN_START) {
-            ai = acc_vec[i];
-            vi = v[i];
-        }
-        if (drift) ui = u[i];
-    }
-    double acc[DM];
-#pragma unroll
-    for (int c = 0; c < DM; ++c) acc[c] = 0.0;
-    if (a < nn) {
-        const int32_t k1 = ne_ptr[a + 1];
-        for (int32_t k = ne_ptr[a] + sub; k < k1; k += 32) {
-            double rv[DM];
-            load_row<DM>(fe + (int64_t)ne_idx[k] * DM, rv);
-#pragma unroll
-            for (int c = 0; c < DM; ++c) acc[c] += rv[c];
-        }
-    }
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1)
-#pragma unroll
-        for (int c = 0; c < DM; ++c) acc[c] += __shfl_xor(acc[c], o, 32);
-    if (!mine) return;
-    const double fint = sub == 0 ? acc[0] : (sub == 1 ? acc[1] : acc[DM - 1]);
-    explicit_kick(mi, s, fi, fint, hh, vi, ai);
-    acc_vec[i] = ai;
-    if (mode == XN_START) return;
-    v[i] = vi;
-    if (drift) u[i] = explicit_drift(ui, vi, ai, h, h2h);
-}
-
-// the first drift of an automatic call, by h_next of the device clock; h_next = 0 writes nothing
-__global__ void __launch_bounds__(XBS) k_explicit_drift_auto(int64_t n, const ExplicitClock* __restrict__ clk,
-                                                             const double* __restrict__ v, const double* __restrict__ a,
-                                                             double* __restrict__ u) {
-    const double h = clk->h_next;
-    if (h == 0.0) return;
-    const int64_t i = (int64_t)blockIdx.x * XBS + threadIdx.x;
-    if (i < n) u[i] = explicit_drift(u[i], v[i], a[i], h, 0.5 * h * h);
 }
 
 // ------------------------------------------------------------------------------- host launchers
@@ -331,11 +271,7 @@ int launch_lumped_mass(Ctx* c, int32_t nq, const double* d_Nq, const double* d_d
         hipLaunchKernelGGL((k_lumped_elem<npe(), dm()>), dim3(grid), dim3(XBS), 0, c->stream, c->ne, nq, c->d_nodes,
                            c->d_elems, d_Nq, d_dNq, d_wq, rho, d_me);
     });
-    if (launched) {
-        const int64_t threads = (int64_t)c->nn * 32;
-        hipLaunchKernelGGL(k_lumped_gather, dim3((unsigned)((threads + XBS - 1) / XBS)), dim3(XBS), 0, c->stream, c->nn,
-                           c->d_ne_ptr, c->d_ne_idx, d_me, d_m);
-    }
+    if (launched) launch_node_sum(c, d_me, d_m);
     timing_end(c, tm);
     if (!launched) {
         set_error("no lumped-mass kernel instantiated for npe=%d dm=%d", c->npe, c->dm);
@@ -354,32 +290,32 @@ int launch_explicit_minv(Ctx* c, const double* d_m, double* d_minv) {
     return FEMCY_OK;
 }
 
-static int launch_node(Ctx* c, const double* d_minv, const double* d_f, double scale, double h, int mode) {
-    const unsigned grid = (unsigned)(((int64_t)c->nn * 32 + XBS - 1) / XBS);   // 32 lanes per node
+int launch_explicit_node(Ctx* c, const double* d_minv, const double* d_f, const ExplicitClock* d_clk, double scale, double h,
+                         int mode) {
+    const unsigned grid = node_gather_grid(c->nn, XBS);
+    double *u = c->d_vec[FEMCY_VEC_DOF], *v = c->d_vec[FEMCY_VEC_VEL], *a = c->d_vec[FEMCY_VEC_ACC];
     size_t tm = timing_begin(c, T_FORCE);
     dispatch_dm(c->dm, [&](auto dm) {
-        hipLaunchKernelGGL((k_explicit_node<dm()>), dim3(grid), dim3(XBS), 0, c->stream, c->nn, c->d_ne_ptr, c->d_ne_idx,
-                           c->d_fe, d_f, d_minv, scale, h, 0.5 * h, 0.5 * h * h, mode, c->d_vec[FEMCY_VEC_DOF],
-                           c->d_vec[FEMCY_VEC_VEL], c->d_vec[FEMCY_VEC_ACC]);
+        if (d_clk)
+            hipLaunchKernelGGL((k_explicit_node_auto<dm()>), dim3(grid), dim3(XBS), 0, c->stream, c->nn, c->d_ne_ptr,
+                               c->d_ne_idx, c->d_fe, d_f, d_minv, d_clk, mode, u, v, a);
+        else
+            hipLaunchKernelGGL((k_explicit_node<dm()>), dim3(grid), dim3(XBS), 0, c->stream, c->nn, c->d_ne_ptr, c->d_ne_idx,
+                               c->d_fe, d_f, d_minv, explicit_step_fixed(scale, h, mode), mode, u, v, a);
     });
     timing_end(c, tm);
     FEMCY_HIP(hipGetLastError());
     return FEMCY_OK;
 }
 
-int launch_explicit_start(Ctx* c, const double* d_minv, const double* d_f, double scale) {
-    return launch_node(c, d_minv, d_f, scale, 0.0, XN_START);
-}
-
-int launch_explicit_node(Ctx* c, const double* d_minv, const double* d_f, double scale, double h, bool drift) {
-    return launch_node(c, d_minv, d_f, scale, h, drift ? XN_KICK_DRIFT : XN_KICK);
-}
-
-int launch_explicit_drift(Ctx* c, double h) {
+int launch_explicit_drift(Ctx* c, const ExplicitClock* d_clk, double h) {
     const unsigned grid = (unsigned)((c->n + XBS - 1) / XBS);
+    double *u = c->d_vec[FEMCY_VEC_DOF], *v = c->d_vec[FEMCY_VEC_VEL], *a = c->d_vec[FEMCY_VEC_ACC];
     size_t tm = timing_begin(c, T_FORCE);
-    hipLaunchKernelGGL(k_explicit_drift, dim3(grid), dim3(XBS), 0, c->stream, c->n, h, 0.5 * h * h,
-                       c->d_vec[FEMCY_VEC_VEL], c->d_vec[FEMCY_VEC_ACC], c->d_vec[FEMCY_VEC_DOF]);
+    if (d_clk)
+        hipLaunchKernelGGL(k_explicit_drift_auto, dim3(grid), dim3(XBS), 0, c->stream, c->n, d_clk, v, a, u);
+    else
+        hipLaunchKernelGGL(k_explicit_drift, dim3(grid), dim3(XBS), 0, c->stream, c->n, h, 0.5 * h * h, v, a, u);
     timing_end(c, tm);
     FEMCY_HIP(hipGetLastError());
     return FEMCY_OK;
@@ -445,29 +381,6 @@ int launch_explicit_bound_max(Ctx* c, const double* d_part, double* out) {
 
 int launch_explicit_clock(Ctx* c, const double* d_part, ExplicitClock* d_clk) {
     hipLaunchKernelGGL(k_explicit_clock, dim3(1), dim3(XBS), 0, c->stream, explicit_bound_partials(c), d_part, d_clk);
-    FEMCY_HIP(hipGetLastError());
-    return FEMCY_OK;
-}
-
-int launch_explicit_node_auto(Ctx* c, const double* d_minv, const double* d_f, const ExplicitClock* d_clk, int mode) {
-    const unsigned grid = (unsigned)(((int64_t)c->nn * 32 + XBS - 1) / XBS);   // 32 lanes per node
-    size_t tm = timing_begin(c, T_FORCE);
-    dispatch_dm(c->dm, [&](auto dm) {
-        hipLaunchKernelGGL((k_explicit_node_auto<dm()>), dim3(grid), dim3(XBS), 0, c->stream, c->nn, c->d_ne_ptr,
-                           c->d_ne_idx, c->d_fe, d_f, d_minv, d_clk, mode, c->d_vec[FEMCY_VEC_DOF], c->d_vec[FEMCY_VEC_VEL],
-                           c->d_vec[FEMCY_VEC_ACC]);
-    });
-    timing_end(c, tm);
-    FEMCY_HIP(hipGetLastError());
-    return FEMCY_OK;
-}
-
-int launch_explicit_drift_auto(Ctx* c, const ExplicitClock* d_clk) {
-    const unsigned grid = (unsigned)((c->n + XBS - 1) / XBS);
-    size_t tm = timing_begin(c, T_FORCE);
-    hipLaunchKernelGGL(k_explicit_drift_auto, dim3(grid), dim3(XBS), 0, c->stream, c->n, d_clk, c->d_vec[FEMCY_VEC_VEL],
-                       c->d_vec[FEMCY_VEC_ACC], c->d_vec[FEMCY_VEC_DOF]);
-    timing_end(c, tm);
     FEMCY_HIP(hipGetLastError());
     return FEMCY_OK;
 }

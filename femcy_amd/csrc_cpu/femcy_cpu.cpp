@@ -1325,8 +1325,17 @@ int femcy_newmark_update(femcy_ctx* ctx, int u_new_vec, int u_vec, int v_vec, in
 // ------------------------------------------------------------------------------ explicit dynamics
 }  // extern "C"
 namespace {
-// the two passes of the device's femcy_lumped_mass_create (csrc/element_math.hpp: lumped_element), the node sums in the
-// order of its half-wavefront gather: partial sums of every 32nd incident element, combined by half_wave_tree
+// out[0..w) = the sum of node a's incident rows of src (w doubles each, w <= 3) in the order of the device's half-wavefront
+// gather (csrc/node_gather.hpp): partial sums of every 32nd incident row, combined by half_wave_tree
+void node_sum(const femcy_ctx* c, int32_t a, const double* src, int w, double* out) {
+    double p[3][32] = {{0.0}};
+    const int32_t k0 = c->ne_ptr[a];
+    for (int32_t k = k0; k < c->ne_ptr[a + 1]; ++k)
+        for (int i = 0; i < w; ++i) p[i][(k - k0) & 31] += src[(int64_t)c->ne_idx[k] * w + i];
+    for (int i = 0; i < w; ++i) out[i] = half_wave_tree(p[i]);
+}
+
+// the two passes of the device's femcy_lumped_mass_create (csrc/element_math.hpp: lumped_element, then node_sum)
 template <int NPE, int DM>
 void lumped_mass(femcy_ctx* c, int32_t nq, const double* Nq, const double* dNq, const double* wq, double rho,
                  std::vector<double>& m, std::vector<double>& me) {
@@ -1341,59 +1350,26 @@ void lumped_mass(femcy_ctx* c, int32_t nq, const double* Nq, const double* dNq, 
     }
     m.assign((size_t)c->nn, 0.0);
 #pragma omp parallel for schedule(static)
-    for (int32_t a = 0; a < c->nn; ++a) {
-        double p[32] = {0.0};
-        for (int32_t k = c->ne_ptr[a]; k < c->ne_ptr[a + 1]; ++k) p[(k - c->ne_ptr[a]) & 31] += me[c->ne_idx[k]];
-        m[a] = half_wave_tree(p);
-    }
+    for (int32_t a = 0; a < c->nn; ++a) node_sum(c, a, me.data(), 1, &m[a]);
 }
 
-// the device's k_explicit_node on the host: node sums of fe in the order of its gather, then explicit_kick / explicit_drift
-// (csrc/element_math.hpp).  mode 0: a_0 only; 1: kick; 2: kick + drift
-void explicit_node(femcy_ctx* c, const Explicit& ex, const double* f, double s, double h, int mode) {
+// the device's node pass (kernels_explicit.hip: explicit_node_pass) on the host: node sums of fe in the order of its gather,
+// then explicit_kick / explicit_drift; what mode and st say is with ExplicitStep in csrc/element_math.hpp
+void explicit_node(femcy_ctx* c, const Explicit& ex, const double* f, const ExplicitStep& st, int mode) {
     const int dm = c->dm;
     double *u = c->vec[FEMCY_VEC_DOF].data(), *v = c->vec[FEMCY_VEC_VEL].data(), *acc = c->vec[FEMCY_VEC_ACC].data();
-    const double hh = 0.5 * h, h2h = 0.5 * h * h;
 #pragma omp parallel for schedule(static)
     for (int32_t a = 0; a < c->nn; ++a) {
-        double p[3][32] = {{0.0}};
-        for (int32_t k = c->ne_ptr[a]; k < c->ne_ptr[a + 1]; ++k)
-            for (int i = 0; i < dm; ++i) p[i][(k - c->ne_ptr[a]) & 31] += c->fe[(int64_t)c->ne_idx[k] * dm + i];
+        double fint[3];
+        node_sum(c, a, c->fe.data(), dm, fint);
         for (int i = 0; i < dm; ++i) {
             const int64_t q = (int64_t)a * dm + i;
-            const double fint = half_wave_tree(p[i]);
-            double vi = mode ? v[q] : 0.0, ai = mode ? acc[q] : 0.0;
-            explicit_kick(ex.minv[q], s, f[q], fint, hh, vi, ai);
+            double vi = mode != XN_START ? v[q] : 0.0, ai = mode != XN_START ? acc[q] : 0.0;
+            explicit_kick(ex.minv[q], st.s, f[q], fint[i], st.hh, vi, ai);
             acc[q] = ai;
-            if (!mode) continue;
+            if (mode == XN_START) continue;
             v[q] = vi;
-            if (mode == 2) u[q] = explicit_drift(u[q], vi, ai, h, h2h);
-        }
-    }
-}
-
-// the device's k_explicit_node_auto: the increments and the load scale come from the clock; h_prev = h_next = 0 writes nothing
-void explicit_node_auto(femcy_ctx* c, const Explicit& ex, const double* f, int mode) {
-    const ExplicitClock& k = ex.clock;
-    if (mode && k.h_prev == 0.0 && k.h_next == 0.0) return;
-    const int dm = c->dm;
-    double *u = c->vec[FEMCY_VEC_DOF].data(), *v = c->vec[FEMCY_VEC_VEL].data(), *acc = c->vec[FEMCY_VEC_ACC].data();
-    const double s = k.ramp ? k.t / k.T : 1.0, h = k.h_next, hh = 0.5 * k.h_prev, h2h = 0.5 * h * h;
-    const bool drift = mode == 2 && h != 0.0;
-#pragma omp parallel for schedule(static)
-    for (int32_t a = 0; a < c->nn; ++a) {
-        double p[3][32] = {{0.0}};
-        for (int32_t q = c->ne_ptr[a]; q < c->ne_ptr[a + 1]; ++q)
-            for (int i = 0; i < dm; ++i) p[i][(q - c->ne_ptr[a]) & 31] += c->fe[(int64_t)c->ne_idx[q] * dm + i];
-        for (int i = 0; i < dm; ++i) {
-            const int64_t q = (int64_t)a * dm + i;
-            const double fint = half_wave_tree(p[i]);
-            double vi = mode ? v[q] : 0.0, ai = mode ? acc[q] : 0.0;
-            explicit_kick(ex.minv[q], s, f[q], fint, hh, vi, ai);
-            acc[q] = ai;
-            if (!mode) continue;
-            v[q] = vi;
-            if (drift) u[q] = explicit_drift(u[q], vi, ai, h, h2h);
+            if (st.drift) u[q] = explicit_drift(u[q], vi, ai, st.h, st.h2h);
         }
     }
 }
@@ -1438,6 +1414,38 @@ double block_reduce_sum(double (&x)[256]) {
         r = w ? r + y[0] : y[0];
     }
     return r;
+}
+
+// nsteps steps from a started state, as the device's explicit_steps runs them: the first drift, then per step the element
+// pass and the node pass.  A fixed run (clock null) takes dt and the load scale scale0 + k dscale from the caller; an
+// automatic one bounds the element frequencies and ticks its clock between the two passes, which then gives both.
+int explicit_steps(femcy_ctx* c, const Explicit& ex, ExplicitClock* clock, int rhs_vec, int32_t nsteps, double dt,
+                   double scale0, double dscale) {
+    if (nsteps == 0) return FEMCY_OK;
+    double* u = c->vec[FEMCY_VEC_DOF].data();
+    const double *v = c->vec[FEMCY_VEC_VEL].data(), *a = c->vec[FEMCY_VEC_ACC].data();
+    if (const double h = clock ? clock->h_next : dt; h != 0.0) {
+        const double h2h = 0.5 * h * h;
+#pragma omp parallel for schedule(static)
+        for (int64_t i = 0; i < c->n; ++i) u[i] = explicit_drift(u[i], v[i], a[i], h, h2h);
+    }
+    for (int32_t k = 1; k <= nsteps; ++k) {
+        const bool last = k == nsteps;      // F and sigma of the last state stay behind for post-processing
+        const int mode = last ? XN_KICK : XN_KICK_DRIFT;
+        geom(c, u, last ? (GEOM_DSDX | GEOM_F | GEOM_SIGMA | GEOM_FE) : (GEOM_DSDX | GEOM_FE));
+        ExplicitStep st;
+        if (clock) {
+            double w2 = 0.0;
+            int rc = element_bound_any(c, ex, u, clock->s_C, &w2);
+            if (rc) return rc;
+            explicit_clock_tick(*clock, w2);
+            if (!explicit_step_clock(*clock, mode, st)) continue;
+        } else {
+            st = explicit_step_fixed(scale0 + k * dscale, dt, mode);
+        }
+        explicit_node(c, ex, c->vec[rhs_vec].data(), st, mode);
+    }
+    return FEMCY_OK;
 }
 }  // namespace
 extern "C" {
@@ -1502,7 +1510,7 @@ int femcy_explicit_start(femcy_ctx* ctx, int32_t id, int rhs_vec, double scale) 
     EXPLICIT_RHS_OR_FAIL("femcy_explicit_start", rhs_vec);
     REQUIRE(std::isfinite(scale), "femcy_explicit_start: the load scale is not finite");
     geom(c, c->vec[FEMCY_VEC_DOF].data(), GEOM_DSDX | GEOM_F | GEOM_SIGMA | GEOM_FE);
-    explicit_node(c, ex, c->vec[rhs_vec].data(), scale, 0.0, 0);
+    explicit_node(c, ex, c->vec[rhs_vec].data(), explicit_step_fixed(scale, 0.0, XN_START), XN_START);
     return FEMCY_OK;
 }
 
@@ -1514,18 +1522,7 @@ int femcy_explicit_advance(femcy_ctx* ctx, int32_t id, int rhs_vec, int32_t nste
     REQUIRE(nsteps >= 0, "femcy_explicit_advance: %d steps", nsteps);
     REQUIRE(std::isfinite(dt) && dt > 0.0, "femcy_explicit_advance: the increment must be finite and positive");
     REQUIRE(std::isfinite(scale0) && std::isfinite(dscale), "femcy_explicit_advance: the load scale is not finite");
-    if (nsteps == 0) return FEMCY_OK;
-    double* u = c->vec[FEMCY_VEC_DOF].data();
-    const double *v = c->vec[FEMCY_VEC_VEL].data(), *a = c->vec[FEMCY_VEC_ACC].data();
-    const double h2h = 0.5 * dt * dt;
-#pragma omp parallel for schedule(static)
-    for (int64_t i = 0; i < c->n; ++i) u[i] = explicit_drift(u[i], v[i], a[i], dt, h2h);
-    for (int32_t k = 1; k <= nsteps; ++k) {
-        const bool last = k == nsteps;      // F and sigma of the last state stay behind for post-processing
-        geom(c, u, last ? (GEOM_DSDX | GEOM_F | GEOM_SIGMA | GEOM_FE) : (GEOM_DSDX | GEOM_FE));
-        explicit_node(c, ex, c->vec[rhs_vec].data(), scale0 + k * dscale, dt, last ? 1 : 2);
-    }
-    return FEMCY_OK;
+    return explicit_steps(c, ex, nullptr, rhs_vec, nsteps, dt, scale0, dscale);
 }
 
 int femcy_explicit_kinetic_energy(femcy_ctx* ctx, int32_t id, int v_vec, double* out) {
@@ -1622,7 +1619,9 @@ int femcy_explicit_auto_begin(femcy_ctx* ctx, int32_t id, int rhs_vec, double s_
     exm.clock.ramp = ramp ? 1 : 0;
     geom(c, u, GEOM_DSDX | GEOM_F | GEOM_SIGMA | GEOM_FE);
     explicit_clock_tick(exm.clock, w2);                        // t = 0, the first h
-    explicit_node_auto(c, exm, c->vec[rhs_vec].data(), 0);
+    ExplicitStep st;
+    explicit_step_clock(exm.clock, XN_START, st);              // always something to do at the start
+    explicit_node(c, exm, c->vec[rhs_vec].data(), st, XN_START);
     exm.auto_begun = true;
     return FEMCY_OK;
 }
@@ -1634,25 +1633,7 @@ int femcy_explicit_auto_advance(femcy_ctx* ctx, int32_t id, int rhs_vec, int32_t
     EXPLICIT_RHS_OR_FAIL("femcy_explicit_auto_advance", rhs_vec);
     REQUIRE(nsteps >= 0, "femcy_explicit_auto_advance: %d steps", nsteps);
     REQUIRE(ex.auto_begun, "femcy_explicit_auto_advance before femcy_explicit_auto_begin");
-    if (nsteps == 0) return FEMCY_OK;
-    Explicit& exm = c->explicits[id];
-    double* u = c->vec[FEMCY_VEC_DOF].data();
-    const double *v = c->vec[FEMCY_VEC_VEL].data(), *a = c->vec[FEMCY_VEC_ACC].data();
-    if (const double h = exm.clock.h_next; h != 0.0) {
-        const double h2h = 0.5 * h * h;
-#pragma omp parallel for schedule(static)
-        for (int64_t i = 0; i < c->n; ++i) u[i] = explicit_drift(u[i], v[i], a[i], h, h2h);
-    }
-    for (int32_t k = 1; k <= nsteps; ++k) {
-        const bool last = k == nsteps;      // F and sigma of the last state stay behind for post-processing
-        geom(c, u, last ? (GEOM_DSDX | GEOM_F | GEOM_SIGMA | GEOM_FE) : (GEOM_DSDX | GEOM_FE));
-        double w2 = 0.0;
-        int rc = element_bound_any(c, exm, u, exm.clock.s_C, &w2);
-        if (rc) return rc;
-        explicit_clock_tick(exm.clock, w2);
-        explicit_node_auto(c, exm, c->vec[rhs_vec].data(), last ? 1 : 2);
-    }
-    return FEMCY_OK;
+    return explicit_steps(c, ex, &c->explicits[id].clock, rhs_vec, nsteps, 0.0, 0.0, 0.0);
 }
 
 int femcy_explicit_auto_state(femcy_ctx* ctx, int32_t id, double* t, double* h_last, double* h_min, int64_t* steps_done) {

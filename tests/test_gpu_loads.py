@@ -1,4 +1,4 @@
-"""*Dload / *Cload on the device: femcy_bodyload_* (k_body_weights, k_body_gather, k_body_apply) and femcy_dofset_add
+"""*Dload / *Cload on the device: femcy_bodyload_* (k_body_weights, k_node_sum, k_body_apply) and femcy_dofset_add
 against closed forms, the numpy restatement (tests/loads_reference.py) and the host backend; the scenarios are those of
 tests/loads_cases.py, which tests/test_loads_cpu.py runs on the host."""
 import os

@@ -4,7 +4,7 @@
 
 Per mesh (1 M C3D4: the twist plate at k = 12; 124 k C3D10: k = 6, quadratic):
   geom_us      k_geom<NPE,DM,false> of femcy_assemble_K on the undeformed mesh (HIP events of the library's timing class)
-  weights_us   k_body_weights + k_body_gather of femcy_bodyload_create (one event pair around both launches)
+  weights_us   k_body_weights + k_node_sum of femcy_bodyload_create (one event pair around both launches)
   apply_us     one femcy_bodyload_apply(add = 1): wall clock of `--apply-reps` back-to-back calls between two stream
                synchronisations, i.e. launch to launch
 No gate hangs on these numbers: create runs once per solve."""

@@ -8,7 +8,7 @@ class (FEMCY_OPT_TIMING) unless said otherwise:
   geom_us            k_geom<NPE,DM,false> of femcy_assemble_K on the undeformed mesh
   nodal_force_us     k_nodal_force of femcy_internal_force (its T_FORCE event pair)
   thermal_create_us  k_thermal_force + k_nodal_force of femcy_thermal_create (one event pair around both launches)
-  body_create_us     k_body_weights + k_body_gather of femcy_bodyload_create (one event pair around both launches)
+  body_create_us     k_body_weights + k_node_sum of femcy_bodyload_create (one event pair around both launches)
   thermal_apply_us   k_thermal_apply of one femcy_thermal_apply(add = 1)
   thermal_stress_us  k_thermal_post of one femcy_thermal_stress
   thermal_apply_wall_us / body_apply_wall_us
