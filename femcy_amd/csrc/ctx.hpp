@@ -7,10 +7,10 @@
 #include <string>
 #include <vector>
 #include "../../include/femcy.h"
+#include "api_checks.hpp"   // set_error, FEMCY_REQUIRE and what the entry points refuse
 
 namespace femcy {
 
-void set_error(const char* fmt, ...);
 struct ExplicitClock;   // element_math.hpp
 
 #define FEMCY_HIP(call)                                                                         \
@@ -107,14 +107,6 @@ public:
     }
     T* get() const { return p_; }
 };
-
-#define FEMCY_REQUIRE(cond, ...)                    \
-    do {                                            \
-        if (!(cond)) {                              \
-            femcy::set_error(__VA_ARGS__);          \
-            return FEMCY_EINVAL;                    \
-        }                                           \
-    } while (0)
 
 // FEMCY_TUNE_PAIRS default: XCD-contiguous (1) + 8 rows per wave (2) + Morton chunk order (32) + 3 chunks per wave (128):
 // 113-115 us on the 1 M-DOF CPE8 beam against 126 with all bits clear (profiles/r06_asm_cpe8_knobs.txt)
@@ -430,6 +422,11 @@ struct Ctx {
     int32_t* d_if_ptr = nullptr;      // [niface_local+1] per local interface DOF (order of d_iface_dof): its
     int32_t* d_if_src = nullptr;      //   contributions in ascending rank order; src = recv index, -1 = own value
 };
+
+template <>
+inline bool vec_allocated(const Ctx* c, int v) {
+    return c->d_vec[v] != nullptr;
+}
 
 enum { COMM_NONE = 0, COMM_RCCL = 1, COMM_LOCAL = 2, COMM_SHM = 3 };
 // timing classes

@@ -166,18 +166,6 @@ void timing_collect(Ctx* c) {
     c->ev_next = 0;
 }
 
-static int check_vec(Ctx* c, int v) {
-    if (v < 0 || v >= FEMCY_VEC_COUNT) {
-        set_error("vector id %d out of range", v);
-        return FEMCY_EINVAL;
-    }
-    if (!c->d_vec[v]) {
-        set_error("vectors are allocated by femcy_set_mesh; call it first");
-        return FEMCY_EINVAL;
-    }
-    return FEMCY_OK;
-}
-
 // element pass of a force evaluation: gradients + per-element nodal forces; F / sigma stay un-stored (gp_lazy)
 int force_pass(Ctx* c, const double* d_u) {
     c->post_small = false;                           // sigma is about to be the stress of this evaluation (now or lazily)
@@ -203,21 +191,37 @@ int ensure_gp_stress(Ctx* c) {
 using namespace femcy;
 
 #define CTX_OR_FAIL(ctx)                            \
-    if (!(ctx)) {                                   \
-        femcy::set_error("null context");           \
-        return FEMCY_EINVAL;                        \
-    }                                               \
+    FEMCY_REQUIRE((ctx), TEXT_NULL_CONTEXT);                        \
     Ctx* c = &(ctx)->c;                             \
     if (hipSetDevice(c->device) != hipSuccess) {    \
         femcy::set_error("hipSetDevice(%d) failed", c->device); \
         return FEMCY_EHIP;                          \
     }
 
-#define VEC_OR_FAIL(v)                      \
-    {                                       \
-        int _rc = check_vec(c, (v));        \
-        if (_rc) return _rc;                \
+// device -> host, landed on return
+static int download(Ctx* c, void* dst, const void* src, size_t bytes) {
+    FEMCY_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+    FEMCY_HIP(hipStreamSynchronize(c->stream));
+    return FEMCY_OK;
+}
+
+// The tail the femcy_*_create calls of the element-pass objects share: wait for the kernels (they read scratch the caller
+// releases when it returns), name the failure, keep the object, hand out its id.  `failed`: the text when the kernels failed;
+// `what`: the object in the out-of-memory text.
+template <class T>
+static int finish_create(Ctx* c, int rc, std::vector<T>& objects, T& obj, const char* failed, const char* what, int32_t* id_out) {
+    if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) {
+        set_error("%s", failed);
+        rc = FEMCY_EHIP;
     }
+    if (rc) {
+        if (rc == FEMCY_ENOMEM) set_error("out of device memory for %s on %d elements", what, c->ne);
+        return rc;
+    }
+    objects.push_back(std::move(obj));
+    *id_out = (int32_t)objects.size() - 1;
+    return FEMCY_OK;
+}
 
 extern "C" {
 
@@ -225,10 +229,7 @@ const char* femcy_last_error(void) { return g_err; }
 int femcy_version(void) { return 100; }
 
 int femcy_ctx_create(int device, femcy_ctx** out) {
-    if (!out) {
-        set_error("out is null");
-        return FEMCY_EINVAL;
-    }
+    FEMCY_REQUIRE(out, TEXT_CTX_OUT_NULL);
     *out = nullptr;
     int count = 0;
     hipError_t e = hipGetDeviceCount(&count);
@@ -331,6 +332,7 @@ int femcy_ctx_destroy(femcy_ctx* ctx) {
 
 int femcy_set_option(femcy_ctx* ctx, int option, int64_t value) {
     CTX_OR_FAIL(ctx);
+    FEMCY_TRY(check_option(c, option, value));
     switch (option) {
         case FEMCY_OPT_ASSEMBLY:
             FEMCY_REQUIRE(value >= FEMCY_ASM_GATHER && value <= FEMCY_ASM_PAIRS, "bad assembly mode %lld", (long long)value);
@@ -458,7 +460,6 @@ int femcy_set_option(femcy_ctx* ctx, int option, int64_t value) {
             c->opt_overlap = (int)value;
             break;
         case FEMCY_OPT_TANGENT:
-            FEMCY_REQUIRE(value == 0 || value == 1, "tangent: 0 (reference) or 1 (consistent)");
             c->opt_tangent = (int)value;
             break;
         case FEMCY_TUNE_VEC_NT:   /* test knob: PCG vector kernels with non-temporal loads / stores */
@@ -481,8 +482,6 @@ int femcy_set_option(femcy_ctx* ctx, int option, int64_t value) {
             c->opt_timing_fence = value ? 1 : 0;
             break;
         case FEMCY_OPT_SELL_SIGMA:
-            FEMCY_REQUIRE(value >= SLICE && value <= (1 << 24), "sorting window must be in [64, 2^24] nodes");
-            FEMCY_REQUIRE(!c->have_pattern, "set the sorting window before femcy_build_pattern");
             c->sell_sigma = (int32_t)value;
             break;
         case FEMCY_OPT_PCG_STORAGE_ORDER:
@@ -491,8 +490,6 @@ int femcy_set_option(femcy_ctx* ctx, int option, int64_t value) {
             c->opt_pos_space = (int)value;
             break;
         case FEMCY_OPT_NODE_ORDER:
-            FEMCY_REQUIRE(value >= 0 && value <= 7, "node order: 0 (caller's numbering), 1 (measured choice), 2..7 (coordinate order k - 2)");
-            FEMCY_REQUIRE(!c->have_pattern, "set the node order before femcy_build_pattern");
             c->opt_node_order = (int)value;
             break;
         case FEMCY_OPT_PCG_GRAPH:
@@ -508,7 +505,7 @@ int femcy_set_option(femcy_ctx* ctx, int option, int64_t value) {
             }
             break;
         default:
-            set_error("unknown option %d", option);
+            set_error(TEXT_UNKNOWN_OPTION, option);
             return FEMCY_EINVAL;
     }
     return FEMCY_OK;
@@ -524,13 +521,7 @@ int femcy_sync(femcy_ctx* ctx) {
 int femcy_set_mesh(femcy_ctx* ctx, int32_t nn, int32_t dm, const double* nodes, int32_t ne, int32_t npe,
                    const int32_t* elems) {
     CTX_OR_FAIL(ctx);
-    FEMCY_REQUIRE(nodes && elems, "null mesh arrays");
-    FEMCY_REQUIRE(nn > 0 && ne > 0, "empty mesh (nn=%d, ne=%d)", nn, ne);
-    FEMCY_REQUIRE(dm == 2 || dm == 3, "dm must be 2 or 3, got %d", dm);
-    FEMCY_REQUIRE(npe >= 2 && npe <= 27, "npe out of range: %d", npe);
-    for (int64_t k = 0; k < (int64_t)ne * npe; ++k)
-        FEMCY_REQUIRE(elems[k] >= 0 && elems[k] < nn, "element %lld references node %d outside [0,%d)",
-                      (long long)(k / npe), elems[k], nn);
+    FEMCY_TRY(check_set_mesh(nn, dm, nodes, ne, npe, elems));
     FEMCY_REQUIRE(!c->comm, "the mesh of a context cannot change once a communicator is attached");
     FEMCY_HIP(hipStreamSynchronize(c->stream));
     // a new mesh invalidates everything that was defined on the old one
@@ -564,10 +555,7 @@ int femcy_set_mesh(femcy_ctx* ctx, int32_t nn, int32_t dm, const double* nodes, 
 
 int femcy_set_element(femcy_ctx* ctx, int32_t nGP, const double* dN, const double* w, int32_t voigt_kind) {
     CTX_OR_FAIL(ctx);
-    FEMCY_REQUIRE(c->have_mesh, "femcy_set_mesh must come first");
-    FEMCY_REQUIRE(dN && w && nGP >= 1 && nGP <= 64, "bad element tables (nGP=%d)", nGP);
-    FEMCY_REQUIRE((voigt_kind == FEMCY_VOIGT_2D && c->dm == 2) || (voigt_kind == FEMCY_VOIGT_3D && c->dm == 3),
-                  "voigt kind %d does not match dm=%d", voigt_kind, c->dm);
+    FEMCY_TRY(check_set_element(c, nGP, dN, w, voigt_kind));
     FEMCY_HIP(hipStreamSynchronize(c->stream));
     c->nGP = nGP;
     c->voigt = voigt_kind;
@@ -605,13 +593,7 @@ int femcy_set_element(femcy_ctx* ctx, int32_t nGP, const double* dN, const doubl
 
 int femcy_set_material(femcy_ctx* ctx, int32_t kind, const double* C, const double* params, int32_t nparams) {
     CTX_OR_FAIL(ctx);
-    FEMCY_REQUIRE(c->have_mesh, "femcy_set_mesh must come first");
-    FEMCY_REQUIRE(C, "null C");
-    FEMCY_REQUIRE(kind >= FEMCY_MAT_LIN3D && kind <= FEMCY_MAT_NEOHOOKE, "unknown material kind %d", kind);
-    // neo-Hookean exists for dm = 3 (the reference's) and, as an extension, for dm = 2 (plane strain)
-    const bool ok_dm = kind == FEMCY_MAT_NEOHOOKE || ((kind == FEMCY_MAT_LIN3D) == (c->dm == 3));
-    FEMCY_REQUIRE(ok_dm, "material kind %d does not match dm=%d", kind, c->dm);
-    FEMCY_REQUIRE(nparams >= 2 && params, "material needs 2 parameters");
+    FEMCY_TRY(check_set_material(c, kind, C, params, nparams));
     // F / sigma "of the last force evaluation" are kept lazily (Ctx::gp_lazy): materialise them with the material they
     // were evaluated with before it changes
     if (c->gp_lazy && c->have_material && c->have_element) {
@@ -646,7 +628,7 @@ int femcy_set_material(femcy_ctx* ctx, int32_t kind, const double* C, const doub
 
 int femcy_build_pattern(femcy_ctx* ctx) {
     CTX_OR_FAIL(ctx);
-    FEMCY_REQUIRE(c->have_mesh, "femcy_set_mesh must come first");
+    FEMCY_TRY(check_have_mesh(c));
     FEMCY_HIP(hipStreamSynchronize(c->stream));
     pcg_graph_reset(c);
     int rc = build_pattern(c);
@@ -659,14 +641,14 @@ int femcy_build_pattern(femcy_ctx* ctx) {
 
 int femcy_get_assembly_used(femcy_ctx* ctx, int32_t* mode) {
     CTX_OR_FAIL(ctx);
-    FEMCY_REQUIRE(mode && c->asm_used >= 0, "no assembly has run on this context");
+    FEMCY_TRY(check_get_assembly_used(c, mode));
     *mode = c->asm_used;
     return FEMCY_OK;
 }
 
 int femcy_get_pattern_info(femcy_ctx* ctx, femcy_pattern_info* out) {
     CTX_OR_FAIL(ctx);
-    FEMCY_REQUIRE(c->have_pattern && out, "pattern not built");
+    FEMCY_REQUIRE(c->have_pattern && out, TEXT_PATTERN_NOT_BUILT);
     out->n = c->n;
     out->nnzb = c->nnzb;
     out->nnz = c->nnzb * c->dm * c->dm;
@@ -680,7 +662,7 @@ int femcy_get_pattern_info(femcy_ctx* ctx, femcy_pattern_info* out) {
 
 int femcy_get_node_order(femcy_ctx* ctx, int32_t* used, double* lines) {
     CTX_OR_FAIL(ctx);
-    FEMCY_REQUIRE(c->have_pattern, "pattern not built");
+    FEMCY_REQUIRE(c->have_pattern, TEXT_PATTERN_NOT_BUILT);
     if (used) *used = c->node_order_used;
     if (lines)
         for (int k = 0; k < 7; ++k) lines[k] = c->node_order_cost[k];
@@ -690,19 +672,15 @@ int femcy_get_node_order(femcy_ctx* ctx, int32_t* used, double* lines) {
 // ---------------------------------------------------------------------------- vector plumbing
 int femcy_vec_upload(femcy_ctx* ctx, int vec, const double* src, int64_t n) {
     CTX_OR_FAIL(ctx);
-    VEC_OR_FAIL(vec);
-    FEMCY_REQUIRE(src && n == c->n, "upload length %lld != n = %lld", (long long)n, (long long)c->n);
+    FEMCY_TRY(check_vec_transfer(c, "upload", vec, src, n));
     FEMCY_HIP(hipMemcpyAsync(c->d_vec[vec], src, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
     FEMCY_HIP(hipStreamSynchronize(c->stream));
     return FEMCY_OK;
 }
 int femcy_vec_download(femcy_ctx* ctx, int vec, double* dst, int64_t n) {
     CTX_OR_FAIL(ctx);
-    VEC_OR_FAIL(vec);
-    FEMCY_REQUIRE(dst && n == c->n, "download length %lld != n = %lld", (long long)n, (long long)c->n);
-    FEMCY_HIP(hipMemcpyAsync(dst, c->d_vec[vec], sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
-    FEMCY_HIP(hipStreamSynchronize(c->stream));
-    return FEMCY_OK;
+    FEMCY_TRY(check_vec_transfer(c, "download", vec, dst, n));
+    return download(c, dst, c->d_vec[vec], sizeof(double) * n);
 }
 int femcy_vec_fill(femcy_ctx* ctx, int vec, double value) {
     CTX_OR_FAIL(ctx);
@@ -721,8 +699,7 @@ int femcy_vec_scatter(femcy_ctx* ctx, int vec, const int32_t* idx, const double*
     CTX_OR_FAIL(ctx);
     VEC_OR_FAIL(vec);
     if (k == 0) return FEMCY_OK;
-    FEMCY_REQUIRE(idx && vals && k > 0, "bad scatter arguments");
-    for (int32_t i = 0; i < k; ++i) FEMCY_REQUIRE(idx[i] >= 0 && idx[i] < c->n, "scatter index %d out of range", idx[i]);
+    FEMCY_TRY(check_vec_scatter(c, idx, vals, k));
     int rc = ensure_scratch(c, k);
     if (rc) return rc;
     // host buffers are only borrowed for the call: staged (the scratch lists are reused by the next scatter, which the
@@ -749,7 +726,7 @@ int femcy_vec_scale(femcy_ctx* ctx, int vec, double s) {
 int femcy_vec_norm(femcy_ctx* ctx, int vec, double* rms) {
     CTX_OR_FAIL(ctx);
     VEC_OR_FAIL(vec);
-    FEMCY_REQUIRE(rms, "null output");
+    FEMCY_REQUIRE(rms, TEXT_NULL_OUTPUT);
     double ss = 0.0;
     int rc = vec_sumsq(c, c->d_vec[vec], &ss);
     if (rc) return rc;
@@ -759,16 +736,11 @@ int femcy_vec_norm(femcy_ctx* ctx, int vec, double* rms) {
 int femcy_vec_absmax(femcy_ctx* ctx, int vec, double* out) {
     CTX_OR_FAIL(ctx);
     VEC_OR_FAIL(vec);
-    FEMCY_REQUIRE(out, "null output");
+    FEMCY_REQUIRE(out, TEXT_NULL_OUTPUT);
     return vec_absmax(c, c->d_vec[vec], out);
 }
 
 // -------------------------------------------------------------------------------- the hot path
-#define READY_OR_FAIL()                                                                                       \
-    FEMCY_REQUIRE(c->have_mesh&& c->have_element&& c->have_material&& c->have_pattern,                        \
-                  "context not fully defined (mesh=%d element=%d material=%d pattern=%d)", (int)c->have_mesh, \
-                  (int)c->have_element, (int)c->have_material, (int)c->have_pattern)
-
 int femcy_assemble_K(femcy_ctx* ctx, int u_vec) {
     CTX_OR_FAIL(ctx);
     READY_OR_FAIL();
@@ -815,12 +787,8 @@ int femcy_residual_and_K(femcy_ctx* ctx, int u_vec, int f_vec) {
     return FEMCY_OK;
 }
 
+// the checked DOFs (and values) of a Dirichlet call into the scratch lists
 static int stage_dofs(Ctx* c, const int32_t* dofs, const double* vals, int32_t k) {
-    for (int32_t i = 0; i < k; ++i)
-        if (dofs[i] < 0 || dofs[i] >= c->n) {
-            set_error("constrained DOF %d out of range", dofs[i]);
-            return FEMCY_EINVAL;
-        }
     if (k == 0) return FEMCY_OK;
     int rc = ensure_scratch(c, k);
     if (rc) return rc;
@@ -834,8 +802,7 @@ int femcy_apply_dirichlet_linear(femcy_ctx* ctx, const int32_t* dofs, const doub
     READY_OR_FAIL();
     VEC_OR_FAIL(rhs_vec);
     if (k == 0 && !c->comm) return FEMCY_OK;
-    FEMCY_REQUIRE(k >= 0 && (k == 0 || (dofs && vals)), "bad Dirichlet arguments");
-    FEMCY_REQUIRE(rhs_vec != FEMCY_VEC_TMP0 && rhs_vec != FEMCY_VEC_TMP1, "rhs may not alias the scratch vectors");
+    FEMCY_TRY(check_dirichlet_linear(c, dofs, vals, k, rhs_vec));
     int rc = stage_dofs(c, dofs, vals, k);
     if (rc) return rc;
     // multi-rank: the elimination below is collective (other ranks may hold prescribed values even if this one
@@ -864,7 +831,7 @@ int femcy_apply_dirichlet_newton(femcy_ctx* ctx, const int32_t* dofs, int32_t k,
     READY_OR_FAIL();
     VEC_OR_FAIL(residual_vec);
     if (k == 0) return FEMCY_OK;
-    FEMCY_REQUIRE(dofs && k > 0, "bad Dirichlet arguments");
+    FEMCY_TRY(check_dirichlet_newton(c, dofs, k));
     int rc = stage_dofs(c, dofs, nullptr, k);
     if (rc) return rc;
     if ((rc = launch_dirichlet_zero(c, c->d_idx_scratch, k, c->d_vec[residual_vec]))) return rc;
@@ -874,8 +841,7 @@ int femcy_apply_dirichlet_newton(femcy_ctx* ctx, const int32_t* dofs, int32_t k,
 
 int femcy_dofset_create(femcy_ctx* ctx, const int32_t* dofs, int32_t k, int32_t* id_out) {
     CTX_OR_FAIL(ctx);
-    FEMCY_REQUIRE(c->have_mesh && id_out && k >= 0 && (k == 0 || dofs), "bad dofset arguments");
-    for (int32_t i = 0; i < k; ++i) FEMCY_REQUIRE(dofs[i] >= 0 && dofs[i] < c->n, "DOF %d out of range", dofs[i]);
+    FEMCY_TRY(check_dofset_create(c, dofs, k, id_out));
     Ctx::DofSet ds;
     ds.k = k;
     FEMCY_HIP(ds.d_dofs.alloc(std::max<size_t>(k, 1) * sizeof(int32_t)));
@@ -886,38 +852,34 @@ int femcy_dofset_create(femcy_ctx* ctx, const int32_t* dofs, int32_t k, int32_t*
     return FEMCY_OK;
 }
 
-#define DOFSET_OR_FAIL(id)                                                              \
-    FEMCY_REQUIRE((id) >= 0 && (size_t)(id) < c->dofsets.size(), "unknown dofset %d", (int)(id)); \
-    const Ctx::DofSet& ds = c->dofsets[(id)]
-
 int femcy_dofset_dirichlet_newton(femcy_ctx* ctx, int32_t id, int residual_vec) {
     CTX_OR_FAIL(ctx);
     READY_OR_FAIL();
     VEC_OR_FAIL(residual_vec);
-    DOFSET_OR_FAIL(id);
+    FEMCY_OBJECT_OR_FAIL(ds, c->dofsets, id, "dofset");
     return launch_dirichlet_zero(c, ds.d_dofs.get(), ds.k, c->d_vec[residual_vec]);
 }
 
 int femcy_dofset_fill(femcy_ctx* ctx, int32_t id, int vec, double value) {
     CTX_OR_FAIL(ctx);
     VEC_OR_FAIL(vec);
-    DOFSET_OR_FAIL(id);
+    FEMCY_OBJECT_OR_FAIL(ds, c->dofsets, id, "dofset");
     return vec_scatter_const(c, c->d_vec[vec], ds.d_dofs.get(), value, ds.k);
 }
 
 int femcy_dofset_add(femcy_ctx* ctx, int32_t id, int vec, double value) {
     CTX_OR_FAIL(ctx);
     VEC_OR_FAIL(vec);
-    DOFSET_OR_FAIL(id);
+    FEMCY_OBJECT_OR_FAIL(ds, c->dofsets, id, "dofset");
     return vec_scatter_add(c, c->d_vec[vec], ds.d_dofs.get(), value, ds.k);
 }
 
 int femcy_dofset_scatter(femcy_ctx* ctx, int32_t id, int vec, const double* vals) {
     CTX_OR_FAIL(ctx);
     VEC_OR_FAIL(vec);
-    DOFSET_OR_FAIL(id);
+    FEMCY_OBJECT_OR_FAIL(ds, c->dofsets, id, "dofset");
     if (ds.k == 0) return FEMCY_OK;
-    FEMCY_REQUIRE(vals, "null values");
+    FEMCY_REQUIRE(vals, TEXT_NULL_VALUES);
     int rc = stage_h2d(c, ds.d_vals.get(), vals, sizeof(double) * ds.k);   // the host buffer is only borrowed for the call
     if (rc) return rc;
     return vec_scatter(c, c->d_vec[vec], ds.d_dofs.get(), ds.d_vals.get(), ds.k);
@@ -927,8 +889,8 @@ int femcy_dofset_dirichlet_linear(femcy_ctx* ctx, int32_t id, double value, int 
     CTX_OR_FAIL(ctx);
     READY_OR_FAIL();
     VEC_OR_FAIL(rhs_vec);
-    DOFSET_OR_FAIL(id);
-    FEMCY_REQUIRE(rhs_vec != FEMCY_VEC_TMP0 && rhs_vec != FEMCY_VEC_TMP1, "rhs may not alias the scratch vectors");
+    FEMCY_OBJECT_OR_FAIL(ds, c->dofsets, id, "dofset");
+    FEMCY_TRY(check_rhs_not_scratch(rhs_vec));
     if (ds.k == 0 && !c->comm) return FEMCY_OK;
     int rc;
     if (value != 0.0) {   // rhs -= K s with s = value on the block's DOFs (see femcy_apply_dirichlet_linear); collective
@@ -949,16 +911,8 @@ int femcy_loadset_create(femcy_ctx* ctx, int32_t nft, int32_t nfn, int32_t nip, 
                          const double* ft_N, const double* ft_dN, const double* ft_normal, const double* ft_weight,
                          int32_t nload, const int32_t* load_elem, const int32_t* load_ft, int32_t* id_out) {
     CTX_OR_FAIL(ctx);
-    FEMCY_REQUIRE(c->have_mesh && id_out, "mesh not set or null id_out");
-    FEMCY_REQUIRE(nft > 0 && nip > 0 && nfn >= c->dm && nfn <= c->npe, "bad facet table sizes (nft %d, nfn %d, nip %d)", nft, nfn, nip);
-    FEMCY_REQUIRE(ft_nodes && ft_N && ft_dN && ft_normal && ft_weight, "null facet tables");
-    FEMCY_REQUIRE(nload >= 0 && (nload == 0 || (load_elem && load_ft)), "bad load facet lists");
-    for (int32_t i = 0; i < nft * nfn; ++i)
-        FEMCY_REQUIRE(ft_nodes[i] >= 0 && ft_nodes[i] < c->npe, "facet table: local node %d out of range", ft_nodes[i]);
-    for (int32_t l = 0; l < nload; ++l) {
-        FEMCY_REQUIRE(load_elem[l] >= 0 && load_elem[l] < c->ne, "load facet %d: element %d out of range", l, load_elem[l]);
-        FEMCY_REQUIRE(load_ft[l] >= 0 && load_ft[l] < nft, "load facet %d: facet type %d out of range", l, load_ft[l]);
-    }
+    FEMCY_TRY(check_loadset_create(c, nft, nfn, nip, ft_nodes, ft_N, ft_dN, ft_normal, ft_weight, nload, load_elem, load_ft,
+                                   id_out));
     // loaded nodes and, per node, its contribution slots (facet * nfn + facet node) in ascending order
     const size_t nslot = (size_t)nload * nfn;
     std::vector<int32_t> slot_node(nslot), order(nslot);
@@ -1003,8 +957,7 @@ int femcy_loadset_create(femcy_ctx* ctx, int32_t nft, int32_t nfn, int32_t nip, 
 
 static int loadset_neumann(Ctx* c, int32_t id, double traction, const double* direction, int rhs_vec, bool add) {
     VEC_OR_FAIL(rhs_vec);
-    FEMCY_REQUIRE(id >= 0 && (size_t)id < c->loadsets.size(), "unknown load set %d", (int)id);
-    const Ctx::LoadSet& ls = c->loadsets[id];
+    FEMCY_OBJECT_OR_FAIL(ls, c->loadsets, id, "load set");
     return apply_load(c, "femcy_loadset_neumann_add", rhs_vec, add, [&](double* dst, bool add_to) -> int {
         if (direction) {
             FEMCY_HIP(hipMemcpyAsync(ls.d_dir.get(), direction, sizeof(double) * c->dm, hipMemcpyHostToDevice, c->stream));
@@ -1027,20 +980,8 @@ int femcy_loadset_neumann_add(femcy_ctx* ctx, int32_t id, double traction, const
 // ----------------------------------------------------------------------------------- body loads
 int femcy_bodyload_create(femcy_ctx* ctx, const double* N, int32_t nsel, const int32_t* sel_elems, int32_t* id_out) {
     CTX_OR_FAIL(ctx);
-    FEMCY_REQUIRE(c->have_mesh && c->have_element && c->have_pattern,
-                  "femcy_bodyload_create needs the mesh, the element tables and the pattern (mesh=%d element=%d pattern=%d)",
-                  (int)c->have_mesh, (int)c->have_element, (int)c->have_pattern);
-    FEMCY_REQUIRE(N && id_out, "null shape-function table or id_out");
-    FEMCY_REQUIRE(sel_elems ? nsel >= 0 : true, "negative selection size %d", nsel);
     std::vector<uint8_t> mask;
-    if (sel_elems) {
-        mask.assign((size_t)c->ne, 0);
-        for (int32_t i = 0; i < nsel; ++i) {
-            FEMCY_REQUIRE(sel_elems[i] >= 0 && sel_elems[i] < c->ne, "body load: element %d out of range", sel_elems[i]);
-            FEMCY_REQUIRE(!mask[sel_elems[i]], "body load: element %d selected twice", sel_elems[i]);
-            mask[sel_elems[i]] = 1;
-        }
-    }
+    FEMCY_TRY(check_bodyload_create(c, N, nsel, sel_elems, id_out, mask));
     Ctx::BodyLoad bl;
     bl.nsel = sel_elems ? nsel : c->ne;
     DevBuf<double> d_N, d_we;      // the tables and the element records are scratch of this call
@@ -1050,38 +991,20 @@ int femcy_bodyload_create(femcy_ctx* ctx, const double* N, int32_t nsel, const i
     if (!rc && d_we.alloc(sizeof(double) * (size_t)c->ne * c->npe) != hipSuccess) rc = FEMCY_ENOMEM;
     if (!rc && bl.d_m.alloc(sizeof(double) * (size_t)c->nn) != hipSuccess) rc = FEMCY_ENOMEM;
     if (!rc) rc = launch_body_weights(c, d_N.get(), d_mask.get(), d_we.get(), bl.d_m.get());
-    // ... which the two kernels read: wait for them before the scratch is released at the end of the call
-    if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) {
-        set_error("body load: the weight kernels failed");
-        rc = FEMCY_EHIP;
-    }
-    if (rc) {
-        if (rc == FEMCY_ENOMEM) set_error("out of device memory for a body load on %d elements", c->ne);
-        return rc;
-    }
-    c->bodyloads.push_back(std::move(bl));
-    *id_out = (int32_t)c->bodyloads.size() - 1;
-    return FEMCY_OK;
+    return finish_create(c, rc, c->bodyloads, bl, "body load: the weight kernels failed", "a body load", id_out);
 }
-
-#define BODYLOAD_OR_FAIL(id)                                                                        \
-    FEMCY_REQUIRE((id) >= 0 && (size_t)(id) < c->bodyloads.size(), "unknown body load %d", (int)(id)); \
-    const Ctx::BodyLoad& bl = c->bodyloads[(id)]
 
 int femcy_bodyload_weights(femcy_ctx* ctx, int32_t id, double* out) {
     CTX_OR_FAIL(ctx);
-    BODYLOAD_OR_FAIL(id);
-    FEMCY_REQUIRE(out, "null output");
-    FEMCY_HIP(hipMemcpyAsync(out, bl.d_m.get(), sizeof(double) * c->nn, hipMemcpyDeviceToHost, c->stream));
-    FEMCY_HIP(hipStreamSynchronize(c->stream));
-    return FEMCY_OK;
+    FEMCY_OBJECT_OR_FAIL(bl, c->bodyloads, id, "body load");
+    FEMCY_REQUIRE(out, TEXT_NULL_OUTPUT);
+    return download(c, out, bl.d_m.get(), sizeof(double) * c->nn);
 }
 
 int femcy_bodyload_apply(femcy_ctx* ctx, int32_t id, const double* b, int rhs_vec, int32_t add) {
     CTX_OR_FAIL(ctx);
-    VEC_OR_FAIL(rhs_vec);
-    BODYLOAD_OR_FAIL(id);
-    FEMCY_REQUIRE(b, "null force");
+    FEMCY_TRY(check_bodyload_apply(c, id, b, rhs_vec));
+    const Ctx::BodyLoad& bl = c->bodyloads[id];
     return apply_load(c, "femcy_bodyload_apply with add", rhs_vec, add != 0,
                       [&](double* dst, bool add_to) { return launch_body_apply(c, bl.d_m.get(), b, add_to, dst); });
 }
@@ -1089,14 +1012,7 @@ int femcy_bodyload_apply(femcy_ctx* ctx, int32_t id, const double* b, int rhs_ve
 // --------------------------------------------------------------------------------- thermal loads
 int femcy_thermal_create(femcy_ctx* ctx, const double* N, double alpha, const double* dT, int32_t* id_out) {
     CTX_OR_FAIL(ctx);
-    FEMCY_REQUIRE(c->have_mesh && c->have_element && c->have_material && c->have_pattern,
-                  "femcy_thermal_create needs the mesh, the element tables, the material and the pattern (mesh=%d element=%d "
-                  "material=%d pattern=%d)", (int)c->have_mesh, (int)c->have_element, (int)c->have_material,
-                  (int)c->have_pattern);
-    FEMCY_REQUIRE(N && dT && id_out, "null shape-function table, temperature field or id_out");
-    FEMCY_REQUIRE(std::isfinite(alpha), "thermal load: the expansion coefficient is not finite");
-    FEMCY_REQUIRE(c->mat_kind != FEMCY_MAT_NEOHOOKE, "thermal load: a neo-Hookean material has no small-strain thermal "
-                  "stress (linear materials only)");
+    FEMCY_TRY(check_thermal_create(c, N, alpha, dT, id_out));
     Ctx::Thermal th;
     dispatch_dm(c->dm, [&](auto dm) {
         constexpr int DM = dm();
@@ -1110,50 +1026,29 @@ int femcy_thermal_create(femcy_ctx* ctx, const double* N, double alpha, const do
     if (!rc && d_fe.alloc(sizeof(double) * (size_t)c->ne * c->npe * c->dm) != hipSuccess) rc = FEMCY_ENOMEM;
     if (!rc && th.d_f.alloc(sizeof(double) * (size_t)c->n) != hipSuccess) rc = FEMCY_ENOMEM;
     if (!rc) rc = launch_thermal_force(c, th, d_fe.get());
-    // ... which the two kernels read: wait for them before the scratch is released at the end of the call
-    if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) {
-        set_error("thermal load: the force kernels failed");
-        rc = FEMCY_EHIP;
-    }
-    if (rc) {
-        if (rc == FEMCY_ENOMEM) set_error("out of device memory for a thermal load on %d elements", c->ne);
-        return rc;
-    }
-    c->thermals.push_back(std::move(th));
-    *id_out = (int32_t)c->thermals.size() - 1;
-    return FEMCY_OK;
+    return finish_create(c, rc, c->thermals, th, "thermal load: the force kernels failed", "a thermal load", id_out);
 }
-
-#define THERMAL_OR_FAIL(id)                                                                            \
-    FEMCY_REQUIRE((id) >= 0 && (size_t)(id) < c->thermals.size(), "unknown thermal load %d", (int)(id)); \
-    const Ctx::Thermal& th = c->thermals[(id)]
 
 int femcy_thermal_force(femcy_ctx* ctx, int32_t id, double* out) {
     CTX_OR_FAIL(ctx);
-    THERMAL_OR_FAIL(id);
-    FEMCY_REQUIRE(out, "null output");
-    FEMCY_HIP(hipMemcpyAsync(out, th.d_f.get(), sizeof(double) * c->n, hipMemcpyDeviceToHost, c->stream));
-    FEMCY_HIP(hipStreamSynchronize(c->stream));
-    return FEMCY_OK;
+    FEMCY_OBJECT_OR_FAIL(th, c->thermals, id, "thermal load");
+    FEMCY_REQUIRE(out, TEXT_NULL_OUTPUT);
+    return download(c, out, th.d_f.get(), sizeof(double) * c->n);
 }
 
 int femcy_thermal_apply(femcy_ctx* ctx, int32_t id, double scale, int rhs_vec, int32_t add) {
     CTX_OR_FAIL(ctx);
     VEC_OR_FAIL(rhs_vec);
-    THERMAL_OR_FAIL(id);
+    FEMCY_OBJECT_OR_FAIL(th, c->thermals, id, "thermal load");
     return apply_load(c, "femcy_thermal_apply with add", rhs_vec, add != 0,
                       [&](double* dst, bool add_to) { return launch_thermal_apply(c, th.d_f.get(), scale, add_to, dst); });
 }
 
 int femcy_thermal_stress(femcy_ctx* ctx, int32_t id, double scale) {
     CTX_OR_FAIL(ctx);
-    THERMAL_OR_FAIL(id);
-    FEMCY_REQUIRE(c->mat_kind != FEMCY_MAT_NEOHOOKE, "thermal stress: a neo-Hookean material has no small-strain thermal "
-                  "stress (linear materials only)");
-    FEMCY_REQUIRE(c->post_small, "femcy_thermal_stress corrects the stress of femcy_compute_strain_stress(large = 0): call "
-                  "that first (the Gauss-point stress does not exist, is the nlgeom one, or has been corrected already)");
+    FEMCY_TRY(check_thermal_stress(c, id));
     c->post_small = false;
-    return launch_thermal_post(c, th, scale);
+    return launch_thermal_post(c, c->thermals[id], scale);
 }
 
 // ------------------------------------------------------------------------------ implicit dynamics
@@ -1164,12 +1059,7 @@ int femcy_mass_create(femcy_ctx* ctx, int32_t nq, const double* Nq, const double
                       int32_t* id_out) {
     CTX_OR_FAIL(ctx);
     SINGLE_RANK_OR_FAIL("femcy_mass_create");
-    FEMCY_REQUIRE(c->have_mesh && c->have_element && c->have_pattern,
-                  "femcy_mass_create needs the mesh, the element tables and the pattern (mesh=%d element=%d pattern=%d)",
-                  (int)c->have_mesh, (int)c->have_element, (int)c->have_pattern);
-    FEMCY_REQUIRE(Nq && dNq && wq && id_out, "null mass-rule table or id_out");
-    FEMCY_REQUIRE(nq >= 1 && nq <= 64, "mass rule: %d points (1 .. 64 are supported)", nq);
-    FEMCY_REQUIRE(std::isfinite(rho) && rho > 0.0, "mass: the density must be finite and positive");
+    FEMCY_TRY(check_mass_rule(c, "femcy_mass_create", nq, Nq, dNq, wq, rho, id_out));
     Ctx::Mass ms;
     DevBuf<double> d_Nq, d_dNq, d_wq, d_vq;     // the tables and the element records are scratch of this call
     const size_t npos = (size_t)c->stored_rows * SLICE;
@@ -1179,32 +1069,16 @@ int femcy_mass_create(femcy_ctx* ctx, int32_t nq, const double* Nq, const double
     if (!rc && d_vq.alloc(sizeof(double) * (size_t)c->ne * nq) != hipSuccess) rc = FEMCY_ENOMEM;
     if (!rc && ms.d_m.alloc(std::max<size_t>(sizeof(double) * npos, 8)) != hipSuccess) rc = FEMCY_ENOMEM;
     if (!rc) rc = launch_mass_blocks(c, nq, d_Nq.get(), d_dNq.get(), d_wq.get(), rho, d_vq.get(), ms.d_m.get());
-    // ... which the two kernels read: wait for them before the scratch is released at the end of the call
-    if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) {
-        set_error("mass: the assembly kernels failed");
-        rc = FEMCY_EHIP;
-    }
-    if (rc) {
-        if (rc == FEMCY_ENOMEM) set_error("out of device memory for a mass matrix on %d elements", c->ne);
-        return rc;
-    }
-    c->masses.push_back(std::move(ms));
-    *id_out = (int32_t)c->masses.size() - 1;
-    return FEMCY_OK;
+    return finish_create(c, rc, c->masses, ms, "mass: the assembly kernels failed", "a mass matrix", id_out);
 }
-
-#define MASS_OR_FAIL(id)                                                                          \
-    FEMCY_REQUIRE((id) >= 0 && (size_t)(id) < c->masses.size(), "unknown mass object %d", (int)(id)); \
-    const Ctx::Mass& ms = c->masses[(id)]
 
 int femcy_mass_get(femcy_ctx* ctx, int32_t id, double* vals) {
     CTX_OR_FAIL(ctx);
     SINGLE_RANK_OR_FAIL("femcy_mass_get");
-    MASS_OR_FAIL(id);
-    FEMCY_REQUIRE(vals, "null output");
+    FEMCY_OBJECT_OR_FAIL(ms, c->masses, id, "mass object");
+    FEMCY_REQUIRE(vals, TEXT_NULL_OUTPUT);
     std::vector<double> m((size_t)c->stored_rows * SLICE);
-    FEMCY_HIP(hipMemcpyAsync(m.data(), ms.d_m.get(), sizeof(double) * m.size(), hipMemcpyDeviceToHost, c->stream));
-    FEMCY_HIP(hipStreamSynchronize(c->stream));
+    FEMCY_TRY(download(c, m.data(), ms.d_m.get(), sizeof(double) * m.size()));
     int64_t w = 0;
     std::vector<std::pair<int32_t, int32_t>> order;
     for (int32_t a = 0; a < c->nn; ++a) {       // the block order of femcy_get_K_bsr
@@ -1221,52 +1095,36 @@ int femcy_mass_get(femcy_ctx* ctx, int32_t id, double* vals) {
 int femcy_mass_apply(femcy_ctx* ctx, int32_t id, int x_vec, int y_vec, double scale, int32_t add) {
     CTX_OR_FAIL(ctx);
     SINGLE_RANK_OR_FAIL("femcy_mass_apply");
-    VEC_OR_FAIL(x_vec);
-    VEC_OR_FAIL(y_vec);
-    MASS_OR_FAIL(id);
-    FEMCY_REQUIRE(x_vec != y_vec, "the mass product cannot run in place");
-    return launch_mass_spmv(c, ms.d_m.get(), c->d_vec[x_vec], c->d_vec[y_vec], scale, add != 0, nullptr, nullptr);
+    FEMCY_TRY(check_mass_apply(c, id, x_vec, y_vec));
+    return launch_mass_spmv(c, c->masses[id].d_m.get(), c->d_vec[x_vec], c->d_vec[y_vec], scale, add != 0, nullptr, nullptr);
 }
 
 int femcy_mass_add_to_K(femcy_ctx* ctx, int32_t id, double cc, int32_t overwrite) {
     CTX_OR_FAIL(ctx);
     SINGLE_RANK_OR_FAIL("femcy_mass_add_to_K");
-    MASS_OR_FAIL(id);
-    FEMCY_REQUIRE(std::isfinite(cc), "femcy_mass_add_to_K: the factor is not finite");
-    return launch_mass_add_to_K(c, ms.d_m.get(), cc, overwrite != 0);
+    FEMCY_TRY(check_mass_add_to_K(c, id, cc));
+    return launch_mass_add_to_K(c, c->masses[id].d_m.get(), cc, overwrite != 0);
 }
 
 int femcy_mass_kinetic_energy(femcy_ctx* ctx, int32_t id, int v_vec, double* out) {
     CTX_OR_FAIL(ctx);
     SINGLE_RANK_OR_FAIL("femcy_mass_kinetic_energy");
     VEC_OR_FAIL(v_vec);
-    MASS_OR_FAIL(id);
-    FEMCY_REQUIRE(out, "null output");
+    FEMCY_OBJECT_OR_FAIL(ms, c->masses, id, "mass object");
+    FEMCY_REQUIRE(out, TEXT_NULL_OUTPUT);
     return launch_mass_energy(c, ms.d_m.get(), c->d_vec[v_vec], out);
 }
 
 int femcy_newmark_predict(femcy_ctx* ctx, int u_vec, int v_vec, int a_vec, int out_vec, double c0, double c1, double c2) {
     CTX_OR_FAIL(ctx);
-    VEC_OR_FAIL(u_vec);
-    VEC_OR_FAIL(v_vec);
-    VEC_OR_FAIL(a_vec);
-    VEC_OR_FAIL(out_vec);
-    FEMCY_REQUIRE(out_vec != u_vec && out_vec != v_vec && out_vec != a_vec,
-                  "femcy_newmark_predict: the output may not be one of the inputs");
+    FEMCY_TRY(check_newmark_predict(c, u_vec, v_vec, a_vec, out_vec));
     return launch_newmark_predict(c, c->d_vec[u_vec], c->d_vec[v_vec], c->d_vec[a_vec], c->d_vec[out_vec], c0, c1, c2);
 }
 
 int femcy_newmark_update(femcy_ctx* ctx, int u_new_vec, int u_vec, int v_vec, int a_vec, double beta, double gamma,
                          double dt) {
     CTX_OR_FAIL(ctx);
-    VEC_OR_FAIL(u_new_vec);
-    VEC_OR_FAIL(u_vec);
-    VEC_OR_FAIL(v_vec);
-    VEC_OR_FAIL(a_vec);
-    FEMCY_REQUIRE(std::isfinite(beta) && beta > 0.0 && std::isfinite(gamma) && std::isfinite(dt) && dt > 0.0,
-                  "femcy_newmark_update: beta and dt must be positive, gamma finite");
-    FEMCY_REQUIRE(v_vec != a_vec && v_vec != u_vec && v_vec != u_new_vec && a_vec != u_vec && a_vec != u_new_vec,
-                  "femcy_newmark_update: velocity and acceleration are written in place and may alias nothing");
+    FEMCY_TRY(check_newmark_update(c, u_new_vec, u_vec, v_vec, a_vec, beta, gamma, dt));
     return launch_newmark_update(c, c->d_vec[u_new_vec], c->d_vec[u_vec], c->d_vec[v_vec], c->d_vec[a_vec], beta, gamma, dt);
 }
 
@@ -1278,12 +1136,7 @@ int femcy_lumped_mass_create(femcy_ctx* ctx, int32_t nq, const double* Nq, const
                              int32_t* id_out) {
     CTX_OR_FAIL(ctx);
     EXPLICIT_SINGLE_RANK_OR_FAIL("femcy_lumped_mass_create");
-    FEMCY_REQUIRE(c->have_mesh && c->have_element && c->have_pattern,
-                  "femcy_lumped_mass_create needs the mesh, the element tables and the pattern (mesh=%d element=%d "
-                  "pattern=%d)", (int)c->have_mesh, (int)c->have_element, (int)c->have_pattern);
-    FEMCY_REQUIRE(Nq && dNq && wq && id_out, "null mass-rule table or id_out");
-    FEMCY_REQUIRE(nq >= 1 && nq <= 64, "mass rule: %d points (1 .. 64 are supported)", nq);
-    FEMCY_REQUIRE(std::isfinite(rho) && rho > 0.0, "mass: the density must be finite and positive");
+    FEMCY_TRY(check_mass_rule(c, "femcy_lumped_mass_create", nq, Nq, dNq, wq, rho, id_out));
     Ctx::LumpedMass lm;
     DevBuf<double> d_Nq, d_dNq, d_wq;           // the tables are scratch of this call
     DevBuf<double>& d_me = lm.d_me;             // the element shares stay: the element-by-element increment divides by them
@@ -1293,41 +1146,22 @@ int femcy_lumped_mass_create(femcy_ctx* ctx, int32_t nq, const double* Nq, const
     if (!rc && d_me.alloc(sizeof(double) * (size_t)c->ne * c->npe) != hipSuccess) rc = FEMCY_ENOMEM;
     if (!rc && lm.d_m.alloc(sizeof(double) * (size_t)c->nn) != hipSuccess) rc = FEMCY_ENOMEM;
     if (!rc) rc = launch_lumped_mass(c, nq, d_Nq.get(), d_dNq.get(), d_wq.get(), rho, d_me.get(), lm.d_m.get());
-    // ... which the two kernels read: wait for them before the scratch is released at the end of the call
-    if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) {
-        set_error("lumped mass: the kernels failed");
-        rc = FEMCY_EHIP;
-    }
-    if (rc) {
-        if (rc == FEMCY_ENOMEM) set_error("out of device memory for a lumped mass on %d elements", c->ne);
-        return rc;
-    }
-    c->lumped_masses.push_back(std::move(lm));
-    *id_out = (int32_t)c->lumped_masses.size() - 1;
-    return FEMCY_OK;
+    return finish_create(c, rc, c->lumped_masses, lm, "lumped mass: the kernels failed", "a lumped mass", id_out);
 }
-
-#define LUMPED_OR_FAIL(id)                                                                                        \
-    FEMCY_REQUIRE((id) >= 0 && (size_t)(id) < c->lumped_masses.size(), "unknown lumped mass %d", (int)(id)); \
-    const Ctx::LumpedMass& lm = c->lumped_masses[(id)]
 
 int femcy_lumped_mass_get(femcy_ctx* ctx, int32_t id, double* out) {
     CTX_OR_FAIL(ctx);
     EXPLICIT_SINGLE_RANK_OR_FAIL("femcy_lumped_mass_get");
-    LUMPED_OR_FAIL(id);
-    FEMCY_REQUIRE(out, "null output");
-    FEMCY_HIP(hipMemcpyAsync(out, lm.d_m.get(), sizeof(double) * c->nn, hipMemcpyDeviceToHost, c->stream));
-    FEMCY_HIP(hipStreamSynchronize(c->stream));
-    return FEMCY_OK;
+    FEMCY_OBJECT_OR_FAIL(lm, c->lumped_masses, id, "lumped mass");
+    FEMCY_REQUIRE(out, TEXT_NULL_OUTPUT);
+    return download(c, out, lm.d_m.get(), sizeof(double) * c->nn);
 }
 
 int femcy_explicit_create(femcy_ctx* ctx, int32_t lumped_id, int32_t ndofsets, const int32_t* dofset_ids, int32_t* id_out) {
     CTX_OR_FAIL(ctx);
     EXPLICIT_SINGLE_RANK_OR_FAIL("femcy_explicit_create");
-    LUMPED_OR_FAIL(lumped_id);
-    FEMCY_REQUIRE(id_out && ndofsets >= 0 && (ndofsets == 0 || dofset_ids), "femcy_explicit_create: null id_out or DOF-set list");
-    for (int32_t k = 0; k < ndofsets; ++k)
-        FEMCY_REQUIRE(dofset_ids[k] >= 0 && (size_t)dofset_ids[k] < c->dofsets.size(), "unknown DOF set %d", dofset_ids[k]);
+    FEMCY_TRY(check_explicit_create(c, lumped_id, ndofsets, dofset_ids, id_out));
+    const Ctx::LumpedMass& lm = c->lumped_masses[lumped_id];
     Ctx::Explicit ex;
     ex.lumped = lumped_id;
     if (ex.d_minv.alloc(sizeof(double) * (size_t)c->n) != hipSuccess) {
@@ -1348,22 +1182,12 @@ int femcy_explicit_create(femcy_ctx* ctx, int32_t lumped_id, int32_t ndofsets, c
     return FEMCY_OK;
 }
 
-// the argument checks the stepping calls share: the integrator, and a load vector that is none of the three state vectors
-#define EXPLICIT_OR_FAIL(name, id)                                                                                \
-    EXPLICIT_SINGLE_RANK_OR_FAIL(name);                                                                           \
-    FEMCY_REQUIRE((id) >= 0 && (size_t)(id) < c->explicits.size(), "unknown explicit integrator %d", (int)(id));   \
-    const Ctx::Explicit& ex = c->explicits[(id)]
-#define EXPLICIT_RHS_OR_FAIL(name, rhs_vec)                                                                        \
-    VEC_OR_FAIL(rhs_vec);                                                                                          \
-    FEMCY_REQUIRE((rhs_vec) != FEMCY_VEC_DOF && (rhs_vec) != FEMCY_VEC_VEL && (rhs_vec) != FEMCY_VEC_ACC,         \
-                  name ": the load vector may not be one of the state vectors DOF, VEL, ACC")
-
 int femcy_explicit_start(femcy_ctx* ctx, int32_t id, int rhs_vec, double scale) {
     CTX_OR_FAIL(ctx);
     READY_OR_FAIL();
-    EXPLICIT_OR_FAIL("femcy_explicit_start", id);
-    EXPLICIT_RHS_OR_FAIL("femcy_explicit_start", rhs_vec);
-    FEMCY_REQUIRE(std::isfinite(scale), "femcy_explicit_start: the load scale is not finite");
+    EXPLICIT_SINGLE_RANK_OR_FAIL("femcy_explicit_start");
+    FEMCY_TRY(check_explicit_start(c, id, rhs_vec, scale));
+    const Ctx::Explicit& ex = c->explicits[id];
     int rc = force_pass(c, c->d_vec[FEMCY_VEC_DOF]);
     if (rc) return rc;
     return launch_explicit_node(c, ex.d_minv.get(), c->d_vec[rhs_vec], nullptr, scale, 0.0, XN_START);
@@ -1400,28 +1224,26 @@ static int explicit_steps(Ctx* c, const Ctx::Explicit& ex, ExplicitClock* clk, i
 int femcy_explicit_advance(femcy_ctx* ctx, int32_t id, int rhs_vec, int32_t nsteps, double dt, double scale0, double dscale) {
     CTX_OR_FAIL(ctx);
     READY_OR_FAIL();
-    EXPLICIT_OR_FAIL("femcy_explicit_advance", id);
-    EXPLICIT_RHS_OR_FAIL("femcy_explicit_advance", rhs_vec);
-    FEMCY_REQUIRE(nsteps >= 0, "femcy_explicit_advance: %d steps", nsteps);
-    FEMCY_REQUIRE(std::isfinite(dt) && dt > 0.0, "femcy_explicit_advance: the increment must be finite and positive");
-    FEMCY_REQUIRE(std::isfinite(scale0) && std::isfinite(dscale), "femcy_explicit_advance: the load scale is not finite");
-    return explicit_steps(c, ex, nullptr, rhs_vec, nsteps, dt, scale0, dscale);
+    EXPLICIT_SINGLE_RANK_OR_FAIL("femcy_explicit_advance");
+    FEMCY_TRY(check_explicit_advance(c, id, rhs_vec, nsteps, dt, scale0, dscale));
+    return explicit_steps(c, c->explicits[id], nullptr, rhs_vec, nsteps, dt, scale0, dscale);
 }
 
 int femcy_explicit_kinetic_energy(femcy_ctx* ctx, int32_t id, int v_vec, double* out) {
     CTX_OR_FAIL(ctx);
-    EXPLICIT_OR_FAIL("femcy_explicit_kinetic_energy", id);
+    EXPLICIT_SINGLE_RANK_OR_FAIL("femcy_explicit_kinetic_energy");
+    FEMCY_OBJECT_OR_FAIL(ex, c->explicits, id, "explicit integrator");
     VEC_OR_FAIL(v_vec);
-    FEMCY_REQUIRE(out, "null output");
+    FEMCY_REQUIRE(out, TEXT_NULL_OUTPUT);
     return launch_explicit_energy(c, c->lumped_masses[ex.lumped].d_m.get(), c->d_vec[v_vec], out);
 }
 
 int femcy_explicit_stable_dt(femcy_ctx* ctx, int32_t id, double* dt, double* omega_bound) {
     CTX_OR_FAIL(ctx);
-    EXPLICIT_OR_FAIL("femcy_explicit_stable_dt", id);
-    FEMCY_REQUIRE(dt && omega_bound, "null output");
-    FEMCY_REQUIRE(c->have_pattern && c->K_serial == c->pattern_serial,
-                  "femcy_explicit_stable_dt bounds the matrix of the last femcy_assemble_K: assemble first");
+    EXPLICIT_SINGLE_RANK_OR_FAIL("femcy_explicit_stable_dt");
+    FEMCY_OBJECT_OR_FAIL(ex, c->explicits, id, "explicit integrator");
+    FEMCY_REQUIRE(dt && omega_bound, TEXT_NULL_OUTPUT);
+    FEMCY_REQUIRE(c->have_pattern && c->K_serial == c->pattern_serial, TEXT_ASSEMBLE_FIRST);
     double w2 = 0.0;
     int rc = launch_rowabs_bound(c, ex.d_minv.get(), &w2);
     if (rc) return rc;
@@ -1431,8 +1253,6 @@ int femcy_explicit_stable_dt(femcy_ctx* ctx, int32_t id, double* dt, double* ome
 }
 
 // ---- element-by-element increment (*Dynamic, explicit, element by element)
-#define POSITIVE_FINITE(x) (std::isfinite(x) && (x) > 0.0)
-
 // the buffers an integrator allocates on first use: the partial maxima of the bound kernel, the clock
 static int explicit_auto_buffers(Ctx* c, Ctx::Explicit& ex) {
     if (!ex.d_bpart.get() && ex.d_bpart.alloc(sizeof(double) * (size_t)explicit_bound_partials(c)) != hipSuccess) {
@@ -1449,14 +1269,12 @@ static int explicit_auto_buffers(Ctx* c, Ctx::Explicit& ex) {
 int femcy_explicit_element_bound(femcy_ctx* ctx, int32_t id, int u_vec, double s_C, double* omega) {
     CTX_OR_FAIL(ctx);
     READY_OR_FAIL();
-    EXPLICIT_OR_FAIL("femcy_explicit_element_bound", id);
-    VEC_OR_FAIL(u_vec);
-    FEMCY_REQUIRE(omega, "null output");
-    FEMCY_REQUIRE(POSITIVE_FINITE(s_C), "femcy_explicit_element_bound: the material stiffness s_C must be finite and positive");
+    EXPLICIT_SINGLE_RANK_OR_FAIL("femcy_explicit_element_bound");
+    FEMCY_TRY(check_explicit_element_bound(c, id, u_vec, s_C, omega));
     Ctx::Explicit& exm = c->explicits[id];
     int rc = explicit_auto_buffers(c, exm);
     if (rc) return rc;
-    rc = launch_explicit_bound(c, c->d_vec[u_vec], c->lumped_masses[ex.lumped].d_me.get(), s_C, exm.d_bpart.get());
+    rc = launch_explicit_bound(c, c->d_vec[u_vec], c->lumped_masses[exm.lumped].d_me.get(), s_C, exm.d_bpart.get());
     if (rc) return rc;
     double w2 = 0.0;
     if ((rc = launch_explicit_bound_max(c, exm.d_bpart.get(), &w2))) return rc;
@@ -1468,10 +1286,8 @@ int femcy_explicit_auto_begin(femcy_ctx* ctx, int32_t id, int rhs_vec, double s_
                               int32_t ramp) {
     CTX_OR_FAIL(ctx);
     READY_OR_FAIL();
-    EXPLICIT_OR_FAIL("femcy_explicit_auto_begin", id);
-    EXPLICIT_RHS_OR_FAIL("femcy_explicit_auto_begin", rhs_vec);
-    FEMCY_REQUIRE(POSITIVE_FINITE(s_C) && POSITIVE_FINITE(scale_factor) && POSITIVE_FINITE(T),
-                  "femcy_explicit_auto_begin: s_C, the scale factor and T must be finite and positive");
+    EXPLICIT_SINGLE_RANK_OR_FAIL("femcy_explicit_auto_begin");
+    FEMCY_TRY(check_explicit_auto_begin(c, id, rhs_vec, s_C, scale_factor, T));
     Ctx::Explicit& exm = c->explicits[id];
     int rc = explicit_auto_buffers(c, exm);
     if (rc) return rc;
@@ -1484,9 +1300,9 @@ int femcy_explicit_auto_begin(femcy_ctx* ctx, int32_t id, int rhs_vec, double s_
     if ((rc = stage_h2d(c, exm.d_clock.get(), &clk, sizeof(clk)))) return rc;
     const double* u = c->d_vec[FEMCY_VEC_DOF];
     if ((rc = force_pass(c, u))) return rc;
-    if ((rc = launch_explicit_bound(c, u, c->lumped_masses[ex.lumped].d_me.get(), s_C, exm.d_bpart.get()))) return rc;
+    if ((rc = launch_explicit_bound(c, u, c->lumped_masses[exm.lumped].d_me.get(), s_C, exm.d_bpart.get()))) return rc;
     if ((rc = launch_explicit_clock(c, exm.d_bpart.get(), exm.d_clock.get()))) return rc;   // t = 0, the first h
-    if ((rc = launch_explicit_node(c, ex.d_minv.get(), c->d_vec[rhs_vec], exm.d_clock.get(), 0.0, 0.0, XN_START))) return rc;
+    if ((rc = launch_explicit_node(c, exm.d_minv.get(), c->d_vec[rhs_vec], exm.d_clock.get(), 0.0, 0.0, XN_START))) return rc;
     exm.auto_begun = true;
     exm.s_C = s_C;
     return FEMCY_OK;
@@ -1495,21 +1311,18 @@ int femcy_explicit_auto_begin(femcy_ctx* ctx, int32_t id, int rhs_vec, double s_
 int femcy_explicit_auto_advance(femcy_ctx* ctx, int32_t id, int rhs_vec, int32_t nsteps) {
     CTX_OR_FAIL(ctx);
     READY_OR_FAIL();
-    EXPLICIT_OR_FAIL("femcy_explicit_auto_advance", id);
-    EXPLICIT_RHS_OR_FAIL("femcy_explicit_auto_advance", rhs_vec);
-    FEMCY_REQUIRE(nsteps >= 0, "femcy_explicit_auto_advance: %d steps", nsteps);
-    FEMCY_REQUIRE(ex.auto_begun, "femcy_explicit_auto_advance before femcy_explicit_auto_begin");
+    EXPLICIT_SINGLE_RANK_OR_FAIL("femcy_explicit_auto_advance");
+    FEMCY_TRY(check_explicit_auto_advance(c, id, rhs_vec, nsteps));
+    const Ctx::Explicit& ex = c->explicits[id];
     return explicit_steps(c, ex, ex.d_clock.get(), rhs_vec, nsteps, 0.0, 0.0, 0.0);
 }
 
 int femcy_explicit_auto_state(femcy_ctx* ctx, int32_t id, double* t, double* h_last, double* h_min, int64_t* steps_done) {
     CTX_OR_FAIL(ctx);
-    EXPLICIT_OR_FAIL("femcy_explicit_auto_state", id);
-    FEMCY_REQUIRE(t && h_last && h_min && steps_done, "null output");
-    FEMCY_REQUIRE(ex.auto_begun, "femcy_explicit_auto_state before femcy_explicit_auto_begin");
+    EXPLICIT_SINGLE_RANK_OR_FAIL("femcy_explicit_auto_state");
+    FEMCY_TRY(check_explicit_auto_state(c, id, t, h_last, h_min, steps_done));
     ExplicitClock clk;
-    FEMCY_HIP(hipMemcpyAsync(&clk, ex.d_clock.get(), sizeof(clk), hipMemcpyDeviceToHost, c->stream));
-    FEMCY_HIP(hipStreamSynchronize(c->stream));
+    FEMCY_TRY(download(c, &clk, c->explicits[id].d_clock.get(), sizeof(clk)));
     *t = clk.t;
     *h_last = clk.h_last;
     *h_min = clk.steps ? clk.h_min : 0.0;
@@ -1519,10 +1332,7 @@ int femcy_explicit_auto_state(femcy_ctx* ctx, int32_t id, double* t, double* h_l
 
 int femcy_spmv(femcy_ctx* ctx, int x_vec, int y_vec) {
     CTX_OR_FAIL(ctx);
-    FEMCY_REQUIRE(c->have_pattern, "pattern not built");
-    VEC_OR_FAIL(x_vec);
-    VEC_OR_FAIL(y_vec);
-    FEMCY_REQUIRE(x_vec != y_vec, "spmv cannot run in place");
+    FEMCY_TRY(check_two_vectors(c, x_vec, y_vec, TEXT_SPMV_IN_PLACE));
     // (node-order product.  Round 5 tried the PCG's storage-order kernel between two permutations here: 78.0 -> 75.7 us
     // per call on the C3D10 plate, 281 -> 329 us on the 8 M C3D4 plate, whose numbering gathers as well as storage order
     // does -- not adopted; profiles/r05_bench_c3d4_n1_public_spmv_storage_order.json)
@@ -1538,10 +1348,7 @@ int femcy_spmv(femcy_ctx* ctx, int x_vec, int y_vec) {
 int femcy_pcg(femcy_ctx* ctx, int b_vec, int x_vec, double eps, int32_t maxit, int32_t* iters, double* rmax0,
               double* rmax) {
     CTX_OR_FAIL(ctx);
-    FEMCY_REQUIRE(c->have_pattern, "pattern not built");
-    VEC_OR_FAIL(b_vec);
-    VEC_OR_FAIL(x_vec);
-    FEMCY_REQUIRE(b_vec != x_vec, "pcg: b and x must be different vectors");
+    FEMCY_TRY(check_two_vectors(c, b_vec, x_vec, TEXT_PCG_IN_PLACE));
     // reference: at most n iterations -- n of the whole (un-partitioned) system, so that every rank stops at the same count
     if (maxit <= 0) maxit = (int32_t)std::min<int64_t>(c->comm ? c->n_global : c->n, INT32_MAX);
     return pcg_solve(c, c->d_vec[b_vec], c->d_vec[x_vec], eps, maxit, iters, rmax0, rmax);
@@ -1549,23 +1356,20 @@ int femcy_pcg(femcy_ctx* ctx, int b_vec, int x_vec, double eps, int32_t maxit, i
 
 int femcy_direct_solve(femcy_ctx* ctx, int b_vec, int x_vec, femcy_direct_info* info) {
     CTX_OR_FAIL(ctx);
-    FEMCY_REQUIRE(c->have_pattern, "pattern not built");
-    VEC_OR_FAIL(b_vec);
-    VEC_OR_FAIL(x_vec);
-    FEMCY_REQUIRE(b_vec != x_vec, "direct solve: b and x must be different vectors");
+    FEMCY_TRY(check_two_vectors(c, b_vec, x_vec, TEXT_DIRECT_IN_PLACE));
     return direct_solve(c, c->d_vec[b_vec], c->d_vec[x_vec], info);
 }
 
 int femcy_direct_plan(femcy_ctx* ctx, femcy_direct_info* info) {
     CTX_OR_FAIL(ctx);
-    FEMCY_REQUIRE(c->have_pattern, "pattern not built");
+    FEMCY_TRY(check_direct_plan(c, info));
     return direct_plan(c, info);
 }
 
 // ------------------------------------------------------------------------------ post-processing
 int femcy_compute_strain_stress(femcy_ctx* ctx, int u_vec, int large) {
     CTX_OR_FAIL(ctx);
-    FEMCY_REQUIRE(c->have_mesh && c->have_element && c->have_material, "context not fully defined");
+    FEMCY_REQUIRE(c->have_mesh && c->have_element && c->have_material, TEXT_NOT_DEFINED);
     VEC_OR_FAIL(u_vec);
     // get_deformation_gradient: F only -- dsdx, vol and (for nlgeom) the Cauchy stress of the last
     // constitutiveOfLargeDeform stay as they are, exactly as in the reference
@@ -1580,7 +1384,7 @@ int femcy_compute_strain_stress(femcy_ctx* ctx, int u_vec, int large) {
 
 int femcy_elastic_energy(femcy_ctx* ctx, int u_vec, double* total) {
     CTX_OR_FAIL(ctx);
-    FEMCY_REQUIRE(c->have_mesh && c->have_element && c->have_material && total, "context not fully defined");
+    FEMCY_REQUIRE(c->have_mesh && c->have_element && c->have_material && total, TEXT_NOT_DEFINED);
     VEC_OR_FAIL(u_vec);
     int rc = ensure_gp_stress(c);
     if (rc) return rc;
@@ -1591,10 +1395,7 @@ int femcy_elastic_energy(femcy_ctx* ctx, int u_vec, double* total) {
 
 int femcy_elastic_energy_small(femcy_ctx* ctx, int u_vec, double* total) {
     CTX_OR_FAIL(ctx);
-    FEMCY_REQUIRE(c->have_mesh && c->have_element && c->have_material && total, "context not fully defined");
-    VEC_OR_FAIL(u_vec);
-    FEMCY_REQUIRE(c->mat_kind != FEMCY_MAT_NEOHOOKE, "femcy_elastic_energy_small: a neo-Hookean material has no small-strain "
-                  "energy (linear materials only)");
+    FEMCY_TRY(check_elastic_energy_small(c, u_vec, total));
     int rc = ensure_gp_stress(c);
     if (rc) return rc;
     if ((rc = launch_geom(c, c->d_vec[u_vec], GEOM_F))) return rc;
@@ -1606,19 +1407,18 @@ int femcy_elastic_energy_small(femcy_ctx* ctx, int u_vec, double* total) {
 
 int femcy_extrapolate(femcy_ctx* ctx, int gp_field, int comp, const double* E, double* out) {
     CTX_OR_FAIL(ctx);
-    FEMCY_REQUIRE(c->have_element && E && out, "element tables not set or null arguments");
-    const double* field = nullptr;
     int width = 1;
+    FEMCY_TRY(check_extrapolate(c, gp_field, comp, E, out, &width));
+    const double* field = nullptr;
     switch (gp_field) {
         case FEMCY_GP_VOL: field = c->d_vol; break;
         case FEMCY_GP_MISES: field = c->d_mises; break;
         case FEMCY_GP_ENERGY: field = c->d_energy; break;
-        case FEMCY_GP_F: field = c->d_F; width = c->dm * c->dm; break;
-        case FEMCY_GP_SIGMA: field = c->d_sigma; width = c->dm * c->dm; break;
-        case FEMCY_GP_STRAIN: field = c->d_strain; width = c->dm * c->dm; break;
-        default: set_error("field %d cannot be extrapolated", gp_field); return FEMCY_EINVAL;
+        case FEMCY_GP_F: field = c->d_F; break;
+        case FEMCY_GP_SIGMA: field = c->d_sigma; break;
+        case FEMCY_GP_STRAIN: field = c->d_strain; break;
+        default: return FEMCY_EINVAL;             // not reached: check_extrapolate has refused everything else
     }
-    FEMCY_REQUIRE(comp >= 0 && comp < width, "component %d out of range for field %d", comp, gp_field);
     if (gp_field == FEMCY_GP_F || gp_field == FEMCY_GP_SIGMA) {
         int rcl = ensure_gp_stress(c);
         if (rcl) return rcl;
@@ -1649,7 +1449,7 @@ static int download_K(Ctx* c, std::vector<double>& vals) {
 
 int femcy_get_K_ell(femcy_ctx* ctx, int32_t* ij, double* A) {
     CTX_OR_FAIL(ctx);
-    FEMCY_REQUIRE(c->have_pattern && ij && A, "pattern not built or null outputs");
+    FEMCY_REQUIRE(c->have_pattern && ij && A, TEXT_GET_K);
     std::vector<double> vals;
     int rc = download_K(c, vals);
     if (rc) return rc;
@@ -1678,7 +1478,7 @@ int femcy_get_K_ell(femcy_ctx* ctx, int32_t* ij, double* A) {
 
 int femcy_get_K_bsr(femcy_ctx* ctx, int32_t* rowptr, int32_t* colidx, double* out) {
     CTX_OR_FAIL(ctx);
-    FEMCY_REQUIRE(c->have_pattern && rowptr && colidx && out, "pattern not built or null outputs");
+    FEMCY_REQUIRE(c->have_pattern && rowptr && colidx && out, TEXT_GET_K);
     std::vector<double> vals;
     int rc = download_K(c, vals);
     if (rc) return rc;
@@ -1704,7 +1504,7 @@ int femcy_get_K_bsr(femcy_ctx* ctx, int32_t* rowptr, int32_t* colidx, double* ou
 
 int femcy_get_gp_field(femcy_ctx* ctx, int which, double* out) {
     CTX_OR_FAIL(ctx);
-    FEMCY_REQUIRE(c->have_element && out, "element tables not set or null output");
+    FEMCY_TRY(check_get_gp_field(c, which, out));
     const size_t ngp = (size_t)c->ne * c->nGP;
     const double* src = nullptr;
     size_t count = 0;
@@ -1716,7 +1516,7 @@ int femcy_get_gp_field(femcy_ctx* ctx, int which, double* out) {
         case FEMCY_GP_STRAIN: src = c->d_strain; count = ngp * c->dm * c->dm; break;
         case FEMCY_GP_MISES: src = c->d_mises; count = ngp; break;
         case FEMCY_GP_ENERGY: src = c->d_energy; count = ngp; break;
-        default: set_error("unknown Gauss-point field %d", which); return FEMCY_EINVAL;
+        default: return FEMCY_EINVAL;             // not reached: check_get_gp_field has refused everything else
     }
     if (which == FEMCY_GP_F || which == FEMCY_GP_SIGMA) {
         int rcl = ensure_gp_stress(c);
@@ -1729,7 +1529,7 @@ int femcy_get_gp_field(femcy_ctx* ctx, int which, double* out) {
 
 int femcy_timing(femcy_ctx* ctx, femcy_timing_t* out) {
     CTX_OR_FAIL(ctx);
-    FEMCY_REQUIRE(out, "null output");
+    FEMCY_REQUIRE(out, TEXT_NULL_OUTPUT);
     timing_collect(c);
     *out = c->timing;
     return FEMCY_OK;
@@ -1764,7 +1564,7 @@ int femcy_probe_mailbox(femcy_ctx* ctx, int32_t rounds, double* us_per_round) {
 }
 int femcy_persist_streamed_bytes(femcy_ctx* ctx, int64_t* bytes) {
     CTX_OR_FAIL(ctx);
-    FEMCY_REQUIRE(bytes, "null output");
+    FEMCY_REQUIRE(bytes, TEXT_NULL_OUTPUT);
     FEMCY_REQUIRE(c->have_pattern, "femcy_build_pattern must come first");
     *bytes = persist_streamed_bytes(c);
     return FEMCY_OK;
@@ -1804,7 +1604,7 @@ int femcy_comm_init(femcy_ctx* ctx, int32_t rank, int32_t nranks, const void* id
                     const int32_t* iface_local_dofs, const int32_t* iface_global_slot, int32_t niface_global,
                     const uint8_t* owner) {
     CTX_OR_FAIL(ctx);
-    FEMCY_REQUIRE(c->have_mesh, "femcy_set_mesh must come first");
+    FEMCY_TRY(check_have_mesh(c));
     FEMCY_REQUIRE(nranks >= 1 && nranks <= 512 && rank >= 0 && rank < nranks && id128, "bad rank/nranks");
     FEMCY_REQUIRE(niface_local >= 0 && niface_global >= niface_local, "bad interface sizes");
     FEMCY_REQUIRE(owner, "owner mask required");

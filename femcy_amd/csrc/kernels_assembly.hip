@@ -1702,12 +1702,6 @@ int launch_energy_sum(Ctx* c, double* total) {
 }
 
 // ------------------------------------------------------------------------------- host launchers
-// what an element pass answers for a mesh whose family dispatch_element does not list
-static int no_kernel(const Ctx* c, const char* what) {
-    set_error("no %s kernel instantiated for npe=%d dm=%d", what, c->npe, c->dm);
-    return FEMCY_ENOKERNEL;
-}
-
 // node sums of per-element nodal forces d_fe [ne][npe][dm] into d_f [n]
 static void launch_node_sums(Ctx* c, const double* d_fe, double* d_f) {
     const int bs = 256;

@@ -650,14 +650,12 @@ int direct_set_update_variant(Ctx* c, int64_t v) {
     return FEMCY_OK;
 }
 
-int direct_set_max_bytes(Ctx* c, int64_t bytes) {
-    FEMCY_REQUIRE(bytes >= (int64_t)1 << 20, "direct solve: the band limit must be at least 1 MiB");
+int direct_set_max_bytes(Ctx* c, int64_t bytes) {      // the range: check_option (api_checks.hpp)
     state_of(c).max_bytes = bytes;
     return FEMCY_OK;
 }
 
-int direct_plan(Ctx* c, femcy_direct_info* info) {
-    FEMCY_REQUIRE(info != nullptr, "femcy_direct_plan: info must not be null");
+int direct_plan(Ctx* c, femcy_direct_info* info) {      // info is not null: check_direct_plan (api_checks.hpp)
     FEMCY_REQUIRE(c->dm == 2 || c->dm == 3, "direct solve: dm = %d", c->dm);
     *info = femcy_direct_info{};
     DirectState& st = state_of(c);

@@ -25,28 +25,22 @@
 #include <new>
 #include <vector>
 #include "../../include/femcy.h"
+#include "../csrc/api_checks.hpp"
 #include "../csrc/band_order.hpp"
 #include "../csrc/element_dispatch.hpp"
 #include "../csrc/element_math.hpp"
 
 using namespace femcy;
 
-namespace {
-
-thread_local char g_err[1024] = "";
-void set_error(const char* fmt, ...) {
+static thread_local char g_err[1024] = "";
+void femcy::set_error(const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
 }
-#define REQUIRE(cond, ...)          \
-    do {                            \
-        if (!(cond)) {              \
-            set_error(__VA_ARGS__); \
-            return FEMCY_EINVAL;    \
-        }                           \
-    } while (0)
+
+namespace {
 
 double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -91,10 +85,10 @@ struct femcy_ctx {
     int64_t n = 0;
     std::vector<double> nodes, dN, w;
     std::vector<int32_t> elems;
-    double C[36] = {0}, params[4] = {0, 0, 0, 0}, cubic[3] = {0, 0, 0};
+    double h_C[36] = {0}, mat_params[4] = {0, 0, 0, 0}, cubic[3] = {0, 0, 0};
     int32_t mat_kind = -1;
     bool C_is_cubic = false, have_mesh = false, have_element = false, have_material = false, have_pattern = false;
-    bool asm_ran = false;                 // femcy_get_assembly_used
+    int asm_used = -1;                    // the mode the last assembly ran (femcy_get_assembly_used)
     // block-CSR matrix: row a = blocks rowptr[a] .. rowptr[a+1], diagonal first, then ascending columns
     std::vector<int64_t> rowptr;
     std::vector<int32_t> col;
@@ -122,15 +116,14 @@ struct femcy_ctx {
     int64_t direct_max_bytes = (int64_t)48 << 30;
 };
 
+template <>
+bool femcy::vec_allocated(const femcy_ctx* c, int v) {
+    return !c->vec[v].empty();
+}
+
 namespace {
 
 enum : unsigned { GEOM_DSDX = 1, GEOM_F = 2, GEOM_SIGMA = 4, GEOM_FE = 8 };
-
-// what an element pass answers for a mesh whose family dispatch_element (csrc/element_dispatch.hpp) does not list
-int no_kernel(const femcy_ctx* c, const char* what) {
-    set_error("no %s kernel instantiated for npe=%d dm=%d", what, c->npe, c->dm);
-    return FEMCY_ENOKERNEL;
-}
 
 // get_dsdx_and_vol (stiffnessMtrx.py:132-150), get_deformation_gradient (:532-556), constitutiveOfLargeDeform and the
 // per-element nodal forces of assemble_nodal_force_GN (:620-644): the element pass of the device's k_geom
@@ -194,7 +187,7 @@ void geom_pass(femcy_ctx* c, const double* u, unsigned what) {
                     for (int i = 0; i < DM; ++i)
                         for (int j = 0; j < DM; ++j) c->F[gp * DM * DM + i * DM + j] = F[i][j];
                 if (what & (GEOM_SIGMA | GEOM_FE)) {
-                    cauchy_large<DM>(c->mat_kind, c->C, c->params[0], c->params[1], F, sig);
+                    cauchy_large<DM>(c->mat_kind, c->h_C, c->mat_params[0], c->mat_params[1], F, sig);
                     if (what & GEOM_SIGMA)
                         for (int i = 0; i < DM; ++i)
                             for (int j = 0; j < DM; ++j) c->sigma[gp * DM * DM + i * DM + j] = sig[i][j];
@@ -257,7 +250,7 @@ void assemble(femcy_ctx* c) {
     const bool consistent = c->opt_tangent == 1;
     const bool neo = c->mat_kind == FEMCY_MAT_NEOHOOKE;
     const int s = DM == 3 ? 6 : 3;
-    const double lam = c->C[0 * s + 1], mu = c->C[(s - 1) * s + (s - 1)];
+    const double lam = c->h_C[0 * s + 1], mu = c->h_C[(s - 1) * s + (s - 1)];
 #pragma omp parallel for schedule(dynamic, 64)
     for (int32_t a = 0; a < c->nn; ++a) {
         double* row = c->K.data() + c->rowptr[a] * DD;
@@ -275,11 +268,11 @@ void assemble(femcy_ctx* c) {
                     const double* gb = c->dsdx.data() + (gp * npe + lb) * DM;
                     if (consistent)
                         kblock_consistent<DM>(ga, gb, c->F.data() + gp * DD, c->sigma.data() + gp * DD, neo, lam, mu,
-                                              c->params[0], c->params[1], c->vol[gp], blk);
+                                              c->mat_params[0], c->mat_params[1], c->vol[gp], blk);
                     else if (DM == 3 && c->C_is_cubic)
                         kblock_cubic3(ga, gb, c->cubic[0], c->cubic[1], c->cubic[2], c->vol[gp], reinterpret_cast<double(&)[9]>(blk));
                     else
-                        kblock_add<DM>(ga, gb, c->C, c->vol[gp], blk);
+                        kblock_add<DM>(ga, gb, c->h_C, c->vol[gp], blk);
                 }
                 double* dst = c->K.data() + c->eslot[((int64_t)e * npe + la) * npe + lb] * DD;
                 for (int q = 0; q < DD; ++q) dst[q] += blk[q];
@@ -288,14 +281,15 @@ void assemble(femcy_ctx* c) {
     }
 }
 int assemble_K(femcy_ctx* c) {
-    c->asm_ran = false;
+    c->asm_used = -1;
     if (c->opt_tangent == 1 && c->mat_kind == FEMCY_MAT_PSTRESS) {
         set_error("the consistent tangent is not available for plane stress");
         return FEMCY_EINVAL;
     }
     const double t = c->opt_timing ? now_ms() : 0.0;
     if (c->dm == 3) assemble<3>(c); else assemble<2>(c);
-    c->asm_ran = c->have_K = true;
+    c->asm_used = FEMCY_ASM_ATOMIC;      // one assembly here: owner-computes by row, no mode to choose
+    c->have_K = true;
     if (c->opt_timing) {
         c->timing.assemble_ms += now_ms() - t;
         c->timing.assemble_launches++;
@@ -375,35 +369,11 @@ void dirichlet_zero(femcy_ctx* c, const int32_t* dofs, int32_t k, double* resid)
     }
 }
 
-int check_vec(femcy_ctx* c, int v) {
-    if (v < 0 || v >= FEMCY_VEC_COUNT) {
-        set_error("vector id %d out of range", v);
-        return FEMCY_EINVAL;
-    }
-    if (c->vec[v].empty()) {
-        set_error("vectors are allocated by femcy_set_mesh; call it first");
-        return FEMCY_EINVAL;
-    }
-    return FEMCY_OK;
-}
-
 }  // namespace
 
-#define CTX_OR_FAIL(ctx)              \
-    if (!(ctx)) {                     \
-        set_error("null context");    \
-        return FEMCY_EINVAL;          \
-    }                                 \
+#define CTX_OR_FAIL(ctx)     \
+    FEMCY_REQUIRE((ctx), TEXT_NULL_CONTEXT); \
     femcy_ctx* c = (ctx)
-#define VEC_OR_FAIL(v)               \
-    {                                \
-        int _rc = check_vec(c, (v)); \
-        if (_rc) return _rc;         \
-    }
-#define READY_OR_FAIL()                                                                                         \
-    REQUIRE(c->have_mesh&& c->have_element&& c->have_material&& c->have_pattern,                                \
-            "context not fully defined (mesh=%d element=%d material=%d pattern=%d)", (int)c->have_mesh,        \
-            (int)c->have_element, (int)c->have_material, (int)c->have_pattern)
 
 extern "C" {
 
@@ -411,10 +381,7 @@ const char* femcy_last_error(void) { return g_err; }
 int femcy_version(void) { return 100; }
 
 int femcy_ctx_create(int device, femcy_ctx** out) {
-    if (!out) {
-        set_error("out is null");
-        return FEMCY_EINVAL;
-    }
+    FEMCY_REQUIRE(out, TEXT_CTX_OUT_NULL);
     if (device != 0) {                              // one host = device 0 (the caller's bookkeeping stays honest)
         set_error("device %d out of range (the CPU backend has one device: 0)", device);
         return FEMCY_EINVAL;
@@ -430,32 +397,25 @@ int femcy_ctx_destroy(femcy_ctx* ctx) {
 
 int femcy_set_option(femcy_ctx* ctx, int option, int64_t value) {
     CTX_OR_FAIL(ctx);
+    FEMCY_TRY(check_option(c, option, value));
     switch (option) {
         case FEMCY_OPT_TANGENT:
-            REQUIRE(value == 0 || value == 1, "tangent: 0 (reference) or 1 (consistent)");
             c->opt_tangent = (int)value;
             return FEMCY_OK;
         case FEMCY_OPT_TIMING:
             c->opt_timing = value > 0 ? 1 : 0;
             return FEMCY_OK;
-        case FEMCY_OPT_SELL_SIGMA:
-            REQUIRE(!c->have_pattern, "set the sorting window before femcy_build_pattern");
-            return FEMCY_OK;
         // schedule / layout knobs of the device kernels: accepted, without effect on the host
         case FEMCY_OPT_ASSEMBLY: case FEMCY_OPT_PCG_POLL: case FEMCY_OPT_SPMV_VARIANT: case FEMCY_OPT_EW_GRID:
         case FEMCY_OPT_PCG_GRAPH: case FEMCY_OPT_PCG_PERSIST: case FEMCY_OPT_PCG_SMALL: case FEMCY_OPT_OVERLAP:
-        case FEMCY_OPT_PCG_PERSIST_MULTI: case FEMCY_OPT_PCG_STORAGE_ORDER:
-            return FEMCY_OK;
-        case FEMCY_OPT_NODE_ORDER:
-            REQUIRE(!c->have_pattern, "set the node order before femcy_build_pattern");
+        case FEMCY_OPT_PCG_PERSIST_MULTI: case FEMCY_OPT_PCG_STORAGE_ORDER: case FEMCY_OPT_SELL_SIGMA: case FEMCY_OPT_NODE_ORDER:
             return FEMCY_OK;
         case FEMCY_OPT_DIRECT_MAX_BYTES:
-            REQUIRE(value >= (int64_t)1 << 20, "direct solve: the band limit must be at least 1 MiB");
             c->direct_max_bytes = value;
             return FEMCY_OK;
         default:
             if (option >= 100 && option <= 119) return FEMCY_OK;   // FEMCY_TUNE_*: device tuning knobs
-            set_error("unknown option %d", option);
+            set_error(TEXT_UNKNOWN_OPTION, option);
             return FEMCY_EINVAL;
     }
 }
@@ -468,13 +428,7 @@ int femcy_sync(femcy_ctx* ctx) {
 int femcy_set_mesh(femcy_ctx* ctx, int32_t nn, int32_t dm, const double* nodes, int32_t ne, int32_t npe,
                    const int32_t* elems) {
     CTX_OR_FAIL(ctx);
-    REQUIRE(nodes && elems, "null mesh arrays");
-    REQUIRE(nn > 0 && ne > 0, "empty mesh (nn=%d, ne=%d)", nn, ne);
-    REQUIRE(dm == 2 || dm == 3, "dm must be 2 or 3, got %d", dm);
-    REQUIRE(npe >= 2 && npe <= 27, "npe out of range: %d", npe);
-    for (int64_t k = 0; k < (int64_t)ne * npe; ++k)
-        REQUIRE(elems[k] >= 0 && elems[k] < nn, "element %lld references node %d outside [0,%d)", (long long)(k / npe),
-                elems[k], nn);
+    FEMCY_TRY(check_set_mesh(nn, dm, nodes, ne, npe, elems));
     c->dofsets.clear();
     c->loadsets.clear();
     c->bodyloads.clear();
@@ -500,10 +454,7 @@ int femcy_set_mesh(femcy_ctx* ctx, int32_t nn, int32_t dm, const double* nodes, 
 
 int femcy_set_element(femcy_ctx* ctx, int32_t nGP, const double* dN, const double* w, int32_t voigt_kind) {
     CTX_OR_FAIL(ctx);
-    REQUIRE(c->have_mesh, "femcy_set_mesh must come first");
-    REQUIRE(dN && w && nGP >= 1 && nGP <= 64, "bad element tables (nGP=%d)", nGP);
-    REQUIRE((voigt_kind == FEMCY_VOIGT_2D && c->dm == 2) || (voigt_kind == FEMCY_VOIGT_3D && c->dm == 3),
-            "voigt kind %d does not match dm=%d", voigt_kind, c->dm);
+    FEMCY_TRY(check_set_element(c, nGP, dN, w, voigt_kind));
     c->nGP = nGP;
     c->s = c->dm == 2 ? 3 : 6;
     c->dN.assign(dN, dN + (size_t)nGP * c->npe * c->dm);
@@ -524,14 +475,9 @@ int femcy_set_element(femcy_ctx* ctx, int32_t nGP, const double* dN, const doubl
 
 int femcy_set_material(femcy_ctx* ctx, int32_t kind, const double* C, const double* params, int32_t nparams) {
     CTX_OR_FAIL(ctx);
-    REQUIRE(c->have_mesh, "femcy_set_mesh must come first");
-    REQUIRE(C, "null C");
-    REQUIRE(kind >= FEMCY_MAT_LIN3D && kind <= FEMCY_MAT_NEOHOOKE, "unknown material kind %d", kind);
-    const bool ok_dm = kind == FEMCY_MAT_NEOHOOKE || ((kind == FEMCY_MAT_LIN3D) == (c->dm == 3));
-    REQUIRE(ok_dm, "material kind %d does not match dm=%d", kind, c->dm);
-    REQUIRE(nparams >= 2 && params, "material needs 2 parameters");
+    FEMCY_TRY(check_set_material(c, kind, C, params, nparams));
     const int s = c->dm == 2 ? 3 : 6;
-    for (int i = 0; i < s * s; ++i) c->C[i] = C[i];
+    for (int i = 0; i < s * s; ++i) c->h_C[i] = C[i];
     c->mat_kind = kind;
     c->C_is_cubic = false;
     if (s == 6) {   // cubic pattern (exact comparisons), as on the device
@@ -545,7 +491,7 @@ int femcy_set_material(femcy_ctx* ctx, int32_t kind, const double* C, const doub
         c->C_is_cubic = ok;
         c->cubic[0] = c11; c->cubic[1] = c12; c->cubic[2] = c44;
     }
-    for (int i = 0; i < 4; ++i) c->params[i] = (i < nparams) ? params[i] : 0.0;
+    for (int i = 0; i < 4; ++i) c->mat_params[i] = (i < nparams) ? params[i] : 0.0;
     c->have_material = true;
     c->post_small = false;
     return FEMCY_OK;
@@ -554,7 +500,7 @@ int femcy_set_material(femcy_ctx* ctx, int32_t kind, const double* C, const doub
 // body.get_nodeEles / get_coElement_nodes + sparseIJ (body.py:165-194, stiffnessMtrx.py:70-89)
 int femcy_build_pattern(femcy_ctx* ctx) {
     CTX_OR_FAIL(ctx);
-    REQUIRE(c->have_mesh, "femcy_set_mesh must come first");
+    FEMCY_TRY(check_have_mesh(c));
     const int32_t nn = c->nn, ne = c->ne, npe = c->npe;
     c->ne_ptr.assign((size_t)nn + 1, 0);
     for (int64_t k = 0; k < (int64_t)ne * npe; ++k) c->ne_ptr[c->elems[k] + 1]++;
@@ -626,14 +572,14 @@ int femcy_build_pattern(femcy_ctx* ctx) {
 // one assembly here: a serial scatter element by element in ascending element order
 int femcy_get_assembly_used(femcy_ctx* ctx, int32_t* mode) {
     CTX_OR_FAIL(ctx);
-    REQUIRE(mode && c->asm_ran, "no assembly has run on this context");
-    *mode = FEMCY_ASM_ATOMIC;
+    FEMCY_TRY(check_get_assembly_used(c, mode));
+    *mode = c->asm_used;
     return FEMCY_OK;
 }
 
 int femcy_get_pattern_info(femcy_ctx* ctx, femcy_pattern_info* out) {
     CTX_OR_FAIL(ctx);
-    REQUIRE(c->have_pattern && out, "pattern not built");
+    FEMCY_REQUIRE(c->have_pattern && out, TEXT_PATTERN_NOT_BUILT);
     out->n = c->n;
     out->nnzb = c->rowptr[c->nn];
     out->nnz = out->nnzb * c->dm * c->dm;
@@ -646,7 +592,7 @@ int femcy_get_pattern_info(femcy_ctx* ctx, femcy_pattern_info* out) {
 }
 int femcy_get_node_order(femcy_ctx* ctx, int32_t* used, double* lines) {
     CTX_OR_FAIL(ctx);
-    REQUIRE(c->have_pattern, "pattern not built");
+    FEMCY_REQUIRE(c->have_pattern, TEXT_PATTERN_NOT_BUILT);
     if (used) *used = 0;                                  // the host backend keeps the caller's numbering (block CSR)
     if (lines)
         for (int k = 0; k < 7; ++k) lines[k] = 0.0;
@@ -656,15 +602,13 @@ int femcy_get_node_order(femcy_ctx* ctx, int32_t* used, double* lines) {
 // ---------------------------------------------------------------------------- vector plumbing
 int femcy_vec_upload(femcy_ctx* ctx, int vec, const double* src, int64_t n) {
     CTX_OR_FAIL(ctx);
-    VEC_OR_FAIL(vec);
-    REQUIRE(src && n == c->n, "upload length %lld != n = %lld", (long long)n, (long long)c->n);
+    FEMCY_TRY(check_vec_transfer(c, "upload", vec, src, n));
     std::memcpy(c->vec[vec].data(), src, sizeof(double) * n);
     return FEMCY_OK;
 }
 int femcy_vec_download(femcy_ctx* ctx, int vec, double* dst, int64_t n) {
     CTX_OR_FAIL(ctx);
-    VEC_OR_FAIL(vec);
-    REQUIRE(dst && n == c->n, "download length %lld != n = %lld", (long long)n, (long long)c->n);
+    FEMCY_TRY(check_vec_transfer(c, "download", vec, dst, n));
     std::memcpy(dst, c->vec[vec].data(), sizeof(double) * n);
     return FEMCY_OK;
 }
@@ -685,8 +629,7 @@ int femcy_vec_scatter(femcy_ctx* ctx, int vec, const int32_t* idx, const double*
     CTX_OR_FAIL(ctx);
     VEC_OR_FAIL(vec);
     if (k == 0) return FEMCY_OK;
-    REQUIRE(idx && vals && k > 0, "bad scatter arguments");
-    for (int32_t i = 0; i < k; ++i) REQUIRE(idx[i] >= 0 && idx[i] < c->n, "scatter index %d out of range", idx[i]);
+    FEMCY_TRY(check_vec_scatter(c, idx, vals, k));
     for (int32_t i = 0; i < k; ++i) c->vec[vec][idx[i]] = vals[i];
     return FEMCY_OK;
 }
@@ -717,7 +660,7 @@ int femcy_vec_scale(femcy_ctx* ctx, int vec, double s) {
 int femcy_vec_norm(femcy_ctx* ctx, int vec, double* rms) {
     CTX_OR_FAIL(ctx);
     VEC_OR_FAIL(vec);
-    REQUIRE(rms, "null output");
+    FEMCY_REQUIRE(rms, TEXT_NULL_OUTPUT);
     const double* p = c->vec[vec].data();
     const int64_t nchunk = (c->n + CHUNK - 1) / CHUNK;
     std::vector<double> part((size_t)nchunk);
@@ -736,7 +679,7 @@ int femcy_vec_norm(femcy_ctx* ctx, int vec, double* rms) {
 int femcy_vec_absmax(femcy_ctx* ctx, int vec, double* out) {
     CTX_OR_FAIL(ctx);
     VEC_OR_FAIL(vec);
-    REQUIRE(out, "null output");
+    FEMCY_REQUIRE(out, TEXT_NULL_OUTPUT);
     double m = 0.0;
     for (double v : c->vec[vec]) m = std::fmax(m, nan_to_inf_abs(v));
     *out = m;
@@ -774,14 +717,6 @@ int femcy_residual_and_K(femcy_ctx* ctx, int u_vec, int f_vec) {
     return assemble_K(c);
 }
 
-static int check_dofs(femcy_ctx* c, const int32_t* dofs, int32_t k) {
-    for (int32_t i = 0; i < k; ++i)
-        if (dofs[i] < 0 || dofs[i] >= c->n) {
-            set_error("constrained DOF %d out of range", dofs[i]);
-            return FEMCY_EINVAL;
-        }
-    return FEMCY_OK;
-}
 // dirichletBC_linearEquations (stiffnessMtrx.py:279-307), race-free: rhs -= K s with the not yet modified matrix
 static int dirichlet_linear(femcy_ctx* c, const int32_t* dofs, const double* vals, double value, int32_t k, int rhs_vec) {
     bool any = false;
@@ -804,10 +739,7 @@ int femcy_apply_dirichlet_linear(femcy_ctx* ctx, const int32_t* dofs, const doub
     READY_OR_FAIL();
     VEC_OR_FAIL(rhs_vec);
     if (k == 0) return FEMCY_OK;
-    REQUIRE(k > 0 && dofs && vals, "bad Dirichlet arguments");
-    REQUIRE(rhs_vec != FEMCY_VEC_TMP0 && rhs_vec != FEMCY_VEC_TMP1, "rhs may not alias the scratch vectors");
-    int rc = check_dofs(c, dofs, k);
-    if (rc) return rc;
+    FEMCY_TRY(check_dirichlet_linear(c, dofs, vals, k, rhs_vec));
     return dirichlet_linear(c, dofs, vals, 0.0, k, rhs_vec);
 }
 int femcy_apply_dirichlet_newton(femcy_ctx* ctx, const int32_t* dofs, int32_t k, int residual_vec) {
@@ -815,30 +747,24 @@ int femcy_apply_dirichlet_newton(femcy_ctx* ctx, const int32_t* dofs, int32_t k,
     READY_OR_FAIL();
     VEC_OR_FAIL(residual_vec);
     if (k == 0) return FEMCY_OK;
-    REQUIRE(dofs && k > 0, "bad Dirichlet arguments");
-    int rc = check_dofs(c, dofs, k);
-    if (rc) return rc;
+    FEMCY_TRY(check_dirichlet_newton(c, dofs, k));
     dirichlet_zero(c, dofs, k, c->vec[residual_vec].data());
     return FEMCY_OK;
 }
 int femcy_dofset_create(femcy_ctx* ctx, const int32_t* dofs, int32_t k, int32_t* id_out) {
     CTX_OR_FAIL(ctx);
-    REQUIRE(c->have_mesh && id_out && k >= 0 && (k == 0 || dofs), "bad dofset arguments");
-    for (int32_t i = 0; i < k; ++i) REQUIRE(dofs[i] >= 0 && dofs[i] < c->n, "DOF %d out of range", dofs[i]);
+    FEMCY_TRY(check_dofset_create(c, dofs, k, id_out));
     DofSet ds;
     if (k) ds.dofs.assign(dofs, dofs + k);
     c->dofsets.push_back(ds);
     *id_out = (int32_t)c->dofsets.size() - 1;
     return FEMCY_OK;
 }
-#define DOFSET_OR_FAIL(id)                                                                      \
-    REQUIRE((id) >= 0 && (size_t)(id) < c->dofsets.size(), "unknown dofset %d", (int)(id)); \
-    const DofSet& ds = c->dofsets[(id)]
 int femcy_dofset_dirichlet_newton(femcy_ctx* ctx, int32_t id, int residual_vec) {
     CTX_OR_FAIL(ctx);
     READY_OR_FAIL();
     VEC_OR_FAIL(residual_vec);
-    DOFSET_OR_FAIL(id);
+    FEMCY_OBJECT_OR_FAIL(ds, c->dofsets, id, "dofset");
     dirichlet_zero(c, ds.dofs.data(), (int32_t)ds.dofs.size(), c->vec[residual_vec].data());
     return FEMCY_OK;
 }
@@ -846,31 +772,31 @@ int femcy_dofset_dirichlet_linear(femcy_ctx* ctx, int32_t id, double value, int 
     CTX_OR_FAIL(ctx);
     READY_OR_FAIL();
     VEC_OR_FAIL(rhs_vec);
-    DOFSET_OR_FAIL(id);
-    REQUIRE(rhs_vec != FEMCY_VEC_TMP0 && rhs_vec != FEMCY_VEC_TMP1, "rhs may not alias the scratch vectors");
+    FEMCY_OBJECT_OR_FAIL(ds, c->dofsets, id, "dofset");
+    FEMCY_TRY(check_rhs_not_scratch(rhs_vec));
     if (ds.dofs.empty()) return FEMCY_OK;
     return dirichlet_linear(c, ds.dofs.data(), nullptr, value, (int32_t)ds.dofs.size(), rhs_vec);
 }
 int femcy_dofset_fill(femcy_ctx* ctx, int32_t id, int vec, double value) {
     CTX_OR_FAIL(ctx);
     VEC_OR_FAIL(vec);
-    DOFSET_OR_FAIL(id);
+    FEMCY_OBJECT_OR_FAIL(ds, c->dofsets, id, "dofset");
     for (int32_t dof : ds.dofs) c->vec[vec][dof] = value;
     return FEMCY_OK;
 }
 int femcy_dofset_add(femcy_ctx* ctx, int32_t id, int vec, double value) {
     CTX_OR_FAIL(ctx);
     VEC_OR_FAIL(vec);
-    DOFSET_OR_FAIL(id);
+    FEMCY_OBJECT_OR_FAIL(ds, c->dofsets, id, "dofset");
     for (int32_t dof : ds.dofs) c->vec[vec][dof] += value;
     return FEMCY_OK;
 }
 int femcy_dofset_scatter(femcy_ctx* ctx, int32_t id, int vec, const double* vals) {
     CTX_OR_FAIL(ctx);
     VEC_OR_FAIL(vec);
-    DOFSET_OR_FAIL(id);
+    FEMCY_OBJECT_OR_FAIL(ds, c->dofsets, id, "dofset");
     if (ds.dofs.empty()) return FEMCY_OK;
-    REQUIRE(vals, "null values");
+    FEMCY_REQUIRE(vals, TEXT_NULL_VALUES);
     for (size_t i = 0; i < ds.dofs.size(); ++i) c->vec[vec][ds.dofs[i]] = vals[i];
     return FEMCY_OK;
 }
@@ -880,16 +806,8 @@ int femcy_loadset_create(femcy_ctx* ctx, int32_t nft, int32_t nfn, int32_t nip, 
                          const double* ft_N, const double* ft_dN, const double* ft_normal, const double* ft_weight,
                          int32_t nload, const int32_t* load_elem, const int32_t* load_ft, int32_t* id_out) {
     CTX_OR_FAIL(ctx);
-    REQUIRE(c->have_mesh && id_out, "mesh not set or null id_out");
-    REQUIRE(nft > 0 && nip > 0 && nfn >= c->dm && nfn <= c->npe, "bad facet table sizes (nft %d, nfn %d, nip %d)", nft, nfn, nip);
-    REQUIRE(ft_nodes && ft_N && ft_dN && ft_normal && ft_weight, "null facet tables");
-    REQUIRE(nload >= 0 && (nload == 0 || (load_elem && load_ft)), "bad load facet lists");
-    for (int32_t i = 0; i < nft * nfn; ++i)
-        REQUIRE(ft_nodes[i] >= 0 && ft_nodes[i] < c->npe, "facet table: local node %d out of range", ft_nodes[i]);
-    for (int32_t l = 0; l < nload; ++l) {
-        REQUIRE(load_elem[l] >= 0 && load_elem[l] < c->ne, "load facet %d: element %d out of range", l, load_elem[l]);
-        REQUIRE(load_ft[l] >= 0 && load_ft[l] < nft, "load facet %d: facet type %d out of range", l, load_ft[l]);
-    }
+    FEMCY_TRY(check_loadset_create(c, nft, nfn, nip, ft_nodes, ft_N, ft_dN, ft_normal, ft_weight, nload, load_elem, load_ft,
+                                   id_out));
     LoadSet ls;
     ls.nft = nft; ls.nfn = nfn; ls.nip = nip; ls.nload = nload;
     const size_t tip = (size_t)nft * nip, nslot = (size_t)nload * nfn;
@@ -925,7 +843,7 @@ int femcy_loadset_create(femcy_ctx* ctx, int32_t nft, int32_t nfn, int32_t nip, 
 // neumannBC (stiffnessMtrx.py:369-411); add: the node sums are added to rhs instead of a zero-filled rhs
 static int loadset_neumann(femcy_ctx* c, int32_t id, double traction, const double* direction, int rhs_vec, bool add) {
     VEC_OR_FAIL(rhs_vec);
-    REQUIRE(id >= 0 && (size_t)id < c->loadsets.size(), "unknown load set %d", (int)id);
+    FEMCY_TRY(check_object(c->loadsets, id, "load set"));
     LoadSet& ls = c->loadsets[id];
     double* rhs = c->vec[rhs_vec].data();
     if (!add) std::fill(rhs, rhs + c->n, 0.0);      // reference :384
@@ -991,20 +909,8 @@ extern "C" {
 
 int femcy_bodyload_create(femcy_ctx* ctx, const double* N, int32_t nsel, const int32_t* sel_elems, int32_t* id_out) {
     CTX_OR_FAIL(ctx);
-    REQUIRE(c->have_mesh && c->have_element && c->have_pattern,
-            "femcy_bodyload_create needs the mesh, the element tables and the pattern (mesh=%d element=%d pattern=%d)",
-            (int)c->have_mesh, (int)c->have_element, (int)c->have_pattern);
-    REQUIRE(N && id_out, "null shape-function table or id_out");
-    REQUIRE(sel_elems ? nsel >= 0 : true, "negative selection size %d", nsel);
     std::vector<uint8_t> mask;
-    if (sel_elems) {
-        mask.assign((size_t)c->ne, 0);
-        for (int32_t i = 0; i < nsel; ++i) {
-            REQUIRE(sel_elems[i] >= 0 && sel_elems[i] < c->ne, "body load: element %d out of range", sel_elems[i]);
-            REQUIRE(!mask[sel_elems[i]], "body load: element %d selected twice", sel_elems[i]);
-            mask[sel_elems[i]] = 1;
-        }
-    }
+    FEMCY_TRY(check_bodyload_create(c, N, nsel, sel_elems, id_out, mask));
     const uint8_t* mk = sel_elems ? mask.data() : nullptr;
     BodyLoad bl;
     if (!dispatch_element(c->npe, c->dm, [&](auto npe, auto dm) { body_weights<npe(), dm()>(c, N, mk, bl.m); }))
@@ -1013,21 +919,17 @@ int femcy_bodyload_create(femcy_ctx* ctx, const double* N, int32_t nsel, const i
     *id_out = (int32_t)c->bodyloads.size() - 1;
     return FEMCY_OK;
 }
-#define BODYLOAD_OR_FAIL(id)                                                                     \
-    REQUIRE((id) >= 0 && (size_t)(id) < c->bodyloads.size(), "unknown body load %d", (int)(id)); \
-    const BodyLoad& bl = c->bodyloads[(id)]
 int femcy_bodyload_weights(femcy_ctx* ctx, int32_t id, double* out) {
     CTX_OR_FAIL(ctx);
-    BODYLOAD_OR_FAIL(id);
-    REQUIRE(out, "null output");
+    FEMCY_OBJECT_OR_FAIL(bl, c->bodyloads, id, "body load");
+    FEMCY_REQUIRE(out, TEXT_NULL_OUTPUT);
     std::copy(bl.m.begin(), bl.m.end(), out);
     return FEMCY_OK;
 }
 int femcy_bodyload_apply(femcy_ctx* ctx, int32_t id, const double* b, int rhs_vec, int32_t add) {
     CTX_OR_FAIL(ctx);
-    VEC_OR_FAIL(rhs_vec);
-    BODYLOAD_OR_FAIL(id);
-    REQUIRE(b, "null force");
+    FEMCY_TRY(check_bodyload_apply(c, id, b, rhs_vec));
+    const BodyLoad& bl = c->bodyloads[id];
     double* rhs = c->vec[rhs_vec].data();
     const int dm = c->dm;
     // the product is rounded before it is added (two passes: no fused multiply-add), as on the device
@@ -1077,20 +979,14 @@ extern "C" {
 
 int femcy_thermal_create(femcy_ctx* ctx, const double* N, double alpha, const double* dT, int32_t* id_out) {
     CTX_OR_FAIL(ctx);
-    REQUIRE(c->have_mesh && c->have_element && c->have_material && c->have_pattern,
-            "femcy_thermal_create needs the mesh, the element tables, the material and the pattern (mesh=%d element=%d "
-            "material=%d pattern=%d)", (int)c->have_mesh, (int)c->have_element, (int)c->have_material, (int)c->have_pattern);
-    REQUIRE(N && dT && id_out, "null shape-function table, temperature field or id_out");
-    REQUIRE(std::isfinite(alpha), "thermal load: the expansion coefficient is not finite");
-    REQUIRE(c->mat_kind != FEMCY_MAT_NEOHOOKE, "thermal load: a neo-Hookean material has no small-strain thermal stress "
-            "(linear materials only)");
+    FEMCY_TRY(check_thermal_create(c, N, alpha, dT, id_out));
     Thermal th;
     th.N.assign(N, N + (size_t)c->nGP * c->npe);
     th.dT.assign(dT, dT + (size_t)c->nn);
     dispatch_dm(c->dm, [&](auto dm) {
         constexpr int DM = dm();
         double s[DM][DM];
-        thermal_unit_stress<DM>(c->mat_kind, c->C, c->params[1], s);
+        thermal_unit_stress<DM>(c->mat_kind, c->h_C, c->mat_params[1], s);
         for (int i = 0; i < DM * DM; ++i) th.s[i] = alpha * s[i / DM][i % DM];
     });
     if (!dispatch_element(c->npe, c->dm, [&](auto npe, auto dm) { thermal_force<npe(), dm()>(c, th); }))
@@ -1099,20 +995,17 @@ int femcy_thermal_create(femcy_ctx* ctx, const double* N, double alpha, const do
     *id_out = (int32_t)c->thermals.size() - 1;
     return FEMCY_OK;
 }
-#define THERMAL_OR_FAIL(id)                                                                       \
-    REQUIRE((id) >= 0 && (size_t)(id) < c->thermals.size(), "unknown thermal load %d", (int)(id)); \
-    const Thermal& th = c->thermals[(id)]
 int femcy_thermal_force(femcy_ctx* ctx, int32_t id, double* out) {
     CTX_OR_FAIL(ctx);
-    THERMAL_OR_FAIL(id);
-    REQUIRE(out, "null output");
+    FEMCY_OBJECT_OR_FAIL(th, c->thermals, id, "thermal load");
+    FEMCY_REQUIRE(out, TEXT_NULL_OUTPUT);
     std::copy(th.f.begin(), th.f.end(), out);
     return FEMCY_OK;
 }
 int femcy_thermal_apply(femcy_ctx* ctx, int32_t id, double scale, int rhs_vec, int32_t add) {
     CTX_OR_FAIL(ctx);
     VEC_OR_FAIL(rhs_vec);
-    THERMAL_OR_FAIL(id);
+    FEMCY_OBJECT_OR_FAIL(th, c->thermals, id, "thermal load");
     double* rhs = c->vec[rhs_vec].data();
     // the product is rounded before it is added (two passes: no fused multiply-add), as on the device
     std::vector<double> f((size_t)c->n);
@@ -1125,11 +1018,8 @@ int femcy_thermal_apply(femcy_ctx* ctx, int32_t id, double scale, int rhs_vec, i
 }
 int femcy_thermal_stress(femcy_ctx* ctx, int32_t id, double scale) {
     CTX_OR_FAIL(ctx);
-    THERMAL_OR_FAIL(id);
-    REQUIRE(c->mat_kind != FEMCY_MAT_NEOHOOKE, "thermal stress: a neo-Hookean material has no small-strain thermal stress "
-            "(linear materials only)");
-    REQUIRE(c->post_small, "femcy_thermal_stress corrects the stress of femcy_compute_strain_stress(large = 0): call that "
-            "first (the Gauss-point stress does not exist, is the nlgeom one, or has been corrected already)");
+    FEMCY_TRY(check_thermal_stress(c, id));
+    const Thermal& th = c->thermals[id];
     c->post_small = false;
     const int64_t ngp = (int64_t)c->ne * c->nGP;
     const int npe = c->npe, nGP = c->nGP;
@@ -1143,7 +1033,7 @@ int femcy_thermal_stress(femcy_ctx* ctx, int32_t id, double scale) {
             const int g = (int)(t - e * nGP);
             double tg = 0.0;
             for (int a = 0; a < npe; ++a) tg += th.N[(size_t)g * npe + a] * th.dT[c->elems[e * npe + a]];
-            thermal_post_point<DM>(c->mat_kind, c->params[1], s, scale * tg, c->sigma.data() + t * DM * DM,
+            thermal_post_point<DM>(c->mat_kind, c->mat_params[1], s, scale * tg, c->sigma.data() + t * DM * DM,
                                    c->mises.data() + t);
         }
     });
@@ -1183,12 +1073,7 @@ extern "C" {
 int femcy_mass_create(femcy_ctx* ctx, int32_t nq, const double* Nq, const double* dNq, const double* wq, double rho,
                       int32_t* id_out) {
     CTX_OR_FAIL(ctx);
-    REQUIRE(c->have_mesh && c->have_element && c->have_pattern,
-            "femcy_mass_create needs the mesh, the element tables and the pattern (mesh=%d element=%d pattern=%d)",
-            (int)c->have_mesh, (int)c->have_element, (int)c->have_pattern);
-    REQUIRE(Nq && dNq && wq && id_out, "null mass-rule table or id_out");
-    REQUIRE(nq >= 1 && nq <= 64, "mass rule: %d points (1 .. 64 are supported)", nq);
-    REQUIRE(std::isfinite(rho) && rho > 0.0, "mass: the density must be finite and positive");
+    FEMCY_TRY(check_mass_rule(c, "femcy_mass_create", nq, Nq, dNq, wq, rho, id_out));
     Mass ms;
     if (!dispatch_element(c->npe, c->dm,
                           [&](auto npe, auto dm) { mass_blocks<npe(), dm()>(c, nq, Nq, dNq, wq, rho, ms.m); }))
@@ -1197,14 +1082,10 @@ int femcy_mass_create(femcy_ctx* ctx, int32_t nq, const double* Nq, const double
     *id_out = (int32_t)c->masses.size() - 1;
     return FEMCY_OK;
 }
-#define MASS_OR_FAIL(id)                                                                    \
-    REQUIRE((id) >= 0 && (size_t)(id) < c->masses.size(), "unknown mass object %d", (int)(id)); \
-    const Mass& ms = c->masses[(id)]
-
 int femcy_mass_get(femcy_ctx* ctx, int32_t id, double* vals) {
     CTX_OR_FAIL(ctx);
-    MASS_OR_FAIL(id);
-    REQUIRE(vals, "null output");
+    FEMCY_OBJECT_OR_FAIL(ms, c->masses, id, "mass object");
+    FEMCY_REQUIRE(vals, TEXT_NULL_OUTPUT);
     int64_t w = 0;
     std::vector<std::pair<int32_t, int64_t>> order;
     for (int32_t a = 0; a < c->nn; ++a) {       // the block order of femcy_get_K_bsr
@@ -1218,10 +1099,8 @@ int femcy_mass_get(femcy_ctx* ctx, int32_t id, double* vals) {
 
 int femcy_mass_apply(femcy_ctx* ctx, int32_t id, int x_vec, int y_vec, double scale, int32_t add) {
     CTX_OR_FAIL(ctx);
-    VEC_OR_FAIL(x_vec);
-    VEC_OR_FAIL(y_vec);
-    MASS_OR_FAIL(id);
-    REQUIRE(x_vec != y_vec, "the mass product cannot run in place");
+    FEMCY_TRY(check_mass_apply(c, id, x_vec, y_vec));
+    const Mass& ms = c->masses[id];
     const double* x = c->vec[x_vec].data();
     double* y = c->vec[y_vec].data();
     const int dm = c->dm;
@@ -1242,8 +1121,8 @@ int femcy_mass_apply(femcy_ctx* ctx, int32_t id, int x_vec, int y_vec, double sc
 
 int femcy_mass_add_to_K(femcy_ctx* ctx, int32_t id, double cc, int32_t overwrite) {
     CTX_OR_FAIL(ctx);
-    MASS_OR_FAIL(id);
-    REQUIRE(std::isfinite(cc), "femcy_mass_add_to_K: the factor is not finite");
+    FEMCY_TRY(check_mass_add_to_K(c, id, cc));
+    const Mass& ms = c->masses[id];
     const int dm = c->dm, dd = dm * dm;
     // the product is rounded before it is added (two statements on a volatile: no fused multiply-add), as on the device
 #pragma omp parallel for schedule(static)
@@ -1262,8 +1141,8 @@ int femcy_mass_add_to_K(femcy_ctx* ctx, int32_t id, double cc, int32_t overwrite
 int femcy_mass_kinetic_energy(femcy_ctx* ctx, int32_t id, int v_vec, double* out) {
     CTX_OR_FAIL(ctx);
     VEC_OR_FAIL(v_vec);
-    MASS_OR_FAIL(id);
-    REQUIRE(out, "null output");
+    FEMCY_OBJECT_OR_FAIL(ms, c->masses, id, "mass object");
+    FEMCY_REQUIRE(out, TEXT_NULL_OUTPUT);
     const double* x = c->vec[v_vec].data();
     const int dm = c->dm;
     const int64_t nchunk = (c->nn + NODE_CHUNK - 1) / NODE_CHUNK;
@@ -1290,12 +1169,7 @@ int femcy_mass_kinetic_energy(femcy_ctx* ctx, int32_t id, int v_vec, double* out
 
 int femcy_newmark_predict(femcy_ctx* ctx, int u_vec, int v_vec, int a_vec, int out_vec, double c0, double c1, double c2) {
     CTX_OR_FAIL(ctx);
-    VEC_OR_FAIL(u_vec);
-    VEC_OR_FAIL(v_vec);
-    VEC_OR_FAIL(a_vec);
-    VEC_OR_FAIL(out_vec);
-    REQUIRE(out_vec != u_vec && out_vec != v_vec && out_vec != a_vec,
-            "femcy_newmark_predict: the output may not be one of the inputs");
+    FEMCY_TRY(check_newmark_predict(c, u_vec, v_vec, a_vec, out_vec));
     const double *u = c->vec[u_vec].data(), *v = c->vec[v_vec].data(), *a = c->vec[a_vec].data();
     double* out = c->vec[out_vec].data();
 #pragma omp parallel for schedule(static)
@@ -1306,14 +1180,7 @@ int femcy_newmark_predict(femcy_ctx* ctx, int u_vec, int v_vec, int a_vec, int o
 int femcy_newmark_update(femcy_ctx* ctx, int u_new_vec, int u_vec, int v_vec, int a_vec, double beta, double gamma,
                          double dt) {
     CTX_OR_FAIL(ctx);
-    VEC_OR_FAIL(u_new_vec);
-    VEC_OR_FAIL(u_vec);
-    VEC_OR_FAIL(v_vec);
-    VEC_OR_FAIL(a_vec);
-    REQUIRE(std::isfinite(beta) && beta > 0.0 && std::isfinite(gamma) && std::isfinite(dt) && dt > 0.0,
-            "femcy_newmark_update: beta and dt must be positive, gamma finite");
-    REQUIRE(v_vec != a_vec && v_vec != u_vec && v_vec != u_new_vec && a_vec != u_vec && a_vec != u_new_vec,
-            "femcy_newmark_update: velocity and acceleration are written in place and may alias nothing");
+    FEMCY_TRY(check_newmark_update(c, u_new_vec, u_vec, v_vec, a_vec, beta, gamma, dt));
     const double *un = c->vec[u_new_vec].data(), *u = c->vec[u_vec].data();
     double *v = c->vec[v_vec].data(), *a = c->vec[a_vec].data();
     const double b0 = 1.0 / (beta * dt * dt), b1 = 1.0 / (beta * dt), b2 = 1.0 / (2.0 * beta) - 1.0;
@@ -1389,8 +1256,8 @@ void element_bound(femcy_ctx* c, const double* u, const double* me_all, double s
             }
             me[a] = me_all[(int64_t)e * NPE + a];
         }
-        explicit_bound_element<NPE, DM>(X, U, c->nGP, c->dN.data(), c->w.data(), c->mat_kind, c->C, c->params[0],
-                                        c->params[1], me, s_C, g, w2);
+        explicit_bound_element<NPE, DM>(X, U, c->nGP, c->dN.data(), c->w.data(), c->mat_kind, c->h_C, c->mat_params[0],
+                                        c->mat_params[1], me, s_C, g, w2);
         if (w2 != w2) w2 = INFINITY;
         best = std::fmax(best, w2);
     }
@@ -1453,12 +1320,7 @@ extern "C" {
 int femcy_lumped_mass_create(femcy_ctx* ctx, int32_t nq, const double* Nq, const double* dNq, const double* wq, double rho,
                              int32_t* id_out) {
     CTX_OR_FAIL(ctx);
-    REQUIRE(c->have_mesh && c->have_element && c->have_pattern,
-            "femcy_lumped_mass_create needs the mesh, the element tables and the pattern (mesh=%d element=%d pattern=%d)",
-            (int)c->have_mesh, (int)c->have_element, (int)c->have_pattern);
-    REQUIRE(Nq && dNq && wq && id_out, "null mass-rule table or id_out");
-    REQUIRE(nq >= 1 && nq <= 64, "mass rule: %d points (1 .. 64 are supported)", nq);
-    REQUIRE(std::isfinite(rho) && rho > 0.0, "mass: the density must be finite and positive");
+    FEMCY_TRY(check_mass_rule(c, "femcy_lumped_mass_create", nq, Nq, dNq, wq, rho, id_out));
     LumpedMass lm;
     if (!dispatch_element(c->npe, c->dm,
                           [&](auto npe, auto dm) { lumped_mass<npe(), dm()>(c, nq, Nq, dNq, wq, rho, lm.m, lm.me); }))
@@ -1467,24 +1329,18 @@ int femcy_lumped_mass_create(femcy_ctx* ctx, int32_t nq, const double* Nq, const
     *id_out = (int32_t)c->lumped_masses.size() - 1;
     return FEMCY_OK;
 }
-#define LUMPED_OR_FAIL(id)                                                                                  \
-    REQUIRE((id) >= 0 && (size_t)(id) < c->lumped_masses.size(), "unknown lumped mass %d", (int)(id)); \
-    const LumpedMass& lm = c->lumped_masses[(id)]
-
 int femcy_lumped_mass_get(femcy_ctx* ctx, int32_t id, double* out) {
     CTX_OR_FAIL(ctx);
-    LUMPED_OR_FAIL(id);
-    REQUIRE(out, "null output");
+    FEMCY_OBJECT_OR_FAIL(lm, c->lumped_masses, id, "lumped mass");
+    FEMCY_REQUIRE(out, TEXT_NULL_OUTPUT);
     std::copy(lm.m.begin(), lm.m.end(), out);
     return FEMCY_OK;
 }
 
 int femcy_explicit_create(femcy_ctx* ctx, int32_t lumped_id, int32_t ndofsets, const int32_t* dofset_ids, int32_t* id_out) {
     CTX_OR_FAIL(ctx);
-    LUMPED_OR_FAIL(lumped_id);
-    REQUIRE(id_out && ndofsets >= 0 && (ndofsets == 0 || dofset_ids), "femcy_explicit_create: null id_out or DOF-set list");
-    for (int32_t k = 0; k < ndofsets; ++k)
-        REQUIRE(dofset_ids[k] >= 0 && (size_t)dofset_ids[k] < c->dofsets.size(), "unknown DOF set %d", dofset_ids[k]);
+    FEMCY_TRY(check_explicit_create(c, lumped_id, ndofsets, dofset_ids, id_out));
+    const LumpedMass& lm = c->lumped_masses[lumped_id];
     Explicit ex;
     ex.lumped = lumped_id;
     ex.minv.resize((size_t)c->n);
@@ -1495,20 +1351,12 @@ int femcy_explicit_create(femcy_ctx* ctx, int32_t lumped_id, int32_t ndofsets, c
     *id_out = (int32_t)c->explicits.size() - 1;
     return FEMCY_OK;
 }
-#define EXPLICIT_OR_FAIL(id)                                                                                    \
-    REQUIRE((id) >= 0 && (size_t)(id) < c->explicits.size(), "unknown explicit integrator %d", (int)(id)); \
-    const Explicit& ex = c->explicits[(id)]
-#define EXPLICIT_RHS_OR_FAIL(name, rhs_vec)                                                                 \
-    VEC_OR_FAIL(rhs_vec);                                                                                   \
-    REQUIRE((rhs_vec) != FEMCY_VEC_DOF && (rhs_vec) != FEMCY_VEC_VEL && (rhs_vec) != FEMCY_VEC_ACC,        \
-            name ": the load vector may not be one of the state vectors DOF, VEL, ACC")
 
 int femcy_explicit_start(femcy_ctx* ctx, int32_t id, int rhs_vec, double scale) {
     CTX_OR_FAIL(ctx);
     READY_OR_FAIL();
-    EXPLICIT_OR_FAIL(id);
-    EXPLICIT_RHS_OR_FAIL("femcy_explicit_start", rhs_vec);
-    REQUIRE(std::isfinite(scale), "femcy_explicit_start: the load scale is not finite");
+    FEMCY_TRY(check_explicit_start(c, id, rhs_vec, scale));
+    const Explicit& ex = c->explicits[id];
     geom(c, c->vec[FEMCY_VEC_DOF].data(), GEOM_DSDX | GEOM_F | GEOM_SIGMA | GEOM_FE);
     explicit_node(c, ex, c->vec[rhs_vec].data(), explicit_step_fixed(scale, 0.0, XN_START), XN_START);
     return FEMCY_OK;
@@ -1517,19 +1365,15 @@ int femcy_explicit_start(femcy_ctx* ctx, int32_t id, int rhs_vec, double scale) 
 int femcy_explicit_advance(femcy_ctx* ctx, int32_t id, int rhs_vec, int32_t nsteps, double dt, double scale0, double dscale) {
     CTX_OR_FAIL(ctx);
     READY_OR_FAIL();
-    EXPLICIT_OR_FAIL(id);
-    EXPLICIT_RHS_OR_FAIL("femcy_explicit_advance", rhs_vec);
-    REQUIRE(nsteps >= 0, "femcy_explicit_advance: %d steps", nsteps);
-    REQUIRE(std::isfinite(dt) && dt > 0.0, "femcy_explicit_advance: the increment must be finite and positive");
-    REQUIRE(std::isfinite(scale0) && std::isfinite(dscale), "femcy_explicit_advance: the load scale is not finite");
-    return explicit_steps(c, ex, nullptr, rhs_vec, nsteps, dt, scale0, dscale);
+    FEMCY_TRY(check_explicit_advance(c, id, rhs_vec, nsteps, dt, scale0, dscale));
+    return explicit_steps(c, c->explicits[id], nullptr, rhs_vec, nsteps, dt, scale0, dscale);
 }
 
 int femcy_explicit_kinetic_energy(femcy_ctx* ctx, int32_t id, int v_vec, double* out) {
     CTX_OR_FAIL(ctx);
-    EXPLICIT_OR_FAIL(id);
+    FEMCY_OBJECT_OR_FAIL(ex, c->explicits, id, "explicit integrator");
     VEC_OR_FAIL(v_vec);
-    REQUIRE(out, "null output");
+    FEMCY_REQUIRE(out, TEXT_NULL_OUTPUT);
     const double* m = c->lumped_masses[ex.lumped].m.data();
     const double* v = c->vec[v_vec].data();
     const int dm = c->dm;
@@ -1562,10 +1406,9 @@ int femcy_explicit_kinetic_energy(femcy_ctx* ctx, int32_t id, int v_vec, double*
 
 int femcy_explicit_stable_dt(femcy_ctx* ctx, int32_t id, double* dt, double* omega_bound) {
     CTX_OR_FAIL(ctx);
-    EXPLICIT_OR_FAIL(id);
-    REQUIRE(dt && omega_bound, "null output");
-    REQUIRE(c->have_pattern && c->have_K,
-            "femcy_explicit_stable_dt bounds the matrix of the last femcy_assemble_K: assemble first");
+    FEMCY_OBJECT_OR_FAIL(ex, c->explicits, id, "explicit integrator");
+    FEMCY_REQUIRE(dt && omega_bound, TEXT_NULL_OUTPUT);
+    FEMCY_REQUIRE(c->have_pattern && c->have_K, TEXT_ASSEMBLE_FIRST);
     const int dm = c->dm, dd = dm * dm;
     double best = 0.0;
     for (int32_t a = 0; a < c->nn; ++a) {      // blocks in storage order, entries of a scalar row in ascending column order
@@ -1582,17 +1425,12 @@ int femcy_explicit_stable_dt(femcy_ctx* ctx, int32_t id, double* dt, double* ome
     return FEMCY_OK;
 }
 
-#define POSITIVE_FINITE(x) (std::isfinite(x) && (x) > 0.0)
-
 int femcy_explicit_element_bound(femcy_ctx* ctx, int32_t id, int u_vec, double s_C, double* omega) {
     CTX_OR_FAIL(ctx);
     READY_OR_FAIL();
-    EXPLICIT_OR_FAIL(id);
-    VEC_OR_FAIL(u_vec);
-    REQUIRE(omega, "null output");
-    REQUIRE(POSITIVE_FINITE(s_C), "femcy_explicit_element_bound: the material stiffness s_C must be finite and positive");
+    FEMCY_TRY(check_explicit_element_bound(c, id, u_vec, s_C, omega));
     double w2 = 0.0;
-    int rc = element_bound_any(c, ex, c->vec[u_vec].data(), s_C, &w2);
+    int rc = element_bound_any(c, c->explicits[id], c->vec[u_vec].data(), s_C, &w2);
     if (rc) return rc;
     *omega = std::sqrt(w2);
     return FEMCY_OK;
@@ -1602,14 +1440,11 @@ int femcy_explicit_auto_begin(femcy_ctx* ctx, int32_t id, int rhs_vec, double s_
                               int32_t ramp) {
     CTX_OR_FAIL(ctx);
     READY_OR_FAIL();
-    EXPLICIT_OR_FAIL(id);
-    EXPLICIT_RHS_OR_FAIL("femcy_explicit_auto_begin", rhs_vec);
-    REQUIRE(POSITIVE_FINITE(s_C) && POSITIVE_FINITE(scale_factor) && POSITIVE_FINITE(T),
-            "femcy_explicit_auto_begin: s_C, the scale factor and T must be finite and positive");
+    FEMCY_TRY(check_explicit_auto_begin(c, id, rhs_vec, s_C, scale_factor, T));
     Explicit& exm = c->explicits[id];
     const double* u = c->vec[FEMCY_VEC_DOF].data();
     double w2 = 0.0;
-    int rc = element_bound_any(c, ex, u, s_C, &w2);
+    int rc = element_bound_any(c, exm, u, s_C, &w2);
     if (rc) return rc;
     exm.clock = ExplicitClock{};
     exm.clock.T = T;
@@ -1629,18 +1464,14 @@ int femcy_explicit_auto_begin(femcy_ctx* ctx, int32_t id, int rhs_vec, double s_
 int femcy_explicit_auto_advance(femcy_ctx* ctx, int32_t id, int rhs_vec, int32_t nsteps) {
     CTX_OR_FAIL(ctx);
     READY_OR_FAIL();
-    EXPLICIT_OR_FAIL(id);
-    EXPLICIT_RHS_OR_FAIL("femcy_explicit_auto_advance", rhs_vec);
-    REQUIRE(nsteps >= 0, "femcy_explicit_auto_advance: %d steps", nsteps);
-    REQUIRE(ex.auto_begun, "femcy_explicit_auto_advance before femcy_explicit_auto_begin");
-    return explicit_steps(c, ex, &c->explicits[id].clock, rhs_vec, nsteps, 0.0, 0.0, 0.0);
+    FEMCY_TRY(check_explicit_auto_advance(c, id, rhs_vec, nsteps));
+    return explicit_steps(c, c->explicits[id], &c->explicits[id].clock, rhs_vec, nsteps, 0.0, 0.0, 0.0);
 }
 
 int femcy_explicit_auto_state(femcy_ctx* ctx, int32_t id, double* t, double* h_last, double* h_min, int64_t* steps_done) {
     CTX_OR_FAIL(ctx);
-    EXPLICIT_OR_FAIL(id);
-    REQUIRE(t && h_last && h_min && steps_done, "null output");
-    REQUIRE(ex.auto_begun, "femcy_explicit_auto_state before femcy_explicit_auto_begin");
+    FEMCY_TRY(check_explicit_auto_state(c, id, t, h_last, h_min, steps_done));
+    const Explicit& ex = c->explicits[id];
     *t = ex.clock.t;
     *h_last = ex.clock.h_last;
     *h_min = ex.clock.steps ? ex.clock.h_min : 0.0;
@@ -1650,18 +1481,14 @@ int femcy_explicit_auto_state(femcy_ctx* ctx, int32_t id, double* t, double* h_l
 
 int femcy_spmv(femcy_ctx* ctx, int x_vec, int y_vec) {
     CTX_OR_FAIL(ctx);
-    REQUIRE(c->have_pattern, "pattern not built");
-    VEC_OR_FAIL(x_vec);
-    VEC_OR_FAIL(y_vec);
-    REQUIRE(x_vec != y_vec, "spmv cannot run in place");
+    FEMCY_TRY(check_two_vectors(c, x_vec, y_vec, TEXT_SPMV_IN_PLACE));
     spmv(c, c->vec[x_vec].data(), c->vec[y_vec].data(), nullptr);
     return FEMCY_OK;
 }
 
 int femcy_direct_plan(femcy_ctx* ctx, femcy_direct_info* info) {
     CTX_OR_FAIL(ctx);
-    REQUIRE(c->have_pattern, "pattern not built");
-    REQUIRE(info != nullptr, "femcy_direct_plan: info must not be null");
+    FEMCY_TRY(check_direct_plan(c, info));
     if (!c->have_band_order) {
         c->band_order = band_order_rcm(c->nn, c->ne, c->npe, c->elems.data());
         c->have_band_order = true;
@@ -1678,10 +1505,7 @@ int femcy_direct_plan(femcy_ctx* ctx, femcy_direct_info* info) {
 // residual check + refinement (csrc/band_order.hpp; the device library does the same on tiles, csrc/kernels_direct.hip)
 int femcy_direct_solve(femcy_ctx* ctx, int b_vec, int x_vec, femcy_direct_info* info) {
     CTX_OR_FAIL(ctx);
-    REQUIRE(c->have_pattern, "pattern not built");
-    VEC_OR_FAIL(b_vec);
-    VEC_OR_FAIL(x_vec);
-    REQUIRE(b_vec != x_vec, "direct solve: b and x must be different vectors");
+    FEMCY_TRY(check_two_vectors(c, b_vec, x_vec, TEXT_DIRECT_IN_PLACE));
     if (!c->have_band_order) {
         c->band_order = band_order_rcm(c->nn, c->ne, c->npe, c->elems.data());
         c->have_band_order = true;
@@ -1775,10 +1599,7 @@ int femcy_direct_solve(femcy_ctx* ctx, int b_vec, int x_vec, femcy_direct_info* 
 int femcy_pcg(femcy_ctx* ctx, int b_vec, int x_vec, double eps, int32_t maxit, int32_t* iters, double* rmax0,
               double* rmax_out) {
     CTX_OR_FAIL(ctx);
-    REQUIRE(c->have_pattern, "pattern not built");
-    VEC_OR_FAIL(b_vec);
-    VEC_OR_FAIL(x_vec);
-    REQUIRE(b_vec != x_vec, "pcg: b and x must be different vectors");
+    FEMCY_TRY(check_two_vectors(c, b_vec, x_vec, TEXT_PCG_IN_PLACE));
     if (maxit <= 0) maxit = (int32_t)std::min<int64_t>(c->n, INT32_MAX);
     const double t_start = now_ms();
     const int64_t n = c->n;
@@ -1866,7 +1687,7 @@ int femcy_pcg(femcy_ctx* ctx, int b_vec, int x_vec, double eps, int32_t maxit, i
 // ------------------------------------------------------------------------------ post-processing
 int femcy_compute_strain_stress(femcy_ctx* ctx, int u_vec, int large) {
     CTX_OR_FAIL(ctx);
-    REQUIRE(c->have_mesh && c->have_element && c->have_material, "context not fully defined");
+    FEMCY_REQUIRE(c->have_mesh && c->have_element && c->have_material, TEXT_NOT_DEFINED);
     VEC_OR_FAIL(u_vec);
     geom(c, c->vec[u_vec].data(), GEOM_F);   // F only: dsdx, vol and (nlgeom) the stress of the last force evaluation stay
     const int64_t ngp = (int64_t)c->ne * c->nGP;
@@ -1874,10 +1695,10 @@ int femcy_compute_strain_stress(femcy_ctx* ctx, int u_vec, int large) {
 #pragma omp parallel for schedule(static)
     for (int64_t t = 0; t < ngp; ++t) {
         if (c->dm == 3)
-            post_point<3>(large ? 1 : 0, c->mat_kind, c->C, c->params[0], c->params[1], c->F.data() + t * dd,
+            post_point<3>(large ? 1 : 0, c->mat_kind, c->h_C, c->mat_params[0], c->mat_params[1], c->F.data() + t * dd,
                           c->sigma.data() + t * dd, c->strain.data() + t * dd, c->mises.data() + t);
         else
-            post_point<2>(large ? 1 : 0, c->mat_kind, c->C, c->params[0], c->params[1], c->F.data() + t * dd,
+            post_point<2>(large ? 1 : 0, c->mat_kind, c->h_C, c->mat_params[0], c->mat_params[1], c->F.data() + t * dd,
                           c->sigma.data() + t * dd, c->strain.data() + t * dd, c->mises.data() + t);
     }
     c->post_small = !large;                    // what femcy_thermal_stress may correct, once
@@ -1886,7 +1707,7 @@ int femcy_compute_strain_stress(femcy_ctx* ctx, int u_vec, int large) {
 
 int femcy_elastic_energy(femcy_ctx* ctx, int u_vec, double* total) {
     CTX_OR_FAIL(ctx);
-    REQUIRE(c->have_mesh && c->have_element && c->have_material && total, "context not fully defined");
+    FEMCY_REQUIRE(c->have_mesh && c->have_element && c->have_material && total, TEXT_NOT_DEFINED);
     VEC_OR_FAIL(u_vec);
     geom(c, c->vec[u_vec].data(), GEOM_F);
     const int64_t ngp = (int64_t)c->ne * c->nGP;
@@ -1897,12 +1718,12 @@ int femcy_elastic_energy(femcy_ctx* ctx, int u_vec, double* total) {
             double F[3][3];
             for (int i = 0; i < 3; ++i)
                 for (int j = 0; j < 3; ++j) F[i][j] = c->F[t * dd + i * 3 + j];
-            c->energy[t] = energy_density<3>(c->mat_kind, c->C, c->params[0], c->params[1], F);
+            c->energy[t] = energy_density<3>(c->mat_kind, c->h_C, c->mat_params[0], c->mat_params[1], F);
         } else {
             double F[2][2];
             for (int i = 0; i < 2; ++i)
                 for (int j = 0; j < 2; ++j) F[i][j] = c->F[t * dd + i * 2 + j];
-            c->energy[t] = energy_density<2>(c->mat_kind, c->C, c->params[0], c->params[1], F);
+            c->energy[t] = energy_density<2>(c->mat_kind, c->h_C, c->mat_params[0], c->mat_params[1], F);
         }
     }
     double s = 0.0;
@@ -1913,10 +1734,7 @@ int femcy_elastic_energy(femcy_ctx* ctx, int u_vec, double* total) {
 
 int femcy_elastic_energy_small(femcy_ctx* ctx, int u_vec, double* total) {
     CTX_OR_FAIL(ctx);
-    REQUIRE(c->have_mesh && c->have_element && c->have_material && total, "context not fully defined");
-    VEC_OR_FAIL(u_vec);
-    REQUIRE(c->mat_kind != FEMCY_MAT_NEOHOOKE, "femcy_elastic_energy_small: a neo-Hookean material has no small-strain energy "
-            "(linear materials only)");
+    FEMCY_TRY(check_elastic_energy_small(c, u_vec, total));
     geom(c, c->vec[u_vec].data(), GEOM_F);
     geom(c, nullptr, GEOM_DSDX);                     // the weights det J w of the UNDEFORMED mesh
     const int64_t ngp = (int64_t)c->ne * c->nGP;
@@ -1927,12 +1745,12 @@ int femcy_elastic_energy_small(femcy_ctx* ctx, int u_vec, double* total) {
             double F[3][3];
             for (int i = 0; i < 3; ++i)
                 for (int j = 0; j < 3; ++j) F[i][j] = c->F[t * dd + i * 3 + j];
-            c->energy[t] = energy_density_small<3>(c->mat_kind, c->C, c->params[0], c->params[1], F);
+            c->energy[t] = energy_density_small<3>(c->mat_kind, c->h_C, c->mat_params[0], c->mat_params[1], F);
         } else {
             double F[2][2];
             for (int i = 0; i < 2; ++i)
                 for (int j = 0; j < 2; ++j) F[i][j] = c->F[t * dd + i * 2 + j];
-            c->energy[t] = energy_density_small<2>(c->mat_kind, c->C, c->params[0], c->params[1], F);
+            c->energy[t] = energy_density_small<2>(c->mat_kind, c->h_C, c->mat_params[0], c->mat_params[1], F);
         }
     }
     double s = 0.0;
@@ -1943,19 +1761,18 @@ int femcy_elastic_energy_small(femcy_ctx* ctx, int u_vec, double* total) {
 
 int femcy_extrapolate(femcy_ctx* ctx, int gp_field, int comp, const double* E, double* out) {
     CTX_OR_FAIL(ctx);
-    REQUIRE(c->have_element && E && out, "element tables not set or null arguments");
-    const double* field = nullptr;
     int width = 1;
+    FEMCY_TRY(check_extrapolate(c, gp_field, comp, E, out, &width));
+    const double* field = nullptr;
     switch (gp_field) {
         case FEMCY_GP_VOL: field = c->vol.data(); break;
         case FEMCY_GP_MISES: field = c->mises.data(); break;
         case FEMCY_GP_ENERGY: field = c->energy.data(); break;
-        case FEMCY_GP_F: field = c->F.data(); width = c->dm * c->dm; break;
-        case FEMCY_GP_SIGMA: field = c->sigma.data(); width = c->dm * c->dm; break;
-        case FEMCY_GP_STRAIN: field = c->strain.data(); width = c->dm * c->dm; break;
-        default: set_error("field %d cannot be extrapolated", gp_field); return FEMCY_EINVAL;
+        case FEMCY_GP_F: field = c->F.data(); break;
+        case FEMCY_GP_SIGMA: field = c->sigma.data(); break;
+        case FEMCY_GP_STRAIN: field = c->strain.data(); break;
+        default: return FEMCY_EINVAL;             // not reached: check_extrapolate has refused everything else
     }
-    REQUIRE(comp >= 0 && comp < width, "component %d out of range for field %d", comp, gp_field);
     for (int64_t e = 0; e < c->ne; ++e)
         for (int a = 0; a < c->npe; ++a) {
             double acc = 0.0;
@@ -1968,7 +1785,7 @@ int femcy_extrapolate(femcy_ctx* ctx, int gp_field, int comp, const double* E, d
 // ---------------------------------------------------------------------------------- inspection
 int femcy_get_K_ell(femcy_ctx* ctx, int32_t* ij, double* A) {
     CTX_OR_FAIL(ctx);
-    REQUIRE(c->have_pattern && ij && A, "pattern not built or null outputs");
+    FEMCY_REQUIRE(c->have_pattern && ij && A, TEXT_GET_K);
     const int dm = c->dm, dd = dm * dm, W = c->max_row_blocks * dm;
     for (int32_t a = 0; a < c->nn; ++a) {
         const int L = (int)(c->rowptr[a + 1] - c->rowptr[a]);
@@ -1993,7 +1810,7 @@ int femcy_get_K_ell(femcy_ctx* ctx, int32_t* ij, double* A) {
 
 int femcy_get_K_bsr(femcy_ctx* ctx, int32_t* rowptr, int32_t* colidx, double* out) {
     CTX_OR_FAIL(ctx);
-    REQUIRE(c->have_pattern && rowptr && colidx && out, "pattern not built or null outputs");
+    FEMCY_REQUIRE(c->have_pattern && rowptr && colidx && out, TEXT_GET_K);
     const int dd = c->dm * c->dm;
     int64_t w = 0;
     rowptr[0] = 0;
@@ -2014,7 +1831,7 @@ int femcy_get_K_bsr(femcy_ctx* ctx, int32_t* rowptr, int32_t* colidx, double* ou
 
 int femcy_get_gp_field(femcy_ctx* ctx, int which, double* out) {
     CTX_OR_FAIL(ctx);
-    REQUIRE(c->have_element && out, "element tables not set or null output");
+    FEMCY_TRY(check_get_gp_field(c, which, out));
     const std::vector<double>* src = nullptr;
     switch (which) {
         case FEMCY_GP_DSDX: src = &c->dsdx; break;
@@ -2024,7 +1841,7 @@ int femcy_get_gp_field(femcy_ctx* ctx, int which, double* out) {
         case FEMCY_GP_STRAIN: src = &c->strain; break;
         case FEMCY_GP_MISES: src = &c->mises; break;
         case FEMCY_GP_ENERGY: src = &c->energy; break;
-        default: set_error("unknown Gauss-point field %d", which); return FEMCY_EINVAL;
+        default: return FEMCY_EINVAL;             // not reached: check_get_gp_field has refused everything else
     }
     std::memcpy(out, src->data(), src->size() * sizeof(double));
     return FEMCY_OK;
@@ -2032,7 +1849,7 @@ int femcy_get_gp_field(femcy_ctx* ctx, int which, double* out) {
 
 int femcy_timing(femcy_ctx* ctx, femcy_timing_t* out) {
     CTX_OR_FAIL(ctx);
-    REQUIRE(out, "null output");
+    FEMCY_REQUIRE(out, TEXT_NULL_OUTPUT);
     *out = c->timing;
     return FEMCY_OK;
 }
@@ -2058,7 +1875,7 @@ int femcy_probe_exchange(femcy_ctx*, int32_t, int32_t, double*) {
 int femcy_persist_streamed_bytes(femcy_ctx* ctx, int64_t* bytes) {
     CTX_OR_FAIL(ctx);
     (void)c;
-    REQUIRE(bytes, "null output");
+    FEMCY_REQUIRE(bytes, TEXT_NULL_OUTPUT);
     *bytes = 0;
     return FEMCY_OK;
 }
