@@ -1,0 +1,872 @@
+"""Slice, step and batch edges of the assembly kernels (csrc/kernels_assembly.hip: k_geom, k_assemble_gather / _rows / _rows2 /
+_rows4 / _pairs / _atomic, k_nodal_force; csrc/pattern.cpp: build_pattern, ensure_pairs), written against the C ABI
+(femcy_amd.backend.Context) so that the host backend (tests/test_asm_shapes_cpu.py, one child process with
+FEMCY_BACKEND=cpu) and the device (tests/test_gpu_asm_shapes.py) run the same code.  Every check compares with a plain
+element-by-element reference in np.longdouble; bit-equality of two runs is asserted only next to that comparison.
+
+The reference (reference()) is restated from the element plug-in's tables (dN at the Gauss points, the weights): J = x^T dN,
+grad N = dN J^-1 by the adjugate, vol = det J w, K^e = sum_g B^T C B vol with the B matrices of oracle/ (Voigt xx yy zz xy zx
+yz, engineering shear), f^e = sum_g grad N . sigma(F) vol.  It is vectorised over elements and reduced into the block
+pattern the library exports by a sort and np.add.reduceat.  Next to every value it returns the MAGNITUDE SUM of the terms
+that value is made of, which bounds the error of a correct evaluation in any order.  For K that is, to first order,
+    A = sum_e sum_g  Avol |B|^T |C| |B|  +  |vol| (B(Adsdx)^T |C| |B| + |B|^T |C| B(Adsdx)),
+the sum's own terms (Avol >= |vol|) and what the roundings of vol and grad N, eps Avol and eps Adsdx, move them by: where
+grad N is small by cancellation (mid-side nodes of C3D10) the second part is what a float64 evaluation can be held to;
+against A0 = sum |vol| |B|^T |C| |B| alone the float64 run of this very restatement is off by 6 300 eps.  What that gives
+away: Avol and Adsdx are formed from |x| |dN| and grow with the distance from the origin; A / A0 over the stored entries is
+10 .. 80 at the median on the 2-D rows and the hexahedra, 130 .. 1 400 on the C3D4 rows, 230 .. 7 300 on the C3D10 rows
+(worst entry 4e6, c3d4-graded), so the bound is 6e-16 A = 1e-14 .. 4e-12 A0 at the median: a contribution left out or
+taken twice moves an entry by its own share of A0.  Then
+    |K_ij - K_ref_ij| <= 4 C_ASM 2^-53 A_ij        for every stored scalar entry; A_ij = 0: a structural zero, exactly 0.
+The modes that take the diagonal block from the row sum K_aa = -sum_b K_ab (GATHER_SYM_ROWSUM, ROWS2) are bounded there by
+the magnitudes they sum, sum_(b != a) A_ab.  k_assemble_gather's cubic form (kblock_cubic3) sums the products of the dense
+form without its zero terms, per Gauss point: it is held to C_ASM; C_CUBIC is for the geometric sum of ROWS2 / ROWS4.
+dsdx, vol, F, sigma (every element and Gauss point of k_geom's STRESS instantiation) and the nodal force follow the same
+scheme with their own constants; sigma's magnitude sum takes every term of F S F^T / J, E = (F^T F - I) / 2 by its
+magnitude, the force's takes |sigma_ref| as it is, so C_FORCE carries the cancellation of E at the strains of disp().  At
+u = 0 every magnitude sum of the force is 0: the node sums must be exactly 0.  Before every assembly that is checked, another
+mode assembles at the other displacement, so that a store left out leaves another state's value behind.
+
+ROWS holds one small generated mesh per edge.  A row is pinned to (nn, ne, nslices, stored_blocks, max_row_blocks) and
+carries the edge it exists for as a predicate over the layout, which is RESTATED here in numpy (Layout): windows of
+FEMCY_OPT_SELL_SIGMA nodes in the caller's numbering (FEMCY_OPT_NODE_ORDER = 0), rows by decreasing length inside a window
+(pcg_shapes.layout), slices of 64; k_assemble_rows4's rows of wave w: slice lanes 8 (i / 2) + 2 w + i % 2, a pair of rows
+per half-wave step of EPG = 3 elements, 32 blocks per write-out trip; k_assemble_rows2's passes of 64 / (npe - 1) elements;
+ensure_pairs' chunks of RPW rows cut into batches of 64 pair words (3-D: step-ordered lists of SW words per step).  A change
+of SLICE, EPG, RPW, the batch size or the sort window that moves a row off its edge fails the row's predicate.
+
+Per row the table names the modes that must run; assembly_used() is asserted for each, nothing is skipped at run time.
+
+Measured constants (x86-64 long double; the float64 run of the same restatement against the long-double one, worst over all
+rows, both materials and both displacements; the tests allow 4 x).  Last column: the worst value the device tests print
+(pytest -s) over every row and mode.
+    C_ASM     worst |K - K_ref|_ij / (eps A_ij), dense B^T C B                 1.40      0.99
+    C_CUBIC   the same for the geometric sum S = sum vol ga (x) gb, constants
+              applied once per block (ROWS2 / ROWS4 with a cubic-pattern C)    0.861     0.588
+    C_DSDX    worst |dsdx - ref| / (eps A_dsdx)                                133.3     134.8   (thin fan tetrahedra: det J cancels)
+    C_VOL     worst |vol - ref| / (eps A_vol)                                  1.87      1.86
+    C_FORCE   worst |f - f_ref|_i / (eps A_f_i)                                3549      2394
+    C_F       worst |F - F_ref| / (eps A_F)                                    1.44      1.57
+    C_SIG     worst |sigma - ref| / (eps A_sigma)                              1.37      1.35
+    C_PROD    pcg_shapes.C_PROD, the product check: on the device at most 0.062 of its bound
+tests/test_asm_shapes_cpu.py measures the float64 column again and fails if it has moved."""
+import collections
+from types import SimpleNamespace
+
+import numpy as np
+
+from femcy_amd import backend as be
+from femcy_amd import meshgen
+from femcy_amd.element_zoo import (Element_linear_hexahedral, Element_linear_quadrilateral, Element_linear_tetrahedral,
+                                   Element_linear_triangular, Element_linear_wedge, Element_quadratic_quadrilateral,
+                                   Element_quadratic_tetrahedral, Element_quadratic_triangular)
+from femcy_amd.material_zoo import LinearIsotropic, LinearIsotropicPlaneStress
+from oracle import femcy_oracle as orc
+
+import loads_reference as lr
+import pcg_shapes as ps
+
+LD = np.longdouble
+EPS = 2.0 ** -53
+SLICE, EPG, TRIP, BATCH, NPE_MAX = 64, 3, 32, 64, 10              # ctx.hpp; kernels_assembly.hip (rows4: EPG, G); pattern.cpp: BAT
+C_ASM, C_CUBIC, C_DSDX, C_VOL, C_FORCE, C_F, C_SIG = 1.40, 0.861, 133.3, 1.87, 3549.0, 1.44, 1.37  # (measured: the docstring)
+LDS_LINE, LDS_DEVICE = 48 * 1024, 160 * 1024                     # FEMCY_LDS_LAUNCH; what a gfx950 workgroup may allocate
+G, A, R, S, SR, R2, R4, P, AUTO = (be.ASM_GATHER, be.ASM_ATOMIC, be.ASM_ROWS, be.ASM_GATHER_SYM, be.ASM_GATHER_SYM_ROWSUM,
+                                   be.ASM_ROWS2, be.ASM_ROWS4, be.ASM_PAIRS, be.ASM_AUTO)
+NAMES = {G: "GATHER", A: "ATOMIC", R: "ROWS", S: "GATHER_SYM", SR: "GATHER_SYM_ROWSUM", R2: "ROWS2", R4: "ROWS4", P: "PAIRS",
+         AUTO: "AUTO"}
+ROWSUM_MODES = (SR, R2)
+PLUGINS = {"CPS3": Element_linear_triangular, "CPS4": Element_linear_quadrilateral, "CPS6": Element_quadratic_triangular,
+           "CPS8": Element_quadratic_quadrilateral, "C3D4": Element_linear_tetrahedral, "C3D10": Element_quadratic_tetrahedral,
+           "C3D8": Element_linear_hexahedral, "C3D6": Element_linear_wedge}
+
+
+def pairs_knob(rpw=16, depth=2, xcd=False, cpw=1, morton=False):
+    """FEMCY_TUNE_PAIRS: bit 0 XCD-contiguous, bits 1-2 rows per wave, bits 3-4 depth - 2, bit 5 Morton, bits 6-9 cpw - 1"""
+    return int(xcd) | ({16: 0, 8: 1}[rpw] << 1) | ((depth - 2) << 3) | (int(morton) << 5) | ((cpw - 1) << 6)
+
+
+# (rows per wave, depth, XCD-contiguous, chunks per wave, Morton): rows 16 and 8, depth 2 / 3 / 4, ranges on and off,
+# chunks per wave 1 / 2 / 16; the last one is the library's default (163)
+KNOBS = ((16, 2, False, 1, False), (8, 3, True, 2, False), (16, 4, True, 16, True), (8, 2, True, 3, True))
+assert pairs_knob(*KNOBS[-1]) == 163
+
+
+# ------------------------------------------------------------------------------------------------------------ meshes
+def grade(nodes, ratio=100.0):
+    """every axis mapped by t -> (ratio^t - 1) / (ratio - 1) on its own extent: cell sizes span `ratio` per axis"""
+    lo, ext = nodes.min(axis=0), np.ptp(nodes, axis=0)
+    t = (nodes - lo) / ext
+    return lo + ext * (ratio ** t - 1.0) / (ratio - 1.0)
+
+
+def fans3d(ks, quadratic):
+    """one fan of k tetrahedra around an axis edge per entry of ks, side by side: both axis nodes (and, quadratic, the axis
+    mid-side node) have k incident elements and rows of k + 2 (4 k + 3) blocks; a ring corner has 2"""
+    nodes, el = [], []
+    for n, k in enumerate(ks):
+        base = sum(len(p) for p in nodes)
+        if k == 1:                                                   # a lone tetrahedron: four nodes of valence 1
+            nodes.append(lr.single("C3D4")[0] + np.array([3.0 * n, 0.0, 0.0]))
+            el.append([base, base + 1, base + 2, base + 3])
+            continue
+        t = 2 * np.pi * np.arange(k) / k
+        ring = np.column_stack([(1.0 + 0.1 * np.cos(3 * t)) * np.cos(t), np.sin(t), 0.5 + 0.05 * np.sin(2 * t)])
+        nodes.append(np.vstack([[0.0, 0.0, 0.0], [0.02, 0.03, 1.0], ring]) + np.array([3.0 * n, 0.0, 0.0]))
+        el += [[base, base + 2 + i, base + 2 + (i + 1) % k, base + 1] for i in range(k)]
+    nodes, el = np.vstack(nodes), np.asarray(el, np.int32)
+    if quadratic:
+        nodes, el = meshgen.to_quadratic(nodes, el)
+    return nodes, el.astype(np.int32)
+
+
+def fans2d(ks):
+    """lr.fan(k) side by side"""
+    nodes, el = [], []
+    for n, k in enumerate(ks):
+        p, e = lr.fan(k)[:2] if k > 1 else lr.single("CPS3")[:2]       # k = 1: a lone triangle, three nodes of valence 1
+        el.append(e + sum(len(q) for q in nodes))
+        nodes.append(p + np.array([3.0 * n, 0.0]))
+    return np.vstack(nodes), np.vstack(el).astype(np.int32)
+
+
+def with_loose(nodes, el, every, tail):
+    """a loose node (no element names it: a row of one block) behind every `every`-th mesh node, then `tail` more behind
+    the mesh"""
+    nm = len(nodes)
+    far = nodes.max(axis=0) + 1.0
+    if every:
+        new = np.arange(nm) + np.arange(nm) // every                      # mesh node a -> its new number
+        total = int(new[-1]) + 1
+        out = np.tile(far, (total, 1)) + np.arange(total)[:, None] * 0.01
+        out[new] = nodes
+        nodes, el = out, new[el]
+    if tail:                                                          # (as pcg_shapes._with_loose: the last mesh node trades
+        nm = len(nodes)                                               # places with the last loose one) -- here the node
+        nodes = np.vstack([nodes, far + 2.0 + 0.01 * np.arange(tail)[:, None] * np.ones(nodes.shape[1])])
+        top = np.argsort(-np.bincount(el.ravel(), minlength=nm), kind="stable")    # of the highest valence, and the next
+        for j, end in enumerate((len(nodes) - 1, len(nodes) - 1 - SLICE)):          # one a slice earlier
+            if end >= nm:
+                a = int(top[j])
+                nodes[[a, end]] = nodes[[end, a]]
+                el = np.where(el == a, end, el)
+    return nodes, el.astype(np.int32)
+
+
+def build(row):
+    """-> (nodes, elements, plug-in)"""
+    kind, args = row.mesh
+    if kind == "plate":
+        etype, cells = args
+        nodes, el, _ = lr.mesh(etype, cells)
+        nodes = grade(nodes)
+    elif kind == "fans3d":
+        etype, ks = args
+        nodes, el = fans3d(ks, etype == "C3D10")
+    elif kind == "fans2d":
+        etype, ks = args
+        nodes, el = fans2d(ks)
+    else:
+        assert kind == "first"                                   # the first ne elements of a plate; the other nodes stay, loose
+        etype, cells, ne = args
+        nodes, el, _ = lr.mesh(etype, cells)
+        el = el[:ne]
+    nodes, el = with_loose(nodes, el, *row.loose)
+    return np.ascontiguousarray(nodes, np.float64), np.ascontiguousarray(el, np.int32), PLUGINS[etype]()
+
+
+def materials(dm):
+    """the isotropic C (cubic pattern in 3-D) and the fully populated symmetric C of test_assemble_K_general_C"""
+    iso = LinearIsotropic(2.0e5, 0.3) if dm == 3 else LinearIsotropicPlaneStress(2.0e5, 0.3)
+    rng = np.random.default_rng(11)
+    M = rng.standard_normal(iso.C.shape)
+    return {"iso": iso, "general": SimpleNamespace(kind=iso.kind, C=iso.C + 0.05 * np.abs(iso.C).max() * (M + M.T),
+                                                   params=iso.params)}
+
+
+def disp(nodes, scale):
+    """test_gpu_parity.smooth_disp: smooth, no RNG, ~scale x the extent"""
+    Lc = np.ptp(nodes, axis=0).max()
+    x = nodes / Lc
+    u = np.stack([np.sin(1.3 * x[:, 0] + 0.4) * np.cos(0.7 * x[:, -1]), 0.5 * np.cos(2.1 * x[:, 1] - 0.2) * x[:, 0],
+                  0.3 * np.sin(x.sum(axis=1))][:nodes.shape[1]], axis=1)
+    return (scale * Lc * u).ravel()
+
+
+SCALES = (0.0, 0.002)
+
+
+# ------------------------------------------------------------------------------------------------- the layout, restated
+def sell_layout(rowlen, sigma):
+    """pcg_shapes.layout with the window as a parameter"""
+    if sigma == ps.SIGMA:
+        return ps.layout(rowlen)
+    nn = len(rowlen)
+    ns = -(-nn // SLICE)
+    node_of = -np.ones(ns * SLICE, dtype=np.int64)
+    for a0 in range(0, nn, sigma):
+        idx = np.arange(a0, min(nn, a0 + sigma))
+        node_of[a0:a0 + len(idx)] = idx[np.argsort(-rowlen[idx], kind="stable")]
+    L = np.where(node_of >= 0, rowlen[np.maximum(node_of, 0)], 0).reshape(ns, SLICE).max(axis=1)
+    return node_of, L
+
+
+class Layout:
+    """what the kernels' loops see of a mesh: rowlen / cnt per node, node_of per storage position, L per slice"""
+
+    def __init__(self, nodes, el, sigma):
+        self.nn, self.dm = nodes.shape
+        self.ne, self.npe = el.shape
+        self.sigma = sigma
+        self.cnt = np.bincount(el.ravel(), minlength=self.nn)
+        a = np.repeat(el, self.npe, axis=1).ravel().astype(np.int64)
+        b = np.tile(el, (1, self.npe)).ravel().astype(np.int64)
+        keys = np.unique(np.concatenate([a * self.nn + b, np.arange(self.nn, dtype=np.int64) * (self.nn + 1)]))
+        self.brow, self.bcol = keys // self.nn, keys % self.nn       # block-CSR, ascending columns: get_K_bsr's order
+        self.rowlen = np.bincount(self.brow, minlength=self.nn)
+        self.node_of, self.L = sell_layout(self.rowlen, sigma)
+        self.nslices = len(self.L)
+        self.pos = np.empty(self.nn, np.int64)
+        self.pos[self.node_of[self.node_of >= 0]] = np.nonzero(self.node_of >= 0)[0]
+        self.stored = int(self.L.sum()) * SLICE
+        self.max_row = int(self.rowlen.max())
+        self.contributors = np.bincount(np.searchsorted(keys, a * self.nn + b), minlength=len(keys))
+
+    def at(self, p, what):
+        """`what` (per node) at storage positions p; 0 on padding"""
+        a = self.node_of[p]
+        return np.where(a >= 0, what[np.maximum(a, 0)], 0)
+
+    # k_assemble_rows4 -------------------------------------------------------------------------------------------
+    def rows4_wave(self, s, w):
+        """storage positions of the rows of wave w in slice s, in the wave's order (valid rows only)"""
+        i = np.arange(SLICE // 4)
+        p = s * SLICE + 8 * (i >> 1) + 2 * w + (i & 1)
+        return p[self.node_of[p] >= 0]
+
+    def rows4_pairs(self):
+        """-> [(slice, wave, cnt of the lower row, cnt of the upper row or -1 = padding, L lower, L upper)]"""
+        out = []
+        for s in range(self.nslices):
+            for w in range(4):
+                p = self.rows4_wave(s, w)
+                c, L = self.at(p, self.cnt), self.at(p, self.rowlen)
+                for b in range(0, len(p), 2):
+                    up = b + 1 < len(p)
+                    out.append((s, w, int(c[b]), int(c[b + 1]) if up else -1, int(L[b]), int(L[b + 1]) if up else 0))
+        return out
+
+    @staticmethod
+    def rows4_steps(c):
+        return max(1, -(-max(c, 0) // EPG))
+
+    # ensure_pairs -----------------------------------------------------------------------------------------------
+    def chunks(self, rpw):
+        """-> per chunk of rpw storage positions: (pair words, batches, rows with elements, min cnt, max cnt)"""
+        c = self.at(np.arange(self.nslices * SLICE), self.cnt).reshape(-1, rpw)
+        if self.dm == 3:
+            ppw = 64 // self.npe
+            sw, bat = -(-rpw // ppw) * ppw, 64 // ppw * ppw
+            words = c.max(axis=1) * sw
+        else:
+            bat, words = BATCH, c.sum(axis=1)
+        return np.column_stack([words, np.maximum(1, -(-words // bat)), (c > 0).sum(axis=1), c.min(axis=1), c.max(axis=1)])
+
+    def pairs_grid(self, rpw, cpw):
+        """-> (units of cpw chunks = waves with work, workgroups of four waves rounded up to the 8 XCDs): the PAIRS launch"""
+        nunits = -(-self.nslices * (SLICE // rpw) // cpw)
+        return nunits, ((nunits + 3) // 4 + 7) // 8 * 8
+
+    # LDS of a workgroup (kernels_assembly.hip: rows_lds .. pairs_lds) -------------------------------------------------
+    def lds(self, mode, rpw=16):
+        m, dm, npe = self.max_row, self.dm, self.npe
+        ngp = {3: 1, 4: {2: 4, 3: 1}[dm], 6: {2: 3, 3: 6}[dm], 8: {2: 4, 3: 8}[dm], 10: 4}[npe]
+        accw = (m * 9 + 1) & ~1
+        if mode == R:
+            return 4 * m * dm * dm * 8
+        if mode == P:
+            return 4 * dm * dm * rpw * (m | 1) * 8
+        rd = ngp * npe * 3
+        if mode == R2:
+            epc = 64 // (npe - 1)
+            return 4 * (epc * rd + ((epc * ngp + 1) & ~1) + accw + 2 * ((epc + 1) // 2 * 2 // 2 + 1)) * 8
+        assert mode == R4
+        epg = 32 // npe
+        return 4 * 2 * (epg * rd + ((epg * ngp + 1) & ~1) + accw + 2) * 8
+
+
+# ------------------------------------------------------------------------------------------------------- the reference
+def _det_inv(J, mag=False):
+    """determinant and inverse by cofactors of J [..., dm, dm]; mag: the sums of the magnitudes of their terms instead"""
+    dm = J.shape[-1]
+    s = 1.0 if mag else -1.0
+    if mag:
+        J = np.abs(J)
+    if dm == 2:
+        det = J[..., 0, 0] * J[..., 1, 1] + s * J[..., 0, 1] * J[..., 1, 0]
+        adj = np.stack([np.stack([J[..., 1, 1], (1.0 if mag else -1.0) * J[..., 0, 1]], -1),
+                        np.stack([(1.0 if mag else -1.0) * J[..., 1, 0], J[..., 0, 0]], -1)], -2)
+        return det, adj
+    adj = np.empty_like(J)
+    for i in range(3):
+        for j in range(3):
+            i1, i2, j1, j2 = (i + 1) % 3, (i + 2) % 3, (j + 1) % 3, (j + 2) % 3
+            adj[..., i, j] = J[..., j1, i1] * J[..., j2, i2] + s * J[..., j1, i2] * J[..., j2, i1]
+    det = J[..., 0, 0] * adj[..., 0, 0] + J[..., 0, 1] * adj[..., 1, 0] + J[..., 0, 2] * adj[..., 2, 0]
+    return det, adj
+
+
+def _B(g):
+    """grad N [..., npe, dm] -> B [..., s, npe, dm] (column (a, i)), the reference's Voigt order, engineering shear"""
+    dm = g.shape[-1]
+    B = np.zeros(g.shape[:-2] + ((3 if dm == 2 else 6),) + g.shape[-2:], dtype=g.dtype)
+    if dm == 2:
+        B[..., 0, :, 0], B[..., 1, :, 1] = g[..., 0], g[..., 1]
+        B[..., 2, :, 0], B[..., 2, :, 1] = g[..., 1], g[..., 0]
+        return B
+    B[..., 0, :, 0], B[..., 1, :, 1], B[..., 2, :, 2] = g[..., 0], g[..., 1], g[..., 2]
+    B[..., 3, :, 0], B[..., 3, :, 1] = g[..., 1], g[..., 0]
+    B[..., 4, :, 0], B[..., 4, :, 2] = g[..., 2], g[..., 0]
+    B[..., 5, :, 1], B[..., 5, :, 2] = g[..., 2], g[..., 1]
+    return B
+
+
+Ref = collections.namedtuple("Ref", "K A Arow A0 dsdx Adsdx vol Avol F AF sig Asig fe f Af")
+
+
+def reference(lay, nodes, el, ELE, mat, u, dt=LD, cubic=False, force=True):
+    """everything in dtype dt.  K, A [nnzb, dm, dm] in the order of lay.brow / lay.bcol; Arow: A with the diagonal blocks
+    replaced by sum_(b != a) A_ab; cubic: K from the geometric sum S, the constants applied once per block"""
+    t = ELE.tables()
+    dN, w = t["dN"].astype(dt), t["w"].astype(dt)
+    dm, npe, nn = lay.dm, lay.npe, lay.nn
+    C = np.asarray(mat.C, np.float64).astype(dt)
+    X = nodes.astype(dt)
+    x = (X + u.reshape(nodes.shape).astype(dt))[el]
+    J = np.einsum("eai,gaj->egij", x, dN)
+    det, adj = _det_inv(J)
+    dsdx = np.einsum("gak,egkj->egaj", dN, adj) / det[..., None, None]
+    vol = det * w
+    mdet, madj = _det_inv(np.einsum("eai,gaj->egij", np.abs(x), np.abs(dN)), mag=True)
+    Adsdx = np.einsum("gak,egkj->egaj", np.abs(dN), madj) / np.abs(det)[..., None, None]
+    Avol = mdet * np.abs(w)
+    # element blocks [e, a, b, i, j] and their magnitude sums
+    B = _B(dsdx)
+    if cubic:
+        Sg = np.einsum("egai,egbj,eg->eabij", dsdx, dsdx, vol)
+        blocks = Sg
+    else:
+        CB = np.einsum("kl,eglbj->egkbj", C, B)
+        blocks = np.einsum("egkai,egkbj,eg->eabij", B, CB, vol)
+    # first-order magnitudes: the sum's own terms, and what the roundings of vol and grad N (eps Avol, eps Adsdx) move them by
+    aB, gB, aC = np.abs(B), _B(Adsdx), np.abs(C)
+    aCB = np.einsum("kl,eglbj->egkbj", aC, aB)
+    mags = (np.einsum("egkai,egkbj,eg->eabij", aB, aCB, Avol)
+            + np.einsum("egkai,egkbj,eg->eabij", gB, aCB, np.abs(vol))
+            + np.einsum("egkai,egkbj,eg->eabij", aB, np.einsum("kl,eglbj->egkbj", aC, gB), np.abs(vol)))
+    a = np.repeat(el, npe, axis=1).ravel().astype(np.int64)
+    b = np.tile(el, (1, npe)).ravel().astype(np.int64)
+    keys = lay.brow * nn + lay.bcol
+    slot = np.searchsorted(keys, a * nn + b)
+    order = np.argsort(slot, kind="stable")                      # ascending (e, la, lb) inside a block
+    starts = np.searchsorted(slot[order], np.arange(len(keys)))
+    have = lay.contributors > 0
+
+    def reduce(v):
+        out = np.zeros((len(keys), dm, dm), dt)
+        if len(order):
+            out[have] = np.add.reduceat(v.reshape(-1, dm, dm)[order], starts[have], axis=0)   # (blocks nobody names: no segment)
+        return out
+
+    K, Amag = reduce(blocks), reduce(mags)
+    A0 = reduce(np.einsum("egkai,egkbj,eg->eabij", aB, aCB, np.abs(vol)))      # the sum's own terms alone
+    if cubic:
+        c11, c12, c44 = C[0, 0], C[0, 1], C[3, 3]
+        tr = np.trace(K, axis1=1, axis2=2)
+        Kc = c12 * K + c44 * np.swapaxes(K, 1, 2)
+        for i in range(3):
+            Kc[:, i, i] = c11 * K[:, i, i] + c44 * (tr - K[:, i, i])
+        K = Kc
+    diag = lay.brow == lay.bcol
+    off = Amag.copy()
+    off[diag] = 0
+    Arow = Amag.copy()
+    rs = np.zeros((nn, dm, dm), dt)
+    np.add.at(rs, lay.brow, off)
+    Arow[diag] = rs
+    F = AF = sig = Asig = fe = f = Af = None
+    if force:
+        U = u.reshape(nodes.shape).astype(dt)[el]
+        J0 = np.einsum("eai,gaj->egij", X[el], dN)
+        d0, a0 = _det_inv(J0)
+        F = np.einsum("eai,egaj->egij", U, np.einsum("gak,egkj->egaj", dN, a0) / d0[..., None, None]) + np.eye(dm, dtype=dt)
+        m0, ma0 = _det_inv(np.einsum("eai,gaj->egij", np.abs(X[el]), np.abs(dN)), mag=True)
+        AF = np.einsum("eai,egaj->egij", np.abs(U), np.einsum("gak,egkj->egaj", np.abs(dN), ma0) / np.abs(d0)[..., None, None]) \
+            + np.eye(dm, dtype=dt)
+        # sigma = F S F^T / J, S = C : E, E = (F^T F - I) / 2 with every term taken by its magnitude (E loses its leading
+        # digits at small strains: that is what a float64 evaluation can be held to, not |sigma| itself)
+        aF = np.abs(F)
+        Em = (np.einsum("egki,egkj->egij", aF, AF) + np.einsum("egki,egkj->egij", AF, aF)) / 2     # (AF >= |F|: it holds the I)
+        pairs_ = [(0, 0), (1, 1), (0, 1)] if dm == 2 else [(0, 0), (1, 1), (2, 2), (0, 1), (2, 0), (1, 2)]
+        ev = np.stack([Em[..., i, j] * (1 if i == j else 2) for i, j in pairs_], axis=-1)
+        sv = np.einsum("kl,egl->egk", np.abs(C), ev)
+        Sm = np.zeros_like(Em)
+        for k, (i, j) in enumerate(pairs_):
+            Sm[..., i, j] = Sm[..., j, i] = sv[..., k]
+        dF = np.abs(_det_inv(F)[0])
+        Asig = np.einsum("egik,egkl,egjl->egij", aF, Sm, aF) / dF[..., None, None]
+        kind = {0: "lin3d", 1: "pstrain", 2: "pstress", 3: "neohooke"}[mat.kind]
+        sig = orc.cauchy_large(orc.Material(kind, tuple(float(v) for v in mat.params)), F)
+        fe = np.einsum("egaj,egji,eg->eai", dsdx, sig, vol)
+        afe = np.einsum("egaj,egji,eg->eai", np.abs(dsdx), np.abs(sig), np.abs(vol))
+        f, Af = np.zeros((nn, dm), dt), np.zeros((nn, dm), dt)
+        np.add.at(f, el.ravel(), fe.reshape(-1, dm))
+        np.add.at(Af, el.ravel(), afe.reshape(-1, dm))
+    return Ref(K, Amag, Arow, A0, dsdx, Adsdx, vol, Avol, F, AF, sig, Asig, fe, f, Af)
+
+
+def ratio(got, ref, scale):
+    """worst |got - ref| / (eps scale) over the entries with scale > 0; the others must be exactly zero"""
+    got, ref, scale = np.asarray(got), np.asarray(ref), np.asarray(scale)
+    zero = scale == 0
+    assert not got[zero].any(), "a structural zero holds %r" % got[zero][np.nonzero(got[zero])[0][:3]]
+    if zero.all():
+        return 0.0, -1
+    r = np.where(zero, 0, np.abs(got.astype(LD) - ref) / (EPS * np.where(zero, 1, scale)))
+    k = int(np.argmax(r))
+    return float(r.ravel()[k]), k
+
+
+# ------------------------------------------------------------------------------------------------------------ the table
+Row = collections.namedtuple("Row", "name mesh loose sigma modes auto knobs refused pins edge why")
+
+
+# (nn, ne, nslices, stored_blocks, max_row_blocks)
+PINS = {
+    "c3d10-graded-loose": (321, 72, 6, 15616, 65),
+    "c3d10-tail-63": (255, 48, 4, 5440, 65),
+    "c3d10-fans": (322, 66, 6, 7680, 67),
+    "c3d4-graded": (128, 216, 2, 1920, 15),
+    "c3d4-fans": (195, 148, 4, 3584, 45),
+    "c3d8-graded": (88, 18, 2, 3456, 27),
+    "c3d6-graded": (118, 36, 2, 2688, 21),
+    "cps3-fan-64": (35, 34, 1, 2240, 35),
+    "cps3-fan-65": (36, 35, 1, 2304, 36),
+    "cps4-graded": (128, 63, 2, 960, 9),
+    "cps6-graded": (148, 60, 3, 3008, 19),
+    "cps8-graded": (116, 30, 2, 2176, 21),
+    "lds-rows-under": (170, 168, 3, 11520, 170),
+    "lds-rows-over": (171, 169, 3, 11584, 171),
+    "lds-rows2-under": (137, 135, 3, 9408, 137),
+    "lds-rows2-over": (138, 136, 3, 9472, 138),
+    "lds-rows4-under": (43, 10, 1, 2752, 43),
+    "lds-rows4-over": (47, 11, 1, 3008, 47),
+    "lds-pairs-under": (23, 22, 1, 1472, 23),
+    "lds-pairs-over": (24, 23, 1, 1536, 24),
+    "lds-rows4-refused": (243, 60, 4, 17984, 243),
+    "lds-rows2-refused": (483, 120, 8, 36672, 483),
+    "rows-grid-loop": (16427, 48, 257, 18624, 15),
+    "valence-cps3": (236, 226, 4, 4992, 66),
+    "valence-c3d4": (242, 226, 4, 5248, 67),
+    "geom-c3d4-1": (100, 1, 2, 320, 4),
+    "geom-c3d4-63": (100, 63, 2, 768, 11),
+    "geom-c3d4-64": (100, 64, 2, 768, 11),
+    "geom-c3d4-65": (100, 65, 2, 768, 11),
+    "geom-c3d4-255": (100, 255, 2, 1536, 15),
+    "geom-c3d4-256": (100, 256, 2, 1536, 15),
+    "geom-c3d4-257": (100, 257, 2, 1536, 15),
+    "geom-c3d10-1": (567, 1, 9, 1152, 10),
+    "geom-c3d10-63": (567, 63, 9, 5120, 42),
+    "geom-c3d10-64": (567, 64, 9, 5120, 42),
+    "geom-c3d10-65": (567, 65, 9, 5120, 42),
+    "geom-c3d10-255": (567, 255, 9, 14144, 65),
+    "geom-c3d10-256": (567, 256, 9, 14400, 65),
+    "geom-c3d10-257": (567, 257, 9, 14400, 65),
+    "geom-c3d8-1": (448, 1, 7, 896, 8),
+    "geom-c3d8-63": (448, 63, 7, 3904, 27),
+    "geom-c3d8-64": (448, 64, 7, 3904, 27),
+    "geom-c3d8-65": (448, 65, 7, 3904, 27),
+    "geom-c3d8-255": (448, 255, 7, 9408, 27),
+    "geom-c3d8-256": (448, 256, 7, 9408, 27),
+    "geom-c3d8-257": (448, 257, 7, 9408, 27),
+}
+
+
+def _r(name, mesh, loose, sigma, modes, auto, edge, why, knobs=(), refused=()):
+    return Row(name, mesh, loose, sigma, modes, auto, knobs, refused, PINS[name], edge, why)
+
+
+def _last_slice_rows(y):
+    return [len(y.rows4_wave(y.nslices - 1, w)) for w in range(4)]
+
+
+def _trips(y):
+    return {min(3, -(-int(v) // TRIP)) for v in y.rowlen[y.cnt > 0]}
+
+
+def _pair(y, lo, hi):
+    """a ROWS4 pair of rows with cnt <= lo on one side and cnt >= hi on the other"""
+    return any(min(c0, c1) <= lo and c1 >= 0 and max(c0, c1) >= hi for _, _, c0, c1, _, _ in y.rows4_pairs())
+
+
+def _cross(y, unit):
+    """a stored block (a, b), a < b, whose transpose lives in another unit of `unit` storage positions"""
+    up = y.brow < y.bcol
+    return bool((y.pos[y.brow[up]] // unit != y.pos[y.bcol[up]] // unit).any())
+
+
+def _loose_slice(y):
+    return bool((y.L == 1).any())
+
+
+def _lds(y, mode, side, rpw=16):
+    v = y.lds(mode, rpw)
+    return LDS_LINE - 1024 < v <= LDS_LINE if side == "under" else LDS_LINE < v < LDS_LINE + 1024
+
+
+T3D = (G, A, R, S, SR)
+K16 = tuple(k for k in KNOBS if k[0] == 16)
+FIRST = {"C3D4": (4, 4, 3), "C3D10": (4, 4, 3), "C3D8": (7, 7, 6)}     # plates of >= 257 elements
+ROWS = [
+    _r("c3d10-graded-loose", ("plate", ("C3D10", (3, 2, 2))), (7, 122), 64, T3D + (R2, R4), R4,
+       lambda y: y.nn % 64 == 1 and _last_slice_rows(y) == [1, 0, 0, 0] and _pair(y, 0, 3 * EPG) and _trips(y) == {1, 2, 3}
+       and {int(c) % 3 for c in y.cnt[y.cnt > 0]} == {0, 1, 2} and _pair(y, EPG, 2 * EPG + 1) and y.nslices >= 3
+       and _cross(y, SLICE) and y.sigma < y.nn and _cross(y, y.sigma) and (y.ne * y.npe ** 2) % 256 != 0,
+       "a graded C3D10 plate with a loose node behind every seventh, windows of 64: loose rows inside slices of coupled "
+       "ones and paired with rows of >= 3 steps, pairs of 1 and >= 3 steps, element counts 0 / 1 / 2 mod 3, one, two and "
+       "three write-out trips, transposes across slices and windows; the last slice holds one row: wave 0 alone, partner "
+       "padding; ne npe^2 is no multiple of 256"),
+    _r("c3d10-tail-63", ("plate", ("C3D10", (2, 2, 2))), (0, 130), 4096, T3D + (R2, R4), R4,
+       lambda y: y.nn % 64 == 63 and _last_slice_rows(y) == [16, 16, 16, 15] and y.L[-1] == 1 and _loose_slice(y)
+       and any(len(y.rows4_wave(s, w)) % 2 == 1 and len(y.rows4_wave(s, w)) > 1 for s in range(y.nslices) for w in range(4)),
+       "loose nodes behind the mesh: slices made only of loose rows, nn = 63 mod 64, wave 3 of the last slice has 15 rows"),
+    _r("c3d10-fans", ("fans3d", ("C3D10", (6, 7, 8, 14, 15, 16))), (0, 40), 4096, T3D + (R2, R4), R4,
+       lambda y: y.nn % 64 == 2 and {6, 7, 8, 14, 15} <= set(y.cnt.tolist()) and 64 // (y.npe - 1) == 7
+       and _trips(y) == {1, 2, 3} and 0 in y.cnt and y.contributors.max() >= 16 and {1, 2} <= set(y.contributors.tolist()),
+       "fans of E - 1, E, E + 1, 2 E, 2 E + 1 (E = 7: a ROWS2 pass) and 16 tetrahedra: rows of 27 .. 67 blocks, blocks "
+       "with 1, 2 and 16 contributors, nn = 2 mod 64"),
+    _r("c3d4-graded", ("plate", ("C3D4", (4, 3, 3))), (0, 48), 64, T3D + (R2,), SR,
+       lambda y: y.nn % 64 == 0 and (y.cnt * y.npe > 64).any() and (y.cnt[y.cnt > 0] * y.npe < 64).any()
+       and {1, 2, 3} <= set(y.contributors.tolist()) and _cross(y, SLICE),
+       "a graded C3D4 plate, nn = 0 mod 64: ROWS lanes below and above 64, blocks with 1, 2, 3 and more contributors"),
+    _r("c3d4-fans", ("fans3d", ("C3D4", (20, 21, 22, 42, 43))), (0, 37), 4096, T3D + (R2,), SR,
+       lambda y: y.nn % 64 == 3 and {0, 20, 21, 22, 42, 43} <= set(y.cnt.tolist()) and 64 // (y.npe - 1) == 21
+       and _last_slice_rows(y) == [2, 1, 0, 0],
+       "fans of E - 1, E, E + 1, 2 E, 2 E + 1 tetrahedra (E = 21) and rows with none; nn = 3 mod 64"),
+    _r("c3d8-graded", ("plate", ("C3D8", (3, 3, 2))), (0, 40), 64, T3D + (P,), P,
+       lambda y: (y.cnt * y.npe == 64).any() and (y.cnt[y.cnt > 0] * y.npe < 64).any()
+       and (lambda c: ((c[:, 3] < c[:, 4]) & (c[:, 3] > 0)).any() and (c[:, 2] == 0).any())(y.chunks(8))
+       and (y.chunks(16)[:, 2] == 0).any(),
+       "a graded C3D8 plate: interior rows of exactly 64 ROWS lanes, chunks whose rows have unequal valence (padding "
+       "words in the step-ordered list), chunks of loose rows only", knobs=KNOBS),
+    _r("c3d6-graded", ("plate", ("C3D6", (3, 3, 2))), (0, 70), 64, T3D + (P,), P,
+       lambda y: (y.cnt * y.npe > 64).any() and (lambda c: ((c[:, 3] < c[:, 4])).any())(y.chunks(16))
+       and (64 // y.npe) * y.npe != 64 and (lambda c: ((c[:, 3] == 0) & (c[:, 4] > 0)).any())(y.chunks(16)),
+       "a graded C3D6 plate with loose rows inside the slices: 10 pairs per step (60 of 64 lanes), steps padded to a multiple "
+       "of 10 words; interior rows of 72 ROWS lanes", knobs=KNOBS),
+    _r("cps3-fan-64", ("fans2d", ("CPS3", (34,))), (0, 0), 4096, (G, SR, P), SR,
+       lambda y: y.chunks(16)[0, 0] == BATCH and y.chunks(16)[0, 1] == 1 and y.contributors.max() == 34,
+       "a fan of 34 triangles: the first chunk of 16 rows has exactly 64 pairs, one full batch", knobs=K16),
+    _r("cps3-fan-65", ("fans2d", ("CPS3", (35,))), (0, 0), 4096, (G, SR, P), SR,
+       lambda y: y.chunks(16)[0, 0] == BATCH + 1 and y.chunks(16)[0, 1] == 2 and y.lds(P, 16) > LDS_LINE,
+       "a fan of 35: 65 pairs, a second batch of one pair", knobs=K16),
+    _r("cps4-graded", ("plate", ("CPS4", (9, 7))), (0, 48), 4096, (G, A, R, S, SR, P), SR,
+       lambda y: (y.chunks(16)[:, 0] == BATCH).any() and (y.chunks(16)[:, 2] == 0).any() and (y.chunks(8)[:, 2] == 0).any()
+       and (y.chunks(16)[:, 0] % (64 // y.npe) != 0).any()
+       and all(y.pairs_grid(k[0], k[3])[0] < 4 * 8 and y.pairs_grid(k[0], k[3])[1] == 8 for k in KNOBS if k[2]),
+       "a graded CPS4 plate: chunks of 16 interior rows have exactly 64 pairs, others no multiple of 16; chunks of loose rows "
+       "only; fewer units than the 8 workgroups of the XCD-contiguous ranges have waves", knobs=KNOBS),
+    _r("cps6-graded", ("plate", ("CPS6", (6, 5))), (0, 5), 64, (G, A, R, S, SR, P), P,
+       lambda y: (y.chunks(16)[:, 0] % (64 // y.npe) != 0).any() and (y.chunks(16)[:, 1] >= 2).any() and _cross(y, 64),
+       "a graded CPS6 plate, windows of 64: 10 pairs per step, pair counts that are no multiple of it, chunks of two "
+       "batches", knobs=KNOBS),
+    _r("cps8-graded", ("plate", ("CPS8", (6, 5))), (0, 3), 4096, (G, A, R, S, SR, P), P,
+       lambda y: (y.chunks(16)[:, 0] % (64 // y.npe) != 0).any() and (y.chunks(8)[:, 0] % (64 // y.npe) != 0).any(),
+       "a graded CPS8 plate: 8 pairs per step, pair counts that are no multiple of it", knobs=KNOBS),
+    _r("lds-rows-under", ("fans3d", ("C3D4", (168,))), (0, 0), 4096, (R,), SR,
+       lambda y: y.max_row == 170 and _lds(y, R, "under"), "ROWS: 4 x 170 x 9 doubles = 48 960 B, no attribute call"),
+    _r("lds-rows-over", ("fans3d", ("C3D4", (169,))), (0, 0), 4096, (R,), SR,
+       lambda y: y.max_row == 171 and _lds(y, R, "over"), "ROWS: 49 248 B, the first size that sets the attribute"),
+    _r("lds-rows2-under", ("fans3d", ("C3D4", (135,))), (0, 0), 4096, (R2,), SR,
+       lambda y: y.max_row == 137 and _lds(y, R2, "under"), "ROWS2 (C3D4): 49 024 B"),
+    _r("lds-rows2-over", ("fans3d", ("C3D4", (136,))), (0, 0), 4096, (R2,), SR,
+       lambda y: y.max_row == 138 and _lds(y, R2, "over"), "ROWS2 (C3D4): 49 280 B"),
+    _r("lds-rows4-under", ("fans3d", ("C3D10", (10,))), (0, 0), 4096, (R4, R2), R4,
+       lambda y: y.max_row == 43 and _lds(y, R4, "under"), "ROWS4: 48 768 B (a fan's rows are 3 mod 4: 43, then 47)"),
+    _r("lds-rows4-over", ("fans3d", ("C3D10", (11,))), (0, 0), 4096, (R4, R2), R4,
+       lambda y: y.max_row == 47 and LDS_LINE < y.lds(R4) < LDS_LINE + 4096, "ROWS4: 51 072 B"),
+    _r("lds-pairs-under", ("fans2d", ("CPS3", (22,))), (0, 0), 4096, (P,), SR,
+       lambda y: y.max_row == 23 and LDS_LINE - 2048 <= y.lds(P, 16) <= LDS_LINE, "PAIRS, 16 rows per wave: 47 104 B", knobs=K16),
+    _r("lds-pairs-over", ("fans2d", ("CPS3", (23,))), (0, 0), 4096, (P,), SR,
+       lambda y: y.max_row == 24 and LDS_LINE < y.lds(P, 16) <= LDS_LINE + 2048, "PAIRS: (24 | 1) slots, 51 200 B", knobs=K16),
+    _r("lds-rows4-refused", ("fans3d", ("C3D10", (60,))), (0, 0), 4096, (R2, G), R2,
+       lambda y: y.lds(R4) > LDS_DEVICE and y.lds(R2) + 512 <= LDS_DEVICE,
+       "a fan of 60: rows of 243 blocks, ROWS4 would need 163 968 B: refused, AUTO takes ROWS2", refused=(R4,)),
+    _r("lds-rows2-refused", ("fans3d", ("C3D10", (120,))), (0, 0), 4096, (R, S), R,
+       lambda y: y.lds(R4) > LDS_DEVICE and y.lds(R2) + 512 > LDS_DEVICE and y.lds(R) + 512 <= LDS_DEVICE,
+       "a fan of 120: rows of 483 blocks, neither ROWS4 nor ROWS2 fits: both refused, AUTO takes ROWS", refused=(R4, R2)),
+    _r("rows-grid-loop", ("plate", ("C3D4", (2, 2, 2))), (0, 16400), 4096, (R,), SR,
+       lambda y: y.nn > 4 * 256 * 16 and (y.nn + 3) // 4 > 256 * 16,
+       "16 400 loose nodes behind a small plate: the capped ROWS grid of 4096 workgroups walks a second round"),
+    _r("valence-cps3", ("fans2d", ("CPS3", (1, 31, 32, 33, 64, 65))), (0, 3), 4096, (SR, P), SR,
+       lambda y: {0, 1, 2, 31, 32, 33, 64, 65} <= set(y.cnt.tolist()), "node sums of 0, 1, 2, 31 .. 65 rows, dm = 2", knobs=K16[:1]),
+    _r("valence-c3d4", ("fans3d", ("C3D4", (1, 31, 32, 33, 64, 65))), (0, 3), 4096, (SR, R2), SR,
+       lambda y: {0, 1, 2, 31, 32, 33, 64, 65} <= set(y.cnt.tolist()), "node sums of 0, 1, 2, 31 .. 65 rows, dm = 3"),
+] + [
+    _r("geom-%s-%d" % (et.lower(), ne), ("first", (et, FIRST[et], ne)), (0, 0), 4096, (G,), {"C3D4": SR, "C3D10": R4, "C3D8": P}[et],
+       (lambda ne: lambda y: y.ne == ne and (ne > 1 or 1 in y.cnt))(ne),
+       "k_geom: %d elements (the last workgroup of 256 threads full, short by one, one over)" % ne, knobs=KNOBS[-1:])
+    for et in ("C3D4", "C3D10", "C3D8") for ne in (1, 63, 64, 65, 255, 256, 257)
+]
+GRADED = ("c3d10-graded-loose", "c3d4-graded", "c3d8-graded", "c3d6-graded", "cps4-graded", "cps6-graded", "cps8-graded")
+
+
+def row_id(row):
+    return row.name
+
+
+# ------------------------------------------------------------------------------------------------------------- a case
+class Case:
+    """one row on one backend: the context with the pattern built, the restated layout and the references (on demand)"""
+
+    def __init__(self, row, backend):
+        self.row, self.backend = row, backend
+        self.nodes, self.el, self.ELE = build(row)
+        self.lay = Layout(self.nodes, self.el, row.sigma)
+        self.mats = materials(self.lay.dm)
+        ctx = self.ctx = be.Context(0, backend=backend)
+        ctx.set_option(be.OPT_NODE_ORDER, 0)                       # the caller's numbering: what Layout restates
+        ctx.set_option(be.OPT_SELL_SIGMA, row.sigma)
+        ctx.set_mesh(self.nodes, self.el)
+        ctx.set_element(self.ELE)
+        ctx.set_material(self.mats["iso"])
+        self.info = ctx.build_pattern()
+        self.us = {s: disp(self.nodes, s) for s in SCALES}
+        self._refs = {}
+        rng = np.random.default_rng(5)
+        self.x = rng.standard_normal(ctx.n) + 0.25
+
+    def ref(self, mat, scale, dt=LD, cubic=False):
+        key = (mat, scale, dt, cubic)
+        if key not in self._refs:
+            self._refs[key] = reference(self.lay, self.nodes, self.el, self.ELE, self.mats[mat], self.us[scale], dt, cubic,
+                                        force=mat == "iso" and not cubic)
+        return self._refs[key]
+
+    def K(self):
+        """the exported blocks [nnzb, dm, dm]; their pattern is the restated one"""
+        Kb = self.ctx.get_K_bsr()
+        assert np.array_equal(Kb.indices, self.lay.bcol) and np.array_equal(np.diff(Kb.indptr), self.lay.rowlen)
+        return Kb.data.copy()
+
+    def close(self):
+        self.ctx.close()
+
+
+_CASES = collections.OrderedDict()
+
+
+def case(name, backend):
+    key = (name, backend)
+    if key not in _CASES:
+        while len(_CASES) >= 1:
+            _CASES.popitem(last=False)[1].close()
+        _CASES[key] = Case(next(r for r in ROWS if r.name == name), backend)
+    return _CASES[key]
+
+
+# -------------------------------------------------------------------------------------------------------------- checks
+def check_table(row):
+    """the table's own arithmetic (no library): pins and the property the row exists for"""
+    nodes, el, _ = build(row)
+    y = Layout(nodes, el, row.sigma)
+    assert (y.nn, y.ne, y.nslices, y.stored, y.max_row) == row.pins, ((y.nn, y.ne, y.nslices, y.stored, y.max_row), row.name)
+    assert row.edge(y), (row.name, row.why)
+    return y
+
+
+def check_edge(name, backend):
+    """the counts of the table, the restatement against the library, and the property the row exists for"""
+    c = case(name, backend)
+    y, info, row = c.lay, c.info, c.row
+    assert (y.nn, y.ne, y.nslices, y.stored, y.max_row) == row.pins, ((y.nn, y.ne, y.nslices, y.stored, y.max_row), row.pins)
+    assert (info.n, info.nnzb, info.max_row_blocks, info.max_node_elems) == (y.nn * y.dm, len(y.brow), y.max_row, y.cnt.max())
+    if backend == "hip":                                           # (the host library stores block-CSR)
+        assert (info.nslices, info.stored_blocks) == (y.nslices, y.stored), (info.nslices, info.stored_blocks, row.pins)
+    assert row.edge(y), (row.name, row.why)
+    if name in GRADED:
+        v = np.abs(c.ref("iso", 0.0).vol.astype(np.float64)).sum(axis=1)
+        assert v.max() / v.min() >= 1000.0, (name, v.max() / v.min())       # three decades
+
+
+def _modes(c):
+    """[(mode to set, mode that must have run, FEMCY_TUNE_PAIRS or None)]"""
+    if c.backend != "hip":
+        return [(AUTO, A, None)]                                   # the host library's one assembly reports ATOMIC
+    out = []
+    for m in c.row.modes + (AUTO,):
+        used = c.row.auto if m == AUTO else m
+        knobs = c.row.knobs if used == P else (None,)
+        out += [(m, used, k) for k in (knobs if m != AUTO else knobs[-1:])]
+    return out
+
+
+def _assemble(c, mode, knob):
+    c.ctx.set_option(be.OPT_ASSEMBLY, mode)
+    if knob is not None:
+        c.ctx.set_option(be.TUNE_PAIRS, pairs_knob(*knob))
+    c.ctx.assemble_K(be.VEC_DOF)
+
+
+def _elsewhere(c, other, scale):
+    """one assembly in mode `other` at the other displacement of SCALES; vec[DOF] is put back"""
+    c.ctx.upload(be.VEC_DOF, c.us[SCALES[1] if scale == SCALES[0] else SCALES[0]])
+    _assemble(c, other, c.row.knobs[0] if other == P else None)
+    c.ctx.upload(be.VEC_DOF, c.us[scale])
+
+
+def _product(c, ref, Aerr, const, what):
+    """one SpMV with a fixed x against K_ref x: sees what get_K_bsr does not export (padding slots, a block in a wrong lane)"""
+    y, dm = c.lay, c.lay.dm
+    xb = c.x.reshape(-1, dm).astype(LD)[y.bcol]                    # [nnzb, dm]
+    yref, mag, amag = (np.zeros((y.nn, dm), LD) for _ in range(3))
+    np.add.at(yref, y.brow, np.einsum("bij,bj->bi", ref.K, xb))
+    np.add.at(mag, y.brow, np.einsum("bij,bj->bi", np.abs(ref.K), np.abs(xb)))
+    np.add.at(amag, y.brow, np.einsum("bij,bj->bi", Aerr, np.abs(xb)))
+    c.ctx.upload(be.VEC_TMP0, c.x)
+    c.ctx.vector(be.VEC_TMP1).fill(np.nan)
+    c.ctx.spmv(be.VEC_TMP0, be.VEC_TMP1)
+    got = c.ctx.download(be.VEC_TMP1).reshape(-1, dm)
+    assert np.isfinite(got).all(), what
+    bound = 4.0 * EPS * (ps.C_PROD * mag + const * amag)
+    bad = np.abs(got.astype(LD) - yref) > bound
+    assert not bad.any(), (what, "node", int(np.nonzero(bad)[0][0]), got[bad][:2], yref[bad][:2])
+    return float((np.abs(got.astype(LD) - yref)[bound > 0] / bound[bound > 0]).max()) if (bound > 0).any() else 0.0
+
+
+def check_assembly(name, backend):
+    """every mode of the row, both materials, both displacements: assembly_used(), the entry-wise bound, the product, and
+    the second assembly (another mode in between) bit-equal to the first.  -> {constant name: worst ratio to eps A}"""
+    c = case(name, backend)
+    ctx, y, worst = c.ctx, c.lay, {"C_ASM": 0.0, "C_CUBIC": 0.0, "C_DSDX": 0.0, "C_VOL": 0.0, "product": 0.0}
+    try:
+        for mat in ("iso", "general"):
+            ctx.set_material(c.mats[mat])
+            for scale in SCALES:
+                ref = c.ref(mat, scale)
+                ctx.upload(be.VEC_DOF, c.us[scale])
+                for mode, used, knob in _modes(c):
+                    what = (name, NAMES[mode], knob, mat, scale)
+                    if backend == "hip":                          # K holds another state's values, written by another mode: a
+                        other = next(m for m in c.row.modes + (G, S) if m != used)      # store that is left out shows
+                        _elsewhere(c, other, scale)
+                    _assemble(c, mode, knob)
+                    assert ctx.assembly_used() == used, (what, ctx.assembly_used())
+                    K1 = c.K()
+                    cname = "C_CUBIC" if used in (R2, R4) and mat == "iso" else "C_ASM"
+                    const = C_CUBIC if cname == "C_CUBIC" else C_ASM
+                    Aerr = ref.Arow if used in ROWSUM_MODES else ref.A
+                    r, k = ratio(K1, ref.K, Aerr)
+                    worst[cname] = max(worst[cname], r)
+                    assert r <= 4.0 * const, (what, "block (%d, %d) entry %d" % (y.brow[k // y.dm ** 2], y.bcol[k // y.dm ** 2],
+                                                                                k % y.dm ** 2), r, 4.0 * const)
+                    worst["product"] = max(worst["product"], _product(c, ref, Aerr, const, what))
+                    if backend == "hip":
+                        _elsewhere(c, other, scale)
+                        _assemble(c, mode, knob)
+                        K2 = c.K()
+                        if used == A:
+                            assert ratio(K2, ref.K, Aerr)[0] <= 4.0 * const, what
+                        else:
+                            assert np.array_equal(K1, K2), (what, "the second assembly differs in",
+                                                            int((K1 != K2).sum()), "entries")
+                    for cn, got, rf, sc, cc in (("C_DSDX", ctx.gauss_field(be.GP_DSDX).to_numpy(), ref.dsdx, ref.Adsdx, C_DSDX),
+                                                ("C_VOL", ctx.gauss_field(be.GP_VOL).to_numpy(), ref.vol, ref.Avol, C_VOL)):
+                        r, k = ratio(got, rf, sc)
+                        worst[cn] = max(worst[cn], r)
+                        assert r <= 4.0 * cc, (what, cn, "entry", k, r, 4.0 * cc)
+                if backend == "hip":
+                    for mode in c.row.refused:
+                        ctx.set_option(be.OPT_ASSEMBLY, mode)
+                        try:
+                            ctx.assemble_K(be.VEC_DOF)
+                        except be.FemcyError as e:
+                            assert "of LDS per workgroup" in str(e) and NAMES[mode] in str(e), str(e)
+                        else:
+                            raise AssertionError("%s ran on %s" % (NAMES[mode], name))
+                        try:
+                            ctx.assembly_used()
+                        except be.FemcyError as e:                 # a refused assembly has not run
+                            assert "no assembly has run" in str(e), str(e)
+                        else:
+                            raise AssertionError("assembly_used() after a refused %s" % NAMES[mode])
+    finally:
+        ctx.set_option(be.OPT_ASSEMBLY, AUTO)
+        ctx.set_option(be.TUNE_PAIRS, -1)
+        ctx.set_material(c.mats["iso"])
+    print(f"{name} [{backend}]: assembly, worst ratios to eps A {({k: round(v, 3) for k, v in worst.items()})} "
+          f"(allowed {4 * C_ASM:.2f} / {4 * C_CUBIC:.2f} / {4 * C_DSDX:.2f} / {4 * C_VOL:.2f}; product as a share of its bound)")
+    return worst
+
+
+def check_force(name, backend):
+    """k_geom's STRESS instantiation -- F, sigma, dsdx and vol of every element and Gauss point, entry by entry -- and the
+    node sums of k_nodal_force against the long-double node sums, at both displacements: at u = 0 every magnitude sum of
+    the force is 0 and the node sums must be exactly 0, loose rows included.  -> worst ratios"""
+    c = case(name, backend)
+    ctx, worst = c.ctx, {"C_FORCE": 0.0, "C_F": 0.0, "C_SIG": 0.0}
+    ctx.set_material(c.mats["iso"])
+    for scale in SCALES:
+        ref = c.ref("iso", scale)
+        ctx.upload(be.VEC_DOF, c.us[scale])
+        ctx.vector(be.VEC_FORCE).fill(np.nan)
+        ctx.internal_force(be.VEC_DOF, be.VEC_FORCE)
+        f = ctx.download(be.VEC_FORCE).reshape(-1, c.lay.dm)
+        if scale == 0.0:
+            assert not ref.Af.any()
+        r, k = ratio(f, ref.f, ref.Af)
+        worst["C_FORCE"] = max(worst["C_FORCE"], r)
+        assert r <= 4.0 * C_FORCE, (name, scale, "node", k // c.lay.dm, "valence", int(c.lay.cnt[k // c.lay.dm]), r)
+        for cn, which, rf, sc, cc in (("C_F", be.GP_F, ref.F, ref.AF, C_F), ("C_SIG", be.GP_SIGMA, ref.sig, ref.Asig, C_SIG),
+                                      ("C_DSDX", be.GP_DSDX, ref.dsdx, ref.Adsdx, C_DSDX), ("C_VOL", be.GP_VOL, ref.vol, ref.Avol, C_VOL)):
+            r, k = ratio(ctx.gauss_field(which).to_numpy(), rf, sc)
+            if cn in worst:
+                worst[cn] = max(worst[cn], r)
+            per = rf[0].size
+            assert r <= 4.0 * cc, (name, scale, cn, "of the force pass: element", k // per, "entry", k % per, r, 4.0 * cc)
+    print(f"{name} [{backend}]: force pass, worst ratios {({k: round(v, 3) for k, v in worst.items()})} "
+          f"(allowed {4 * C_FORCE:.0f} / {4 * C_F:.2f} / {4 * C_SIG:.2f})")
+    return worst
+
+
+# -------------------------------------------------------------------------------------- the constants, measured
+def measure_constants(row):
+    """the float64 run of reference() against the long-double one on this row\n    -> (C_ASM, C_CUBIC, C_DSDX, C_VOL, C_FORCE, C_F, C_SIG)"""
+    c = Case.__new__(Case)
+    c.row = row
+    c.nodes, c.el, c.ELE = build(row)
+    c.lay = Layout(c.nodes, c.el, row.sigma)
+    c.mats, c.us, c._refs = materials(c.lay.dm), {s: disp(c.nodes, s) for s in SCALES}, {}
+    out = [0.0] * 7
+    for mat in ("iso", "general"):
+        for scale in SCALES:
+            ld, f64 = c.ref(mat, scale), c.ref(mat, scale, np.float64)
+            got = [ratio(f64.K, ld.K, ld.A)[0], 0.0, ratio(f64.dsdx, ld.dsdx, ld.Adsdx)[0], ratio(f64.vol, ld.vol, ld.Avol)[0], 0.0, 0.0, 0.0]
+            if mat == "iso" and c.lay.dm == 3:
+                got[1] = ratio(c.ref(mat, scale, np.float64, True).K, ld.K, ld.A)[0]
+            if mat == "iso":
+                got[4:] = [ratio(f64.f, ld.f, ld.Af)[0], ratio(f64.F, ld.F, ld.AF)[0], ratio(f64.sig, ld.sig, ld.Asig)[0]]
+            out = [max(a, b) for a, b in zip(out, got)]
+    return out
+
+
+def CONSTANTS():
+    return C_ASM, C_CUBIC, C_DSDX, C_VOL, C_FORCE, C_F, C_SIG
+
+
+def check_fit(row):
+    """what the float64 restatement cannot keep with half the margin, no kernel can be held to"""
+    got = measure_constants(row)
+    for g, rec, nm in zip(got, CONSTANTS(), ("C_ASM", "C_CUBIC", "C_DSDX", "C_VOL", "C_FORCE", "C_F", "C_SIG")):
+        assert g <= 2.0 * rec, (row.name, nm, g, rec)
+    return got
