@@ -1,6 +1,9 @@
 """-m gpu: the persistent one-launch PCG (kernels_pcg_persist.hip; vectors and part of the matrix in registers, part in
 LDS, three grid barriers per iteration) against the three-kernel loop and the numpy restatement of the reference
-recurrence (conjugateGradientSolver.py:103-127), on meshes large enough to fill the chip (>= 256 slices of 64 nodes)."""
+recurrence (conjugateGradientSolver.py:103-127), on meshes large enough to fill the chip (>= 256 slices of 64 nodes).
+These tests compare norm-wise and assert speed; the element-wise checks of every launch shape (slices per wave, register
+and LDS rows, prefetch, variants) against a long-double reference are in tests/persist_shapes.py, run by
+tests/test_gpu_persist_shapes.py on meshes of under 45 000 DOF."""
 import numpy as np
 import pytest
 
