@@ -77,6 +77,7 @@ EXPORTS = [
     "femcy_lumped_mass_create", "femcy_lumped_mass_get", "femcy_explicit_create", "femcy_explicit_start",
     "femcy_explicit_advance", "femcy_explicit_kinetic_energy", "femcy_explicit_stable_dt",
     "femcy_explicit_element_bound", "femcy_explicit_auto_begin", "femcy_explicit_auto_advance", "femcy_explicit_auto_state",
+    "femcy_explicit_set_damping",
     "femcy_loadset_create", "femcy_loadset_neumann", "femcy_loadset_neumann_add", "femcy_spmv", "femcy_pcg", "femcy_compute_strain_stress", "femcy_elastic_energy", "femcy_elastic_energy_small", "femcy_extrapolate",
     "femcy_get_K_ell", "femcy_get_K_bsr", "femcy_get_gp_field", "femcy_timing",
     "femcy_timing_reset", "femcy_comm_unique_id", "femcy_comm_local_id", "femcy_comm_init", "femcy_comm_info", "femcy_comm_set_neighbours",
@@ -185,6 +186,7 @@ def _bind(lib, kind):
         "femcy_explicit_element_bound": [p, i32, cint, f64, C.POINTER(f64)],
         "femcy_explicit_auto_begin": [p, i32, cint, f64, f64, f64, i32],
         "femcy_explicit_auto_advance": [p, i32, cint, i32],
+        "femcy_explicit_set_damping": [p, i32, f64, f64, f64, f64],
         "femcy_explicit_auto_state": [p, i32, C.POINTER(f64), C.POINTER(f64), C.POINTER(f64), C.POINTER(C.c_int64)],
         "femcy_loadset_create": [p, i32, i32, i32, p, p, p, p, p, i32, p, p, C.POINTER(i32)],
         "femcy_loadset_neumann": [p, i32, f64, p, cint],
@@ -607,6 +609,11 @@ class Context:
     def explicit_auto_advance(self, ex: int, nsteps: int, rhs_vec: int = VEC_RHS):
         """nsteps steps with the increment re-estimated on the device in each; steps past T are no-ops; only enqueues"""
         self._call("femcy_explicit_auto_advance", int(ex), int(rhs_vec), int(nsteps))
+
+    def explicit_set_damping(self, ex: int, alpha: float = 0.0, b1: float = 0.0, b2: float = 0.0, M_d: float = 0.0):
+        """mass-proportional damping alpha and bulk viscosity (b1, b2, dilatational modulus M_d) of an integrator, from the
+        next stepping call on; all zero restores the undamped launches and bits"""
+        self._call("femcy_explicit_set_damping", int(ex), float(alpha), float(b1), float(b2), float(M_d))
 
     def explicit_auto_state(self, ex: int):
         """-> (t, h_last, h_min, steps_done): the synchronising read-back of the device clock"""

@@ -355,6 +355,17 @@ int check_explicit_rhs(const C* c, const char* entry, int32_t id, int rhs_vec) {
 }
 
 template <class C>
+int check_explicit_set_damping(const C* c, int32_t id, double alpha, double b1, double b2, double M_d) {
+    FEMCY_TRY(check_object(c->explicits, id, "explicit integrator"));
+    auto ok = [](double x) { return std::isfinite(x) && x >= 0.0; };
+    FEMCY_REQUIRE(ok(alpha) && ok(b1) && ok(b2) && ok(M_d),
+                  "femcy_explicit_set_damping: alpha, b1, b2 and M_d must be finite and not negative");
+    FEMCY_REQUIRE(M_d > 0.0 || (b1 == 0.0 && b2 == 0.0),
+                  "femcy_explicit_set_damping: bulk viscosity needs a positive dilatational modulus M_d");
+    return FEMCY_OK;
+}
+
+template <class C>
 int check_explicit_start(const C* c, int32_t id, int rhs_vec, double scale) {
     FEMCY_TRY(check_explicit_rhs(c, "femcy_explicit_start", id, rhs_vec));
     FEMCY_REQUIRE(std::isfinite(scale), "femcy_explicit_start: the load scale is not finite");

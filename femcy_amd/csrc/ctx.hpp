@@ -343,7 +343,7 @@ struct Ctx {
     // An automatic run (femcy_explicit_auto_*) also reads the element shares me [ne][npe] the nodal masses were summed from,
     // and keeps its clock (element_math.hpp: ExplicitClock) and the partial maxima of the bound kernel [ceil(ne / 256)] on
     // the device; both are allocated by the first call that needs them.
-    struct LumpedMass { DevBuf<double> d_m, d_me; };
+    struct LumpedMass { DevBuf<double> d_m, d_me; double rho = 0.0; };
     std::vector<LumpedMass> lumped_masses;
     struct Explicit {
         DevBuf<double> d_minv, d_bpart;
@@ -351,6 +351,9 @@ struct Ctx {
         int32_t lumped = -1;
         bool auto_begun = false;
         double s_C = 0.0;
+        double alpha = 0.0, b1 = 0.0, b2 = 0.0, Md = 0.0;      // femcy_explicit_set_damping; all 0: the undamped launches
+        bool damped() const { return alpha != 0.0 || b1 != 0.0 || b2 != 0.0; }
+        bool bulk() const { return b1 != 0.0 || b2 != 0.0; }
     };
     std::vector<Explicit> explicits;
     int64_t K_serial = -1;            // pattern_serial of the last successful assembly: K holds a matrix when they agree
@@ -443,7 +446,16 @@ void spmv_split(Ctx* c);
 // what the element pass leaves in memory: current-configuration gradients + det J w (always computed), the
 // deformation gradient, the Cauchy stress, the per-element nodal forces
 enum : unsigned { GEOM_DSDX = 1, GEOM_F = 2, GEOM_SIGMA = 4, GEOM_FE = 8 };
-int launch_geom(Ctx* c, const double* d_u, unsigned what);
+// gd (a damped explicit step with bulk viscosity, what includes GEOM_FE): the element pass adds the bulk-viscosity pressure
+// at v_{n+1/2} = v + h/2 a from d_v, d_a (d_a null: the start, v_0 alone), h from the argument or, with d_clk, the device
+// clock's h_next
+struct GeomDamping {
+    const double *d_v, *d_a;
+    const ExplicitClock* d_clk;
+    double h;
+    double alpha, b1, b2, Md, rho0;      // element_math.hpp: ExplicitDamping
+};
+int launch_geom(Ctx* c, const double* d_u, unsigned what, const GeomDamping* gd = nullptr);
 int ensure_gp_stress(Ctx* c);   // F / sigma of the last force evaluation, recomputed on demand (see Ctx::gp_lazy)
 int launch_post(Ctx* c, int large);
 int launch_energy(Ctx* c);
@@ -483,7 +495,7 @@ int launch_lumped_mass(Ctx* c, int32_t nq, const double* d_Nq, const double* d_d
 int launch_explicit_minv(Ctx* c, const double* d_m, double* d_minv);
 int launch_explicit_drift(Ctx* c, const ExplicitClock* d_clk, double h);
 int launch_explicit_node(Ctx* c, const double* d_minv, const double* d_f, const ExplicitClock* d_clk, double scale, double h,
-                         int mode);
+                         int mode, double alpha = 0.0);
 int launch_explicit_energy(Ctx* c, const double* d_m, const double* d_v, double* out);   // 1/2 sum m v^2, fixed order
 // max over the rows i with minv_i != 0 of minv_i sum_j |K_ij| (Gershgorin bound on the spectrum of M_L^-1 K)
 int launch_rowabs_bound(Ctx* c, const double* d_minv, double* out);
@@ -491,7 +503,9 @@ int launch_rowabs_bound(Ctx* c, const double* d_minv, double* out);
 // [explicit_bound_partials(c)], recomputed from the mesh.  _bound_max: their maximum, fetched (synchronises).  _clock: their
 // maximum + one tick of the device clock.  All but _bound_max only enqueue.
 int explicit_bound_partials(const Ctx* c);
-int launch_explicit_bound(Ctx* c, const double* d_u, const double* d_me, double s_C, double* d_part);
+// gd: omega_eff,e^2 with the damping of gd at v_{n+1/2}, formed as the element pass forms it
+int launch_explicit_bound(Ctx* c, const double* d_u, const double* d_me, double s_C, double* d_part,
+                          const GeomDamping* gd = nullptr);
 int launch_explicit_bound_max(Ctx* c, const double* d_part, double* out);
 int launch_explicit_clock(Ctx* c, const double* d_part, ExplicitClock* d_clk);
 // pos_space: x and y are in STORAGE order (entry p * dm + c belongs to the node at storage position p = slice * 64 + lane;

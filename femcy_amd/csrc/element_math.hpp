@@ -817,6 +817,61 @@ FEMCY_HD void explicit_kick(double minv, double s, double f, double fint, double
 }
 FEMCY_HD double explicit_drift(double u, double v, double a, double h, double h2h) { return fma(h2h, a, fma(h, v, u)); }
 
+// Damping (*Bulk Viscosity, *Damping alpha=; femcy_explicit_set_damping).  Both forces are evaluated at u_{n+1} with the
+// LAGGED half-step velocity, the one the drift by h to u_{n+1} used (hh = h / 2):
+//   v_{n+1/2} = fma(h / 2, a_n, v_n)
+//   a_{n+1}   = minv (s f - f_int(u_{n+1}) - f_bv(u_{n+1}, v_{n+1/2})) - alpha v_{n+1/2},   v_{n+1} = v_n + h/2 (a_n + a_{n+1})
+// At the start v_{-1/2} := v_0: the callers pass a = 0 there (vec[ACC] is not read), and fma(hh, 0, v) is v.  A held DOF
+// (minv = 0) takes no damping force either, so that it keeps a = 0.
+FEMCY_HD double explicit_vhalf(double v, double a, double hh) { return fma(hh, a, v); }
+FEMCY_HD void explicit_kick_damped(double minv, double s, double f, double fint, double hh, double alpha, double& v, double& a) {
+    const double vh = explicit_vhalf(v, a, hh);
+    double an = minv * fma(s, f, -fint);
+    if (minv != 0.0) an = fma(-alpha, vh, an);
+    v = fma(hh, a + an, v);
+    a = an;
+}
+
+// Bulk viscosity at one Gauss point of the stiffness rule, on the CURRENT configuration.  With G_a = grad_x N_a (formed from
+// dNg and inv = J_x^-1 as the element pass forms them) and vh the element's rows of v_{n+1/2}:
+//   rate = sum_a vh_a . G_a        (the dm-dimensional divergence; plane stress: in the plane only)
+//   gmax = max_a |G_a|^2,  L = gmax^(-1/2)      (C3D4: the smallest altitude; a bar of length L: L)
+//   rho  = rho0 / |det F|
+//   p    = b1 sqrt(rho M_d) L rate + rho (b2 L)^2 |rate| min(0, rate)
+// p enters the force accumulation as sigma + p I and nothing else: the stored stress never contains it.
+// NPE > 0: the number of nodes at compile time (device); NPE = 0: npe at run time (host).
+struct ExplicitDamping {
+    double alpha, b1, b2, Md, rho0;
+};
+template <int NPE, int DM>
+FEMCY_HD void bulk_rate_point(int npe, const double* __restrict__ dNg, const double (&inv)[DM][DM], const double* vh,
+                              double& rate, double& gmax) {
+    const int n = NPE > 0 ? NPE : npe;
+    rate = 0.0;
+    gmax = 0.0;
+#pragma unroll
+    for (int a = 0; a < n; ++a) {
+        double gg = 0.0;
+#pragma unroll
+        for (int j = 0; j < DM; ++j) {
+            double acc = 0.0;
+#pragma unroll
+            for (int k = 0; k < DM; ++k) acc += dNg[a * DM + k] * inv[k][j];
+            rate = fma(vh[a * DM + j], acc, rate);
+            gg = fma(acc, acc, gg);
+        }
+        gmax = fmax(gmax, gg);
+    }
+}
+FEMCY_HD double bulk_pressure(const ExplicitDamping& d, double rate, double gmax, double detF) {
+    const double L = 1.0 / sqrt(gmax), rho = d.rho0 / fabs(detF), bl = d.b2 * L;
+    return d.b1 * sqrt(rho * d.Md) * L * rate + rho * (bl * bl) * fabs(rate) * fmin(0.0, rate);
+}
+// the quadratic term's share of the critical fraction, L sqrt(rho / M_d) max(0, -rate) (b2^2 is applied by the caller)
+FEMCY_HD double bulk_xi_point(const ExplicitDamping& d, double rate, double gmax, double detF) {
+    return sqrt(d.rho0 / fabs(detF) / d.Md / gmax) * fmax(0.0, -rate);
+}
+
 // The element-by-element estimate of the highest frequency (*Dynamic, explicit, element by element), at the CURRENT
 // configuration x = X + u.  With m_a^e the element's own HRZ share of the lumped mass (lumped_element), v_q = |det J_x| w_q at
 // the stiffness rule's Gauss points, sigma_q = cauchy_large(F_q) and s_C = max eps:C:eps / eps:eps of the small-strain matrix,
@@ -848,12 +903,19 @@ FEMCY_HD void explicit_bound_point(const double* __restrict__ G, double v, const
 
 // the whole element from its coordinates X, displacements U and masses me: gradients, F and sigma as the element pass of the
 // internal force forms them (dN[g][a][:], w[g]: the plug-in's tables at the Gauss points)
-template <int NPE, int DM>
-FEMCY_HD void explicit_bound_element(const double (&X)[NPE][DM], const double (&U)[NPE][DM], int32_t nGP,
-                                     const double* __restrict__ dN, const double* __restrict__ w, int kind,
-                                     const double* __restrict__ C, double p0, double p1, const double (&me)[NPE], double s_C,
-                                     double& g, double& w2) {
+// DAMP (femcy_explicit_set_damping; vh = the element's rows of v_{n+1/2}, d the coefficients): omega_e^2 is replaced by
+//   omega_eff,e^2 = omega_e^2 (sqrt(1 + xi_e^2) + xi_e)^2,
+//   xi_e = alpha / (2 omega_e) + b1 + b2^2 max_q [L_q sqrt(rho_q / M_d) max(0, -rate_q)]
+// the critical fraction of the lagged damping forces in the element's highest mode (bulk_rate_point, bulk_xi_point).  An
+// element with omega_e = 0 and alpha != 0 gives xi_e = inf and omega_eff,e^2 = NaN, which the callers count as an infinite
+// frequency: no increment, the safe side.
+template <int NPE, int DM, bool DAMP>
+FEMCY_HD void explicit_bound_element_impl(const double (&X)[NPE][DM], const double (&U)[NPE][DM], const double* vh,
+                                          const ExplicitDamping* d, int32_t nGP, const double* __restrict__ dN,
+                                          const double* __restrict__ w, int kind, const double* __restrict__ C, double p0,
+                                          double p1, const double (&me)[NPE], double s_C, double& g, double& w2) {
     double rme[NPE];
+    double xq = 0.0;
 #pragma unroll
     for (int a = 0; a < NPE; ++a) rme[a] = 1.0 / me[a];
     g = 0.0;
@@ -876,7 +938,7 @@ FEMCY_HD void explicit_bound_element(const double (&X)[NPE][DM], const double (&
                 F[i][j] = i == j ? 1.0 : 0.0;
             }
         const double det = det_inv<DM>(J, inv);
-        det_inv<DM>(J0, inv0);
+        [[maybe_unused]] const double det0 = det_inv<DM>(J0, inv0);
 #pragma unroll
         for (int a = 0; a < NPE; ++a) {
 #pragma unroll
@@ -898,7 +960,34 @@ FEMCY_HD void explicit_bound_element(const double (&X)[NPE][DM], const double (&
 #pragma unroll
             for (int j = 0; j < DM; ++j) sl[i * DM + j] = sig[i][j];
         explicit_bound_point<NPE, DM>(G, fabs(det) * w[q], sl, rme, s_C, g, w2);
+        if constexpr (DAMP) {
+            if (d->b2 != 0.0) {
+                double rate, gmax;
+                bulk_rate_point<NPE, DM>(NPE, dNg, inv, vh, rate, gmax);
+                xq = fmax(xq, bulk_xi_point(*d, rate, gmax, det / det0));
+            }
+        }
     }
+    if constexpr (DAMP) {
+        const double om = sqrt(w2);
+        const double xi = (d->alpha != 0.0 ? d->alpha / (2.0 * om) : 0.0) + d->b1 + d->b2 * d->b2 * xq;
+        const double k = sqrt(1.0 + xi * xi) + xi;
+        w2 *= k * k;
+    }
+}
+template <int NPE, int DM>
+FEMCY_HD void explicit_bound_element(const double (&X)[NPE][DM], const double (&U)[NPE][DM], int32_t nGP,
+                                     const double* __restrict__ dN, const double* __restrict__ w, int kind,
+                                     const double* __restrict__ C, double p0, double p1, const double (&me)[NPE], double s_C,
+                                     double& g, double& w2) {
+    explicit_bound_element_impl<NPE, DM, false>(X, U, nullptr, nullptr, nGP, dN, w, kind, C, p0, p1, me, s_C, g, w2);
+}
+template <int NPE, int DM>
+FEMCY_HD void explicit_bound_element_damped(const double (&X)[NPE][DM], const double (&U)[NPE][DM], const double (&vh)[NPE][DM],
+                                            const ExplicitDamping& d, int32_t nGP, const double* __restrict__ dN,
+                                            const double* __restrict__ w, int kind, const double* __restrict__ C, double p0,
+                                            double p1, const double (&me)[NPE], double s_C, double& g, double& w2) {
+    explicit_bound_element_impl<NPE, DM, true>(X, U, &vh[0][0], &d, nGP, dN, w, kind, C, p0, p1, me, s_C, g, w2);
 }
 
 // the clock of an automatic run, advanced once per step on whichever backend: t is the time of the state the element pass
@@ -943,19 +1032,20 @@ enum { XN_START = 0, XN_KICK = 1, XN_KICK_DRIFT = 2 };
 struct ExplicitStep {
     double s, hh, h, h2h;
     bool drift;
+    double alpha;   // mass-proportional damping (explicit_kick_damped); 0: the undamped kick, today's arithmetic
 };
 // a fixed increment h: kick and drift by the same h (h > 0 in a step, 0 with XN_START)
-FEMCY_HD ExplicitStep explicit_step_fixed(double s, double h, int mode) {
-    return {s, 0.5 * h, h, 0.5 * h * h, mode == XN_KICK_DRIFT && h != 0.0};
+FEMCY_HD ExplicitStep explicit_step_fixed(double s, double h, int mode, double alpha = 0.0) {
+    return {s, 0.5 * h, h, 0.5 * h * h, mode == XN_KICK_DRIFT && h != 0.0, alpha};
 }
 // from the clock of an automatic run: the kick uses h_prev (the increment that led to the state being kicked), the drift
 // h_next and is skipped when that is 0; the scale is 1 (STEP) or t / T (RAMP) at the time t of the state being kicked.
 // false: h_prev = h_next = 0 in a step, nothing may be written -- the steps of a batch that overshoots T leave u, v, a bit
 // for bit alone.
-FEMCY_HD bool explicit_step_clock(const ExplicitClock& k, int mode, ExplicitStep& st) {
+FEMCY_HD bool explicit_step_clock(const ExplicitClock& k, int mode, ExplicitStep& st, double alpha = 0.0) {
     const double hp = k.h_prev, h = k.h_next;
     if (mode != XN_START && hp == 0.0 && h == 0.0) return false;
-    st = {k.ramp ? k.t / k.T : 1.0, 0.5 * hp, h, 0.5 * h * h, mode == XN_KICK_DRIFT && h != 0.0};
+    st = {k.ramp ? k.t / k.T : 1.0, 0.5 * hp, h, 0.5 * h * h, mode == XN_KICK_DRIFT && h != 0.0, alpha};
     return true;
 }
 

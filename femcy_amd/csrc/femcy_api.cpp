@@ -167,13 +167,13 @@ void timing_collect(Ctx* c) {
 }
 
 // element pass of a force evaluation: gradients + per-element nodal forces; F / sigma stay un-stored (gp_lazy)
-int force_pass(Ctx* c, const double* d_u) {
+int force_pass(Ctx* c, const double* d_u, const GeomDamping* gd = nullptr) {
     c->post_small = false;                           // sigma is about to be the stress of this evaluation (now or lazily)
     if (c->opt_tangent == 1) {                       // the consistent tangent reads F and sigma right away
         c->gp_lazy = false;
-        return launch_geom(c, d_u, GEOM_DSDX | GEOM_F | GEOM_SIGMA | GEOM_FE);
+        return launch_geom(c, d_u, GEOM_DSDX | GEOM_F | GEOM_SIGMA | GEOM_FE, gd);
     }
-    int rc = launch_geom(c, d_u, GEOM_DSDX | GEOM_FE);
+    int rc = launch_geom(c, d_u, GEOM_DSDX | GEOM_FE, gd);
     if (rc) return rc;
     FEMCY_HIP(hipMemcpyAsync(c->d_u_lazy, d_u, sizeof(double) * c->n, hipMemcpyDeviceToDevice, c->stream));
     c->gp_lazy = true;
@@ -1145,6 +1145,7 @@ int femcy_lumped_mass_create(femcy_ctx* ctx, int32_t nq, const double* Nq, const
     if (!rc) rc = to_device(d_wq, wq, sizeof(double) * nq);
     if (!rc && d_me.alloc(sizeof(double) * (size_t)c->ne * c->npe) != hipSuccess) rc = FEMCY_ENOMEM;
     if (!rc && lm.d_m.alloc(sizeof(double) * (size_t)c->nn) != hipSuccess) rc = FEMCY_ENOMEM;
+    lm.rho = rho;                               // rho_0 of the bulk viscosity (femcy_explicit_set_damping)
     if (!rc) rc = launch_lumped_mass(c, nq, d_Nq.get(), d_dNq.get(), d_wq.get(), rho, d_me.get(), lm.d_m.get());
     return finish_create(c, rc, c->lumped_masses, lm, "lumped mass: the kernels failed", "a lumped mass", id_out);
 }
@@ -1182,15 +1183,35 @@ int femcy_explicit_create(femcy_ctx* ctx, int32_t lumped_id, int32_t ndofsets, c
     return FEMCY_OK;
 }
 
+// what the damped kernels of an integrator take: v and a (start: a null, v_{-1/2} := v_0 and vec[ACC] is not read), the
+// increment of the drift that led to the state from h or, in an automatic run, from the clock
+static GeomDamping damping_of(const Ctx* c, const Ctx::Explicit& ex, const ExplicitClock* clk, double h, bool start) {
+    return {c->d_vec[FEMCY_VEC_VEL], start ? nullptr : c->d_vec[FEMCY_VEC_ACC], start ? nullptr : clk, h, ex.alpha, ex.b1, ex.b2,
+            ex.Md, c->lumped_masses[ex.lumped].rho};
+}
+
+int femcy_explicit_set_damping(femcy_ctx* ctx, int32_t id, double alpha, double b1, double b2, double M_d) {
+    CTX_OR_FAIL(ctx);
+    EXPLICIT_SINGLE_RANK_OR_FAIL("femcy_explicit_set_damping");
+    FEMCY_TRY(check_explicit_set_damping(c, id, alpha, b1, b2, M_d));
+    Ctx::Explicit& ex = c->explicits[id];
+    ex.alpha = alpha;
+    ex.b1 = b1;
+    ex.b2 = b2;
+    ex.Md = M_d;
+    return FEMCY_OK;
+}
+
 int femcy_explicit_start(femcy_ctx* ctx, int32_t id, int rhs_vec, double scale) {
     CTX_OR_FAIL(ctx);
     READY_OR_FAIL();
     EXPLICIT_SINGLE_RANK_OR_FAIL("femcy_explicit_start");
     FEMCY_TRY(check_explicit_start(c, id, rhs_vec, scale));
     const Ctx::Explicit& ex = c->explicits[id];
-    int rc = force_pass(c, c->d_vec[FEMCY_VEC_DOF]);
+    const GeomDamping gd = damping_of(c, ex, nullptr, 0.0, true);
+    int rc = force_pass(c, c->d_vec[FEMCY_VEC_DOF], ex.bulk() ? &gd : nullptr);
     if (rc) return rc;
-    return launch_explicit_node(c, ex.d_minv.get(), c->d_vec[rhs_vec], nullptr, scale, 0.0, XN_START);
+    return launch_explicit_node(c, ex.d_minv.get(), c->d_vec[rhs_vec], nullptr, scale, 0.0, XN_START, ex.alpha);
 }
 
 // nsteps steps from a started state: the first drift, then per step the element pass and the node pass (kick, and the drift
@@ -1202,16 +1223,20 @@ static int explicit_steps(Ctx* c, const Ctx::Explicit& ex, ExplicitClock* clk, i
     if (nsteps == 0) return FEMCY_OK;
     double* u = c->d_vec[FEMCY_VEC_DOF];
     const double* me = c->lumped_masses[ex.lumped].d_me.get();
+    // damping (femcy_explicit_set_damping): the damped element pass only with bulk viscosity, the damped bound with any
+    // coefficient; with none of them set these are the launches of an undamped integrator
+    const GeomDamping gd = damping_of(c, ex, clk, dt, false);
+    const GeomDamping *gd_geom = ex.bulk() ? &gd : nullptr, *gd_bound = ex.damped() ? &gd : nullptr;
     int rc = launch_explicit_drift(c, clk, dt);
     for (int32_t k = 1; !rc && k <= nsteps; ++k) {
         // the element pass of force_pass without its per-call copy of u: the lazy state is set once, below
-        if ((rc = launch_geom(c, u, GEOM_DSDX | GEOM_FE))) break;
+        if ((rc = launch_geom(c, u, GEOM_DSDX | GEOM_FE, gd_geom))) break;
         if (clk) {
-            if ((rc = launch_explicit_bound(c, u, me, ex.s_C, ex.d_bpart.get()))) break;
+            if ((rc = launch_explicit_bound(c, u, me, ex.s_C, ex.d_bpart.get(), gd_bound))) break;
             if ((rc = launch_explicit_clock(c, ex.d_bpart.get(), clk))) break;
         }
         rc = launch_explicit_node(c, ex.d_minv.get(), c->d_vec[rhs_vec], clk, scale0 + k * dscale, dt,
-                                  k < nsteps ? XN_KICK_DRIFT : XN_KICK);
+                                  k < nsteps ? XN_KICK_DRIFT : XN_KICK, ex.alpha);
     }
     if (rc) return rc;
     // post-processing reads "the stress of the last force evaluation": that of the last state (the last step did not drift)
@@ -1274,7 +1299,9 @@ int femcy_explicit_element_bound(femcy_ctx* ctx, int32_t id, int u_vec, double s
     Ctx::Explicit& exm = c->explicits[id];
     int rc = explicit_auto_buffers(c, exm);
     if (rc) return rc;
-    rc = launch_explicit_bound(c, c->d_vec[u_vec], c->lumped_masses[exm.lumped].d_me.get(), s_C, exm.d_bpart.get());
+    const GeomDamping gd = damping_of(c, exm, nullptr, 0.0, true);      // v_{1/2} := vec[VEL]
+    rc = launch_explicit_bound(c, c->d_vec[u_vec], c->lumped_masses[exm.lumped].d_me.get(), s_C, exm.d_bpart.get(),
+                               exm.damped() ? &gd : nullptr);
     if (rc) return rc;
     double w2 = 0.0;
     if ((rc = launch_explicit_bound_max(c, exm.d_bpart.get(), &w2))) return rc;
@@ -1299,10 +1326,14 @@ int femcy_explicit_auto_begin(femcy_ctx* ctx, int32_t id, int rhs_vec, double s_
     clk.ramp = ramp ? 1 : 0;
     if ((rc = stage_h2d(c, exm.d_clock.get(), &clk, sizeof(clk)))) return rc;
     const double* u = c->d_vec[FEMCY_VEC_DOF];
-    if ((rc = force_pass(c, u))) return rc;
-    if ((rc = launch_explicit_bound(c, u, c->lumped_masses[exm.lumped].d_me.get(), s_C, exm.d_bpart.get()))) return rc;
+    const GeomDamping gd = damping_of(c, exm, nullptr, 0.0, true);      // v_{-1/2} := v_0, vec[ACC] is not read
+    if ((rc = force_pass(c, u, exm.bulk() ? &gd : nullptr))) return rc;
+    if ((rc = launch_explicit_bound(c, u, c->lumped_masses[exm.lumped].d_me.get(), s_C, exm.d_bpart.get(),
+                                    exm.damped() ? &gd : nullptr)))
+        return rc;
     if ((rc = launch_explicit_clock(c, exm.d_bpart.get(), exm.d_clock.get()))) return rc;   // t = 0, the first h
-    if ((rc = launch_explicit_node(c, exm.d_minv.get(), c->d_vec[rhs_vec], exm.d_clock.get(), 0.0, 0.0, XN_START))) return rc;
+    if ((rc = launch_explicit_node(c, exm.d_minv.get(), c->d_vec[rhs_vec], exm.d_clock.get(), 0.0, 0.0, XN_START, exm.alpha)))
+        return rc;
     exm.auto_begun = true;
     exm.s_C = s_C;
     return FEMCY_OK;

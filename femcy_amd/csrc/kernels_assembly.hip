@@ -79,15 +79,45 @@ __device__ __forceinline__ void block_store_strided(double* __restrict__ dst, co
 }
 
 // ------------------------------------------------------------------------------------ geometry
+// What the element pass of a damped explicit step takes besides k_geom's arguments: v, a (null: the start, v_{-1/2} := v_0,
+// vec[ACC] is not read), the coefficients, and the increment h of the drift that led to u in the node pass's two entry forms
+// -- from the host, or from the device clock, whose h_next is that increment until k_explicit_clock ticks.
+struct GeomDampHost {
+    const double *vel, *accv;
+    ExplicitDamping d;
+    double hh;
+    __device__ double half_increment() const { return hh; }
+};
+struct GeomDampClock {
+    const double *vel, *accv;
+    ExplicitDamping d;
+    const ExplicitClock* clk;
+    __device__ double half_increment() const { return 0.5 * clk->h_next; }
+};
+
+// the element's rows of v_{n+1/2}: registers in a damped pass, nothing otherwise
+template <bool DAMP, int NPE, int DM>
+struct HalfStepRows {
+    double row[NPE][DM];
+};
+template <int NPE, int DM>
+struct HalfStepRows<false, NPE, DM> {};
+
 // one thread per element, Gauss points looped inside (dN[g] is then wave-uniform -> scalar loads)
-template <int NPE, int DM, bool STRESS>
+// DAMPING is empty (every instantiation but the damped explicit step: the kernel then has the arguments and the code it
+// always had) or one of GeomDampHost / GeomDampClock: the element's rows of v and a are gathered beside those of u,
+// v_{n+1/2} = explicit_vhalf(v, a, h / 2) is formed at once, and the bulk-viscosity pressure of element_math.hpp enters the
+// force accumulation as sigma + p I; what is stored as stress does not contain it.
+template <int NPE, int DM, bool STRESS, class... DAMPING>
 __global__ void __launch_bounds__(256) k_geom(int32_t ne, int32_t nGP, const double* __restrict__ nodes,
                                               const double* __restrict__ u, const int32_t* __restrict__ elems,
                                               const double* __restrict__ dN, const double* __restrict__ w,
                                               int mat_kind, const double* __restrict__ C, double p0, double p1,
                                               double* __restrict__ dsdx, double* __restrict__ vol,
                                               double* __restrict__ Fout, double* __restrict__ Sout,
-                                              double* __restrict__ fe) {
+                                              double* __restrict__ fe, DAMPING... damping) {
+    constexpr bool DAMP = sizeof...(DAMPING) == 1;
+    static_assert(sizeof...(DAMPING) <= 1 && (!DAMP || STRESS), "at most one damping argument, on the stress pass");
     // staged stores (block_store) when an element's record is contiguous and small enough for the LDS transpose:
     // one Gauss point (C3D4, CPS3) for dsdx / F / sigma, always for the per-element nodal forces
     constexpr int WG = NPE * DM, WT = DM * DM;
@@ -110,6 +140,7 @@ __global__ void __launch_bounds__(256) k_geom(int32_t ne, int32_t nGP, const dou
     const int32_t e = valid ? e0 + (int32_t)threadIdx.x : ne - 1;      // idle lanes recompute the last element, store nothing
     const bool staged = STAGE && nGP == 1;
     double X[NPE][DM], U[NPE][DM];
+    [[maybe_unused]] HalfStepRows<DAMP, NPE, DM> vh;
     // per-element nodal forces fe[a][:] = sum_g gradN_a . sigma * vol (internal force only): the node gather then
     // reads dm doubles per incident element instead of a gradient row, a stress tensor and a weight
     double facc[STRESS ? NPE : 1][DM];
@@ -128,6 +159,17 @@ __global__ void __launch_bounds__(256) k_geom(int32_t ne, int32_t nGP, const dou
         } else {
 #pragma unroll
             for (int i = 0; i < DM; ++i) U[a][i] = 0.0;
+        }
+        if constexpr (DAMP) {
+            const auto& dp = (damping, ...);
+            load_row<DM>(dp.vel + (int64_t)nd * DM, vh.row[a]);
+            if (dp.accv) {
+                double A[DM];
+                load_row<DM>(dp.accv + (int64_t)nd * DM, A);
+                const double hh = dp.half_increment();
+#pragma unroll
+                for (int i = 0; i < DM; ++i) vh.row[a][i] = explicit_vhalf(vh.row[a][i], A[i], hh);
+            }
         }
     }
     for (int g = 0; g < nGP; ++g) {
@@ -180,7 +222,11 @@ __global__ void __launch_bounds__(256) k_geom(int32_t ne, int32_t nGP, const dou
                     for (int a = 0; a < NPE; ++a) acc += X[a][i] * dNg[a * DM + j];
                     J0[i][j] = acc;
                 }
-            det_inv<DM>(J0, inv0);
+            [[maybe_unused]] double det0 = 0.0;          // det J_X: det F = det J_x / det J_X, read by the damped pass alone
+            if constexpr (DAMP)
+                det0 = det_inv<DM>(J0, inv0);
+            else
+                det_inv<DM>(J0, inv0);
 #pragma unroll
             for (int i = 0; i < DM; ++i)
 #pragma unroll
@@ -238,6 +284,13 @@ __global__ void __launch_bounds__(256) k_geom(int32_t ne, int32_t nGP, const dou
                 }
                 if (fe) {
                     const double vg = det * w[g];
+                    if constexpr (DAMP) {
+                        double rate, gmax;
+                        bulk_rate_point<NPE, DM>(NPE, dNg, inv, &vh.row[0][0], rate, gmax);
+                        const double p = bulk_pressure((damping, ...).d, rate, gmax, det / det0);
+#pragma unroll
+                        for (int i = 0; i < DM; ++i) sig[i][i] += p;
+                    }
 #pragma unroll
                     for (int a = 0; a < NPE; ++a) {
                         double ga[DM];
@@ -1718,16 +1771,32 @@ void launch_node_sum(Ctx* c, const double* d_src, double* d_m) {
                        c->d_ne_idx, d_src, d_m);
 }
 
-int launch_geom(Ctx* c, const double* d_u, unsigned what) {
+int launch_geom(Ctx* c, const double* d_u, unsigned what, const GeomDamping* gd) {
     const int bs = 256, grid = (c->ne + bs - 1) / bs;
     const bool with_stress = (what & (GEOM_F | GEOM_SIGMA | GEOM_FE)) != 0;
+    if (gd && !(what & GEOM_FE)) {      // the damped pass exists for the force accumulation alone
+        set_error("launch_geom: a damped element pass without GEOM_FE");
+        return FEMCY_EINVAL;
+    }
+    double* dsdx = (what & GEOM_DSDX) ? c->d_dsdx : nullptr;
+    double *Fo = (what & GEOM_F) ? c->d_F : nullptr, *So = (what & GEOM_SIGMA) ? c->d_sigma : nullptr;
     size_t th = timing_begin(c, T_GEOM);
     const bool launched = dispatch_element(c->npe, c->dm, [&](auto npe, auto dm) {
-        if (with_stress)
+        const ExplicitDamping dmp = gd ? ExplicitDamping{gd->alpha, gd->b1, gd->b2, gd->Md, gd->rho0} : ExplicitDamping{};
+        if (gd && gd->d_clk)
+            hipLaunchKernelGGL((k_geom<npe(), dm(), true, GeomDampClock>), dim3(grid), dim3(bs), 0, c->stream, c->ne, c->nGP,
+                               c->d_nodes, d_u, c->d_elems, c->d_dN, c->d_w, c->mat_kind, c->d_C, c->mat_params[0],
+                               c->mat_params[1], dsdx, c->d_vol, Fo, So, c->d_fe,
+                               GeomDampClock{gd->d_v, gd->d_a, dmp, gd->d_clk});
+        else if (gd)
+            hipLaunchKernelGGL((k_geom<npe(), dm(), true, GeomDampHost>), dim3(grid), dim3(bs), 0, c->stream, c->ne, c->nGP,
+                               c->d_nodes, d_u, c->d_elems, c->d_dN, c->d_w, c->mat_kind, c->d_C, c->mat_params[0],
+                               c->mat_params[1], dsdx, c->d_vol, Fo, So, c->d_fe,
+                               GeomDampHost{gd->d_v, gd->d_a, dmp, 0.5 * gd->h});
+        else if (with_stress)
             hipLaunchKernelGGL((k_geom<npe(), dm(), true>), dim3(grid), dim3(bs), 0, c->stream, c->ne, c->nGP, c->d_nodes,
                                d_u, c->d_elems, c->d_dN, c->d_w, c->mat_kind, c->d_C, c->mat_params[0], c->mat_params[1],
-                               (what & GEOM_DSDX) ? c->d_dsdx : nullptr, c->d_vol, (what & GEOM_F) ? c->d_F : nullptr,
-                               (what & GEOM_SIGMA) ? c->d_sigma : nullptr, (what & GEOM_FE) ? c->d_fe : nullptr);
+                               dsdx, c->d_vol, Fo, So, (what & GEOM_FE) ? c->d_fe : nullptr);
         else
             hipLaunchKernelGGL((k_geom<npe(), dm(), false>), dim3(grid), dim3(bs), 0, c->stream, c->ne, c->nGP, c->d_nodes,
                                d_u, c->d_elems, c->d_dN, c->d_w, c->mat_kind, c->d_C, c->mat_params[0], c->mat_params[1],

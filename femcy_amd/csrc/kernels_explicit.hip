@@ -7,7 +7,9 @@
 // are read and a, v, u written once per step, dm contiguous doubles per node each.  The node pass has two entry points that
 // differ only in where the step's numbers (ExplicitStep, element_math.hpp) come from: k_explicit_node takes them from the
 // host, k_explicit_node_auto from the device clock of an element-by-element run; k_explicit_drift / _auto likewise.  The
-// node sums of the lumped mass are k_node_sum of kernels_assembly.hip (launch_node_sum).
+// node sums of the lumped mass are k_node_sum of kernels_assembly.hip (launch_node_sum).  With damping set
+// (femcy_explicit_set_damping) the element pass is k_geom<..., true, GeomDampHost / GeomDampClock>, which adds the bulk
+// viscosity, the node pass subtracts alpha v_{n+1/2} (explicit_kick_damped) and the bound kernel returns omega_eff.
 #include <algorithm>
 #include <cmath>
 #include "ctx.hpp"
@@ -70,6 +72,8 @@ __device__ __forceinline__ void explicit_node_pass(int32_t nn, const int32_t* __
         if (mode != XN_START) {
             ai = acc_vec[i];
             vi = v[i];
+        } else if (st.alpha != 0.0) {
+            vi = v[i];                                  // v_{-1/2} := v_0; vec[ACC] is not read at the start
         }
         if (st.drift) ui = u[i];
     }
@@ -77,7 +81,10 @@ __device__ __forceinline__ void explicit_node_pass(int32_t nn, const int32_t* __
     node_gather<DM>(a, sub, nn, ne_ptr, ne_idx, fe, acc);
     if (!mine) return;
     const double fint = sub == 0 ? acc[0] : (sub == 1 ? acc[1] : acc[DM - 1]);
-    explicit_kick(mi, st.s, fi, fint, st.hh, vi, ai);
+    if (st.alpha != 0.0)
+        explicit_kick_damped(mi, st.s, fi, fint, st.hh, st.alpha, vi, ai);
+    else
+        explicit_kick(mi, st.s, fi, fint, st.hh, vi, ai);
     acc_vec[i] = ai;
     if (mode == XN_START) return;
     v[i] = vi;
@@ -102,10 +109,10 @@ __global__ void __launch_bounds__(XBS) k_explicit_node_auto(int32_t nn, const in
                                                             const double* __restrict__ fe, const double* __restrict__ f,
                                                             const double* __restrict__ minv,
                                                             const ExplicitClock* __restrict__ clk, int mode,
-                                                            double* __restrict__ u, double* __restrict__ v,
-                                                            double* __restrict__ acc_vec) {
+                                                            double alpha, double* __restrict__ u,
+                                                            double* __restrict__ v, double* __restrict__ acc_vec) {
     ExplicitStep st;
-    if (!explicit_step_clock(*clk, mode, st)) return;
+    if (!explicit_step_clock(*clk, mode, st, alpha)) return;
     explicit_node_pass<DM>(nn, ne_ptr, ne_idx, fe, f, minv, st, mode, u, v, acc_vec);
 }
 
@@ -220,26 +227,52 @@ __global__ void __launch_bounds__(XBS) k_rowabs_bound(int64_t npos, const int32_
 // profiles/explicit_auto.json.)  The workgroup's maximum goes to
 // part[blockIdx.x] (ceil(ne / 256) partials, no grid-stride loop: k_explicit_clock loops over any number of them).  A NaN
 // counts as infinity, as in k_rowabs_bound, so that a broken element gives no increment.
-template <int NPE, int DM>
+// DAMPING (empty, or one BoundDamping: an integrator with damping set): omega_eff,e^2 of explicit_bound_element_damped, with
+// v_{n+1/2} gathered and formed as the damped element pass does it -- hh from the host or, with clk, half of the clock's
+// h_next, read before k_explicit_clock ticks.  Without it the kernel has the arguments and the code it always had.
+struct BoundDamping {
+    const double *vel, *accv;
+    ExplicitDamping d;
+    double hh;
+    const ExplicitClock* clk;
+};
+template <int NPE, int DM, class... DAMPING>
 __global__ void __launch_bounds__(XBS) k_explicit_bound(int32_t ne, int32_t nGP, const double* __restrict__ nodes,
                                                         const double* __restrict__ u, const int32_t* __restrict__ elems,
                                                         const double* __restrict__ dN, const double* __restrict__ w,
                                                         int mat_kind, const double* __restrict__ C, double p0, double p1,
                                                         const double* __restrict__ me_in, double s_C,
-                                                        double* __restrict__ part) {
+                                                        double* __restrict__ part, DAMPING... damping) {
+    constexpr bool DAMP = sizeof...(DAMPING) == 1;
+    static_assert(sizeof...(DAMPING) <= 1, "at most one damping argument");
     __shared__ double sm[XBS / 64];
     const int32_t e = blockIdx.x * blockDim.x + threadIdx.x;
     double best = 0.0;
     if (e < ne) {
         double X[NPE][DM], U[NPE][DM], me[NPE], g, w2;
+        [[maybe_unused]] double Vh[DAMP ? NPE : 1][DM];
 #pragma unroll
         for (int a = 0; a < NPE; ++a) {
             const int32_t nd = elems[(int64_t)e * NPE + a];
             load_row<DM>(nodes + (int64_t)nd * DM, X[a]);
             load_row<DM>(u + (int64_t)nd * DM, U[a]);
             me[a] = me_in[(int64_t)e * NPE + a];
+            if constexpr (DAMP) {
+                const BoundDamping& dp = (damping, ...);
+                load_row<DM>(dp.vel + (int64_t)nd * DM, Vh[a]);
+                if (dp.accv) {
+                    double A[DM];
+                    load_row<DM>(dp.accv + (int64_t)nd * DM, A);
+                    const double hh = dp.clk ? 0.5 * dp.clk->h_next : dp.hh;
+#pragma unroll
+                    for (int i = 0; i < DM; ++i) Vh[a][i] = explicit_vhalf(Vh[a][i], A[i], hh);
+                }
+            }
         }
-        explicit_bound_element<NPE, DM>(X, U, nGP, dN, w, mat_kind, C, p0, p1, me, s_C, g, w2);
+        if constexpr (DAMP)
+            explicit_bound_element_damped<NPE, DM>(X, U, Vh, (damping, ...).d, nGP, dN, w, mat_kind, C, p0, p1, me, s_C, g, w2);
+        else
+            explicit_bound_element<NPE, DM>(X, U, nGP, dN, w, mat_kind, C, p0, p1, me, s_C, g, w2);
         best = w2 != w2 ? INFINITY : w2;
     }
     const double r = block_reduce<true>(best, sm);
@@ -291,17 +324,17 @@ int launch_explicit_minv(Ctx* c, const double* d_m, double* d_minv) {
 }
 
 int launch_explicit_node(Ctx* c, const double* d_minv, const double* d_f, const ExplicitClock* d_clk, double scale, double h,
-                         int mode) {
+                         int mode, double alpha) {
     const unsigned grid = node_gather_grid(c->nn, XBS);
     double *u = c->d_vec[FEMCY_VEC_DOF], *v = c->d_vec[FEMCY_VEC_VEL], *a = c->d_vec[FEMCY_VEC_ACC];
     size_t tm = timing_begin(c, T_FORCE);
     dispatch_dm(c->dm, [&](auto dm) {
         if (d_clk)
             hipLaunchKernelGGL((k_explicit_node_auto<dm()>), dim3(grid), dim3(XBS), 0, c->stream, c->nn, c->d_ne_ptr,
-                               c->d_ne_idx, c->d_fe, d_f, d_minv, d_clk, mode, u, v, a);
+                               c->d_ne_idx, c->d_fe, d_f, d_minv, d_clk, mode, alpha, u, v, a);
         else
             hipLaunchKernelGGL((k_explicit_node<dm()>), dim3(grid), dim3(XBS), 0, c->stream, c->nn, c->d_ne_ptr, c->d_ne_idx,
-                               c->d_fe, d_f, d_minv, explicit_step_fixed(scale, h, mode), mode, u, v, a);
+                               c->d_fe, d_f, d_minv, explicit_step_fixed(scale, h, mode, alpha), mode, u, v, a);
     });
     timing_end(c, tm);
     FEMCY_HIP(hipGetLastError());
@@ -355,11 +388,18 @@ int launch_rowabs_bound(Ctx* c, const double* d_minv, double* out) {
 
 int explicit_bound_partials(const Ctx* c) { return (c->ne + XBS - 1) / XBS; }
 
-int launch_explicit_bound(Ctx* c, const double* d_u, const double* d_me, double s_C, double* d_part) {
+int launch_explicit_bound(Ctx* c, const double* d_u, const double* d_me, double s_C, double* d_part, const GeomDamping* gd) {
     const int grid = explicit_bound_partials(c);
     size_t tm = timing_begin(c, T_GEOM);
     const bool launched = dispatch_element(c->npe, c->dm, [&](auto npe, auto dm) {
-        hipLaunchKernelGGL((k_explicit_bound<npe(), dm()>), dim3(grid), dim3(XBS), 0, c->stream, c->ne, c->nGP, c->d_nodes, d_u,
+        if (gd)
+            hipLaunchKernelGGL((k_explicit_bound<npe(), dm(), BoundDamping>), dim3(grid), dim3(XBS), 0, c->stream, c->ne,
+                               c->nGP, c->d_nodes, d_u, c->d_elems, c->d_dN, c->d_w, c->mat_kind, c->d_C, c->mat_params[0],
+                               c->mat_params[1], d_me, s_C, d_part,
+                               BoundDamping{gd->d_v, gd->d_a, {gd->alpha, gd->b1, gd->b2, gd->Md, gd->rho0}, 0.5 * gd->h,
+                                            gd->d_clk});
+        else
+            hipLaunchKernelGGL((k_explicit_bound<npe(), dm()>), dim3(grid), dim3(XBS), 0, c->stream, c->ne, c->nGP, c->d_nodes, d_u,
                            c->d_elems, c->d_dN, c->d_w, c->mat_kind, c->d_C, c->mat_params[0], c->mat_params[1], d_me, s_C,
                            d_part);
     });

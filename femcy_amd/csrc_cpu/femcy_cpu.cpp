@@ -64,6 +64,7 @@ struct Mass {
     std::vector<double> m;   // [blocks of the block-CSR matrix] one scalar per block, K's block order
 };
 struct LumpedMass {
+    double rho = 0.0;        // the density it was created with: rho_0 of the bulk viscosity
     std::vector<double> m;   // [nn] HRZ-lumped nodal masses
     std::vector<double> me;  // [ne][npe] the element shares they were summed from (the element-by-element increment)
 };
@@ -72,6 +73,16 @@ struct Explicit {
     int32_t lumped;
     femcy::ExplicitClock clock{};   // femcy_explicit_auto_*
     bool auto_begun = false;
+    double alpha = 0.0, b1 = 0.0, b2 = 0.0, Md = 0.0;      // femcy_explicit_set_damping; all 0: undamped
+    bool damped() const { return alpha != 0.0 || b1 != 0.0 || b2 != 0.0; }
+    bool bulk() const { return b1 != 0.0 || b2 != 0.0; }
+};
+// a damped element pass or bound (the device's GeomDamping): v, a (null: the start, v_{-1/2} := v_0) and hh = h / 2 of the
+// drift that led to the state
+struct HostDamping {
+    const double *v, *a;
+    double hh;
+    femcy::ExplicitDamping d;
 };
 struct Thermal {
     std::vector<double> f, dT, N;  // [n] load at scale 1, [nn] temperature changes, [nGP][npe] shape functions
@@ -127,18 +138,24 @@ enum : unsigned { GEOM_DSDX = 1, GEOM_F = 2, GEOM_SIGMA = 4, GEOM_FE = 8 };
 
 // get_dsdx_and_vol (stiffnessMtrx.py:132-150), get_deformation_gradient (:532-556), constitutiveOfLargeDeform and the
 // per-element nodal forces of assemble_nodal_force_GN (:620-644): the element pass of the device's k_geom
-template <int DM>
-void geom_pass(femcy_ctx* c, const double* u, unsigned what) {
+// DAMPED: hd is set (a damped explicit step); the undamped pass carries nothing of it
+template <int DM, bool DAMPED>
+void geom_pass(femcy_ctx* c, const double* u, unsigned what, [[maybe_unused]] const HostDamping* hd) {
     const int npe = c->npe, nGP = c->nGP;
 #pragma omp parallel for schedule(static)
     for (int32_t e = 0; e < c->ne; ++e) {
         double X[27][DM], U[27][DM], facc[27][DM];
+        [[maybe_unused]] double Vh[DAMPED ? 27 : 1][DM];
         for (int a = 0; a < npe; ++a) {
             const int32_t nd = c->elems[(int64_t)e * npe + a];
             for (int i = 0; i < DM; ++i) {
                 X[a][i] = c->nodes[(int64_t)nd * DM + i];
                 U[a][i] = u ? u[(int64_t)nd * DM + i] : 0.0;
                 facc[a][i] = 0.0;
+                if constexpr (DAMPED) {
+                    const double vi = hd->v[(int64_t)nd * DM + i];
+                    Vh[a][i] = hd->a ? explicit_vhalf(vi, hd->a[(int64_t)nd * DM + i], hd->hh) : vi;
+                }
             }
         }
         for (int g = 0; g < nGP; ++g) {
@@ -171,7 +188,7 @@ void geom_pass(femcy_ctx* c, const double* u, unsigned what) {
                         J0[i][j] = acc;
                         F[i][j] = 0.0;
                     }
-                det_inv<DM>(J0, inv0);
+                [[maybe_unused]] const double det0 = det_inv<DM>(J0, inv0);
                 for (int a = 0; a < npe; ++a) {
                     double dsdX[DM];
                     for (int j = 0; j < DM; ++j) {
@@ -193,6 +210,12 @@ void geom_pass(femcy_ctx* c, const double* u, unsigned what) {
                             for (int j = 0; j < DM; ++j) c->sigma[gp * DM * DM + i * DM + j] = sig[i][j];
                     if (what & GEOM_FE) {
                         const double vg = det * c->w[g];
+                        if constexpr (DAMPED) {      // bulk viscosity: sigma + p I in the force accumulation only
+                            double rate, gmax;
+                            bulk_rate_point<0, DM>(npe, dNg, inv, &Vh[0][0], rate, gmax);
+                            const double p = bulk_pressure(hd->d, rate, gmax, det / det0);
+                            for (int i = 0; i < DM; ++i) sig[i][i] += p;
+                        }
                         for (int a = 0; a < npe; ++a) {
                             double ga[DM];
                             for (int j = 0; j < DM; ++j) {
@@ -215,10 +238,14 @@ void geom_pass(femcy_ctx* c, const double* u, unsigned what) {
                 for (int i = 0; i < DM; ++i) c->fe[((int64_t)e * npe + a) * DM + i] = facc[a][i];
     }
 }
-void geom(femcy_ctx* c, const double* u, unsigned what) {
+void geom(femcy_ctx* c, const double* u, unsigned what, const HostDamping* hd = nullptr) {
     if (what & GEOM_SIGMA) c->post_small = false;
     const double t = c->opt_timing ? now_ms() : 0.0;
-    if (c->dm == 3) geom_pass<3>(c, u, what); else geom_pass<2>(c, u, what);
+    if (hd) {
+        if (c->dm == 3) geom_pass<3, true>(c, u, what, hd); else geom_pass<2, true>(c, u, what, hd);
+    } else {
+        if (c->dm == 3) geom_pass<3, false>(c, u, what, nullptr); else geom_pass<2, false>(c, u, what, nullptr);
+    }
     if (c->opt_timing) {
         c->timing.geom_ms += now_ms() - t;
         c->timing.geom_launches++;
@@ -1231,8 +1258,12 @@ void explicit_node(femcy_ctx* c, const Explicit& ex, const double* f, const Expl
         node_sum(c, a, c->fe.data(), dm, fint);
         for (int i = 0; i < dm; ++i) {
             const int64_t q = (int64_t)a * dm + i;
-            double vi = mode != XN_START ? v[q] : 0.0, ai = mode != XN_START ? acc[q] : 0.0;
-            explicit_kick(ex.minv[q], st.s, f[q], fint[i], st.hh, vi, ai);
+            // at the start vec[ACC] is not read; vec[VEL] only by the damped kick (v_{-1/2} := v_0)
+            double vi = mode != XN_START || st.alpha != 0.0 ? v[q] : 0.0, ai = mode != XN_START ? acc[q] : 0.0;
+            if (st.alpha != 0.0)
+                explicit_kick_damped(ex.minv[q], st.s, f[q], fint[i], st.hh, st.alpha, vi, ai);
+            else
+                explicit_kick(ex.minv[q], st.s, f[q], fint[i], st.hh, vi, ai);
             acc[q] = ai;
             if (mode == XN_START) continue;
             v[q] = vi;
@@ -1243,29 +1274,42 @@ void explicit_node(femcy_ctx* c, const Explicit& ex, const double* f, const Expl
 
 // max_e omega_e^2 at u (csrc/element_math.hpp: explicit_bound_element); a NaN counts as infinity
 template <int NPE, int DM>
-void element_bound(femcy_ctx* c, const double* u, const double* me_all, double s_C, double& out) {
+void element_bound(femcy_ctx* c, const double* u, const double* me_all, double s_C, const HostDamping* hd, double& out) {
     double best = 0.0;
 #pragma omp parallel for schedule(static) reduction(max : best)
     for (int32_t e = 0; e < c->ne; ++e) {
-        double X[NPE][DM], U[NPE][DM], me[NPE], g, w2;
+        double X[NPE][DM], U[NPE][DM], Vh[NPE][DM], me[NPE], g, w2;
         for (int a = 0; a < NPE; ++a) {
             const int32_t nd = c->elems[(int64_t)e * NPE + a];
             for (int i = 0; i < DM; ++i) {
                 X[a][i] = c->nodes[(int64_t)nd * DM + i];
                 U[a][i] = u[(int64_t)nd * DM + i];
+                if (hd) {
+                    const double vi = hd->v[(int64_t)nd * DM + i];
+                    Vh[a][i] = hd->a ? explicit_vhalf(vi, hd->a[(int64_t)nd * DM + i], hd->hh) : vi;
+                }
             }
             me[a] = me_all[(int64_t)e * NPE + a];
         }
-        explicit_bound_element<NPE, DM>(X, U, c->nGP, c->dN.data(), c->w.data(), c->mat_kind, c->h_C, c->mat_params[0],
-                                        c->mat_params[1], me, s_C, g, w2);
+        if (hd)
+            explicit_bound_element_damped<NPE, DM>(X, U, Vh, hd->d, c->nGP, c->dN.data(), c->w.data(), c->mat_kind, c->h_C,
+                                                   c->mat_params[0], c->mat_params[1], me, s_C, g, w2);
+        else
+            explicit_bound_element<NPE, DM>(X, U, c->nGP, c->dN.data(), c->w.data(), c->mat_kind, c->h_C, c->mat_params[0],
+                                            c->mat_params[1], me, s_C, g, w2);
         if (w2 != w2) w2 = INFINITY;
         best = std::fmax(best, w2);
     }
     out = best;
 }
-int element_bound_any(femcy_ctx* c, const Explicit& ex, const double* u, double s_C, double* w2) {
+// what the damped passes of an integrator take (the device's damping_of): start: v_{-1/2} := v_0, vec[ACC] is not read
+HostDamping damping_of(const femcy_ctx* c, const Explicit& ex, double h, bool start) {
+    return {c->vec[FEMCY_VEC_VEL].data(), start ? nullptr : c->vec[FEMCY_VEC_ACC].data(), 0.5 * h,
+            {ex.alpha, ex.b1, ex.b2, ex.Md, c->lumped_masses[ex.lumped].rho}};
+}
+int element_bound_any(femcy_ctx* c, const Explicit& ex, const double* u, double s_C, double* w2, const HostDamping* hd = nullptr) {
     const double* me = c->lumped_masses[ex.lumped].me.data();
-    if (!dispatch_element(c->npe, c->dm, [&](auto npe, auto dm) { element_bound<npe(), dm()>(c, u, me, s_C, *w2); }))
+    if (!dispatch_element(c->npe, c->dm, [&](auto npe, auto dm) { element_bound<npe(), dm()>(c, u, me, s_C, hd, *w2); }))
         return no_kernel(c, "element-bound");
     return FEMCY_OK;
 }
@@ -1299,16 +1343,18 @@ int explicit_steps(femcy_ctx* c, const Explicit& ex, ExplicitClock* clock, int r
     for (int32_t k = 1; k <= nsteps; ++k) {
         const bool last = k == nsteps;      // F and sigma of the last state stay behind for post-processing
         const int mode = last ? XN_KICK : XN_KICK_DRIFT;
-        geom(c, u, last ? (GEOM_DSDX | GEOM_F | GEOM_SIGMA | GEOM_FE) : (GEOM_DSDX | GEOM_FE));
+        // the increment of the drift that led to u: the clock's h_next until it ticks
+        const HostDamping hd = damping_of(c, ex, clock ? clock->h_next : dt, false);
+        geom(c, u, last ? (GEOM_DSDX | GEOM_F | GEOM_SIGMA | GEOM_FE) : (GEOM_DSDX | GEOM_FE), ex.bulk() ? &hd : nullptr);
         ExplicitStep st;
         if (clock) {
             double w2 = 0.0;
-            int rc = element_bound_any(c, ex, u, clock->s_C, &w2);
+            int rc = element_bound_any(c, ex, u, clock->s_C, &w2, ex.damped() ? &hd : nullptr);
             if (rc) return rc;
             explicit_clock_tick(*clock, w2);
-            if (!explicit_step_clock(*clock, mode, st)) continue;
+            if (!explicit_step_clock(*clock, mode, st, ex.alpha)) continue;
         } else {
-            st = explicit_step_fixed(scale0 + k * dscale, dt, mode);
+            st = explicit_step_fixed(scale0 + k * dscale, dt, mode, ex.alpha);
         }
         explicit_node(c, ex, c->vec[rhs_vec].data(), st, mode);
     }
@@ -1322,6 +1368,7 @@ int femcy_lumped_mass_create(femcy_ctx* ctx, int32_t nq, const double* Nq, const
     CTX_OR_FAIL(ctx);
     FEMCY_TRY(check_mass_rule(c, "femcy_lumped_mass_create", nq, Nq, dNq, wq, rho, id_out));
     LumpedMass lm;
+    lm.rho = rho;
     if (!dispatch_element(c->npe, c->dm,
                           [&](auto npe, auto dm) { lumped_mass<npe(), dm()>(c, nq, Nq, dNq, wq, rho, lm.m, lm.me); }))
         return no_kernel(c, "lumped-mass");
@@ -1357,8 +1404,20 @@ int femcy_explicit_start(femcy_ctx* ctx, int32_t id, int rhs_vec, double scale) 
     READY_OR_FAIL();
     FEMCY_TRY(check_explicit_start(c, id, rhs_vec, scale));
     const Explicit& ex = c->explicits[id];
-    geom(c, c->vec[FEMCY_VEC_DOF].data(), GEOM_DSDX | GEOM_F | GEOM_SIGMA | GEOM_FE);
-    explicit_node(c, ex, c->vec[rhs_vec].data(), explicit_step_fixed(scale, 0.0, XN_START), XN_START);
+    const HostDamping hd = damping_of(c, ex, 0.0, true);
+    geom(c, c->vec[FEMCY_VEC_DOF].data(), GEOM_DSDX | GEOM_F | GEOM_SIGMA | GEOM_FE, ex.bulk() ? &hd : nullptr);
+    explicit_node(c, ex, c->vec[rhs_vec].data(), explicit_step_fixed(scale, 0.0, XN_START, ex.alpha), XN_START);
+    return FEMCY_OK;
+}
+
+int femcy_explicit_set_damping(femcy_ctx* ctx, int32_t id, double alpha, double b1, double b2, double M_d) {
+    CTX_OR_FAIL(ctx);
+    FEMCY_TRY(check_explicit_set_damping(c, id, alpha, b1, b2, M_d));
+    Explicit& ex = c->explicits[id];
+    ex.alpha = alpha;
+    ex.b1 = b1;
+    ex.b2 = b2;
+    ex.Md = M_d;
     return FEMCY_OK;
 }
 
@@ -1430,7 +1489,9 @@ int femcy_explicit_element_bound(femcy_ctx* ctx, int32_t id, int u_vec, double s
     READY_OR_FAIL();
     FEMCY_TRY(check_explicit_element_bound(c, id, u_vec, s_C, omega));
     double w2 = 0.0;
-    int rc = element_bound_any(c, c->explicits[id], c->vec[u_vec].data(), s_C, &w2);
+    const Explicit& ex = c->explicits[id];
+    const HostDamping hd = damping_of(c, ex, 0.0, true);      // v_{1/2} := vec[VEL]
+    int rc = element_bound_any(c, ex, c->vec[u_vec].data(), s_C, &w2, ex.damped() ? &hd : nullptr);
     if (rc) return rc;
     *omega = std::sqrt(w2);
     return FEMCY_OK;
@@ -1444,7 +1505,8 @@ int femcy_explicit_auto_begin(femcy_ctx* ctx, int32_t id, int rhs_vec, double s_
     Explicit& exm = c->explicits[id];
     const double* u = c->vec[FEMCY_VEC_DOF].data();
     double w2 = 0.0;
-    int rc = element_bound_any(c, exm, u, s_C, &w2);
+    const HostDamping hd = damping_of(c, exm, 0.0, true);      // v_{-1/2} := v_0, vec[ACC] is not read
+    int rc = element_bound_any(c, exm, u, s_C, &w2, exm.damped() ? &hd : nullptr);
     if (rc) return rc;
     exm.clock = ExplicitClock{};
     exm.clock.T = T;
@@ -1452,10 +1514,10 @@ int femcy_explicit_auto_begin(femcy_ctx* ctx, int32_t id, int rhs_vec, double s_
     exm.clock.s_C = s_C;
     exm.clock.h_min = INFINITY;
     exm.clock.ramp = ramp ? 1 : 0;
-    geom(c, u, GEOM_DSDX | GEOM_F | GEOM_SIGMA | GEOM_FE);
+    geom(c, u, GEOM_DSDX | GEOM_F | GEOM_SIGMA | GEOM_FE, exm.bulk() ? &hd : nullptr);
     explicit_clock_tick(exm.clock, w2);                        // t = 0, the first h
     ExplicitStep st;
-    explicit_step_clock(exm.clock, XN_START, st);              // always something to do at the start
+    explicit_step_clock(exm.clock, XN_START, st, exm.alpha);   // always something to do at the start
     explicit_node(c, exm, c->vec[rhs_vec].data(), st, XN_START);
     exm.auto_begun = true;
     return FEMCY_OK;

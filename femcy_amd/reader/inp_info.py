@@ -31,8 +31,9 @@ with fixed increments (read_procedure); `*Step, amplitude=RAMP|STEP` -> amplitud
 initial_velocity_info.  `*Dynamic, explicit[, direct user control][, scale factor=][, output_every=]` with data `, T` (`dt, T`
 under direct user control) -> procedure = "explicit", dynamic = {"direct_user_control", "scale_factor", "output_every"} and
 time_incs whose increments are None until the driver has estimated one; `element by element` in place of `direct user
-control` -> dynamic_auto = True: the driver re-estimates the increment in every step.  A deck with `*Static` has procedure = "static" and
-reads as before.
+control` -> dynamic_auto = True: the driver re-estimates the increment in every step.  `*Bulk Viscosity` (data `b1, b2`,
+defaults 0.06, 1.2) inside an explicit step -> bulk_viscosity = (b1, b2), None without the keyword; `*Damping, alpha=` in the
+`*Material` block -> damping_alpha (read_damping).  A deck with `*Static` has procedure = "static" and reads as before.
 """
 import sys
 from typing import Dict, List
@@ -139,6 +140,7 @@ class InpInfo(InpInfoBase):
         self.geometric_nonlinear = self.read_geometric_nonlinear(file)
         self.procedure, self.dynamic, self.amplitude = self.read_procedure(file)
         self.time_incs = self.read_time_inc(file)
+        self.bulk_viscosity, self.damping_alpha = self.read_damping(file)
         self.initial_velocity_info = self.read_initial_velocity(file)
 
     # ------------------------------------------------------------------ nodes and elements
@@ -287,6 +289,8 @@ class InpInfo(InpInfoBase):
             elif line[0:8].lower() == "*density":             # Abaqus/CAE writes it first; it is not the material type
                 continue
             elif line[0:10].lower() == "*expansion":          # neither is the expansion coefficient (read_thermal)
+                continue
+            elif line[0:8].lower() == "*damping":             # nor the damping (read_damping); CAE writes it before *Density
                 continue
             elif expect_type:
                 expect_type = False
@@ -532,6 +536,45 @@ class InpInfo(InpInfoBase):
             raise ValueError("*Temperature in a *Dynamic, explicit step has not been supported: thermal loads are small "
                              "strain, an explicit step is not")
         return procedure, dynamic, amplitude or ("RAMP" if procedure == "static" else "STEP")
+
+    def read_damping(self, fileName):
+        """-> bulk_viscosity ((b1, b2) or None), damping_alpha.  `*Bulk Viscosity` inside the step, data line `b1, b2`; an
+        absent line or an empty field gives Abaqus's defaults 0.06 and 1.2.  Without the keyword there is NO bulk viscosity
+        (None): unlike Abaqus/Explicit, where it is on by default, so that existing decks keep their results.
+        `*Damping, alpha=` in the `*Material` block: mass-proportional damping, 0.0 without it.  `beta=` other than 0,
+        `composite=` and `structural=` are refused (stiffness-proportional damping is not built), negative values too, and
+        either keyword in a deck whose procedure is not "explicit": the implicit integrator is undamped."""
+        bulk, alpha = None, 0.0
+        for line, block in _deck(fileName).keywords():
+            fields = [t.strip() for t in line.split(",")]
+            key = fields[0].lower()
+            params = {t.split("=")[0].strip().lower(): t.split("=")[1].strip() for t in fields[1:] if "=" in t}
+            if key == "*bulk viscosity":
+                data = [t for t in block if t.strip()]
+                cols = [t.strip() for t in data[0].split(",")] if data else []
+                b1 = float(cols[0]) if len(cols) > 0 and cols[0] else 0.06
+                b2 = float(cols[1]) if len(cols) > 1 and cols[1] else 1.2
+                if not (b1 >= 0.0 and b2 >= 0.0 and np.isfinite(b1) and np.isfinite(b2)):
+                    raise ValueError("*Bulk Viscosity: b1 = {} and b2 = {} are refused (neither may be negative)".format(b1, b2))
+                bulk = (b1, b2)
+            elif key == "*damping":
+                for name in ("composite", "structural"):
+                    if name in params:
+                        raise ValueError("*Damping, {}= has not been supported: mass-proportional damping (alpha=) "
+                                         "is".format(name))
+                if float(params.get("beta", 0.0)) != 0.0:
+                    raise ValueError("*Damping, beta={} has not been supported: stiffness-proportional damping is not built, "
+                                     "mass-proportional damping (alpha=) is".format(params["beta"]))
+                alpha = float(params.get("alpha", 0.0))
+                if not (alpha >= 0.0 and np.isfinite(alpha)):
+                    raise ValueError("*Damping, alpha={} is refused (it may not be negative)".format(params["alpha"]))
+        if self.procedure != "explicit":
+            if bulk is not None:
+                raise ValueError("*Bulk Viscosity has not been supported outside a *Dynamic, explicit step")
+            if alpha != 0.0:
+                raise ValueError("*Damping has not been supported outside a *Dynamic, explicit step: the implicit "
+                                 "integrator is the undamped Newmark scheme")
+        return bulk, alpha
 
     def read_initial_velocity(self, fileName):
         """`*Initial Conditions, type=VELOCITY` data lines `nset-or-node-label, dof, value` -> [{"node_set", "dof",

@@ -24,7 +24,9 @@ class InpInfoBase:
                   # the step's procedure: "static" | "dynamic" (*Dynamic, direct) | "explicit" (*Dynamic, explicit), its
                   # parameters ({"beta", "gamma"}; {"direct_user_control", "scale_factor", "output_every"}) or None, the load amplitude "RAMP" | "STEP", *Initial Conditions, type=VELOCITY as [{"node_set", "dof", "val"}]
                   # dynamic_auto: `element by element` on *Dynamic, explicit (bool; kept beside the dictionary)
-                  "procedure", "dynamic", "amplitude", "initial_velocity_info", "dynamic_auto")
+                  "procedure", "dynamic", "amplitude", "initial_velocity_info", "dynamic_auto",
+                  # damping of an explicit step: *Bulk Viscosity as (b1, b2) or None, *Damping, alpha= (0.0 without it)
+                  "bulk_viscosity", "damping_alpha")
 
     def __init_subclass__(cls, **kwargs):
         super().__init_subclass__(**kwargs)

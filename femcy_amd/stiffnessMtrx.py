@@ -654,7 +654,11 @@ class System_of_equations:
         (`femcy_explicit_auto_*`), and the last step takes what is left of T.  Batches of `output_every` steps run until the
         clock read back after a batch says t == T (the steps of the last batch past T are no-ops); the records carry "kinc"
         (real steps so far), "time1" (the device clock), "dt" (the last increment) and "dt_min"; `stable_dt` is the first
-        estimate, `dt` the last increment.  An increment that collapses to 0 before T raises the same error."""
+        estimate, `dt` the last increment.  An increment that collapses to 0 before T raises the same error.
+        `*Bulk Viscosity` and `*Damping, alpha=` (`inp.bulk_viscosity`, `inp.damping_alpha`) go to the integrator once
+        (`femcy_explicit_set_damping`, M_d from `dilatational_modulus`); the fixed increment estimated from the matrix is
+        then 2 / omega x (sqrt(1 + xi^2) - xi) with xi = b1 + alpha / (2 omega), which `stable_dt` reports -- the quadratic
+        bulk term cannot be known in advance and is left to `scale factor`; `direct user control` is taken as given."""
         if self.part is not None:
             raise ValueError("a *Dynamic, explicit step on more than one rank has not been supported: the lumped mass is "
                              "single-rank")
@@ -679,6 +683,10 @@ class System_of_equations:
         held = [self._dofset(np.array([*bc["node_set"]]), bc["dof"]) for bc in inp.dirichlet_bc_info]
         self.lumped_mass = ctx.lumped_mass(self.ELE, inp.density)
         self.explicit = ex = ctx.explicit(self.lumped_mass, held)
+        bulk, alpha = getattr(inp, "bulk_viscosity", None), float(getattr(inp, "damping_alpha", 0.0) or 0.0)
+        b1, b2 = bulk if bulk is not None else (0.0, 0.0)
+        if bulk is not None or alpha != 0.0:
+            ctx.explicit_set_damping(ex, alpha, b1, b2, self.dilatational_modulus() if bulk is not None else 0.0)
         if getattr(inp, "dynamic_auto", False):
             return self._solve_explicit_auto(inp, ex, held, max_time)
         if inp.dynamic["direct_user_control"]:
@@ -687,6 +695,11 @@ class System_of_equations:
             ctx.assemble_K(-1)                                        # the matrix of the undeformed mesh, for the estimate only
             self.stats["assemblies"] += 1
             self.stable_dt, self.omega_bound = ctx.explicit_stable_dt(ex)
+            if bulk is not None or alpha != 0.0:
+                # lagged damping of critical fraction xi: h <= (2 / omega)(sqrt(1 + xi^2) - xi); the quadratic bulk term is
+                # not known in advance and left to `scale factor`
+                xi = b1 + alpha / (2.0 * self.omega_bound)
+                self.stable_dt *= np.sqrt(1.0 + xi * xi) - xi
             dt = inp.dynamic["scale_factor"] * self.stable_dt
         if not (np.isfinite(dt) and dt > 0.0):
             raise be.FemcyError("explicit step: no usable increment (dt = {})".format(dt), status=be.FEMCY_ENUMERIC)
@@ -731,6 +744,12 @@ class System_of_equations:
         C = np.asarray(self.material.C, dtype=np.float64)
         d = np.where(np.arange(len(C)) < self.dm, 1.0, np.sqrt(2.0))
         return float(np.linalg.eigvalsh(d[:, None] * C * d[None, :]).max())
+
+    def dilatational_modulus(self):
+        """M_d = rho c_d^2 of the bulk viscosity: C[0][0] of the small-strain matrix -- lambda + 2 mu in 3-D and plane
+        strain, E / (1 - nu^2) in plane stress; neo-Hookean: 2 D1 + 4 C1, lambda + 2 mu with the constants as
+        `material_stiffness` reads them."""
+        return float(np.asarray(self.material.C, dtype=np.float64)[0][0])
 
     def _solve_explicit_auto(self, inp, ex, held, max_time):
         """the `element by element` branch of solve_explicit, from the integrator on"""

@@ -507,6 +507,22 @@ int femcy_explicit_auto_begin(femcy_ctx* ctx, int32_t id, int rhs_vec, double s_
                               int32_t ramp);
 int femcy_explicit_auto_advance(femcy_ctx* ctx, int32_t id, int rhs_vec, int32_t nsteps);
 int femcy_explicit_auto_state(femcy_ctx* ctx, int32_t id, double* t, double* h_last, double* h_min, int64_t* steps_done);
+/* Damping of an explicit integrator (*Bulk Viscosity: b1, b2; *Damping, alpha=): from the next stepping call on, and it may
+ * be called between calls.  Both forces are evaluated at u_{n+1} with the LAGGED half-step velocity of the drift by h that
+ * led there,
+ *   v_{n+1/2} = fma(h / 2, a_n, v_n)                            (v_{-1/2} := v_0 at _start / _auto_begin: vec[ACC] is not read)
+ *   a_{n+1}   = minv (s f - f_int(u_{n+1}) - f_bv(u_{n+1}, v_{n+1/2})) - alpha v_{n+1/2},   v_{n+1} = v_n + h/2 (a_n + a_{n+1}).
+ * Bulk viscosity, at every Gauss point q of the stiffness rule on the current configuration (plane stress: in the plane):
+ *   rate_q = sum_a v_{a,n+1/2} . grad_x N_a,   L_q = (max_a |grad_x N_a|^2)^(-1/2),   rho_q = rho_0 / det F_q,
+ *   p_q    = b1 sqrt(rho_q M_d) L_q rate_q + rho_q (b2 L_q)^2 |rate_q| min(0, rate_q),
+ *   fe[a] += grad_x N_a p_q vol_q,
+ * with rho_0 the density of the lumped mass and M_d = rho c_d^2 the dilatational modulus.  The stored and recovered stress
+ * never contains p_q.  The element-by-element estimate becomes omega_eff,e = omega_e (sqrt(1 + xi_e^2) + xi_e) with
+ *   xi_e = alpha / (2 omega_e) + b1 + b2^2 max_q [L_q sqrt(rho_q / M_d) max(0, -rate_q)]
+ * (femcy_explicit_element_bound stand-alone and _auto_begin take v_{1/2} := vec[VEL]); femcy_explicit_stable_dt is unchanged.
+ * All four zero: the undamped launches and bits.  Refused with FEMCY_EINVAL, the context stays usable: an unknown id, a
+ * value that is not finite or negative, M_d <= 0 while b1 or b2 is not zero, and once femcy_comm_init has run. */
+int femcy_explicit_set_damping(femcy_ctx* ctx, int32_t id, double alpha, double b1, double b2, double M_d);
 /* compute_Ad (conjugateGradientSolver.py:53-58): vec[y] = K vec[x] */
 int femcy_spmv(femcy_ctx* ctx, int x_vec, int y_vec);
 /* ConjugateGradientSolver_rowMajor.re_init + solve (conjugateGradientSolver.py:32-51, 103-127):
