@@ -25,6 +25,7 @@ Deliberate deviations, all outside the arithmetic of the path:
 """
 import copy
 import time
+from types import SimpleNamespace
 from typing import Tuple
 
 import numpy as np
@@ -35,6 +36,65 @@ from . import user_defined as ud
 from .body import Body
 from .conjugateGradientSolver import ConjugateGradientSolver_rowMajor as CG
 from .fields import HostField
+
+
+def deck_view(inp) -> SimpleNamespace:
+    """what the step drivers read of a deck, with the keywords a deck may lack at their defaults: the reader's `InpInfo` carries
+    all of them, `partition.LocalDeck` and the bare namespaces of the tests only those of a static step."""
+    def opt(name, default=None):
+        return getattr(inp, name, default)
+    return SimpleNamespace(
+        neumann_bc_info=inp.neumann_bc_info, dirichlet_bc_info=inp.dirichlet_bc_info, time_incs=inp.time_incs,
+        geometric_nonlinear=inp.geometric_nonlinear, procedure=opt("procedure", "static"), amplitude=opt("amplitude", "RAMP"),
+        density=opt("density"), body_force_info=opt("body_force_info") or [], cload_info=opt("cload_info") or [],
+        expansion=opt("expansion"), temperature_info=opt("temperature_info"),
+        initial_velocity_info=opt("initial_velocity_info") or [], dynamic=opt("dynamic"),
+        dynamic_auto=bool(opt("dynamic_auto", False)), bulk_viscosity=opt("bulk_viscosity"),
+        damping_alpha=float(opt("damping_alpha", 0.0) or 0.0))
+
+
+class LoadSchedule:
+    """the loads of one step and how they grow with time, built once per `solve*` call: working copies of the deck's `*Dsload`,
+    `*Dload`, `*Cload` and `*Boundary` entries, the thermal load object, and the `boundary_conditions` dict that
+    `impose_boundary_condition` takes, at any fraction of the deck's values.  `dirichlet`: whether the `*Boundary` entries are in
+    that dict (`solve`) or treated by the caller (the dynamic procedures: after the inertia term, or through the held DOFs)."""
+
+    def __init__(self, system, deck, dirichlet: bool):
+        self.deck, self.max_time = deck, deck.time_incs["max_time"]
+        self.dirichletBCs = copy.deepcopy(deck.dirichlet_bc_info)
+        for bc in self.dirichletBCs:
+            bc["node_set"] = HostField(np.array([*bc["node_set"]]), dtype=np.int32)
+        self.bcs = {"neumannBCs": copy.deepcopy(deck.neumann_bc_info), "dirichletBCs": self.dirichletBCs if dirichlet else []}
+        if deck.body_force_info or deck.cload_info:      # decks without *Dload / *Cload make the calls they always made
+            self.bcs["bodyForces"] = copy.deepcopy(deck.body_force_info)
+            self.bcs["cloads"] = copy.deepcopy(deck.cload_info)
+        if deck.temperature_info is not None and deck.expansion is not None:
+            if system.geometric_nonlinear or deck.geometric_nonlinear:
+                raise ValueError("a thermal load (*Expansion + *Temperature) with nlgeom has not been supported: the "
+                                 "thermal strain is a small-strain one")
+            final, initial = (np.asarray(deck.temperature_info[k], dtype=np.float64) for k in ("final", "initial"))
+            self.bcs["thermal"] = {"id": system.ctx.thermal(system.ELE, deck.expansion, final - initial), "scale": 0.0}
+        self.any_load = bool(self.bcs["neumannBCs"] or deck.body_force_info or deck.cload_info or "thermal" in self.bcs)
+
+    def amplitude(self, t: float) -> float:
+        """the fraction of the loads that acts at time t: 1 throughout a STEP, t / T on a ramp"""
+        return 1.0 if self.deck.amplitude == "STEP" else t / self.max_time
+
+    def at(self, ratio: float) -> dict:
+        """the `boundary_conditions` dict with every load -- and every Dirichlet value in it -- at `ratio` x the deck's; the
+        temperature ramps over the step like every other load"""
+        deck, bcs = self.deck, self.bcs
+        for nb, nb0 in zip(bcs["neumannBCs"], deck.neumann_bc_info):
+            nb["traction"] = nb0["traction"] * ratio
+        for bf, bf0 in zip(bcs.get("bodyForces", ()), deck.body_force_info):
+            bf["force"] = np.asarray(bf0["force"], dtype=np.float64) * ratio
+        for cl, cl0 in zip(bcs.get("cloads", ()), deck.cload_info):
+            cl["val"] = cl0["val"] * ratio
+        if "thermal" in bcs:
+            bcs["thermal"]["scale"] = ratio
+        for bc, bc0 in zip(bcs["dirichletBCs"], deck.dirichlet_bc_info):
+            bc["val"] = bc0["val"] * ratio
+        return bcs
 
 
 class System_of_equations:
@@ -73,7 +133,7 @@ class System_of_equations:
         # the same answer on every run and every machine -- round 6; round 5 timed both solvers on the running system,
         # which made the 1e-9 ... 1e-12 difference between them, and with it borderline Newton counts, depend on the
         # load of the host).  "auto-timed" keeps that exploration for whoever wants the faster solver and accepts that.
-        self._auto = {"first": None, "ms": {}, "tried": set(), "pcg_ok": True, "pick": None}
+        self._auto = {"first": None, "ms": {}, "samples": {}, "tried": set(), "pcg_ok": True, "pick": None}
         self.direct_log = []              # the solver that served each solve of the direct branch, in order
 
         # ---- device state: mesh, element tables, material, sparsity pattern
@@ -169,6 +229,12 @@ class System_of_equations:
         self.ctx.assemble_K(be.VEC_DOF)
         self.stats["assemblies"] += 1
 
+    def _first_assembly_took(self, t0: float):
+        if not self.compiled:
+            self.compiled = True
+            self.ctx.sync()
+            self._say("\033[35;1m first assembly took {:.4f} s\033[0m".format(time.time() - t0))
+
     assemble_sparseMtrx = assemble_stiffnessMtrx
     assemble_stiffnessMtrx_faster = assemble_stiffnessMtrx
 
@@ -208,6 +274,12 @@ class System_of_equations:
         self.cg_log.append({"iters": it, "r0": r0, "rmax": rmax, "time1": self.time1, "converged": self.PCG.converged})
         return self._take_solution()
 
+    def _tight_pcg(self):
+        """the PCG where a direct solve is meant: eps = direct_eps.  CG in floating point can need more than n iterations on
+        an ill-conditioned K (nu -> 0.5), so the cap is 10 n here instead of the reference CG's n.  Whether an unconverged
+        iterate is an error is the caller's business (`PCG.converged`)."""
+        return self.solve_by_CG(eps=self.direct_eps, maxit=int(min(10 * self.n_system, 2 ** 31 - 1)))
+
     # sub-diagonals above which the FIRST solve of direct = "auto" goes to the tight PCG.  Cube-like C3D4 meshes, medians of
     # five (profiles/r05_direct_mfma_update.txt): 512 sub-diagonals 3.7 ms against 14.6 (PCG), 1 328: 20.3 against 45.3,
     # 2 192: 51.0 against 59.1, 2 888: 86.4 against 69.0 -- the crossover lies near 2 500
@@ -241,7 +313,7 @@ class System_of_equations:
         elif first in a["ms"] and a["ms"][first] <= self.AUTO_TRY_OTHER_MS:
             a["pick"] = first                                    # a millisecond-sized solve: nothing to gain by exploring
         else:
-            cnt = a.setdefault("samples", {})
+            cnt = a["samples"]
             if cnt.get(other, 0) < cnt.get(first, 0) and cnt.get(other, 0) < 2:
                 return other
             if cnt.get(first, 0) < 2:
@@ -265,7 +337,7 @@ class System_of_equations:
                 # down (NaN: FEMCY_ENUMERIC) or wanders -- the factorisation (L S L^T takes negative pivots, as the
                 # reference's LU does) then serves this solve and every later one
                 try:
-                    du = self.solve_by_CG(eps=self.direct_eps, maxit=int(min(10 * self.n_system, 2 ** 31 - 1)))
+                    du = self._tight_pcg()
                     failed, applied = not self.PCG.converged, True
                 except be.FemcyError as e:
                     if e.status != be.FEMCY_ENUMERIC:
@@ -274,7 +346,7 @@ class System_of_equations:
                 if not failed:
                     if timed:
                         a["ms"]["pcg"] = min(a["ms"].get("pcg", 1e30), (time.perf_counter() - t0) * 1e3)
-                    a.setdefault("samples", {})["pcg"] = a.get("samples", {}).get("pcg", 0) + 1
+                    a["samples"]["pcg"] = a["samples"].get("pcg", 0) + 1
                     self.direct_log.append("pcg")
                     return du
                 a["pcg_ok"], a["pick"] = False, "cholesky"
@@ -289,7 +361,7 @@ class System_of_equations:
                 a["ms"]["cholesky"] = min(a["ms"].get("cholesky", 1e30), (time.perf_counter() - t0) * 1e3)
             # (a rejected factorisation -- ENUMERIC, served by the tight PCG inside _solve_direct -- still counts as a sample:
             # the exploration must end)
-            a.setdefault("samples", {})["cholesky"] = a.get("samples", {}).get("cholesky", 0) + 1
+            a["samples"]["cholesky"] = a["samples"].get("cholesky", 0) + 1
             return du
         return self._solve_direct()
 
@@ -316,9 +388,7 @@ class System_of_equations:
                 self.stats["direct_solves"] += 1
                 self.direct_log.append("cholesky")
                 return self._take_solution()
-        # a mesh split over ranks (or direct="pcg"): CG in floating point can need more than n iterations on an
-        # ill-conditioned K (nu -> 0.5), so the cap is 10 n here instead of the reference CG's n
-        du = self.solve_by_CG(eps=self.direct_eps, maxit=int(min(10 * self.n_system, 2 ** 31 - 1)))
+        du = self._tight_pcg()                         # a mesh split over ranks (or direct="pcg")
         if not self.PCG.converged:
             # a direct solver would have returned the solution (or failed loudly); an unconverged iterate must not be
             # used as if it were one: report it like a numerical breakdown, so that a Newton step is cut back
@@ -452,52 +522,68 @@ class System_of_equations:
             else:   # Newton: prescribed values go into dof now, K / residual are treated later
                 self.dirichletBC_dof(bc["node_set"], bc["dof"], bc["val"], bc["user"], self.time1)
 
+    # ------------------------------------------------------- shared by the transient drivers
+    def _transient_gate(self, deck, step: str, mass: str):
+        """what neither dynamic procedure takes; `step` and `mass` are the words in which the two name themselves"""
+        if self.part is not None:
+            raise ValueError("a {} on more than one rank has not been supported: the {} is single-rank".format(step, mass))
+        if deck.density is None:
+            raise ValueError("*Dynamic needs a *Density in the *Material block")
+        if any(bc["val"] != 0.0 for bc in deck.dirichlet_bc_info):
+            raise ValueError("a non-zero *Boundary value in a *Dynamic step (prescribed motion) has not been supported")
+
+    def _external_force(self, loads: LoadSchedule, ratio: float):
+        """rhs = `ratio` x the loads of a dynamic step, which reads rhs whatever the deck holds: zeroed here if it holds no load"""
+        if not loads.any_load:
+            self.rhs.fill(0.0)
+        self.impose_boundary_condition(loads.at(ratio))
+
+    def _initial_state(self, deck, held):
+        """t = 0 of a dynamic step: u_0 = 0, v_0 from `*Initial Conditions, type=VELOCITY`, 0 on the `*Boundary` entries `held`"""
+        ctx = self.ctx
+        self.velocity, self.acceleration = ctx.vector(be.VEC_VEL), ctx.vector(be.VEC_ACC)
+        self.dof.fill(0.0)
+        self.dof_old.fill(0.0)
+        self.velocity.fill(0.0)
+        for iv in deck.initial_velocity_info:
+            ctx.dofset_fill(self._dofset(iv["node_set"], iv["dof"]), be.VEC_VEL, iv["val"])
+        for bc in held:
+            ctx.dofset_fill(self._dofset(bc["node_set"], bc["dof"]), be.VEC_VEL, 0.0)
+        self.time0 = self.time1 = 0.0
+
+    def _energies(self, kinetic: float) -> dict:
+        return {"kinetic": kinetic, "strain_energy": self.get_elasEng()}
+
+    def _record(self, kinc: int, dt: float, kinetic: float, **more):
+        """the entry of `increments` after a step, or a batch of steps, that ended at `time1`"""
+        self.increments.append({"kinc": kinc, "time1": self.time1, "dt": dt, **more, "converged": True, "newton_loop": 0,
+                                **self._energies(kinetic)})
+
+    def _displacements_are_finite(self, after: str):
+        if not np.isfinite(self.ctx.vec_absmax(be.VEC_DOF)):
+            raise be.FemcyError("explicit step: the displacements are not finite after {} (an unstable increment)".format(after),
+                                status=be.FEMCY_ENUMERIC)
+
     # --------------------------------------------------------------------- time stepping
     def solve(self, inp, show_newton_steps: bool = False, save2path: str = None):
         """multiple time increments with automatic cut-back (reference :647-711).  A `*Dynamic` step goes to
         `solve_dynamic`; a deck without it makes the calls it always made."""
         self._linear_energy = False      # get_elasEng: the reference's energy, unless solve_dynamic says otherwise
-        if getattr(inp, "procedure", "static") == "dynamic":
+        deck = deck_view(inp)
+        if deck.procedure == "dynamic":
             return self.solve_dynamic(inp)
-        if getattr(inp, "procedure", "static") == "explicit":
+        if deck.procedure == "explicit":
             return self.solve_explicit(inp)
-        max_inc, min_inc = inp.time_incs["max_inc"], inp.time_incs["min_inc"]
-        max_time = inp.time_incs["max_time"]
-        self.dt = inp.time_incs["ini_inc"]
-        neumannBCs = copy.deepcopy(inp.neumann_bc_info)
-        dirichletBCs = copy.deepcopy(inp.dirichlet_bc_info)
-        for bc in dirichletBCs:
-            bc["node_set"] = HostField(np.array([*bc["node_set"]]), dtype=np.int32)
-        boundary_conditions = {"neumannBCs": neumannBCs, "dirichletBCs": dirichletBCs}
-        body_force_info, cload_info = getattr(inp, "body_force_info", None) or [], getattr(inp, "cload_info", None) or []
-        if body_force_info or cload_info:          # decks without *Dload / *Cload make the calls they always made
-            boundary_conditions["bodyForces"] = copy.deepcopy(body_force_info)
-            boundary_conditions["cloads"] = copy.deepcopy(cload_info)
-        temperature_info, expansion = getattr(inp, "temperature_info", None), getattr(inp, "expansion", None)
-        if temperature_info is not None and expansion is not None:
-            if self.geometric_nonlinear or inp.geometric_nonlinear:
-                raise ValueError("a thermal load (*Expansion + *Temperature) with nlgeom has not been supported: the "
-                                 "thermal strain is a small-strain one")
-            dT = np.asarray(temperature_info["final"], dtype=np.float64) - np.asarray(temperature_info["initial"], dtype=np.float64)
-            boundary_conditions["thermal"] = {"id": self.ctx.thermal(self.ELE, expansion, dT), "scale": 0.0}
+        max_inc, min_inc, max_time = deck.time_incs["max_inc"], deck.time_incs["min_inc"], deck.time_incs["max_time"]
+        self.dt = deck.time_incs["ini_inc"]
+        loads = LoadSchedule(self, deck, dirichlet=True)       # rhs: a deck with no load never refreshes it, as in the reference
         self.increments = []
         kinc = -1
         while self.time1 < max_time:
             kinc += 1
             self.time1 = min(self.time0 + self.dt, max_time)
             self._say("\033[40;33;1m >>>>> kinc = {}, time0 = {}, dt = {} \033[0m".format(kinc, self.time0, self.dt))
-            load_ratio = 1.0 if getattr(inp, "amplitude", "RAMP") == "STEP" else self.time1 / max_time
-            for i, nb in enumerate(neumannBCs):
-                nb["traction"] = inp.neumann_bc_info[i]["traction"] * load_ratio
-            for i, bf in enumerate(boundary_conditions.get("bodyForces", ())):
-                bf["force"] = np.asarray(body_force_info[i]["force"], dtype=np.float64) * load_ratio
-            for i, cl in enumerate(boundary_conditions.get("cloads", ())):
-                cl["val"] = cload_info[i]["val"] * load_ratio
-            if "thermal" in boundary_conditions:     # the temperature ramps over the step like every other load
-                boundary_conditions["thermal"]["scale"] = load_ratio
-            for i, bc in enumerate(dirichletBCs):
-                bc["val"] = inp.dirichlet_bc_info[i]["val"] * load_ratio
-            converged, newton_loop = self.advance_inc(inp, boundary_conditions, show_newton_steps, save2path)
+            converged, newton_loop = self.advance_inc(inp, loads.at(loads.amplitude(self.time1)), show_newton_steps, save2path)
             self.increments.append({"kinc": kinc, "time1": self.time1, "dt": self.dt, "converged": converged,
                                     "newton_loop": newton_loop})
             if not converged:
@@ -532,79 +618,37 @@ class System_of_equations:
         if getattr(self.material, "kind", None) == FEMCY_MAT_NEOHOOKE:
             raise ValueError("a *Dynamic step with a neo-Hookean material has not been supported: the integrator is linear "
                              "(small strain)")
-        if self.part is not None:
-            raise ValueError("a *Dynamic step on more than one rank has not been supported: the mass matrix is "
-                             "single-rank")
-        if getattr(inp, "density", None) is None:
-            raise ValueError("*Dynamic needs a *Density in the *Material block")
-        if any(bc["val"] != 0.0 for bc in inp.dirichlet_bc_info):
-            raise ValueError("a non-zero *Boundary value in a *Dynamic step (prescribed motion) has not been supported")
-        beta, gamma = inp.dynamic["beta"], inp.dynamic["gamma"]
-        dt, max_time = inp.time_incs["ini_inc"], inp.time_incs["max_time"]
+        deck = deck_view(inp)
+        self._transient_gate(deck, "*Dynamic step", "mass matrix")
+        beta, gamma = deck.dynamic["beta"], deck.dynamic["gamma"]
+        dt, max_time = deck.time_incs["ini_inc"], deck.time_incs["max_time"]
         ctx = self.ctx
-        neumannBCs = copy.deepcopy(inp.neumann_bc_info)
-        dirichletBCs = copy.deepcopy(inp.dirichlet_bc_info)
-        for bc in dirichletBCs:
-            bc["node_set"] = HostField(np.array([*bc["node_set"]]), dtype=np.int32)
-        loads = {"neumannBCs": neumannBCs, "dirichletBCs": []}        # Dirichlet rows are treated after the inertia term
-        body_force_info, cload_info = getattr(inp, "body_force_info", None) or [], getattr(inp, "cload_info", None) or []
-        if body_force_info or cload_info:
-            loads["bodyForces"] = copy.deepcopy(body_force_info)
-            loads["cloads"] = copy.deepcopy(cload_info)
-        temperature_info, expansion = getattr(inp, "temperature_info", None), getattr(inp, "expansion", None)
-        if temperature_info is not None and expansion is not None:
-            dT = np.asarray(temperature_info["final"], dtype=np.float64) - np.asarray(temperature_info["initial"], dtype=np.float64)
-            loads["thermal"] = {"id": ctx.thermal(self.ELE, expansion, dT), "scale": 0.0}
-        any_load = bool(neumannBCs or body_force_info or cload_info or "thermal" in loads)
-
-        def external_force(t):
-            """rhs = f(t) through impose_boundary_condition, load ratio = amplitude(t)"""
-            ratio = 1.0 if inp.amplitude == "STEP" else t / max_time
-            for i, nb in enumerate(neumannBCs):
-                nb["traction"] = inp.neumann_bc_info[i]["traction"] * ratio
-            for i, bf in enumerate(loads.get("bodyForces", ())):
-                bf["force"] = np.asarray(body_force_info[i]["force"], dtype=np.float64) * ratio
-            for i, cl in enumerate(loads.get("cloads", ())):
-                cl["val"] = cload_info[i]["val"] * ratio
-            if "thermal" in loads:
-                loads["thermal"]["scale"] = ratio
-            if not any_load:
-                self.rhs.fill(0.0)
-            self.impose_boundary_condition(loads)
+        loads = LoadSchedule(self, deck, dirichlet=False)             # Dirichlet rows are treated after the inertia term
 
         def dirichlet_rows():
-            for bc in dirichletBCs:
+            for bc in loads.dirichletBCs:
                 self.dirichletBC_linearEquations(bc["node_set"], bc["dof"], 0.0)
 
         def linear_solve():
             if self.n_system < self.cg_branch_from:
                 return self.solve_by_scipy()
-            du = self.solve_by_CG(eps=self.direct_eps, maxit=int(min(10 * self.n_system, 2 ** 31 - 1)))
+            du = self._tight_pcg()
             if not self.PCG.converged:
                 raise be.FemcyError("dynamic step: the PCG stopped at max|r| = {:.3e} > {:.1e} * {:.3e}".format(
                     self.PCG.rmax, self.direct_eps, self.PCG.r0), status=be.FEMCY_ENUMERIC)
             return du
 
-        vel, acc = ctx.vector(be.VEC_VEL), ctx.vector(be.VEC_ACC)
-        self.velocity, self.acceleration = vel, acc
         self._linear_energy = True
-        self.mass = ctx.mass(self.ELE, inp.density)
+        self.mass = ctx.mass(self.ELE, deck.density)
         # ---- t = 0: u_0 = 0, v_0 from the deck (0 where the body is held), M a_0 = f(0+) - K u_0
-        self.dof.fill(0.0)
-        self.dof_old.fill(0.0)
-        vel.fill(0.0)
-        for iv in getattr(inp, "initial_velocity_info", None) or []:
-            ctx.dofset_fill(self._dofset(iv["node_set"], iv["dof"]), be.VEC_VEL, iv["val"])
-        for bc in dirichletBCs:
-            ctx.dofset_fill(self._dofset(bc["node_set"], bc["dof"]), be.VEC_VEL, 0.0)
-        self.time0 = self.time1 = 0.0
-        external_force(0.0)
+        self._initial_state(deck, loads.dirichletBCs)
+        self._external_force(loads, loads.amplitude(0.0))
         ctx.mass_add_to_K(self.mass, 1.0, overwrite=True)
         dirichlet_rows()
         linear_solve()
-        acc.copy_from(self.dof)
+        self.acceleration.copy_from(self.dof)
         self.dof.fill(0.0)
-        self.initial_energy = {"kinetic": ctx.mass_kinetic_energy(self.mass, be.VEC_VEL), "strain_energy": self.get_elasEng()}
+        self.initial_energy = self._energies(ctx.mass_kinetic_energy(self.mass, be.VEC_VEL))
         self.increments = []
         kinc = 0
         while self.time0 < max_time * (1.0 - 1.0e-12):
@@ -617,22 +661,17 @@ class System_of_equations:
             a0 = 1.0 / (beta * h * h)
             ctx.assemble_K(-1)                                        # K of the undeformed mesh (small strain)
             self.stats["assemblies"] += 1
-            if not self.compiled:
-                self.compiled = True
-                ctx.sync()
-                self._say("\033[35;1m first assembly took {:.4f} s\033[0m".format(time.time() - t0))
+            self._first_assembly_took(t0)
             ctx.mass_add_to_K(self.mass, a0)
             ctx.newmark_predict(be.VEC_DOF, be.VEC_VEL, be.VEC_ACC, be.VEC_RESIDUAL, a0, 1.0 / (beta * h),
                                 1.0 / (2.0 * beta) - 1.0)
-            external_force(self.time1)
+            self._external_force(loads, loads.amplitude(self.time1))
             ctx.mass_apply(self.mass, be.VEC_RESIDUAL, be.VEC_RHS, 1.0, add=True)
             dirichlet_rows()
             linear_solve()                                            # dof = u_{n+1}; dof_old still holds u_n
             ctx.newmark_update(be.VEC_DOF, be.VEC_DOF_OLD, be.VEC_VEL, be.VEC_ACC, beta, gamma, h)
             self.dof_old.copy_from(self.dof)
-            self.increments.append({"kinc": kinc, "time1": self.time1, "dt": h, "converged": True, "newton_loop": 0,
-                                    "kinetic": ctx.mass_kinetic_energy(self.mass, be.VEC_VEL),
-                                    "strain_energy": self.get_elasEng()})
+            self._record(kinc, h, ctx.mass_kinetic_energy(self.mass, be.VEC_VEL))
             self.time0 = self.time1
             kinc += 1
 
@@ -659,38 +698,26 @@ class System_of_equations:
         (`femcy_explicit_set_damping`, M_d from `dilatational_modulus`); the fixed increment estimated from the matrix is
         then 2 / omega x (sqrt(1 + xi^2) - xi) with xi = b1 + alpha / (2 omega), which `stable_dt` reports -- the quadratic
         bulk term cannot be known in advance and is left to `scale factor`; `direct user control` is taken as given."""
-        if self.part is not None:
-            raise ValueError("a *Dynamic, explicit step on more than one rank has not been supported: the lumped mass is "
-                             "single-rank")
-        if getattr(inp, "density", None) is None:
-            raise ValueError("*Dynamic needs a *Density in the *Material block")
-        if any(bc["val"] != 0.0 for bc in inp.dirichlet_bc_info):
-            raise ValueError("a non-zero *Boundary value in a *Dynamic step (prescribed motion) has not been supported")
-        if getattr(inp, "temperature_info", None) is not None:
+        deck = deck_view(inp)
+        self._transient_gate(deck, "*Dynamic, explicit step", "lumped mass")
+        if deck.temperature_info is not None:
             raise ValueError("*Temperature in a *Dynamic, explicit step has not been supported: thermal loads are small "
                              "strain, an explicit step is not")
-        ctx = self.ctx
         self.geometric_nonlinear = True                               # post-processing: Green strain, the stress of f_int
-        max_time = inp.time_incs["max_time"]
-        loads = {"neumannBCs": copy.deepcopy(inp.neumann_bc_info), "dirichletBCs": []}
-        body_force_info, cload_info = getattr(inp, "body_force_info", None) or [], getattr(inp, "cload_info", None) or []
-        if body_force_info or cload_info:
-            loads["bodyForces"] = copy.deepcopy(body_force_info)
-            loads["cloads"] = copy.deepcopy(cload_info)
-        if not (loads["neumannBCs"] or body_force_info or cload_info):
-            self.rhs.fill(0.0)
-        self.impose_boundary_condition(loads)                         # rhs = f at scale 1, once
-        held = [self._dofset(np.array([*bc["node_set"]]), bc["dof"]) for bc in inp.dirichlet_bc_info]
-        self.lumped_mass = ctx.lumped_mass(self.ELE, inp.density)
+        loads = LoadSchedule(self, deck, dirichlet=False)             # the held DOFs belong to the integrator
+        ctx, max_time = self.ctx, loads.max_time
+        self._external_force(loads, 1.0)                              # rhs = f at scale 1, once
+        held = [self._dofset(bc["node_set"], bc["dof"]) for bc in loads.dirichletBCs]
+        self.lumped_mass = ctx.lumped_mass(self.ELE, deck.density)
         self.explicit = ex = ctx.explicit(self.lumped_mass, held)
-        bulk, alpha = getattr(inp, "bulk_viscosity", None), float(getattr(inp, "damping_alpha", 0.0) or 0.0)
+        bulk, alpha = deck.bulk_viscosity, deck.damping_alpha
         b1, b2 = bulk if bulk is not None else (0.0, 0.0)
         if bulk is not None or alpha != 0.0:
             ctx.explicit_set_damping(ex, alpha, b1, b2, self.dilatational_modulus() if bulk is not None else 0.0)
-        if getattr(inp, "dynamic_auto", False):
-            return self._solve_explicit_auto(inp, ex, held, max_time)
-        if inp.dynamic["direct_user_control"]:
-            dt = inp.time_incs["ini_inc"]
+        if deck.dynamic_auto:
+            return self._solve_explicit_auto(deck, loads, ex)
+        if deck.dynamic["direct_user_control"]:
+            dt = deck.time_incs["ini_inc"]
         else:
             ctx.assemble_K(-1)                                        # the matrix of the undeformed mesh, for the estimate only
             self.stats["assemblies"] += 1
@@ -700,40 +727,27 @@ class System_of_equations:
                 # not known in advance and left to `scale factor`
                 xi = b1 + alpha / (2.0 * self.omega_bound)
                 self.stable_dt *= np.sqrt(1.0 + xi * xi) - xi
-            dt = inp.dynamic["scale_factor"] * self.stable_dt
+            dt = deck.dynamic["scale_factor"] * self.stable_dt
         if not (np.isfinite(dt) and dt > 0.0):
             raise be.FemcyError("explicit step: no usable increment (dt = {})".format(dt), status=be.FEMCY_ENUMERIC)
         nsteps = max(1, int(np.ceil(max_time / dt * (1.0 - 1.0e-12))))
         self.dt = h = max_time / nsteps                               # <= dt: T is a whole number of steps
-        ramp = inp.amplitude == "RAMP"
-        dscale = h / max_time if ramp else 0.0
-        vel, acc = ctx.vector(be.VEC_VEL), ctx.vector(be.VEC_ACC)
-        self.velocity, self.acceleration = vel, acc
-        self.dof.fill(0.0)
-        self.dof_old.fill(0.0)
-        vel.fill(0.0)
-        for iv in getattr(inp, "initial_velocity_info", None) or []:
-            ctx.dofset_fill(self._dofset(iv["node_set"], iv["dof"]), be.VEC_VEL, iv["val"])
-        for ds in held:
-            ctx.dofset_fill(ds, be.VEC_VEL, 0.0)
-        self.time0 = self.time1 = 0.0
-        ctx.explicit_start(ex, be.VEC_RHS, 0.0 if ramp else 1.0)
-        self.initial_energy = {"kinetic": ctx.explicit_kinetic_energy(ex, be.VEC_VEL), "strain_energy": self.get_elasEng()}
+        scale0 = loads.amplitude(0.0)                                 # step k scales rhs by scale0 + k dscale: 1 and 0 in a
+        dscale = loads.amplitude(h) - scale0                          # STEP, 0 and h / T on a ramp
+        self._initial_state(deck, loads.dirichletBCs)
+        ctx.explicit_start(ex, be.VEC_RHS, scale0)
+        self.initial_energy = self._energies(ctx.explicit_kinetic_energy(ex, be.VEC_VEL))
         self.increments = []
-        done, batch = 0, inp.dynamic["output_every"]
+        done, batch = 0, deck.dynamic["output_every"]
         while done < nsteps:
             k = min(batch, nsteps - done)                             # the last batch is clipped
             self._say("\033[40;33;1m >>>>> steps {} .. {} of {}, dt = {} \033[0m".format(done + 1, done + k, nsteps, h))
-            ctx.explicit_advance(ex, k, h, be.VEC_RHS, (done * dscale) if ramp else 1.0, dscale)
+            ctx.explicit_advance(ex, k, h, be.VEC_RHS, scale0 + done * dscale, dscale)
             self.stats["force_evals"] += k
             done += k
             self.time0, self.time1 = self.time1, max_time if done == nsteps else done * h
-            if not np.isfinite(ctx.vec_absmax(be.VEC_DOF)):
-                raise be.FemcyError("explicit step: the displacements are not finite after {} steps of dt = {} (an unstable "
-                                    "increment)".format(done, h), status=be.FEMCY_ENUMERIC)
-            self.increments.append({"kinc": done, "time1": self.time1, "dt": h, "converged": True, "newton_loop": 0,
-                                    "kinetic": ctx.explicit_kinetic_energy(ex, be.VEC_VEL),
-                                    "strain_energy": self.get_elasEng()})
+            self._displacements_are_finite("{} steps of dt = {}".format(done, h))
+            self._record(done, h, ctx.explicit_kinetic_energy(ex, be.VEC_VEL))
         self.dof_old.copy_from(self.dof)
 
     def material_stiffness(self):
@@ -751,21 +765,12 @@ class System_of_equations:
         `material_stiffness` reads them."""
         return float(np.asarray(self.material.C, dtype=np.float64)[0][0])
 
-    def _solve_explicit_auto(self, inp, ex, held, max_time):
+    def _solve_explicit_auto(self, deck, loads, ex):
         """the `element by element` branch of solve_explicit, from the integrator on"""
-        ctx = self.ctx
-        ramp = inp.amplitude == "RAMP"
-        s_C, sf, batch = self.material_stiffness(), inp.dynamic["scale_factor"], inp.dynamic["output_every"]
-        vel, acc = ctx.vector(be.VEC_VEL), ctx.vector(be.VEC_ACC)
-        self.velocity, self.acceleration = vel, acc
-        self.dof.fill(0.0)
-        self.dof_old.fill(0.0)
-        vel.fill(0.0)
-        for iv in getattr(inp, "initial_velocity_info", None) or []:
-            ctx.dofset_fill(self._dofset(iv["node_set"], iv["dof"]), be.VEC_VEL, iv["val"])
-        for ds in held:
-            ctx.dofset_fill(ds, be.VEC_VEL, 0.0)
-        self.time0 = self.time1 = 0.0
+        ctx, max_time = self.ctx, loads.max_time
+        ramp = loads.amplitude(0.0) < 1.0                             # the device ramps the load itself, by its own clock
+        s_C, sf, batch = self.material_stiffness(), deck.dynamic["scale_factor"], deck.dynamic["output_every"]
+        self._initial_state(deck, loads.dirichletBCs)
         self.omega_bound = ctx.explicit_element_bound(ex, s_C, be.VEC_DOF)
         self.stable_dt = 2.0 / self.omega_bound if self.omega_bound > 0.0 else np.inf
         if not np.isfinite(self.omega_bound):
@@ -773,7 +778,7 @@ class System_of_equations:
                                 status=be.FEMCY_ENUMERIC)
         ctx.explicit_auto_begin(ex, s_C, sf, max_time, ramp, be.VEC_RHS)
         self.stats["force_evals"] += 1
-        self.initial_energy = {"kinetic": ctx.explicit_kinetic_energy(ex, be.VEC_VEL), "strain_energy": self.get_elasEng()}
+        self.initial_energy = self._energies(ctx.explicit_kinetic_energy(ex, be.VEC_VEL))
         self.increments = []
         done, t = 0, 0.0
         while t < max_time:
@@ -782,16 +787,12 @@ class System_of_equations:
             self.stats["force_evals"] += batch
             t, h_last, h_min, steps = ctx.explicit_auto_state(ex)
             self.time0, self.time1, self.dt = self.time1, t, h_last
-            if not np.isfinite(ctx.vec_absmax(be.VEC_DOF)):
-                raise be.FemcyError("explicit step: the displacements are not finite after {} steps, the last of dt = {} (an "
-                                    "unstable increment)".format(steps, h_last), status=be.FEMCY_ENUMERIC)
+            self._displacements_are_finite("{} steps, the last of dt = {}".format(steps, h_last))
             if steps == done and t < max_time:
                 raise be.FemcyError("explicit step: the increment collapsed to 0 at t = {} of {} after {} steps (an unstable "
                                     "increment)".format(t, max_time, steps), status=be.FEMCY_ENUMERIC)
             done = steps
-            self.increments.append({"kinc": done, "time1": t, "dt": h_last, "dt_min": h_min, "converged": True,
-                                    "newton_loop": 0, "kinetic": ctx.explicit_kinetic_energy(ex, be.VEC_VEL),
-                                    "strain_energy": self.get_elasEng()})
+            self._record(done, h_last, ctx.explicit_kinetic_energy(ex, be.VEC_VEL), dt_min=h_min)
         self.dof_old.copy_from(self.dof)
 
     def _residual(self, dirichletBCs):
@@ -811,10 +812,7 @@ class System_of_equations:
         t0 = time.time()
         self.get_dsdx_and_vol()
         self.assemble_stiffnessMtrx()
-        if not self.compiled:
-            self.compiled = True
-            self.ctx.sync()
-            self._say("\033[35;1m first assembly took {:.4f} s\033[0m".format(time.time() - t0))
+        self._first_assembly_took(t0)
         self.impose_boundary_condition(boundary_conditions)
 
         if not inp.geometric_nonlinear:
