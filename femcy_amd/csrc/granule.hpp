@@ -30,6 +30,15 @@ __device__ __forceinline__ void granule_store(const __amdgpu_buffer_rsrc_t rs, i
 // ONE wave sweeps: NV granules per workgroup, stored [G][NV]; lane sweeps workgroups lane, lane + 64, ...; sums /
 // maxima in a fixed order (the same in every workgroup).  op[v]: 0 = sum, 1 = max.  Returns false on poison or
 // time-out (the caller's workgroup then poisons its own granules, which every other sweep sees).
+//
+// A sweep is ONE load round trip: the SWEEP_ROWS * NV loads of a chunk (SWEEP_ROWS rows of 64 workgroups = 256
+// workgroups, the whole grid of a 256-CU device) are issued back to back into registers and examined behind a single
+// wait.  Written as `for (k = lane; k < G; k += 64)` the loop is divergent with a run-time trip count, the compiler
+// keeps it rolled with s_waitcnt vmcnt(0) behind every load, and a sweep of 256 workgroups is four DEPENDENT sc1
+// round trips -- paid once more, in full, after the last granule has become visible.  A lane whose workgroup index is
+// >= G loads a clamped, in-range granule and a select discards it: it counts as "tag matches" and leaves the lane's
+// sum / maximum as it is.  The order of combination is what it was (per lane ascending k, then across the wave).
+constexpr int SWEEP_ROWS = 4;
 template <int NV>
 __device__ __forceinline__ bool granule_sweep(const __amdgpu_buffer_rsrc_t rs, int base, int G, unsigned long long tag,
                                               uint32_t spin_limit, double (&out)[NV], const int (&op)[NV]) {
@@ -40,17 +49,27 @@ __device__ __forceinline__ bool granule_sweep(const __amdgpu_buffer_rsrc_t rs, i
 #pragma unroll
         for (int v = 0; v < NV; ++v) acc[v] = 0.0;
         bool ok = true, poison = false;
-        for (int k = lane; k < G; k += 64) {
-            u32x4 w[NV];
+        for (int k0 = 0; k0 < G; k0 += 64 * SWEEP_ROWS) {          // wave-uniform; a second chunk only when G > 256
+            u32x4 w[SWEEP_ROWS][NV];
 #pragma unroll
-            for (int v = 0; v < NV; ++v) w[v] = __builtin_amdgcn_raw_buffer_load_b128(rs, (base + k * NV + v) * 16, 0, AUX_SC1);
+            for (int j = 0; j < SWEEP_ROWS; ++j) {
+                const int kc = min(k0 + 64 * j + lane, G - 1);
 #pragma unroll
-            for (int v = 0; v < NV; ++v) {
-                const unsigned long long t = ((unsigned long long)w[v].w << 32) | w[v].z;
-                ok = ok && (t == tag);
-                poison = poison || (t == TAG_POISON);
-                const double val = __hiloint2double((int)w[v].y, (int)w[v].x);
-                acc[v] = op[v] ? fmax(acc[v], val) : acc[v] + val;
+                for (int v = 0; v < NV; ++v)
+                    w[j][v] = __builtin_amdgcn_raw_buffer_load_b128(rs, (base + kc * NV + v) * 16, 0, AUX_SC1);
+            }
+#pragma unroll
+            for (int j = 0; j < SWEEP_ROWS; ++j) {
+                const bool in = k0 + 64 * j + lane < G;
+#pragma unroll
+                for (int v = 0; v < NV; ++v) {
+                    const unsigned long long t = ((unsigned long long)w[j][v].w << 32) | w[j][v].z;
+                    ok = ok && (!in || t == tag);
+                    poison = poison || (in && t == TAG_POISON);
+                    const double val = __hiloint2double((int)w[j][v].y, (int)w[j][v].x);
+                    const double comb = op[v] ? fmax(acc[v], val) : acc[v] + val;
+                    acc[v] = in ? comb : acc[v];
+                }
             }
         }
         if (__any(poison)) return false;
@@ -59,7 +78,10 @@ __device__ __forceinline__ bool granule_sweep(const __amdgpu_buffer_rsrc_t rs, i
             for (int v = 0; v < NV; ++v) out[v] = op[v] ? wave_max(acc[v]) : wave_sum(acc[v]);
             return true;
         }
-        __builtin_amdgcn_s_sleep(1);      // 64 cycles between sweeps; polling back to back measured no gain
+        // the re-poll, measured with femcy_probe_exchange(2000, 1) on the one-round-trip sweep (2.14-2.18 us per exchange,
+        // spread of repeated runs 0.04): without this sleep 2.16 -- no gain; a second sweep issued while the first is
+        // in flight (examined behind s_waitcnt vmcnt(N) on the older half) 2.29-2.30 -- slower, twice the poll traffic
+        __builtin_amdgcn_s_sleep(1);      // 64 cycles between sweeps
         if (++spins > spin_limit) return false;
     }
 }

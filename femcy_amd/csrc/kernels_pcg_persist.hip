@@ -20,7 +20,10 @@
 //         (write-through) stores and sc1 loads (round 2);
 //       - tagged granules (VAR & 2): every workgroup publishes {value, round} as ONE 16-byte sc1 store and one wave per
 //         workgroup sweeps all G granules until every tag shows the round -- barrier and exchange in one store
-//         latency + one load latency instead of store-ack + two atomics + poll + data load.
+//         latency + the sweeps instead of store-ack + two atomics + poll + data load.  A sweep is ONE load round
+//         trip since round 7 (granule.hpp: its loads are issued together); until then the rolled loop made it four
+//         dependent ones at G = 256, so an exchange never was just the store + load pair (femcy_probe_exchange:
+//         2.64-2.69 -> 2.14-2.18 us per exchange; 26.97 -> 26.39 us per iteration at 1 M C3D4).
 // Round 3 variants (template parameter VAR, bits; measurements in DESIGN.md section 3):
 //   1  the streamed block rows are loaded non-temporally, except the first `l2_rows` streamed rows of every slice, which
 //      keep the default policy: the stream is latency-bound at one wave per SIMD (femcy_probe_stream: 7.4 TB/s from the
@@ -1465,8 +1468,11 @@ int probe_stream(Ctx* c, int64_t bytes, int32_t reps, int32_t mode, double* us_p
 // solver's launch shape; form 0 = counters + data (grid_barrier), 1 = tagged granules
 int probe_exchange(Ctx* c, int32_t rounds, int32_t form, double* us_per_exchange) {
     FEMCY_REQUIRE(rounds >= 1 && rounds <= (1 << 20) && (form == 0 || form == 1), "probe_exchange: rounds 1..2^20, form 0 / 1");
-    const int G = (c->persist_cus / PNX) * PNX;
-    FEMCY_REQUIRE(G >= PNX, "device reports %d compute units", c->persist_cus);
+    FEMCY_REQUIRE(c->persist_cus >= PNX, "device reports %d compute units", c->persist_cus);
+    // the solver's workgroup count, FEMCY_TUNE_PERSIST_WGS included; the probe has no fall-back, so never more than
+    // one workgroup per CU, whatever FEMCY_TUNE_SKIP_OCCUPANCY_CHECK says
+    const int G = ((c->opt_persist_wgs > 0 ? c->opt_persist_wgs : c->persist_cus) / PNX) * PNX;
+    FEMCY_REQUIRE(G >= PNX && G <= c->persist_cus, "probe_exchange: %d workgroups on %d compute units", G, c->persist_cus);
     PersistPcg a{};
     int rc = persist_buffers(c, G, 2, &a);
     if (rc) return rc;
