@@ -391,10 +391,9 @@ int comm_allgather_host(Ctx* c, const void* send, int32_t bytes, void* recv) {
     }
     const int R_ = c->nranks;
     const int64_t nd = (bytes + 7) / 8;                  // carried as doubles (bit patterns are only copied)
-    double *d_s = nullptr, *d_r = nullptr;
-    FEMCY_HIP(dmalloc(&d_s, sizeof(double) * nd));
-    if (dmalloc(&d_r, sizeof(double) * nd * R_) != hipSuccess) {
-        (void)hipFree(d_s);
+    DevBuf<double> d_s, d_r;
+    FEMCY_HIP(d_s.alloc(sizeof(double) * nd));
+    if (d_r.alloc(sizeof(double) * nd * R_) != hipSuccess) {
         set_error("allgather_host: hipMalloc failed");
         return FEMCY_ENOMEM;
     }
@@ -405,8 +404,6 @@ int comm_allgather_host(Ctx* c, const void* send, int32_t bytes, void* recv) {
     if (!rc) rc = comm_allgather(c, d_s, d_r, nd);
     if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = FEMCY_EHIP;
     if (!rc && hipMemcpy(hr.data(), d_r, sizeof(double) * nd * R_, hipMemcpyDeviceToHost) != hipSuccess) rc = FEMCY_EHIP;
-    (void)hipFree(d_s);
-    (void)hipFree(d_r);
     if (rc == FEMCY_EHIP) set_error("allgather_host: a HIP copy failed");
     if (rc) return rc;
     for (int r = 0; r < R_; ++r) std::memcpy((char*)recv + (size_t)r * bytes, hr.data() + (size_t)r * nd, (size_t)bytes);
@@ -444,18 +441,19 @@ int comm_mailbox_export(Ctx* c, void* blob256) {
     FEMCY_REQUIRE(R <= 16, "the mailbox path supports up to 16 ranks");
     const int64_t nb_total = c->h_nb_ptr.back();
     const int64_t words = 12 * (int64_t)R + 4 * nb_total + 16;
-    if (!c->d_mbox || c->mbox_words < words) {
-        if (c->d_mbox) (void)hipFree(c->d_mbox);
-        c->d_mbox = nullptr;
+    const size_t mbox_bytes = sizeof(unsigned long long) * words;
+    if (c->d_mbox.capacity() < mbox_bytes) {
+        c->d_mbox.reset();
         // fine-grained: remote (xGMI) writes must become visible to this device's polls without a kernel boundary
-        c->mbox_finegrained = hipExtMallocWithFlags((void**)&c->d_mbox, sizeof(unsigned long long) * words,
-                                                    hipDeviceMallocFinegrained) == hipSuccess;
-        if (!c->mbox_finegrained) {
+        void* fine = nullptr;
+        c->mbox_finegrained = hipExtMallocWithFlags(&fine, mbox_bytes, hipDeviceMallocFinegrained) == hipSuccess;
+        if (c->mbox_finegrained)
+            c->d_mbox.adopt((unsigned long long*)fine, mbox_bytes);
+        else {
             (void)hipGetLastError();
-            FEMCY_HIP(dmalloc(&c->d_mbox, sizeof(unsigned long long) * words));
+            FEMCY_HIP(c->d_mbox.alloc(mbox_bytes));
         }
-        c->mbox_words = words;
-        FEMCY_HIP(dfill_sync(c->d_mbox, 0, sizeof(unsigned long long) * words));
+        FEMCY_HIP(dfill_sync(c->d_mbox, 0, mbox_bytes));
     }
     MboxBlob b;
     std::memset(&b, 0, sizeof(b));
@@ -465,7 +463,7 @@ int comm_mailbox_export(Ctx* c, void* blob256) {
     b.pid = (int64_t)getpid();
     b.nonce = process_nonce();
     b.finegrained = c->mbox_finegrained ? 1 : 0;
-    b.devptr = (uint64_t)(uintptr_t)c->d_mbox;
+    b.devptr = (uint64_t)(uintptr_t)c->d_mbox.get();
     b.device = c->device;
     b.nb_total = (int32_t)nb_total;
     const int nnb = (int)c->h_nb_rank.size();
@@ -554,13 +552,9 @@ int comm_mailbox_import(Ctx* c, int32_t nblobs, const void* blobs) {
             tab[p * 4 + 3] = bq.nb_total;
         }
     }
-    if (c->d_mr_tab) (void)hipFree(c->d_mr_tab);
-    c->d_mr_tab = nullptr;
-    FEMCY_HIP(dmalloc(&c->d_mr_tab, tab.size() * sizeof(int32_t)));
-    FEMCY_HIP(hipMemcpy(c->d_mr_tab, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    if (c->d_peer_tab) (void)hipFree(c->d_peer_tab);
-    c->d_peer_tab = nullptr;
-    FEMCY_HIP(dmalloc(&c->d_peer_tab, sizeof(unsigned long long*) * 16));
+    int rc;
+    if ((rc = dev_upload(c->d_mr_tab, tab))) return rc;
+    FEMCY_HIP(c->d_peer_tab.alloc(sizeof(unsigned long long*) * 16));
     FEMCY_HIP(hipMemcpy(c->d_peer_tab, c->h_peer_mbox.data(), sizeof(unsigned long long*) * R, hipMemcpyHostToDevice));
     c->persist_multi_local = ok;
     return FEMCY_OK;
@@ -586,12 +580,6 @@ int comm_persist_agree(Ctx* c, int32_t* enabled) {
 int comm_destroy(Ctx* c) {
     for (void* q : c->ipc_opened) (void)hipIpcCloseMemHandle(q);
     c->ipc_opened.clear();
-    if (c->d_mbox) (void)hipFree(c->d_mbox);
-    if (c->d_mr_tab) (void)hipFree(c->d_mr_tab);
-    if (c->d_peer_tab) (void)hipFree(c->d_peer_tab);
-    c->d_mbox = nullptr;
-    c->d_mr_tab = nullptr;
-    c->d_peer_tab = nullptr;
     c->persist_multi = c->persist_multi_local = false;
     if (c->comm && c->comm_local) {
         LocalGroup* g = (LocalGroup*)c->comm;

@@ -78,35 +78,84 @@ inline hipError_t dmalloc(T** p, size_t bytes) {
     return dmalloc(reinterpret_cast<void**>(p), bytes);
 }
 
-// Move-only owner of one device allocation (through dmalloc): the members of the objects a context hands out by id (Ctx::
-// DofSet ... Mass) and the scratch of the calls that create them.  The memory is released when the owner goes, so whoever
-// drops one while kernels may still read it synchronises the stream first.
+// Move-only owner of one device allocation: every device buffer of the backend is one (the members of Ctx, of the objects
+// it hands out by id, of the direct solver's state, and the scratch of single calls).  The memory is released when the
+// owner goes or is given a new allocation, so whoever drops one while kernels may still read it synchronises the stream
+// first (femcy_ctx_destroy states the order for a whole context).  It reads as the pointer it owns -- kernel arguments,
+// arithmetic, null tests; where a type is deduced from the argument (hipExtLaunchKernelGGL, ?: against nullptr,
+// reinterpret_cast) say get().  A failed allocation leaves it null with capacity 0, never the address it held before.
 template <class T>
 class DevBuf {
     T* p_ = nullptr;
+    size_t cap_ = 0;   // bytes
 
 public:
     DevBuf() = default;
-    DevBuf(DevBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DevBuf(DevBuf&& o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr, o.cap_ = 0; }
     DevBuf& operator=(DevBuf&& o) noexcept {
         if (this != &o) {
             reset();
-            p_ = o.p_;
-            o.p_ = nullptr;
+            p_ = o.p_, cap_ = o.cap_;
+            o.p_ = nullptr, o.cap_ = 0;
         }
         return *this;
     }
     ~DevBuf() { reset(); }
     void reset() {
         if (p_) (void)hipFree(p_);
-        p_ = nullptr;
+        p_ = nullptr, cap_ = 0;
     }
     hipError_t alloc(size_t bytes) {
         reset();
-        return dmalloc(&p_, bytes);
+        const hipError_t e = dmalloc(&p_, bytes);
+        if (e != hipSuccess) p_ = nullptr;
+        else cap_ = bytes;
+        return e;
+    }
+    // a new allocation (the contents go) only if the buffer holds fewer than `bytes`; *grew says which it was
+    hipError_t grow(size_t bytes, bool* grew = nullptr) {
+        const bool g = !p_ || bytes > cap_;
+        if (grew) *grew = g;
+        return g ? alloc(bytes) : hipSuccess;
+    }
+    // take over an allocation of `bytes` that did not come from dmalloc (hipFree releases it all the same)
+    void adopt(T* p, size_t bytes) {
+        reset();
+        p_ = p, cap_ = p ? bytes : 0;
     }
     T* get() const { return p_; }
+    size_t capacity() const { return cap_; }
+    operator T*() const { return p_; }
+    T* operator->() const { return p_; }
 };
+
+// The two ways device memory is obtained.  dev_alloc: `count` elements (at least one), anew, or with `grew` only if the
+// buffer is too small (*grew: whether it was); `zero` fills what was allocated with zeros, landed on return (dfill_sync).
+// dev_upload: a new buffer holding `bytes` of host memory.  After a failure the buffer is null.  An allocation that fails is
+// FEMCY_ENOMEM with the text below, or `nomem` for the sites that have always reported it as a HIP error.
+template <class T>
+inline int dev_alloc(DevBuf<T>& d, size_t count, bool zero = true, bool* grew = nullptr, int nomem = FEMCY_ENOMEM) {
+    const size_t bytes = (count ? count : 1) * sizeof(T);
+    bool fresh = true;
+    const hipError_t e = grew ? d.grow(bytes, &fresh) : d.alloc(bytes);
+    if (grew) *grew = fresh;
+    if (e != hipSuccess) {
+        set_error("dmalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
+        return nomem;
+    }
+    if (zero && fresh) FEMCY_HIP(dfill_sync(d.get(), 0, bytes));
+    return FEMCY_OK;
+}
+template <class T>
+inline int dev_upload(DevBuf<T>& d, const void* h, size_t bytes) {
+    FEMCY_HIP(d.alloc(bytes > 8 ? bytes : 8));
+    if (bytes) FEMCY_HIP(hipMemcpy(d.get(), h, bytes, hipMemcpyHostToDevice));
+    return FEMCY_OK;
+}
+template <class T>
+inline int dev_upload(DevBuf<T>& d, const std::vector<T>& h) {
+    return dev_upload(d, h.data(), h.size() * sizeof(T));
+}
 
 // FEMCY_TUNE_PAIRS default: XCD-contiguous (1) + 8 rows per wave (2) + Morton chunk order (32) + 3 chunks per wave (128):
 // 113-115 us on the 1 M-DOF CPE8 beam against 126 with all bits clear (profiles/r06_asm_cpe8_knobs.txt)
@@ -165,11 +214,11 @@ struct Ctx {
     int32_t nn = 0, dm = 0, ne = 0, npe = 0, nGP = 0, voigt = 0, s = 0;
     int64_t n = 0;
     std::vector<int32_t> h_elems;
-    double* d_nodes = nullptr;
-    int32_t* d_elems = nullptr;
-    double* d_dN = nullptr;
-    double* d_w = nullptr;
-    double* d_C = nullptr;
+    DevBuf<double> d_nodes;
+    DevBuf<int32_t> d_elems;
+    DevBuf<double> d_dN;
+    DevBuf<double> d_w;
+    DevBuf<double> d_C;
     int32_t mat_kind = -1;
     double mat_params[4] = {0, 0, 0, 0};
     double h_C[36] = {0};             // host copy of C (the consistent tangent reads lambda, mu from it)
@@ -180,7 +229,7 @@ struct Ctx {
 
     // ---- blocked SELL-64 matrix (lane = node, diagonal block in slot 0)
     int32_t nslices = 0;
-    int32_t* d_asm_order = nullptr;   // row-centric assembly (rows4): slices by decreasing work (workgroup b takes entry b)
+    DevBuf<int32_t> d_asm_order;   // row-centric assembly (rows4): slices by decreasing work (workgroup b takes entry b)
     XcdRanges xcd{};                  // SpMV: slice range per XCD
     int32_t spmv_grid = 0;            // 8 * max blocks per XCD
     int32_t spmv_wps = 1;             // wavefronts per slice (1, 2 or 4)
@@ -195,68 +244,67 @@ struct Ctx {
     int32_t spmv_cap_auto = 256;      // spmv_split: 512 for long ranges of a large matrix, else 256
     int32_t opt_spmv_rot = -1;        // FEMCY_TUNE_SPMV_ROT: -1 = by the spread of the row lengths (spmv_split), 64 = balanced lists
     int32_t spmv_rot = 0;             // rotation of the product's rounds against each other (k_spmv), 0 = none
-    int32_t* d_spmv_perm = nullptr;   // [8][spmv_perm_rounds][workgroups per XCD] balanced task lists (spmv_split), or nullptr
+    DevBuf<int32_t> d_spmv_perm;   // [8][spmv_perm_rounds][workgroups per XCD] balanced task lists (spmv_split), or nullptr
     int32_t spmv_perm_rounds = 0;
     int64_t stored_rows = 0;          // sum over slices of slice_len (in block rows of 64 lanes)
     int64_t nnzb = 0;
     int32_t max_row_blocks = 0, max_node_elems = 0;
     std::vector<int32_t> h_slice_len, h_rowlen, h_bcol, h_pos;
     std::vector<int64_t> h_slice_off;
-    int32_t* d_slice_len = nullptr;
-    int64_t* d_slice_off = nullptr;
-    int32_t* d_rowlen = nullptr;      // [nn] blocks per node (indexed by node)
-    int32_t* d_pos = nullptr;         // [nn] node -> storage position (slice*64 + lane): SELL-C-sigma row order
-    int32_t* d_node_of = nullptr;     // [nslices*64] storage position -> node, -1 for padding lanes
+    DevBuf<int32_t> d_slice_len;
+    DevBuf<int64_t> d_slice_off;
+    DevBuf<int32_t> d_rowlen;      // [nn] blocks per node (indexed by node)
+    DevBuf<int32_t> d_pos;         // [nn] node -> storage position (slice*64 + lane): SELL-C-sigma row order
+    DevBuf<int32_t> d_node_of;     // [nslices*64] storage position -> node, -1 for padding lanes
     int32_t sell_sigma = 4096;        // sorting window (nodes); 64 = natural order.  (32768 measured -1 % ... +1 % per PCG
                                       // iteration inside bench.py on the C3D4 and C3D10 plates: no reason to move it)
-    int32_t* d_bcol = nullptr;        // [stored_rows*64]
-    double* d_Kvals = nullptr;        // [stored_rows*dm*dm*64]
-    uint16_t* d_slotj = nullptr;      // [ne*npe*npe] element-local (a,b) -> slot j in row of node a
-    int32_t* d_ctr_ptr = nullptr;     // [stored_rows*64+1] contributions per stored block
-    int32_t* d_ctr = nullptr;         // [ne*npe*npe] packed (e*npe+la)*npe+lb
-    int32_t* d_tpos = nullptr;        // [stored_rows*64] position of the transposed block (b,a) if a < b; p on the
+    DevBuf<int32_t> d_bcol;        // [stored_rows*64]
+    DevBuf<double> d_Kvals;        // [stored_rows*dm*dm*64]
+    DevBuf<uint16_t> d_slotj;      // [ne*npe*npe] element-local (a,b) -> slot j in row of node a
+    DevBuf<int32_t> d_ctr_ptr;     // [stored_rows*64+1] contributions per stored block
+    DevBuf<int32_t> d_ctr;         // [ne*npe*npe] packed (e*npe+la)*npe+lb
+    DevBuf<int32_t> d_tpos;        // [stored_rows*64] position of the transposed block (b,a) if a < b; p on the
                                       // diagonal; -2 if a > b (the mirror lane stores it); -1 padding
-    int32_t* d_ne_ptr = nullptr;      // [nn+1] node -> incident elements
-    int32_t* d_ne_idx = nullptr;      // [ne*npe] packed e*npe+la
+    DevBuf<int32_t> d_ne_ptr;      // [nn+1] node -> incident elements
+    DevBuf<int32_t> d_ne_idx;      // [ne*npe] packed e*npe+la
     // pair lists of FEMCY_ASM_PAIRS (pattern.cpp: ensure_pairs, built on first use): per chunk of 16 (or 8) consecutive storage
     // positions the (row, incident element) pairs in (row, ascending element) order -- code e*npe+la and row inside the chunk;
     // 3-D: in step order, the s-th element of every row of the chunk, padded to whole steps
     std::vector<int32_t> h_node_of, h_ne_ptr, h_ne_idx;   // what they are built from (build_pattern: PAIRS families only)
-    int32_t* d_pr_ptr = nullptr;      // PairBatch descriptors (32 B) in PROCESSING order
-    int32_t* d_pr_unit = nullptr;     // [units + 1] first batch of every wavefront's unit of chunks
-    int32_t* d_pr_code = nullptr;     // [ne*npe + 64] row inside the chunk << 27 | e*npe+la
+    DevBuf<int32_t> d_pr_ptr;      // PairBatch descriptors (32 B) in PROCESSING order
+    DevBuf<int32_t> d_pr_unit;     // [units + 1] first batch of every wavefront's unit of chunks
+    DevBuf<int32_t> d_pr_code;     // [ne*npe + 64] row inside the chunk << 27 | e*npe+la
     int64_t pairs_serial = -1;        // pattern_serial * 64 + rows per chunk the lists were built for
     int tune_pairs = FEMCY_PAIRS_DEFAULT;   // FEMCY_TUNE_PAIRS (kernels_assembly.hip)
 
     // ---- Gauss-point fields
-    double* d_dsdx = nullptr;
-    double* d_vol = nullptr;
-    double* d_F = nullptr;
-    double* d_sigma = nullptr;
-    double* d_strain = nullptr;
-    double* d_mises = nullptr;
-    double* d_energy = nullptr;
-    double* d_fe = nullptr;           // [ne][npe][dm] per-element nodal forces of the last femcy_internal_force
+    DevBuf<double> d_dsdx;
+    DevBuf<double> d_vol;
+    DevBuf<double> d_F;
+    DevBuf<double> d_sigma;
+    DevBuf<double> d_strain;
+    DevBuf<double> d_mises;
+    DevBuf<double> d_energy;
+    DevBuf<double> d_fe;           // [ne][npe][dm] per-element nodal forces of the last femcy_internal_force
     // The force evaluation of a Newton residual does not store F and sigma (at 1 M C3D4 they are 143 of the 334 MB the
     // element pass would write, and nothing on the solve path reads them).  The reference's post-processing reads
     // "the stress of the last force evaluation", so that state is kept as a copy of the displacement it was made
     // with (8 n bytes) and F / sigma are recomputed from it when somebody asks (ensure_gp_stress).
     bool gp_lazy = false;
-    double* d_u_lazy = nullptr;
+    DevBuf<double> d_u_lazy;
 
     // ---- vectors
-    double* d_vec[FEMCY_VEC_COUNT] = {nullptr};
-    double *d_r = nullptr, *d_d = nullptr, *d_M = nullptr, *d_Ad = nullptr;
-    double* d_part1 = nullptr;        // [MAX_PARTIALS] d.Ad partials (SpMV launch)
-    double* d_part2 = nullptr;        // [2*MAX_PARTIALS] (r.M.r, max|r|) partials
-    PcgState* d_state = nullptr;
+    DevBuf<double> d_vec[FEMCY_VEC_COUNT];
+    DevBuf<double> d_r, d_d, d_M, d_Ad;
+    DevBuf<double> d_part1;        // [MAX_PARTIALS] d.Ad partials (SpMV launch)
+    DevBuf<double> d_part2;        // [2*MAX_PARTIALS] (r.M.r, max|r|) partials
+    DevBuf<PcgState> d_state;
     PcgState* h_state = nullptr;      // pinned
     char* h_stage = nullptr;          // pinned staging area for small host -> device payloads (stage_h2d)
     size_t stage_cap = 0, stage_used = 0;
     double* h_scalar = nullptr;       // pinned scratch for reductions
-    int32_t* d_idx_scratch = nullptr;
-    double* d_val_scratch = nullptr;
-    int64_t scratch_cap = 0;
+    DevBuf<int32_t> d_idx_scratch;
+    DevBuf<double> d_val_scratch;
 
     // ---- hipGraph of one poll-burst of PCG iterations (single rank, timing off)
     hipGraphExec_t pcg_graph = nullptr;
@@ -283,34 +331,30 @@ struct Ctx {
     bool small_failed = false;        // the same for k_pcg_small
     int opt_skip_occupancy = 0;       // FEMCY_TUNE_SKIP_OCCUPANCY_CHECK
     uint32_t barrier_spin_limit = 1u << 20;   // polls (s_sleep 1 each, ~0.3 us) before a grid barrier gives up: ~0.5 s
-    int32_t* d_persist_assign = nullptr;   // [waves][SPW] slices of each wave (LPT-balanced per XCD range), -1 = none
+    DevBuf<int32_t> d_persist_assign;   // [waves][SPW] slices of each wave (LPT-balanced per XCD range), -1 = none
     std::vector<int64_t> persist_assign_key;
     int64_t pattern_serial = 0;       // bumped by femcy_build_pattern
-    double* d_persist = nullptr;      // d double buffer, partials, granules, barrier counters
-    int64_t persist_cap = 0;
+    DevBuf<double> d_persist;      // d double buffer, partials, granules, barrier counters
     // ---- three-launch PCG with its vectors in storage order (single rank)
-    int32_t* d_bcolp = nullptr;       // block columns as storage positions (PCG with its vectors in storage order)
+    DevBuf<int32_t> d_bcolp;       // block columns as storage positions (PCG with its vectors in storage order)
     int64_t bcolp_serial = -1;
     int opt_pos_space = 1;            // FEMCY_OPT_PCG_STORAGE_ORDER: the three-kernel PCG of a single rank keeps r, d, M, Ad, x
                                       // in storage order (gathers of neighbouring lanes then hit neighbouring addresses)
-    double* d_posb = nullptr;         // right-hand side / solution in storage order
-    double* d_posx = nullptr;
-    int64_t pos_cap = 0;
+    DevBuf<double> d_posb;         // right-hand side / solution in storage order
+    DevBuf<double> d_posx;
     int opt_node_order = 1;           // FEMCY_OPT_NODE_ORDER: 0 = rows sorted inside windows of the caller's numbering,
                                       // 1 (default) = inside windows of the best of a few coordinate orders if it beats the
                                       // caller's numbering by 10 % (measured on the pattern), 2 + k = forced: coordinate order k
     int node_order_used = 0;          // 0 natural, 1 + k = coordinate order k (femcy_pattern_info)
     double node_order_cost[8] = {0};  // mean 128-byte lines per wave gather, natural first (diagnostics)
     std::vector<double> h_nodes;      // host copy of the coordinates (femcy_set_mesh) for the ordering
-    char* d_probe = nullptr;          // femcy_probe_stream's buffer
-    int64_t probe_cap = 0;
+    DevBuf<char> d_probe;          // femcy_probe_stream's buffer
     // ---- one-launch PCG for small systems (k_pcg_small)
     int opt_small_rr = -1;            // test knob 108: block rows per wave of the small-system PCG kept in registers
     int opt_small = 1;                // FEMCY_OPT_PCG_SMALL
     int small_max_lds = 65536;        // LDS a workgroup may allocate (device attribute, femcy_ctx_create)
     int small_max_wg = 128;           // workgroups that are certainly co-resident at one per CU
-    double* d_small = nullptr;        // Ad double buffer, d.Ad partials, barrier counter
-    int64_t small_cap = 0;
+    DevBuf<double> d_small;        // Ad double buffer, d.Ad partials, barrier counter
     int ew_cap = 512;                 // FEMCY_OPT_EW_GRID
 
     // ---- device-resident DOF lists of *Boundary blocks
@@ -382,22 +426,21 @@ struct Ctx {
     bool comm_local = false;
     uint64_t comm_token = 0;
     int32_t niface_local = 0, niface_global = 0;
-    int32_t* d_iface_dof = nullptr;
-    int32_t* d_iface_slot = nullptr;
-    int32_t* d_slot2dof = nullptr;    // [niface_global] local DOF of each global interface slot, -1 if not held
-    uint8_t* d_owner = nullptr;
-    double* d_commbuf = nullptr;      // [niface_global + 8]
-    double* d_gather = nullptr;       // [nranks*2]
+    DevBuf<int32_t> d_iface_dof;
+    DevBuf<int32_t> d_iface_slot;
+    DevBuf<int32_t> d_slot2dof;    // [niface_global] local DOF of each global interface slot, -1 if not held
+    DevBuf<uint8_t> d_owner;
+    DevBuf<double> d_commbuf;      // [niface_global + 8]
+    DevBuf<double> d_gather;       // [nranks*2]
 
     // ---- persistent PCG across ranks (kernels_pcg_persist.hip "persistent PCG across ranks"): this rank's mailbox,
     // the peers' mailboxes as mapped on this device, the per-position interface table
-    unsigned long long* d_mbox = nullptr;
-    int64_t mbox_words = 0;
+    DevBuf<unsigned long long> d_mbox;
     bool mbox_finegrained = false;
     std::vector<unsigned long long*> h_peer_mbox;   // [nranks], own entry = d_mbox
     std::vector<void*> ipc_opened;                  // mappings to close
-    unsigned long long** d_peer_tab = nullptr;      // device copy of h_peer_mbox
-    int32_t* d_mr_tab = nullptr;                    // [nslices * 64][4]
+    DevBuf<unsigned long long*> d_peer_tab;         // device copy of h_peer_mbox
+    DevBuf<int32_t> d_mr_tab;                    // [nslices * 64][4]
     std::vector<int32_t> h_nb_dofs;                 // host copy of the neighbour DOF lists
     bool persist_multi_local = false;               // this rank could take the path
     bool persist_multi = false;                     // ... and every rank agreed (femcy_comm_persist_agree)
@@ -413,17 +456,17 @@ struct Ctx {
     int opt_overlap = 1;              // FEMCY_OPT_OVERLAP
     bool split_ready = false;
     std::vector<int32_t> h_iface_dof; // host copy of the local interface DOFs (femcy_comm_init)
-    int32_t* d_split_list = nullptr;  // [nslices] slices holding an interface node first, then the others
+    DevBuf<int32_t> d_split_list;  // [nslices] slices holding an interface node first, then the others
     int32_t n_if_slices = 0;
 
     // ---- neighbour exchange (femcy_comm_set_neighbours): the alternative to the packed all-reduce
     int exchange = 0;                 // FEMCY_OPT_EXCHANGE: 0 packed all-reduce, 1 neighbour send/recv
     std::vector<int32_t> h_nb_rank, h_nb_ptr;   // neighbours (ascending) and their segments of the send / recv buffers
-    int32_t* d_nb_dofs = nullptr;     // [nb_total] local DOF of every send entry
-    double* d_nb_send = nullptr;      // [nb_total]
-    double* d_nb_recv = nullptr;      // [nb_total]
-    int32_t* d_if_ptr = nullptr;      // [niface_local+1] per local interface DOF (order of d_iface_dof): its
-    int32_t* d_if_src = nullptr;      //   contributions in ascending rank order; src = recv index, -1 = own value
+    DevBuf<int32_t> d_nb_dofs;     // [nb_total] local DOF of every send entry
+    DevBuf<double> d_nb_send;      // [nb_total]
+    DevBuf<double> d_nb_recv;      // [nb_total]
+    DevBuf<int32_t> d_if_ptr;      // [niface_local+1] per local interface DOF (order of d_iface_dof): its
+    DevBuf<int32_t> d_if_src;      //   contributions in ascending rank order; src = recv index, -1 = own value
 };
 
 template <>

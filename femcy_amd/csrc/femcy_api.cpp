@@ -23,37 +23,8 @@ void set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
-template <class T>
-static int dev_alloc(T** p, size_t count, bool zero = true) {
-    if (*p) {
-        (void)hipFree(*p);
-        *p = nullptr;
-    }
-    size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-    hipError_t e = dmalloc(p, bytes);
-    if (e != hipSuccess) {
-        set_error("dmalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
-        return FEMCY_ENOMEM;
-    }
-    if (zero) FEMCY_HIP(dfill_sync(*p, 0, bytes));       // landed on return: ctx.hpp
-    return FEMCY_OK;
-}
-
-template <class T>
-static void dev_free(T** p) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-}
-
-// a new device buffer holding `bytes` of host memory
-template <class T>
-static int to_device(DevBuf<T>& d, const void* h, size_t bytes) {
-    FEMCY_HIP(d.alloc(std::max<size_t>(bytes, 8)));
-    if (bytes) FEMCY_HIP(hipMemcpy(d.get(), h, bytes, hipMemcpyHostToDevice));
-    return FEMCY_OK;
-}
-
-// the objects a context hands out by id; their buffers go with them (DevBuf), so the streams are drained by the caller
+// the objects a context hands out by id, dropped when the mesh they were made on goes; their buffers go with them (DevBuf),
+// so the streams are drained by the caller
 static void drop_objects(Ctx* c) {
     c->dofsets.clear();
     c->loadsets.clear();
@@ -85,13 +56,11 @@ static int apply_load(Ctx* c, const char* who, int rhs_vec, bool add, Apply&& ap
 }
 
 int ensure_scratch(Ctx* c, int64_t k) {
-    if (k <= c->scratch_cap) return FEMCY_OK;
-    int64_t cap = std::max<int64_t>(k, 1024);
+    const size_t cap = (size_t)std::max<int64_t>(k, 1024);
+    bool grew;
     int rc;
-    if ((rc = dev_alloc(&c->d_idx_scratch, (size_t)cap, false))) return rc;
-    if ((rc = dev_alloc(&c->d_val_scratch, (size_t)cap, false))) return rc;
-    c->scratch_cap = cap;
-    return FEMCY_OK;
+    if ((rc = dev_alloc(c->d_idx_scratch, cap, false, &grew))) return rc;
+    return dev_alloc(c->d_val_scratch, cap, false, &grew);
 }
 
 // Small host -> device payloads (the values of a prescribed-displacement block, index lists of a scatter) go through a
@@ -254,8 +223,8 @@ int femcy_ctx_create(int device, femcy_ctx** out) {
     }
     int rc = FEMCY_OK;
     // + a zero slot behind each partial array (read by out-of-range lanes of the PCG kernels, never written)
-    if ((rc = dev_alloc(&c->d_part1, (size_t)MAX_PARTIALS + 8)) || (rc = dev_alloc(&c->d_part2, (size_t)2 * MAX_PARTIALS + 8)) ||
-        (rc = dev_alloc(&c->d_state, 1))) {
+    if ((rc = dev_alloc(c->d_part1, (size_t)MAX_PARTIALS + 8)) || (rc = dev_alloc(c->d_part2, (size_t)2 * MAX_PARTIALS + 8)) ||
+        (rc = dev_alloc(c->d_state, 1))) {
         delete ctx;
         return rc;
     }
@@ -289,44 +258,23 @@ int femcy_ctx_destroy(femcy_ctx* ctx) {
     comm_destroy(c);
     pcg_graph_reset(c);
     direct_release(c);
-    dev_free(&c->d_nodes); dev_free(&c->d_elems); dev_free(&c->d_dN); dev_free(&c->d_w); dev_free(&c->d_C);
-    dev_free(&c->d_slice_len); dev_free(&c->d_slice_off); dev_free(&c->d_rowlen); dev_free(&c->d_bcol);
-    dev_free(&c->d_pos); dev_free(&c->d_node_of);
-    dev_free(&c->d_Kvals); dev_free(&c->d_slotj); dev_free(&c->d_ctr_ptr); dev_free(&c->d_ctr); dev_free(&c->d_tpos);
-    dev_free(&c->d_ne_ptr); dev_free(&c->d_ne_idx); dev_free(&c->d_asm_order); dev_free(&c->d_spmv_perm);
-    dev_free(&c->d_pr_ptr); dev_free(&c->d_pr_unit); dev_free(&c->d_pr_code);
-    dev_free(&c->d_dsdx); dev_free(&c->d_vol); dev_free(&c->d_F); dev_free(&c->d_sigma);
-    dev_free(&c->d_strain); dev_free(&c->d_mises); dev_free(&c->d_energy); dev_free(&c->d_fe);
-    for (auto& v : c->d_vec) dev_free(&v);
-    dev_free(&c->d_r); dev_free(&c->d_d); dev_free(&c->d_M); dev_free(&c->d_Ad); dev_free(&c->d_u_lazy);
-    dev_free(&c->d_part1); dev_free(&c->d_part2); dev_free(&c->d_state);
-    dev_free(&c->d_idx_scratch); dev_free(&c->d_val_scratch);
-    dev_free(&c->d_iface_dof); dev_free(&c->d_iface_slot); dev_free(&c->d_slot2dof); dev_free(&c->d_owner); dev_free(&c->d_commbuf);
-    dev_free(&c->d_gather);
-    dev_free(&c->d_nb_dofs); dev_free(&c->d_nb_send); dev_free(&c->d_nb_recv); dev_free(&c->d_if_ptr); dev_free(&c->d_if_src);
-    dev_free(&c->d_split_list);
-    dev_free(&c->d_small);
-    dev_free(&c->d_persist);
-    dev_free(&c->d_persist_assign);
-    dev_free(&c->d_bcolp);
-    dev_free(&c->d_posb); dev_free(&c->d_posx);
-    dev_free(&c->d_probe);
     if (c->ev_iface) (void)hipEventDestroy(c->ev_iface);
     if (c->ev_xchg) (void)hipEventDestroy(c->ev_xchg);
-    if (c->comm_stream) {
-        (void)hipStreamSynchronize(c->comm_stream);
-        (void)hipStreamDestroy(c->comm_stream);
-    }
     if (c->h_state) (void)hipHostFree(c->h_state);
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     if (c->h_scalar) (void)hipHostFree(c->h_scalar);
-    drop_objects(c);       // here, with the device current and every stream drained: not left to `delete ctx`
     for (auto& p : c->ev_pool) {
         (void)hipEventDestroy(p.a);
         (void)hipEventDestroy(p.b);
     }
-    if (c->stream) (void)hipStreamDestroy(c->stream);
+    // The one place that orders the device frees of a context.  Every buffer is a DevBuf -- a member of Ctx or of an object
+    // it handed out by id -- and all of them go HERE, with `delete`: the context's device current, both streams drained,
+    // after comm_destroy / pcg_graph_reset / direct_release (the peers' mappings, the graph and the factorisation that read
+    // them are gone), and before either stream is destroyed -- which is why the stream handles outlive the context.
+    const hipStream_t stream = c->stream, comm_stream = c->comm_stream;
     delete ctx;
+    if (comm_stream) (void)hipStreamDestroy(comm_stream);
+    if (stream) (void)hipStreamDestroy(stream);
     return FEMCY_OK;
 }
 
@@ -533,18 +481,18 @@ int femcy_set_mesh(femcy_ctx* ctx, int32_t nn, int32_t dm, const double* nodes, 
     c->h_elems.assign(elems, elems + (int64_t)ne * npe);
     c->h_nodes.assign(nodes, nodes + (int64_t)nn * dm);
     int rc;
-    if ((rc = dev_alloc(&c->d_nodes, (size_t)nn * dm, false))) return rc;
-    if ((rc = dev_alloc(&c->d_elems, (size_t)ne * npe, false))) return rc;
+    if ((rc = dev_alloc(c->d_nodes, (size_t)nn * dm, false))) return rc;
+    if ((rc = dev_alloc(c->d_elems, (size_t)ne * npe, false))) return rc;
     FEMCY_HIP(hipMemcpy(c->d_nodes, nodes, sizeof(double) * nn * dm, hipMemcpyHostToDevice));
     FEMCY_HIP(hipMemcpy(c->d_elems, elems, sizeof(int32_t) * (size_t)ne * npe, hipMemcpyHostToDevice));
     // vectors are padded (zero) so that double2 kernels may touch one element past n
     const size_t nalloc = (size_t)((c->n + 63) / 64 * 64 + 64);
     for (auto& v : c->d_vec)
-        if ((rc = dev_alloc(&v, nalloc))) return rc;
+        if ((rc = dev_alloc(v, nalloc))) return rc;
     // the PCG work vectors also hold the storage-order form (whole slices of 64 nodes)
     const size_t palloc = std::max(nalloc, (size_t)((int64_t)(nn + SLICE - 1) / SLICE * SLICE * dm + 64));
-    if ((rc = dev_alloc(&c->d_r, palloc)) || (rc = dev_alloc(&c->d_d, palloc)) || (rc = dev_alloc(&c->d_M, palloc)) ||
-        (rc = dev_alloc(&c->d_Ad, palloc)) || (rc = dev_alloc(&c->d_u_lazy, nalloc)))
+    if ((rc = dev_alloc(c->d_r, palloc)) || (rc = dev_alloc(c->d_d, palloc)) || (rc = dev_alloc(c->d_M, palloc)) ||
+        (rc = dev_alloc(c->d_Ad, palloc)) || (rc = dev_alloc(c->d_u_lazy, nalloc)))
         return rc;
     c->gp_lazy = false;
     pcg_graph_reset(c);
@@ -574,16 +522,16 @@ int femcy_set_element(femcy_ctx* ctx, int32_t nGP, const double* dN, const doubl
         }
     c->s = (c->dm == 2) ? 3 : 6;
     int rc;
-    if ((rc = dev_alloc(&c->d_dN, (size_t)nGP * c->npe * c->dm, false))) return rc;
-    if ((rc = dev_alloc(&c->d_w, (size_t)nGP, false))) return rc;
+    if ((rc = dev_alloc(c->d_dN, (size_t)nGP * c->npe * c->dm, false))) return rc;
+    if ((rc = dev_alloc(c->d_w, (size_t)nGP, false))) return rc;
     FEMCY_HIP(hipMemcpy(c->d_dN, dN, sizeof(double) * nGP * c->npe * c->dm, hipMemcpyHostToDevice));
     FEMCY_HIP(hipMemcpy(c->d_w, w, sizeof(double) * nGP, hipMemcpyHostToDevice));
     const size_t ngp = (size_t)c->ne * nGP;
-    if ((rc = dev_alloc(&c->d_dsdx, ngp * c->npe * c->dm)) || (rc = dev_alloc(&c->d_vol, ngp)) ||
-        (rc = dev_alloc(&c->d_F, ngp * c->dm * c->dm)) || (rc = dev_alloc(&c->d_sigma, ngp * c->dm * c->dm)) ||
-        (rc = dev_alloc(&c->d_strain, ngp * c->dm * c->dm)) || (rc = dev_alloc(&c->d_mises, ngp)) ||
-        (rc = dev_alloc(&c->d_fe, (size_t)c->ne * c->npe * c->dm)) ||
-        (rc = dev_alloc(&c->d_energy, ngp)))
+    if ((rc = dev_alloc(c->d_dsdx, ngp * c->npe * c->dm)) || (rc = dev_alloc(c->d_vol, ngp)) ||
+        (rc = dev_alloc(c->d_F, ngp * c->dm * c->dm)) || (rc = dev_alloc(c->d_sigma, ngp * c->dm * c->dm)) ||
+        (rc = dev_alloc(c->d_strain, ngp * c->dm * c->dm)) || (rc = dev_alloc(c->d_mises, ngp)) ||
+        (rc = dev_alloc(c->d_fe, (size_t)c->ne * c->npe * c->dm)) ||
+        (rc = dev_alloc(c->d_energy, ngp)))
         return rc;
     c->have_element = true;
     c->post_small = false;
@@ -603,7 +551,7 @@ int femcy_set_material(femcy_ctx* ctx, int32_t kind, const double* C, const doub
     FEMCY_HIP(hipStreamSynchronize(c->stream));
     const int s = (c->dm == 2) ? 3 : 6;
     int rc;
-    if ((rc = dev_alloc(&c->d_C, (size_t)s * s, false))) return rc;
+    if ((rc = dev_alloc(c->d_C, (size_t)s * s, false))) return rc;
     FEMCY_HIP(hipMemcpy(c->d_C, C, sizeof(double) * s * s, hipMemcpyHostToDevice));
     for (int i = 0; i < s * s; ++i) c->h_C[i] = C[i];
     c->mat_kind = kind;
@@ -934,16 +882,16 @@ int femcy_loadset_create(femcy_ctx* ctx, int32_t nft, int32_t nfn, int32_t nip, 
     ls.nft = nft; ls.nfn = nfn; ls.nip = nip; ls.nload = nload; ls.nnode = (int32_t)ld_node.size();
     int rc = FEMCY_OK;
     const size_t tip = (size_t)nft * nip;
-    if (!rc) rc = to_device(ls.d_ft_nodes, ft_nodes, sizeof(int32_t) * nft * nfn);
-    if (!rc) rc = to_device(ls.d_N, ft_N, sizeof(double) * tip * c->npe);
-    if (!rc) rc = to_device(ls.d_dN, ft_dN, sizeof(double) * tip * c->npe * c->dm);
-    if (!rc) rc = to_device(ls.d_normal, ft_normal, sizeof(double) * tip * c->dm);
-    if (!rc) rc = to_device(ls.d_weight, ft_weight, sizeof(double) * tip);
-    if (!rc) rc = to_device(ls.d_elem, load_elem, sizeof(int32_t) * nload);
-    if (!rc) rc = to_device(ls.d_ft, load_ft, sizeof(int32_t) * nload);
-    if (!rc) rc = to_device(ls.d_node, ld_node.data(), sizeof(int32_t) * ld_node.size());
-    if (!rc) rc = to_device(ls.d_ptr, ld_ptr.data(), sizeof(int32_t) * ld_ptr.size());
-    if (!rc) rc = to_device(ls.d_slot, order.data(), sizeof(int32_t) * nslot);
+    if (!rc) rc = dev_upload(ls.d_ft_nodes, ft_nodes, sizeof(int32_t) * nft * nfn);
+    if (!rc) rc = dev_upload(ls.d_N, ft_N, sizeof(double) * tip * c->npe);
+    if (!rc) rc = dev_upload(ls.d_dN, ft_dN, sizeof(double) * tip * c->npe * c->dm);
+    if (!rc) rc = dev_upload(ls.d_normal, ft_normal, sizeof(double) * tip * c->dm);
+    if (!rc) rc = dev_upload(ls.d_weight, ft_weight, sizeof(double) * tip);
+    if (!rc) rc = dev_upload(ls.d_elem, load_elem, sizeof(int32_t) * nload);
+    if (!rc) rc = dev_upload(ls.d_ft, load_ft, sizeof(int32_t) * nload);
+    if (!rc) rc = dev_upload(ls.d_node, ld_node.data(), sizeof(int32_t) * ld_node.size());
+    if (!rc) rc = dev_upload(ls.d_ptr, ld_ptr.data(), sizeof(int32_t) * ld_ptr.size());
+    if (!rc) rc = dev_upload(ls.d_slot, order.data(), sizeof(int32_t) * nslot);
     if (!rc && ls.d_contrib.alloc(std::max<size_t>(nslot, 1) * c->dm * sizeof(double)) != hipSuccess) rc = FEMCY_ENOMEM;
     if (!rc && ls.d_dir.alloc(3 * sizeof(double)) != hipSuccess) rc = FEMCY_ENOMEM;
     if (rc) {
@@ -986,8 +934,8 @@ int femcy_bodyload_create(femcy_ctx* ctx, const double* N, int32_t nsel, const i
     bl.nsel = sel_elems ? nsel : c->ne;
     DevBuf<double> d_N, d_we;      // the tables and the element records are scratch of this call
     DevBuf<uint8_t> d_mask;
-    int rc = to_device(d_N, N, sizeof(double) * c->nGP * c->npe);
-    if (!rc && sel_elems) rc = to_device(d_mask, mask.data(), mask.size());
+    int rc = dev_upload(d_N, N, sizeof(double) * c->nGP * c->npe);
+    if (!rc && sel_elems) rc = dev_upload(d_mask, mask.data(), mask.size());
     if (!rc && d_we.alloc(sizeof(double) * (size_t)c->ne * c->npe) != hipSuccess) rc = FEMCY_ENOMEM;
     if (!rc && bl.d_m.alloc(sizeof(double) * (size_t)c->nn) != hipSuccess) rc = FEMCY_ENOMEM;
     if (!rc) rc = launch_body_weights(c, d_N.get(), d_mask.get(), d_we.get(), bl.d_m.get());
@@ -1021,8 +969,8 @@ int femcy_thermal_create(femcy_ctx* ctx, const double* N, double alpha, const do
         for (int i = 0; i < DM * DM; ++i) th.ts.s[i] = alpha * s[i / DM][i % DM];
     });
     DevBuf<double> d_fe;           // the element records are scratch of this call
-    int rc = to_device(th.d_N, N, sizeof(double) * c->nGP * c->npe);
-    if (!rc) rc = to_device(th.d_dT, dT, sizeof(double) * (size_t)c->nn);
+    int rc = dev_upload(th.d_N, N, sizeof(double) * c->nGP * c->npe);
+    if (!rc) rc = dev_upload(th.d_dT, dT, sizeof(double) * (size_t)c->nn);
     if (!rc && d_fe.alloc(sizeof(double) * (size_t)c->ne * c->npe * c->dm) != hipSuccess) rc = FEMCY_ENOMEM;
     if (!rc && th.d_f.alloc(sizeof(double) * (size_t)c->n) != hipSuccess) rc = FEMCY_ENOMEM;
     if (!rc) rc = launch_thermal_force(c, th, d_fe.get());
@@ -1063,9 +1011,9 @@ int femcy_mass_create(femcy_ctx* ctx, int32_t nq, const double* Nq, const double
     Ctx::Mass ms;
     DevBuf<double> d_Nq, d_dNq, d_wq, d_vq;     // the tables and the element records are scratch of this call
     const size_t npos = (size_t)c->stored_rows * SLICE;
-    int rc = to_device(d_Nq, Nq, sizeof(double) * nq * c->npe);
-    if (!rc) rc = to_device(d_dNq, dNq, sizeof(double) * nq * c->npe * c->dm);
-    if (!rc) rc = to_device(d_wq, wq, sizeof(double) * nq);
+    int rc = dev_upload(d_Nq, Nq, sizeof(double) * nq * c->npe);
+    if (!rc) rc = dev_upload(d_dNq, dNq, sizeof(double) * nq * c->npe * c->dm);
+    if (!rc) rc = dev_upload(d_wq, wq, sizeof(double) * nq);
     if (!rc && d_vq.alloc(sizeof(double) * (size_t)c->ne * nq) != hipSuccess) rc = FEMCY_ENOMEM;
     if (!rc && ms.d_m.alloc(std::max<size_t>(sizeof(double) * npos, 8)) != hipSuccess) rc = FEMCY_ENOMEM;
     if (!rc) rc = launch_mass_blocks(c, nq, d_Nq.get(), d_dNq.get(), d_wq.get(), rho, d_vq.get(), ms.d_m.get());
@@ -1140,9 +1088,9 @@ int femcy_lumped_mass_create(femcy_ctx* ctx, int32_t nq, const double* Nq, const
     Ctx::LumpedMass lm;
     DevBuf<double> d_Nq, d_dNq, d_wq;           // the tables are scratch of this call
     DevBuf<double>& d_me = lm.d_me;             // the element shares stay: the element-by-element increment divides by them
-    int rc = to_device(d_Nq, Nq, sizeof(double) * nq * c->npe);
-    if (!rc) rc = to_device(d_dNq, dNq, sizeof(double) * nq * c->npe * c->dm);
-    if (!rc) rc = to_device(d_wq, wq, sizeof(double) * nq);
+    int rc = dev_upload(d_Nq, Nq, sizeof(double) * nq * c->npe);
+    if (!rc) rc = dev_upload(d_dNq, dNq, sizeof(double) * nq * c->npe * c->dm);
+    if (!rc) rc = dev_upload(d_wq, wq, sizeof(double) * nq);
     if (!rc && d_me.alloc(sizeof(double) * (size_t)c->ne * c->npe) != hipSuccess) rc = FEMCY_ENOMEM;
     if (!rc && lm.d_m.alloc(sizeof(double) * (size_t)c->nn) != hipSuccess) rc = FEMCY_ENOMEM;
     lm.rho = rho;                               // rho_0 of the bulk viscosity (femcy_explicit_set_damping)
@@ -1454,18 +1402,13 @@ int femcy_extrapolate(femcy_ctx* ctx, int gp_field, int comp, const double* E, d
         int rcl = ensure_gp_stress(c);
         if (rcl) return rcl;
     }
-    struct Tmp {   // freed on every return path
-        double* p = nullptr;
-        ~Tmp() {
-            if (p) (void)hipFree(p);
-        }
-    } tE, tout;
+    DevBuf<double> tE, tout;   // freed on every return path, behind the synchronisation below
     const size_t nE = (size_t)c->npe * c->nGP, nout = (size_t)c->ne * c->npe;
-    FEMCY_HIP(dmalloc(&tE.p, nE * sizeof(double)));
-    FEMCY_HIP(dmalloc(&tout.p, nout * sizeof(double)));
-    FEMCY_HIP(hipMemcpyAsync(tE.p, E, nE * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    int rc = launch_extrapolate(c, tE.p, field, width, comp, tout.p);
-    if (!rc) FEMCY_HIP(hipMemcpyAsync(out, tout.p, nout * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    FEMCY_HIP(tE.alloc(nE * sizeof(double)));
+    FEMCY_HIP(tout.alloc(nout * sizeof(double)));
+    FEMCY_HIP(hipMemcpyAsync(tE, E, nE * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    int rc = launch_extrapolate(c, tE, field, width, comp, tout);
+    if (!rc) FEMCY_HIP(hipMemcpyAsync(out, tout, nout * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     FEMCY_HIP(hipStreamSynchronize(c->stream));
     return rc;
 }
@@ -1649,18 +1592,18 @@ int femcy_comm_init(femcy_ctx* ctx, int32_t rank, int32_t nranks, const void* id
     c->niface_global = niface_global;
     c->h_iface_dof.assign(iface_local_dofs, iface_local_dofs + niface_local);
     c->split_ready = false;
-    if ((rc = dev_alloc(&c->d_iface_dof, (size_t)std::max(niface_local, 1), false))) return rc;
-    if ((rc = dev_alloc(&c->d_iface_slot, (size_t)std::max(niface_local, 1), false))) return rc;
-    if ((rc = dev_alloc(&c->d_owner, (size_t)c->n + 64))) return rc;
-    if ((rc = dev_alloc(&c->d_commbuf, (size_t)niface_global + 8))) return rc;
-    if ((rc = dev_alloc(&c->d_gather, (size_t)nranks * 2 + 2))) return rc;
+    if ((rc = dev_alloc(c->d_iface_dof, (size_t)std::max(niface_local, 1), false))) return rc;
+    if ((rc = dev_alloc(c->d_iface_slot, (size_t)std::max(niface_local, 1), false))) return rc;
+    if ((rc = dev_alloc(c->d_owner, (size_t)c->n + 64))) return rc;
+    if ((rc = dev_alloc(c->d_commbuf, (size_t)niface_global + 8))) return rc;
+    if ((rc = dev_alloc(c->d_gather, (size_t)nranks * 2 + 2))) return rc;
     {
         std::vector<int32_t> slot2dof((size_t)std::max(niface_global, 1), -1);
         for (int32_t i = 0; i < niface_local; ++i) {
             FEMCY_REQUIRE(slot2dof[iface_global_slot[i]] < 0, "interface slot %d listed twice", iface_global_slot[i]);
             slot2dof[iface_global_slot[i]] = iface_local_dofs[i];
         }
-        if ((rc = dev_alloc(&c->d_slot2dof, slot2dof.size(), false))) return rc;
+        if ((rc = dev_alloc(c->d_slot2dof, slot2dof.size(), false))) return rc;
         FEMCY_HIP(hipMemcpy(c->d_slot2dof, slot2dof.data(), sizeof(int32_t) * slot2dof.size(), hipMemcpyHostToDevice));
     }
     if (niface_local > 0) {
@@ -1720,10 +1663,10 @@ int femcy_comm_set_neighbours(femcy_ctx* ctx, int32_t nnb, const int32_t* nb_ran
         ptr[i + 1] = (int32_t)src.size();
     }
     int rc;
-    if ((rc = dev_alloc(&c->d_nb_dofs, (size_t)std::max(total, 1), false)) ||
-        (rc = dev_alloc(&c->d_nb_send, (size_t)std::max(total, 1))) ||
-        (rc = dev_alloc(&c->d_nb_recv, (size_t)std::max(total, 1))) || (rc = dev_alloc(&c->d_if_ptr, ptr.size(), false)) ||
-        (rc = dev_alloc(&c->d_if_src, std::max<size_t>(src.size(), 1), false)))
+    if ((rc = dev_alloc(c->d_nb_dofs, (size_t)std::max(total, 1), false)) ||
+        (rc = dev_alloc(c->d_nb_send, (size_t)std::max(total, 1))) ||
+        (rc = dev_alloc(c->d_nb_recv, (size_t)std::max(total, 1))) || (rc = dev_alloc(c->d_if_ptr, ptr.size(), false)) ||
+        (rc = dev_alloc(c->d_if_src, std::max<size_t>(src.size(), 1), false)))
         return rc;
     if (total) FEMCY_HIP(hipMemcpy(c->d_nb_dofs, nb_dofs, sizeof(int32_t) * total, hipMemcpyHostToDevice));
     FEMCY_HIP(hipMemcpy(c->d_if_ptr, ptr.data(), sizeof(int32_t) * ptr.size(), hipMemcpyHostToDevice));
@@ -1796,12 +1739,11 @@ int femcy_comm_tune(femcy_ctx* ctx, int32_t iters, int32_t* chosen, double* us) 
     double pack[3] = {t_us[0], t_us[1], same ? 0.0 : 1.0};
     std::vector<double> all((size_t)c->nranks * 3);
     FEMCY_HIP(hipMemcpy(c->d_commbuf, pack, sizeof(pack), hipMemcpyHostToDevice));
-    double* d_all = nullptr;
-    FEMCY_HIP(dmalloc(&d_all, sizeof(double) * all.size()));
+    DevBuf<double> d_all;
+    FEMCY_HIP(d_all.alloc(sizeof(double) * all.size()));
     rc = comm_allgather(c, c->d_commbuf, d_all, 3);
     if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = FEMCY_EHIP;
     if (!rc && hipMemcpy(all.data(), d_all, sizeof(double) * all.size(), hipMemcpyDeviceToHost) != hipSuccess) rc = FEMCY_EHIP;
-    (void)hipFree(d_all);
     if (rc) return rc;
     double m0 = 0.0, m1 = 0.0, bad = 0.0;
     for (int r = 0; r < c->nranks; ++r) {

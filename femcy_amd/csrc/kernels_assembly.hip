@@ -2077,7 +2077,7 @@ int launch_assemble(Ctx* c) {
             const int grid = ((nunits + 3) / 4 + 7) / 8 * 8;
 #define FEMCY_PAIRS_K(NPE_, NGP_, DM_, RPW_, DEPTH_, X_)                                                               \
     FEMCY_LDS_LAUNCH((k_assemble_pairs<NPE_, NGP_, DM_, RPW_, DEPTH_, X_>), grid, lds, nunits, c->max_row_blocks,      \
-                     c->d_pr_unit, (const PairBatch*)c->d_pr_ptr, c->d_pr_code, c->d_slotj, c->d_dsdx, c->d_vol,       \
+                     c->d_pr_unit, (const PairBatch*)c->d_pr_ptr.get(), c->d_pr_code, c->d_slotj, c->d_dsdx, c->d_vol,       \
                      sum_map<DM_>(c), c->d_Kvals)
 #define FEMCY_PAIRS_D(NPE_, NGP_, DM_, RPW_, X_)                                                                       \
     do {                                                                                                               \

@@ -35,6 +35,7 @@
 #include <unordered_map>
 #include "band_order.hpp"
 #include "ctx.hpp"
+#include "element_dispatch.hpp"
 
 namespace femcy {
 
@@ -54,21 +55,23 @@ constexpr int DIRECT_MFMA_MIN_TILES = 8, DIRECT_MFMA_VARIANT = 1;
 constexpr int DIRECT_OVERLAP_MIN_TILES = 24, DIRECT_OVERLAP_VARIANT = -1;
 constexpr int TS = NB * NB;     // doubles per tile
 
-struct DirectState {
+// the device buffers of a factorisation, apart so that release() drops them as one
+struct DirectBuffers {
+    DevBuf<int32_t> d_rank, d_node_at;
+    DevBuf<double> d_band, d_dfac;
+    DevBuf<double> d_sgn;         // [P * 32] the signs S
+    DevBuf<double> d_invd;        // [P * 32] 1 / l_kk
+    DevBuf<double> d_wb, d_wy, d_wx;
+    DevBuf<double> d_res, d_Kx;   // [n] caller's numbering: residual, K x
+    DevBuf<double> d_norms;       // max|res| (NaN if any entry is), max|b|
+    DevBuf<int32_t> d_flag;       // [0] 1 + first pivot that is zero / NaN, [1] negative pivots
+};
+
+struct DirectState : DirectBuffers {
     int64_t pattern_serial = -1;
     int64_t max_bytes = (int64_t)48 << 30;
     int32_t half_band_nodes = 0, bw = 0, T = 0, P = 0;
     int64_t band_tiles = 0;
-    int32_t* d_rank = nullptr;
-    int32_t* d_node_at = nullptr;
-    double* d_band = nullptr;
-    double* d_dfac = nullptr;
-    double* d_sgn = nullptr;      // [P * 32] the signs S
-    double* d_invd = nullptr;     // [P * 32] 1 / l_kk
-    double *d_wb = nullptr, *d_wy = nullptr, *d_wx = nullptr;
-    double *d_res = nullptr, *d_Kx = nullptr;   // [n] caller's numbering: residual, K x
-    double* d_norms = nullptr;    // max|res| (NaN if any entry is), max|b|
-    int32_t* d_flag = nullptr;    // [0] 1 + first pivot that is zero / NaN, [1] negative pivots
     char* h_back = nullptr;       // pinned: 2 int32 + 2 doubles
     int update_variant = -1;      // FEMCY_TUNE_DIRECT_UPDATE: -1 auto, 0 VALU, 1 / 2 matrix cores (k_band_update_mfma / _mfma2),
                                   // 3 = 1 on two streams (the update beside the next panel)
@@ -78,9 +81,7 @@ struct DirectState {
     BandOrder order;              // host copy of the band order of pattern `order_serial`
     int64_t order_serial = -1;
     void release() {
-        for (void* q : {(void*)d_rank, (void*)d_node_at, (void*)d_band, (void*)d_dfac, (void*)d_sgn, (void*)d_invd, (void*)d_wb, (void*)d_wy,
-                        (void*)d_wx, (void*)d_res, (void*)d_Kx, (void*)d_norms, (void*)d_flag})
-            if (q) (void)hipFree(q);
+        static_cast<DirectBuffers&>(*this) = DirectBuffers{};
         if (h_back) (void)hipHostFree(h_back);
         if (s2) {
             (void)hipStreamSynchronize(s2);
@@ -91,15 +92,14 @@ struct DirectState {
             }
             s2 = nullptr;
         }
-        d_rank = d_node_at = d_flag = nullptr;
-        d_band = d_dfac = d_sgn = d_invd = d_wb = d_wy = d_wx = d_res = d_Kx = d_norms = nullptr;
         h_back = nullptr;
         pattern_serial = -1;
     }
 };
 
 std::mutex g_mu;
-std::unordered_map<const Ctx*, DirectState> g_states;
+// (never destroyed: a state whose context was not closed must not free device memory while the process unloads)
+std::unordered_map<const Ctx*, DirectState>& g_states = *new std::unordered_map<const Ctx*, DirectState>;
 
 DirectState& state_of(const Ctx* c) {
     std::lock_guard<std::mutex> lk(g_mu);
@@ -569,19 +569,13 @@ __global__ void __launch_bounds__(64) k_band_bwd(int32_t p, int32_t T, int32_t T
     if (tile) wy[(int64_t)(p - tt) * NB + col] -= s;
 }
 
+// dev_alloc with the direct solve's own text; the sticky HIP error of the failed allocation is cleared
 template <class Tp>
-int alloc(Tp** p, size_t count) {
-    if (*p) {
-        (void)hipFree(*p);
-        *p = nullptr;
-    }
-    if (dmalloc(p, std::max<size_t>(count, 1) * sizeof(Tp)) != hipSuccess) {
-        (void)hipGetLastError();
-        *p = nullptr;
-        set_error("direct solve: out of device memory (%zu bytes)", count * sizeof(Tp));
-        return FEMCY_ENOMEM;
-    }
-    return FEMCY_OK;
+int alloc(DevBuf<Tp>& d, size_t count) {
+    if (dev_alloc(d, count, false) == FEMCY_OK) return FEMCY_OK;
+    (void)hipGetLastError();
+    set_error("direct solve: out of device memory (%zu bytes)", count * sizeof(Tp));
+    return FEMCY_ENOMEM;
 }
 
 // order + storage for the current pattern
@@ -616,12 +610,12 @@ int prepare(Ctx* c, DirectState& st) {
     st.P = (int32_t)P;
     st.band_tiles = P * (T + 1);
     int rc;
-    if ((rc = alloc(&st.d_rank, (size_t)c->nn)) || (rc = alloc(&st.d_node_at, (size_t)c->nn)) ||
-        (rc = alloc(&st.d_band, (size_t)st.band_tiles * TS)) || (rc = alloc(&st.d_dfac, (size_t)P * TS)) ||
-        (rc = alloc(&st.d_sgn, (size_t)P * NB)) || (rc = alloc(&st.d_invd, (size_t)P * NB)) || (rc = alloc(&st.d_wb, (size_t)P * NB)) ||
-        (rc = alloc(&st.d_wy, (size_t)P * NB)) || (rc = alloc(&st.d_wx, (size_t)P * NB)) ||
-        (rc = alloc(&st.d_res, (size_t)c->n)) || (rc = alloc(&st.d_Kx, (size_t)c->n)) || (rc = alloc(&st.d_norms, 2)) ||
-        (rc = alloc(&st.d_flag, 2))) {
+    if ((rc = alloc(st.d_rank, (size_t)c->nn)) || (rc = alloc(st.d_node_at, (size_t)c->nn)) ||
+        (rc = alloc(st.d_band, (size_t)st.band_tiles * TS)) || (rc = alloc(st.d_dfac, (size_t)P * TS)) ||
+        (rc = alloc(st.d_sgn, (size_t)P * NB)) || (rc = alloc(st.d_invd, (size_t)P * NB)) || (rc = alloc(st.d_wb, (size_t)P * NB)) ||
+        (rc = alloc(st.d_wy, (size_t)P * NB)) || (rc = alloc(st.d_wx, (size_t)P * NB)) ||
+        (rc = alloc(st.d_res, (size_t)c->n)) || (rc = alloc(st.d_Kx, (size_t)c->n)) || (rc = alloc(st.d_norms, 2)) ||
+        (rc = alloc(st.d_flag, 2))) {
         st.release();
         st.max_bytes = keep_limit;
         return rc;
@@ -695,12 +689,10 @@ int direct_solve(Ctx* c, const double* d_b, double* d_x, femcy_direct_info* info
         const int32_t maxL = *std::max_element(c->h_slice_len.begin(), c->h_slice_len.end());
         const int64_t threads = (int64_t)c->nslices * maxL * SLICE;
         const int grid = (int)((threads + 255) / 256);
-        if (c->dm == 3)
-            hipLaunchKernelGGL((k_band_fill<3>), dim3(grid), dim3(256), 0, s, c->nslices, maxL, c->d_slice_len, c->d_slice_off,
+        dispatch_dm(c->dm, [&](auto dm) {
+            hipLaunchKernelGGL((k_band_fill<dm()>), dim3(grid), dim3(256), 0, s, c->nslices, maxL, c->d_slice_len, c->d_slice_off,
                                c->d_node_of, c->d_rowlen, c->d_bcol, c->d_Kvals, st.d_rank, T, st.d_band);
-        else
-            hipLaunchKernelGGL((k_band_fill<2>), dim3(grid), dim3(256), 0, s, c->nslices, maxL, c->d_slice_len, c->d_slice_off,
-                               c->d_node_of, c->d_rowlen, c->d_bcol, c->d_Kvals, st.d_rank, T, st.d_band);
+        });
     }
     // band order of a right-hand side, the two sweeps, back to the caller's numbering (set or add)
     auto solve_into = [&](const double* d_rhs, double* d_out, int add, double* d_band_pad) -> int {

@@ -27,6 +27,7 @@
 #include <type_traits>
 #include <hip/hip_ext.h>
 #include "ctx.hpp"
+#include "element_dispatch.hpp"
 #include "element_math.hpp"
 #include "wave_reduce.hpp"
 
@@ -828,17 +829,13 @@ int launch_spmv(Ctx* c, const double* d_x, double* d_y, double* d_partials, int*
 int ensure_pos_vectors(Ctx* c) {
     int rc = ensure_bcolp(c);
     if (rc) return rc;
-    const int64_t need = (int64_t)c->nslices * SLICE * c->dm + 64;
-    if (c->pos_cap < need) {
-        if (c->d_posb) (void)hipFree(c->d_posb);
-        if (c->d_posx) (void)hipFree(c->d_posx);
-        c->d_posb = c->d_posx = nullptr;
-        c->pos_cap = 0;
-        FEMCY_HIP(dmalloc(&c->d_posb, sizeof(double) * need));
-        FEMCY_HIP(dmalloc(&c->d_posx, sizeof(double) * need));
+    const size_t need = (size_t)c->nslices * SLICE * c->dm + 64;
+    bool grew_b = false, grew_x = false;
+    if ((rc = dev_alloc(c->d_posb, need, false, &grew_b, FEMCY_EHIP)) || (rc = dev_alloc(c->d_posx, need, false, &grew_x, FEMCY_EHIP)))
+        return rc;
+    if (grew_b || grew_x) {   // (together: both are only ever sized here); a captured graph holds the old addresses
         FEMCY_HIP(hipMemsetAsync(c->d_posb, 0, sizeof(double) * need, c->stream));
         FEMCY_HIP(hipMemsetAsync(c->d_posx, 0, sizeof(double) * need, c->stream));
-        c->pos_cap = need;
         pcg_graph_reset(c);
     }
     return FEMCY_OK;
@@ -853,11 +850,13 @@ int spmv_public_storage_order(Ctx* c, const double* d_x, double* d_y) {
     if (rc) return rc;
     const int32_t npos = c->nslices * SLICE;
     const int pg = (npos + BS - 1) / BS;
-    if (c->dm == 3) hipLaunchKernelGGL((k_to_pos<3>), dim3(pg), dim3(BS), 0, c->stream, npos, c->d_node_of, d_x, c->d_posb);
-    else hipLaunchKernelGGL((k_to_pos<2>), dim3(pg), dim3(BS), 0, c->stream, npos, c->d_node_of, d_x, c->d_posb);
+    dispatch_dm(c->dm, [&](auto dm) {
+        hipLaunchKernelGGL((k_to_pos<dm()>), dim3(pg), dim3(BS), 0, c->stream, npos, c->d_node_of, d_x, c->d_posb);
+    });
     if ((rc = launch_spmv(c, c->d_posb, c->d_posx, nullptr, nullptr, true))) return rc;
-    if (c->dm == 3) hipLaunchKernelGGL((k_from_pos<3>), dim3(pg), dim3(BS), 0, c->stream, npos, c->d_node_of, (const double*)c->d_posx, d_y);
-    else hipLaunchKernelGGL((k_from_pos<2>), dim3(pg), dim3(BS), 0, c->stream, npos, c->d_node_of, (const double*)c->d_posx, d_y);
+    dispatch_dm(c->dm, [&](auto dm) {
+        hipLaunchKernelGGL((k_from_pos<dm()>), dim3(pg), dim3(BS), 0, c->stream, npos, c->d_node_of, (const double*)c->d_posx, d_y);
+    });
     FEMCY_HIP(hipGetLastError());
     return FEMCY_OK;
 }
@@ -912,10 +911,8 @@ int split_prepare(Ctx* c) {
     c->n_if_slices = (int32_t)list.size();
     for (int32_t s2 = 0; s2 < c->nslices; ++s2)
         if (!is_if[s2]) list.push_back(s2);
-    if (c->d_split_list) (void)hipFree(c->d_split_list);
-    c->d_split_list = nullptr;
-    FEMCY_HIP(dmalloc(&c->d_split_list, std::max<size_t>(list.size(), 1) * sizeof(int32_t)));
-    FEMCY_HIP(hipMemcpy(c->d_split_list, list.data(), list.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    int rc = dev_upload(c->d_split_list, list);
+    if (rc) return rc;
     if (!c->comm_stream) FEMCY_HIP(hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking));
     if (!c->ev_iface) FEMCY_HIP(hipEventCreateWithFlags(&c->ev_iface, hipEventDisableTiming));
     if (!c->ev_xchg) FEMCY_HIP(hipEventCreateWithFlags(&c->ev_xchg, hipEventDisableTiming));
@@ -1255,12 +1252,9 @@ static int pcg_small_solve(Ctx* c, const double* d_b, double* d_x, double eps, i
     const size_t lds = (size_t)(npad + 4 * c->dm * 64 + 2 * (BS / 64)) * sizeof(double);
     if (lds + 256 > (size_t)c->small_max_lds) return FEMCY_OK;    // + the kernel's static LDS
     const int G = c->nslices;
-    if (!c->d_small || c->small_cap < 2 * npad + 2 * G + 8) {
-        if (c->d_small) (void)hipFree(c->d_small);
-        c->d_small = nullptr;
-        c->small_cap = 2 * npad + 2 * G + 8;
-        FEMCY_HIP(dmalloc(&c->d_small, sizeof(double) * c->small_cap));
-    }
+    bool grew;
+    int rc = dev_alloc(c->d_small, (size_t)(2 * npad + 2 * G + 8), false, &grew, FEMCY_EHIP);
+    if (rc) return rc;
     SmallPcg a;
     a.slice_len = c->d_slice_len; a.slice_off = c->d_slice_off; a.bcol = c->d_bcol; a.node_of = c->d_node_of;
     a.vals = c->d_Kvals; a.b = d_b; a.M = c->d_M; a.x = d_x;
@@ -1307,6 +1301,28 @@ void pcg_graph_reset(Ctx* c) {
 }
 
 // ----------------------------------------------------------------------------------------- PCG
+// The end of every solve, whichever form ran it: h_state (fetched by the caller) goes to the caller's outputs and to the
+// counters of that form; a breakdown is FEMCY_ENUMERIC.
+enum SolveKind { SOLVE_SMALL, SOLVE_PERSIST, SOLVE_THREE };
+static int pcg_report(Ctx* c, SolveKind kind, int32_t* iters, double* r0, double* rmax) {
+    const PcgState& st = *c->h_state;
+    if (iters) *iters = st.iters;
+    if (r0) *r0 = st.r0;
+    if (rmax) *rmax = st.rmax;
+    c->timing.pcg_iters += st.iters;
+    if (kind == SOLVE_SMALL) c->timing.solves_small++;
+    if (kind == SOLVE_THREE) c->timing.solves_three++;
+    if (kind == SOLVE_PERSIST) {
+        c->timing.solves_persist++;
+        if (c->opt_timing) c->timing.persist_iters += st.iters;
+    }
+    if (st.done == 2) {
+        set_error("PCG breakdown: NaN/Inf residual after %d iterations (r0 = %g)", st.iters, st.r0);
+        return FEMCY_ENUMERIC;
+    }
+    return FEMCY_OK;
+}
+
 int pcg_solve(Ctx* c, const double* d_b, double* d_x, double eps, int32_t maxit, int32_t* iters, double* r0,
               double* rmax) {
     const bool multi = c->comm != nullptr;   // a 1-rank communicator still runs the exchange path (testable on one GPU)
@@ -1314,12 +1330,10 @@ int pcg_solve(Ctx* c, const double* d_b, double* d_x, double eps, int32_t maxit,
 
     // M = 1 / diag(K) (M_init).  Multi-rank: K is sub-assembled, so diag is summed over the interface first.
     const int jg = (c->nn + BS - 1) / BS;
-    if (c->dm == 3)
-        hipLaunchKernelGGL((k_jacobi<3>), dim3(jg), dim3(BS), 0, c->stream, c->nn, c->d_pos, c->d_slice_off, c->d_Kvals,
+    dispatch_dm(c->dm, [&](auto dm) {
+        hipLaunchKernelGGL((k_jacobi<dm()>), dim3(jg), dim3(BS), 0, c->stream, c->nn, c->d_pos, c->d_slice_off, c->d_Kvals,
                            c->d_M, multi ? 0 : 1);
-    else
-        hipLaunchKernelGGL((k_jacobi<2>), dim3(jg), dim3(BS), 0, c->stream, c->nn, c->d_pos, c->d_slice_off, c->d_Kvals,
-                           c->d_M, multi ? 0 : 1);
+    });
     if (multi) {
         int rc = iface_sum(c, c->d_M);
         if (rc) return rc;
@@ -1349,21 +1363,7 @@ int pcg_solve(Ctx* c, const double* d_b, double* d_x, double eps, int32_t maxit,
         }
         if (handled) {
             timing_end(c, th);
-            if (iters) *iters = c->h_state->iters;
-            if (r0) *r0 = c->h_state->r0;
-            if (rmax) *rmax = c->h_state->rmax;
-            c->timing.pcg_iters += c->h_state->iters;
-            if (persist) {
-                c->timing.solves_persist++;
-                if (c->opt_timing) c->timing.persist_iters += c->h_state->iters;
-            } else {
-                c->timing.solves_small++;
-            }
-            if (c->h_state->done == 2) {
-                set_error("PCG breakdown: NaN/Inf residual after %d iterations (r0 = %g)", c->h_state->iters, c->h_state->r0);
-                return FEMCY_ENUMERIC;
-            }
-            return FEMCY_OK;
+            return pcg_report(c, persist ? SOLVE_PERSIST : SOLVE_SMALL, iters, r0, rmax);
         }
     }
     // ---- three launches per iteration.  Single rank: the loop runs in STORAGE order (opt_pos_space) -- b is permuted
@@ -1378,13 +1378,10 @@ int pcg_solve(Ctx* c, const double* d_b, double* d_x, double eps, int32_t maxit,
         int rc = ensure_pos_vectors(c);
         if (rc) return rc;
         const int pg = (npos + BS - 1) / BS;
-        if (c->dm == 3) {
-            hipLaunchKernelGGL((k_jacobi_pos<3>), dim3(pg), dim3(BS), 0, c->stream, npos, c->d_node_of, c->d_slice_off, c->d_Kvals, c->d_M);
-            hipLaunchKernelGGL((k_to_pos<3>), dim3(pg), dim3(BS), 0, c->stream, npos, c->d_node_of, d_b, c->d_posb);
-        } else {
-            hipLaunchKernelGGL((k_jacobi_pos<2>), dim3(pg), dim3(BS), 0, c->stream, npos, c->d_node_of, c->d_slice_off, c->d_Kvals, c->d_M);
-            hipLaunchKernelGGL((k_to_pos<2>), dim3(pg), dim3(BS), 0, c->stream, npos, c->d_node_of, d_b, c->d_posb);
-        }
+        dispatch_dm(c->dm, [&](auto dm) {
+            hipLaunchKernelGGL((k_jacobi_pos<dm()>), dim3(pg), dim3(BS), 0, c->stream, npos, c->d_node_of, c->d_slice_off, c->d_Kvals, c->d_M);
+            hipLaunchKernelGGL((k_to_pos<dm()>), dim3(pg), dim3(BS), 0, c->stream, npos, c->d_node_of, d_b, c->d_posb);
+        });
         vb = c->d_posb;
         vx = c->d_posx;
     }
@@ -1400,8 +1397,8 @@ int pcg_solve(Ctx* c, const double* d_b, double* d_x, double eps, int32_t maxit,
     int64_t emax = 1;
     for (int k = 0; k < NXCD; ++k) emax = std::max<int64_t>(emax, er.start[k + 1] - er.start[k]);
     const int g = NXCD * (int)std::max<int64_t>(1, std::min<int64_t>((emax + BS - 1) / BS, std::max(1, c->ew_cap / NXCD)));
-    hipLaunchKernelGGL(k_pcg_init, dim3(g), dim3(BS), 0, c->stream, n2, (const double2*)vb, (const double2*)c->d_M,
-                       (double2*)vx, (double2*)c->d_r, (double2*)c->d_d, (const uint8_t*)(multi ? c->d_owner : nullptr),
+    hipLaunchKernelGGL(k_pcg_init, dim3(g), dim3(BS), 0, c->stream, n2, (const double2*)vb, (const double2*)c->d_M.get(),
+                       (double2*)vx, (double2*)c->d_r.get(), (double2*)c->d_d.get(), (const uint8_t*)(multi ? c->d_owner : nullptr),
                        c->d_part2);
     if (multi) {
         hipLaunchKernelGGL(k_sum_partials2, dim3(1), dim3(BS), 0, c->stream, g, c->d_part2, c->d_commbuf);
@@ -1461,7 +1458,7 @@ int pcg_solve(Ctx* c, const double* d_b, double* d_x, double eps, int32_t maxit,
         }
 #define FEMCY_XR(NT_, MU_)                                                                                         \
     hipLaunchKernelGGL((k_update_xr<NT_, MU_>), dim3(g), dim3(BS), 0, c->stream, er, np1, c->d_part1, dAd_red,       \
-                       c->d_state, (const double2*)c->d_Ad, (const double2*)c->d_M, (double2*)c->d_r,                \
+                       c->d_state, (const double2*)c->d_Ad.get(), (const double2*)c->d_M.get(), (double2*)c->d_r.get(),                \
                        (const uint8_t*)(multi ? c->d_owner : nullptr), c->d_part2)
         if (multi) { if (c->vec_nt) FEMCY_XR(true, true); else FEMCY_XR(false, true); }
         else       { if (c->vec_nt) FEMCY_XR(true, false); else FEMCY_XR(false, false); }
@@ -1474,7 +1471,7 @@ int pcg_solve(Ctx* c, const double* d_b, double* d_x, double eps, int32_t maxit,
 #define FEMCY_UD(NT_)                                                                              \
     hipLaunchKernelGGL(k_update_d<NT_>, dim3(g), dim3(BS), 0, c->stream, er, g, c->d_part2,         \
                        (const double*)(multi ? c->d_gather : nullptr), (int)c->nranks, c->d_state, \
-                       (const double2*)c->d_r, (const double2*)c->d_M, (double2*)c->d_d, (double2*)vx)
+                       (const double2*)c->d_r.get(), (const double2*)c->d_M.get(), (double2*)c->d_d.get(), (double2*)vx)
         if (c->vec_nt) FEMCY_UD(true); else FEMCY_UD(false);
 #undef FEMCY_UD
         return FEMCY_OK;
@@ -1527,40 +1524,32 @@ int pcg_solve(Ctx* c, const double* d_b, double* d_x, double eps, int32_t maxit,
     }
     if (pos) {
         const int pg = (npos + BS - 1) / BS;
-        if (c->dm == 3) hipLaunchKernelGGL((k_from_pos<3>), dim3(pg), dim3(BS), 0, c->stream, npos, c->d_node_of, (const double*)c->d_posx, d_x);
-        else hipLaunchKernelGGL((k_from_pos<2>), dim3(pg), dim3(BS), 0, c->stream, npos, c->d_node_of, (const double*)c->d_posx, d_x);
+        dispatch_dm(c->dm, [&](auto dm) {
+            hipLaunchKernelGGL((k_from_pos<dm()>), dim3(pg), dim3(BS), 0, c->stream, npos, c->d_node_of, (const double*)c->d_posx, d_x);
+        });
         FEMCY_HIP(hipGetLastError());
     }
     timing_end(c, th);
-    if (iters) *iters = c->h_state->iters;
-    if (r0) *r0 = c->h_state->r0;
-    if (rmax) *rmax = c->h_state->rmax;
-    c->timing.pcg_iters += c->h_state->iters;
-    c->timing.solves_three++;
-    if (c->h_state->done == 2) {
-        if (getenv("FEMCY_DEBUG_DUMP_BREAKDOWN")) {              // where did the first non-finite entry appear?
-            const int64_t nd = pos ? (int64_t)npos * c->dm : c->n;
-            std::vector<double> h((size_t)nd);
-            const struct { const char* name; const double* p; } vecs[] = {{"b", vb}, {"M", c->d_M}, {"r", c->d_r}, {"d", c->d_d}, {"Ad", c->d_Ad}, {"x", vx}};
-            for (const auto& v : vecs) {
-                (void)hipMemcpy(h.data(), v.p, sizeof(double) * nd, hipMemcpyDeviceToHost);
-                int64_t bad = 0, first = -1, zeros = 0;
-                for (int64_t i = 0; i < nd; ++i) {
-                    if (!std::isfinite(h[i])) { if (first < 0) first = i; ++bad; }
-                    if (h[i] == 0.0) ++zeros;
-                }
-                fprintf(stderr, "[femcy debug] %s: %lld of %lld non-finite (first at %lld = slice %lld lane %lld comp %lld), %lld zeros\n", v.name,
-                        (long long)bad, (long long)nd, (long long)first, (long long)(first / (64 * c->dm)), (long long)(first / c->dm % 64),
-                        (long long)(first % c->dm), (long long)zeros);
+    if (c->h_state->done == 2 && getenv("FEMCY_DEBUG_DUMP_BREAKDOWN")) {   // where did the first non-finite entry appear?
+        const int64_t nd = pos ? (int64_t)npos * c->dm : c->n;
+        std::vector<double> h((size_t)nd);
+        const struct { const char* name; const double* p; } vecs[] = {{"b", vb}, {"M", c->d_M}, {"r", c->d_r}, {"d", c->d_d}, {"Ad", c->d_Ad}, {"x", vx}};
+        for (const auto& v : vecs) {
+            (void)hipMemcpy(h.data(), v.p, sizeof(double) * nd, hipMemcpyDeviceToHost);
+            int64_t bad = 0, first = -1, zeros = 0;
+            for (int64_t i = 0; i < nd; ++i) {
+                if (!std::isfinite(h[i])) { if (first < 0) first = i; ++bad; }
+                if (h[i] == 0.0) ++zeros;
             }
-            fprintf(stderr, "[femcy debug] state: iters %d r0 %g rmax %g dAd %g alpha %g rMr %g %g; pos %d npos %d n %lld g %d\n", c->h_state->iters,
-                    c->h_state->r0, c->h_state->rmax, c->h_state->dAd, c->h_state->alpha, c->h_state->rMr[0], c->h_state->rMr[1], (int)pos, (int)npos,
-                    (long long)c->n, g);
+            fprintf(stderr, "[femcy debug] %s: %lld of %lld non-finite (first at %lld = slice %lld lane %lld comp %lld), %lld zeros\n", v.name,
+                    (long long)bad, (long long)nd, (long long)first, (long long)(first / (64 * c->dm)), (long long)(first / c->dm % 64),
+                    (long long)(first % c->dm), (long long)zeros);
         }
-        set_error("PCG breakdown: NaN/Inf residual after %d iterations (r0 = %g)", c->h_state->iters, c->h_state->r0);
-        return FEMCY_ENUMERIC;
+        fprintf(stderr, "[femcy debug] state: iters %d r0 %g rmax %g dAd %g alpha %g rMr %g %g; pos %d npos %d n %lld g %d\n", c->h_state->iters,
+                c->h_state->r0, c->h_state->rmax, c->h_state->dAd, c->h_state->alpha, c->h_state->rMr[0], c->h_state->rMr[1], (int)pos, (int)npos,
+                (long long)c->n, g);
     }
-    return FEMCY_OK;
+    return pcg_report(c, SOLVE_THREE, iters, r0, rmax);
 }
 
 // ------------------------------------------------------------------------------ implicit dynamics
@@ -1675,12 +1664,11 @@ int launch_mass_spmv(Ctx* c, const double* d_m, const double* d_x, double* d_y, 
         return FEMCY_EINVAL;
     }
     size_t tm = timing_begin(c, T_GEOM);          // events only under FEMCY_OPT_TIMING (tools/dynamic_record.py)
-#define MASS_SPMV_ARGS                                                                                            \
-    c->nn, c->xcd, (const int32_t*)c->d_slice_len, (const int64_t*)c->d_slice_off, (const int32_t*)c->d_bcol,     \
-        (const int32_t*)c->d_node_of, d_m, d_x, d_y, scale, add ? 1 : 0, d_partials
-    if (c->dm == 3) hipLaunchKernelGGL((k_mass_spmv<3>), dim3(grid), dim3(BS), 0, c->stream, MASS_SPMV_ARGS);
-    else hipLaunchKernelGGL((k_mass_spmv<2>), dim3(grid), dim3(BS), 0, c->stream, MASS_SPMV_ARGS);
-#undef MASS_SPMV_ARGS
+    dispatch_dm(c->dm, [&](auto dm) {
+        hipLaunchKernelGGL((k_mass_spmv<dm()>), dim3(grid), dim3(BS), 0, c->stream, c->nn, c->xcd, (const int32_t*)c->d_slice_len,
+                           (const int64_t*)c->d_slice_off, (const int32_t*)c->d_bcol, (const int32_t*)c->d_node_of, d_m, d_x, d_y,
+                           scale, add ? 1 : 0, d_partials);
+    });
     timing_end(c, tm);
     FEMCY_HIP(hipGetLastError());
     if (np) *np = grid;
@@ -1692,8 +1680,9 @@ int launch_mass_add_to_K(Ctx* c, const double* d_m, double cc, bool overwrite) {
     const unsigned grid = (unsigned)((npos + BS - 1) / BS);
     if (!grid) return FEMCY_OK;
     size_t tm = timing_begin(c, T_GEOM);
-    if (c->dm == 3) hipLaunchKernelGGL((k_mass_add_to_K<3>), dim3(grid), dim3(BS), 0, c->stream, npos, d_m, cc, overwrite ? 1 : 0, c->d_Kvals);
-    else hipLaunchKernelGGL((k_mass_add_to_K<2>), dim3(grid), dim3(BS), 0, c->stream, npos, d_m, cc, overwrite ? 1 : 0, c->d_Kvals);
+    dispatch_dm(c->dm, [&](auto dm) {
+        hipLaunchKernelGGL((k_mass_add_to_K<dm()>), dim3(grid), dim3(BS), 0, c->stream, npos, d_m, cc, overwrite ? 1 : 0, c->d_Kvals);
+    });
     timing_end(c, tm);
     FEMCY_HIP(hipGetLastError());
     return FEMCY_OK;

@@ -1080,12 +1080,9 @@ __global__ void __launch_bounds__(64) k_probe_mailbox(PersistPcg a, int rounds, 
 
 int persist_buffers(Ctx* c, int G, int64_t npad, PersistPcg* a) {
     const int64_t need = 3 * npad + 2 * G + 4 * G + 8 * G + 160;  // d (<= 3 buffers) + partials + granules (4 G x 16 B) + counters
-    if (!c->d_persist || c->persist_cap < need) {
-        if (c->d_persist) (void)hipFree(c->d_persist);
-        c->d_persist = nullptr;
-        c->persist_cap = need;
-        FEMCY_HIP(dmalloc(&c->d_persist, sizeof(double) * need));
-    }
+    bool grew;
+    int rc = dev_alloc(c->d_persist, (size_t)need, false, &grew, FEMCY_EHIP);
+    if (rc) return rc;
     a->dbuf = c->d_persist;
     a->part1 = c->d_persist + 3 * npad;
     a->part2 = a->part1 + 2 * G;
@@ -1110,10 +1107,9 @@ __global__ void k_bcol_to_pos(int64_t n, const int32_t* __restrict__ bcol, const
 }
 int ensure_bcolp(Ctx* c) {
     if (c->bcolp_serial == c->pattern_serial && c->d_bcolp) return FEMCY_OK;
-    if (c->d_bcolp) (void)hipFree(c->d_bcolp);
-    c->d_bcolp = nullptr;
     const int64_t nb = c->stored_rows * SLICE;
-    FEMCY_HIP(dmalloc(&c->d_bcolp, std::max<int64_t>(nb, 1) * sizeof(int32_t)));
+    int rc = dev_alloc(c->d_bcolp, (size_t)nb, false, nullptr, FEMCY_EHIP);
+    if (rc) return rc;
     hipLaunchKernelGGL(k_bcol_to_pos, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, c->stream, nb,
                        (const int32_t*)c->d_bcol, (const int32_t*)c->d_pos, c->d_bcolp);
     FEMCY_HIP(hipGetLastError());
@@ -1257,9 +1253,9 @@ int pcg_persist_solve(Ctx* c, const double* d_b, double* d_x, double eps, int32_
                         load[best] += c->h_slice_len[s];
                     }
                 }
-                if (c->d_persist_assign) (void)hipFree(c->d_persist_assign);
-                c->d_persist_assign = nullptr;
-                FEMCY_HIP(dmalloc(&c->d_persist_assign, assign.size() * sizeof(int32_t)));
+                // copied on the context's own stream, not by dev_upload: across ranks a peer's kernel may already be polling
+                // for this rank's, and a copy on the null stream could wait for it
+                FEMCY_HIP(c->d_persist_assign.alloc(assign.size() * sizeof(int32_t)));
                 FEMCY_HIP(hipMemcpyAsync(c->d_persist_assign, assign.data(), assign.size() * sizeof(int32_t),
                                          hipMemcpyHostToDevice, c->stream));
                 FEMCY_HIP(hipStreamSynchronize(c->stream));
@@ -1416,13 +1412,10 @@ int probe_stream(Ctx* c, int64_t bytes, int32_t reps, int32_t mode, double* us_p
     G = (int)std::max<int64_t>(PNX, std::min<int64_t>(G, (n16 / tile) / PNX * PNX));   // >= one tile per workgroup
     const int64_t chunk = (n16 / G) / tile * tile;
     FEMCY_REQUIRE(chunk > 0, "probe_stream: %lld bytes are less than one tile per workgroup", (long long)bytes);
-    if (!c->d_probe || c->probe_cap < bytes) {
-        if (c->d_probe) (void)hipFree(c->d_probe);
-        c->d_probe = nullptr;
-        c->probe_cap = bytes;
-        FEMCY_HIP(dmalloc(&c->d_probe, (size_t)bytes + 64));
-        FEMCY_HIP(hipMemsetAsync(c->d_probe, 0, (size_t)bytes, c->stream));
-    }
+    bool grew;
+    int rc = dev_alloc(c->d_probe, (size_t)bytes + 64, false, &grew, FEMCY_EHIP);
+    if (rc) return rc;
+    if (grew) FEMCY_HIP(hipMemsetAsync(c->d_probe, 0, (size_t)bytes, c->stream));
     // dynamic LDS sets the residency: one workgroup per CU as the solver, or exactly per_cu of them
     const size_t lds = per_cu == 1 ? (size_t)(c->small_max_lds - 1024)
                                    : (per_cu < 8 ? (size_t)(c->small_max_lds / per_cu - 2048) : 0);
@@ -1433,14 +1426,14 @@ int probe_stream(Ctx* c, int64_t bytes, int32_t reps, int32_t mode, double* us_p
     do {                                                                                                           \
         const void* fn = reinterpret_cast<const void*>(&k_probe_stream<U_>);                                       \
         if (lds > 48 * 1024) FEMCY_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL(k_probe_stream<U_>, dim3(G), dim3(PBS), lds, c->stream, (const double2*)c->d_probe, n16, \
+        hipLaunchKernelGGL(k_probe_stream<U_>, dim3(G), dim3(PBS), lds, c->stream, (const double2*)c->d_probe.get(), n16, \
                            (int)(REPS_), nt, c->d_part1);                                                          \
     } while (0)
 #define FEMCY_PROBE_DMA(U_, REPS_)                                                                                 \
     do {                                                                                                           \
         const void* fn = reinterpret_cast<const void*>(&k_probe_stream_lds<U_>);                                   \
         if (lds > 48 * 1024) FEMCY_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL(k_probe_stream_lds<U_>, dim3(G), dim3(PBS), lds, c->stream, (const double2*)c->d_probe, n16, \
+        hipLaunchKernelGGL(k_probe_stream_lds<U_>, dim3(G), dim3(PBS), lds, c->stream, (const double2*)c->d_probe.get(), n16, \
                            (int)(REPS_), nt, c->d_part1);                                                          \
     } while (0)
     for (int pass = 0; pass < 2; ++pass) {                       // warm-up launch (2 passes), then the timed one

@@ -29,18 +29,6 @@ static void parallel_for(int64_t n, F f) {
     for (auto& x : th) x.join();
 }
 
-template <class T>
-static int upload(T** dptr, const std::vector<T>& h) {
-    if (*dptr) {
-        (void)hipFree(*dptr);
-        *dptr = nullptr;
-    }
-    size_t bytes = std::max<size_t>(h.size(), 1) * sizeof(T);
-    FEMCY_HIP(dmalloc(dptr, bytes));
-    if (!h.empty()) FEMCY_HIP(hipMemcpy(*dptr, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    return FEMCY_OK;
-}
-
 // SpMV work split: XCD k gets the contiguous slice range holding the k-th eighth of the stored blocks; long
 // rows are shared by WPS wavefronts of one workgroup (FEMCY_OPT_SPMV_VARIANT: 0 = choose from the mean row
 // length, else 1 / 2 / 4).
@@ -164,7 +152,7 @@ void spmv_split(Ctx* c) {
                 }
             }
         }
-        if (upload(&c->d_spmv_perm, perm) == FEMCY_OK)
+        if (dev_upload(c->d_spmv_perm, perm) == FEMCY_OK)
             c->spmv_perm_rounds = rounds;
         else
             c->spmv_rot = 19;                                     // no table: the rotation
@@ -320,7 +308,7 @@ int ensure_pairs(Ctx* c, int RPW, bool spatial, int cpw) {
                       "pairs per step %d)", RPW, PPW);
     }
     int rc;
-    if ((rc = upload(&c->d_pr_unit, unit_ptr)) || (rc = upload(&c->d_pr_ptr, desc)) || (rc = upload(&c->d_pr_code, code))) return rc;
+    if ((rc = dev_upload(c->d_pr_unit, unit_ptr)) || (rc = dev_upload(c->d_pr_ptr, desc)) || (rc = dev_upload(c->d_pr_code, code))) return rc;
     c->pairs_serial = key;
     return FEMCY_OK;
 }
@@ -633,25 +621,23 @@ int build_pattern(Ctx* c) {
     spmv_split(c);
 
     int rc;
-    if ((rc = upload(&c->d_slice_len, slice_len))) return rc;
-    if ((rc = upload(&c->d_slice_off, c->h_slice_off))) return rc;
-    if ((rc = upload(&c->d_rowlen, rowlen))) return rc;
-    if ((rc = upload(&c->d_pos, pos))) return rc;
-    if ((rc = upload(&c->d_node_of, node_of))) return rc;
-    if ((rc = upload(&c->d_bcol, bcol))) return rc;
-    if ((rc = upload(&c->d_slotj, slotj))) return rc;
-    if ((rc = upload(&c->d_ctr_ptr, ctr_cnt))) return rc;
-    if ((rc = upload(&c->d_ctr, ctr))) return rc;
-    if ((rc = upload(&c->d_tpos, tpos))) return rc;
-    if ((rc = upload(&c->d_ne_ptr, ne_ptr))) return rc;
-    if ((rc = upload(&c->d_ne_idx, ne_idx))) return rc;
-    if ((rc = upload(&c->d_asm_order, asm_order))) return rc;
+    if ((rc = dev_upload(c->d_slice_len, slice_len))) return rc;
+    if ((rc = dev_upload(c->d_slice_off, c->h_slice_off))) return rc;
+    if ((rc = dev_upload(c->d_rowlen, rowlen))) return rc;
+    if ((rc = dev_upload(c->d_pos, pos))) return rc;
+    if ((rc = dev_upload(c->d_node_of, node_of))) return rc;
+    if ((rc = dev_upload(c->d_bcol, bcol))) return rc;
+    if ((rc = dev_upload(c->d_slotj, slotj))) return rc;
+    if ((rc = dev_upload(c->d_ctr_ptr, ctr_cnt))) return rc;
+    if ((rc = dev_upload(c->d_ctr, ctr))) return rc;
+    if ((rc = dev_upload(c->d_tpos, tpos))) return rc;
+    if ((rc = dev_upload(c->d_ne_ptr, ne_ptr))) return rc;
+    if ((rc = dev_upload(c->d_ne_idx, ne_idx))) return rc;
+    if ((rc = dev_upload(c->d_asm_order, asm_order))) return rc;
 
-    if (c->d_Kvals) (void)hipFree(c->d_Kvals);
-    size_t kbytes = (size_t)stored_rows * dm * dm * SLICE * sizeof(double);
-    FEMCY_HIP(dmalloc(&c->d_Kvals, std::max<size_t>(kbytes, 8)));
-    FEMCY_HIP(dfill_sync(c->d_Kvals, 0, kbytes));       // landed on return (ctx.hpp: the round-5 NaN was this fill running late)
-    return FEMCY_OK;
+    // zero-filled, landed on return (ctx.hpp: the round-5 NaN was this fill running late).  K is the largest allocation
+    // of the library: when it fails d_Kvals is null, not the address of the matrix it replaced
+    return dev_alloc(c->d_Kvals, (size_t)stored_rows * dm * dm * SLICE, true, nullptr, FEMCY_EHIP);
 }
 
 }  // namespace femcy
