@@ -77,7 +77,7 @@ EXPORTS = [
     "femcy_lumped_mass_create", "femcy_lumped_mass_get", "femcy_explicit_create", "femcy_explicit_start",
     "femcy_explicit_advance", "femcy_explicit_kinetic_energy", "femcy_explicit_stable_dt",
     "femcy_explicit_element_bound", "femcy_explicit_auto_begin", "femcy_explicit_auto_advance", "femcy_explicit_auto_state",
-    "femcy_explicit_set_damping",
+    "femcy_explicit_set_damping", "femcy_lumped_mass_scale", "femcy_lumped_mass_get_scaling",
     "femcy_loadset_create", "femcy_loadset_neumann", "femcy_loadset_neumann_add", "femcy_spmv", "femcy_pcg", "femcy_compute_strain_stress", "femcy_elastic_energy", "femcy_elastic_energy_small", "femcy_extrapolate",
     "femcy_get_K_ell", "femcy_get_K_bsr", "femcy_get_gp_field", "femcy_timing",
     "femcy_timing_reset", "femcy_comm_unique_id", "femcy_comm_local_id", "femcy_comm_init", "femcy_comm_info", "femcy_comm_set_neighbours",
@@ -99,6 +99,9 @@ class FemcyError(RuntimeError):
 
 FEMCY_ENUMERIC = -4
 FEMCY_ENOMEM = -6
+# femcy_lumped_mass_scale: the rule that turns a target increment into factors (*Fixed Mass Scaling, type=)
+MS_BELOW_MIN, MS_SET_EQUAL_DT, MS_UNIFORM = 0, 1, 2
+MS_TYPES = {"below min": MS_BELOW_MIN, "set equal dt": MS_SET_EQUAL_DT, "uniform": MS_UNIFORM}
 
 
 class DirectInfo(C.Structure):
@@ -187,6 +190,8 @@ def _bind(lib, kind):
         "femcy_explicit_auto_begin": [p, i32, cint, f64, f64, f64, i32],
         "femcy_explicit_auto_advance": [p, i32, cint, i32],
         "femcy_explicit_set_damping": [p, i32, f64, f64, f64, f64],
+        "femcy_lumped_mass_scale": [p, i32, f64, f64, f64, i32, C.POINTER(f64), C.POINTER(f64), C.POINTER(i64), C.POINTER(f64)],
+        "femcy_lumped_mass_get_scaling": [p, i32, p],
         "femcy_explicit_auto_state": [p, i32, C.POINTER(f64), C.POINTER(f64), C.POINTER(f64), C.POINTER(C.c_int64)],
         "femcy_loadset_create": [p, i32, i32, i32, p, p, p, p, p, i32, p, p, C.POINTER(i32)],
         "femcy_loadset_neumann": [p, i32, f64, p, cint],
@@ -566,6 +571,23 @@ class Context:
     def lumped_mass_get(self, lm: int) -> np.ndarray:
         out = np.empty(self.nn, dtype=np.float64)
         self._call("femcy_lumped_mass_get", int(lm), _ptr(out))
+        return out
+
+    def lumped_mass_scale(self, lm: int, s_C: float = 0.0, factor=None, dt=None, type="below min") -> dict:
+        """fixed mass scaling of the lumped mass lm, before an integrator is made from it: every element's shares times
+        `factor`, and / or times what brings its estimated increment 2 / omega_e to `dt` under `type` ("below min": only the
+        elements below dt, "set equal dt": every element, "uniform": one factor for all; or an MS_* constant).  s_C: the
+        material stiffness of explicit_element_bound, read with dt.  -> {"mass0", "mass1", "scaled_elements", "max_factor"}"""
+        m0, m1, fmax, k = C.c_double(), C.c_double(), C.c_double(), C.c_int64()
+        kind = MS_TYPES.get(type.lower(), -1) if isinstance(type, str) else int(type)
+        self._call("femcy_lumped_mass_scale", int(lm), float(s_C), float(factor or 0.0), float(dt or 0.0), kind,
+                   C.byref(m0), C.byref(m1), C.byref(k), C.byref(fmax))
+        return {"mass0": m0.value, "mass1": m1.value, "scaled_elements": int(k.value), "max_factor": fmax.value}
+
+    def lumped_mass_scaling(self, lm: int) -> np.ndarray:
+        """[ne] the cumulative mass-scaling factor of every element; 1.0 before any lumped_mass_scale"""
+        out = np.empty(self.ne, dtype=np.float64)
+        self._call("femcy_lumped_mass_get_scaling", int(lm), _ptr(out))
         return out
 
     def explicit(self, lm: int, dofsets=()) -> int:

@@ -344,6 +344,26 @@ int check_explicit_create(const C* c, int32_t lumped_id, int32_t ndofsets, const
     return FEMCY_OK;
 }
 
+// femcy_lumped_mass_scale, after the state check (the estimate reads the element tables and the material)
+template <class C>
+int check_lumped_mass_scale(const C* c, int32_t lumped_id, double s_C, double factor, double dt, int32_t type,
+                            const double* mass_before, const double* mass_after, const int64_t* n_scaled,
+                            const double* factor_max) {
+    FEMCY_TRY(check_object(c->lumped_masses, lumped_id, "lumped mass"));
+    FEMCY_REQUIRE(mass_before && mass_after && n_scaled && factor_max, TEXT_NULL_OUTPUT);
+    FEMCY_REQUIRE(std::isfinite(factor) && factor >= 0.0 && std::isfinite(dt) && dt >= 0.0,
+                  "femcy_lumped_mass_scale: factor and dt must be finite and not negative");
+    FEMCY_REQUIRE(factor != 0.0 || dt != 0.0, "femcy_lumped_mass_scale: give a factor, a target increment dt or both");
+    FEMCY_REQUIRE(type == FEMCY_MS_BELOW_MIN || type == FEMCY_MS_SET_EQUAL_DT || type == FEMCY_MS_UNIFORM,
+                  "femcy_lumped_mass_scale: unknown type %d", (int)type);
+    FEMCY_REQUIRE(dt == 0.0 || positive_finite(s_C),
+                  "femcy_lumped_mass_scale: the material stiffness s_C must be finite and positive");
+    for (size_t k = 0; k < c->explicits.size(); ++k)
+        FEMCY_REQUIRE(c->explicits[k].lumped != lumped_id, "femcy_lumped_mass_scale: explicit integrator %d refers to lumped "
+                      "mass %d; scale before femcy_explicit_create (its inverse mass is derived once)", (int)k, (int)lumped_id);
+    return FEMCY_OK;
+}
+
 // the checks the stepping calls share: the integrator, and a load vector that is none of the three state vectors
 template <class C>
 int check_explicit_rhs(const C* c, const char* entry, int32_t id, int rhs_vec) {

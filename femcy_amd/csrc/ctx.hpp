@@ -387,7 +387,8 @@ struct Ctx {
     // An automatic run (femcy_explicit_auto_*) also reads the element shares me [ne][npe] the nodal masses were summed from,
     // and keeps its clock (element_math.hpp: ExplicitClock) and the partial maxima of the bound kernel [ceil(ne / 256)] on
     // the device; both are allocated by the first call that needs them.
-    struct LumpedMass { DevBuf<double> d_m, d_me; double rho = 0.0; };
+    // d_scale [ne]: the cumulative factors of femcy_lumped_mass_scale, allocated by its first call (none yet: all 1)
+    struct LumpedMass { DevBuf<double> d_m, d_me, d_scale; double rho = 0.0; };
     std::vector<LumpedMass> lumped_masses;
     struct Explicit {
         DevBuf<double> d_minv, d_bpart;
@@ -551,6 +552,15 @@ int launch_explicit_bound(Ctx* c, const double* d_u, const double* d_me, double 
                           const GeomDamping* gd = nullptr);
 int launch_explicit_bound_max(Ctx* c, const double* d_part, double* out);
 int launch_explicit_clock(Ctx* c, const double* d_part, ExplicitClock* d_clk);
+// fixed mass scaling (femcy_lumped_mass_scale).  launch_mass_total: the sum of d_m [nn] in a fixed order, fetched.
+// launch_mass_scale_factors: d_fac [ne] = k_e from omega_e^2 at u = 0 with the shares d_me, its partials into d_part
+// [3 explicit_bound_partials(c)], and out[0..3) = max omega_e^2 (NaN as infinity), max k_e (anything but a finite positive
+// factor as infinity), the number of k_e != 1; measure: out[0] alone and d_fac is not written.  Both synchronise.
+// launch_mass_scale_apply: d_me[e][:] *= d_fac[e], d_cum[e] = (first ? 1 : d_cum[e]) d_fac[e], d_m = node sums; only enqueues.
+int launch_mass_total(Ctx* c, const double* d_m, double* out);
+int launch_mass_scale_factors(Ctx* c, const double* d_me, double s_C, double w2max, double factor, double tau, int type,
+                              bool measure, double* d_fac, double* d_part, double* out);
+int launch_mass_scale_apply(Ctx* c, const double* d_fac, bool first, double* d_me, double* d_cum, double* d_m);
 // pos_space: x and y are in STORAGE order (entry p * dm + c belongs to the node at storage position p = slice * 64 + lane;
 // the padding lanes of the last slice hold zeros) -- the form the three-kernel PCG runs in since round 4
 int launch_spmv(Ctx* c, const double* d_x, double* d_y, double* d_partials, int* nblocks_out, bool pos_space = false);

@@ -990,6 +990,26 @@ FEMCY_HD void explicit_bound_element_damped(const double (&X)[NPE][DM], const do
     explicit_bound_element_impl<NPE, DM, true>(X, U, &vh[0][0], &d, nGP, dN, w, kind, C, p0, p1, me, s_C, g, w2);
 }
 
+// Fixed mass scaling (femcy_lumped_mass_scale): the factor k_e of one element from w2 = its undamped omega_e^2 at u = 0 with
+// its current shares, w2max = max_e omega_e^2 (read by FEMCY_MS_UNIFORM alone), the caller's factor f and target increment
+// tau (0: not given) and the type.  omega_e^2 is linear in 1 / m_a^e, so with dt_e = 2 / omega_e
+//   f alone                 k_e = f
+//   tau, BELOW_MIN          k_e = max(1, omega_e^2 tau^2 / 4)
+//   tau, SET_EQUAL_DT       k_e = omega_e^2 tau^2 / 4
+//   tau, UNIFORM            k_e = max_e omega_e^2 tau^2 / 4
+//   f and tau               f first: omega_e^2 / f enters the tau rule, k_e is the product
+// A NaN w2 comes back as NaN under every rule with tau but FEMCY_MS_BELOW_MIN's fmax; the callers test omega_e^2 themselves.
+FEMCY_HD double mass_scale_factor(double w2, double w2max, double f, double tau, int type) {
+    const double f1 = f != 0.0 ? f : 1.0;
+    if (tau == 0.0) return f1;
+    const double r = ((type == FEMCY_MS_UNIFORM ? w2max : w2) / f1) * (tau * tau) * 0.25;
+    return f1 * (type == FEMCY_MS_BELOW_MIN ? fmax(1.0, r) : r);
+}
+// what a reduction over the elements carries of one of them: omega_e^2 with NaN counted as infinity (k_explicit_bound), and
+// k_e with anything but a finite positive number counted as infinity, so that one finite maximum vouches for every factor
+FEMCY_HD double mass_scale_nan_to_inf(double w2) { return w2 != w2 ? INFINITY : w2; }
+FEMCY_HD double mass_scale_bad_to_inf(double k) { return k > 0.0 ? k : INFINITY; }
+
 // the clock of an automatic run, advanced once per step on whichever backend: t is the time of the state the element pass
 // has just seen, h_next the increment of the next drift, t_next the time that drift reaches.
 struct ExplicitClock {

@@ -1106,6 +1106,69 @@ int femcy_lumped_mass_get(femcy_ctx* ctx, int32_t id, double* out) {
     return download(c, out, lm.d_m.get(), sizeof(double) * c->nn);
 }
 
+// Set-up, synchronising: the total mass, the factors (FEMCY_MS_UNIFORM: a measuring pass first, its maximum comes back as an
+// argument), and only once the host has seen that omega_e^2 and every factor are finite and positive the apply pass, the
+// node sums and the total again.  The estimate of a call without dt serves that test alone and takes s_C = 1.
+int femcy_lumped_mass_scale(femcy_ctx* ctx, int32_t lumped_id, double s_C, double factor, double dt, int32_t type,
+                            double* mass_before, double* mass_after, int64_t* n_scaled, double* factor_max) {
+    CTX_OR_FAIL(ctx);
+    READY_OR_FAIL();
+    EXPLICIT_SINGLE_RANK_OR_FAIL("femcy_lumped_mass_scale");
+    FEMCY_TRY(check_lumped_mass_scale(c, lumped_id, s_C, factor, dt, type, mass_before, mass_after, n_scaled, factor_max));
+    Ctx::LumpedMass& lm = c->lumped_masses[lumped_id];
+    const int np = explicit_bound_partials(c);
+    const bool first = !lm.d_scale.get();
+    DevBuf<double> d_fac, d_part, d_scale;      // scratch of this call; d_scale moves to lm with the first apply pass
+    if (d_fac.alloc(sizeof(double) * (size_t)c->ne) != hipSuccess || d_part.alloc(sizeof(double) * 3 * (size_t)np) != hipSuccess ||
+        (first && d_scale.alloc(sizeof(double) * (size_t)c->ne) != hipSuccess)) {
+        set_error("out of device memory for the mass scaling of %d elements", c->ne);
+        return FEMCY_ENOMEM;
+    }
+    const double sc = dt != 0.0 ? s_C : 1.0;
+    double res[3] = {0.0, 0.0, 0.0}, w2max = 0.0, m0 = 0.0, m1 = 0.0;
+    int rc = launch_mass_total(c, lm.d_m.get(), &m0);
+    if (!rc && dt != 0.0 && type == FEMCY_MS_UNIFORM) {
+        rc = launch_mass_scale_factors(c, lm.d_me.get(), sc, 0.0, factor, dt, type, true, d_fac.get(), d_part.get(), res);
+        w2max = res[0];
+    }
+    if (!rc && std::isfinite(w2max))
+        rc = launch_mass_scale_factors(c, lm.d_me.get(), sc, w2max, factor, dt, type, false, d_fac.get(), d_part.get(), res);
+    if (rc) {
+        (void)hipStreamSynchronize(c->stream);      // the scratch goes: nothing may still write it
+        return rc;
+    }
+    if (!std::isfinite(w2max) || !std::isfinite(res[0]) || !std::isfinite(res[1])) {
+        set_error("femcy_lumped_mass_scale: an element frequency or a factor is not finite and positive (max omega_e^2 = %g, "
+                  "max factor = %g): a broken element; the lumped mass is unchanged", std::isfinite(w2max) ? res[0] : w2max,
+                  res[1]);
+        return FEMCY_ENUMERIC;
+    }
+    rc = launch_mass_scale_apply(c, d_fac.get(), first, lm.d_me.get(), first ? d_scale.get() : lm.d_scale.get(), lm.d_m.get());
+    if (first) lm.d_scale = std::move(d_scale);
+    if (!rc) rc = launch_mass_total(c, lm.d_m.get(), &m1);
+    if (rc) {
+        (void)hipStreamSynchronize(c->stream);
+        return rc;
+    }
+    *mass_before = m0;
+    *mass_after = m1;
+    *n_scaled = (int64_t)res[2];
+    *factor_max = res[1];
+    return FEMCY_OK;
+}
+
+int femcy_lumped_mass_get_scaling(femcy_ctx* ctx, int32_t lumped_id, double* out) {
+    CTX_OR_FAIL(ctx);
+    EXPLICIT_SINGLE_RANK_OR_FAIL("femcy_lumped_mass_get_scaling");
+    FEMCY_OBJECT_OR_FAIL(lm, c->lumped_masses, lumped_id, "lumped mass");
+    FEMCY_REQUIRE(out, TEXT_NULL_OUTPUT);
+    if (!lm.d_scale.get()) {
+        std::fill(out, out + c->ne, 1.0);
+        return FEMCY_OK;
+    }
+    return download(c, out, lm.d_scale.get(), sizeof(double) * c->ne);
+}
+
 int femcy_explicit_create(femcy_ctx* ctx, int32_t lumped_id, int32_t ndofsets, const int32_t* dofset_ids, int32_t* id_out) {
     CTX_OR_FAIL(ctx);
     EXPLICIT_SINGLE_RANK_OR_FAIL("femcy_explicit_create");

@@ -291,6 +291,78 @@ __global__ void __launch_bounds__(XBS) k_explicit_clock(int np, const double* __
     }
 }
 
+// ------------------------------------------------------------------------------- fixed mass scaling
+// The factors of femcy_lumped_mass_scale, one thread per element in the launch shape of k_explicit_bound: omega_e^2 is
+// explicit_bound_element at U = 0 with the element's current shares, the call femcy_explicit_element_bound makes at u = 0, so
+// the same bits; k_e is mass_scale_factor (element_math.hpp).  np = gridDim.x partials of each of
+//   part[0 .. np)      max omega_e^2, NaN counted as infinity
+//   part[np .. 2 np)   max k_e, anything but a finite positive factor counted as infinity
+//   part[2 np .. 3 np) the number of elements with k_e != 1 (a sum of 0.0 / 1.0: exact)
+// through block_reduce, in a fixed order.  measure: only the first (FEMCY_MS_UNIFORM needs max_e omega_e^2 before any factor
+// is known), fac is not written.
+template <int NPE, int DM>
+__global__ void __launch_bounds__(XBS) k_mass_scale_factors(int32_t ne, int32_t nGP, const double* __restrict__ nodes,
+                                                            const int32_t* __restrict__ elems,
+                                                            const double* __restrict__ dN, const double* __restrict__ w,
+                                                            int mat_kind, const double* __restrict__ C, double p0, double p1,
+                                                            const double* __restrict__ me_in, double s_C, double w2max,
+                                                            double factor, double tau, int type, bool measure,
+                                                            double* __restrict__ fac, double* __restrict__ part) {
+    __shared__ double sm[XBS / 64];
+    const int32_t e = blockIdx.x * blockDim.x + threadIdx.x;
+    double best = 0.0, kbest = 0.0, scaled = 0.0;
+    if (e < ne) {
+        double X[NPE][DM], U[NPE][DM], me[NPE], g, w2;
+#pragma unroll
+        for (int a = 0; a < NPE; ++a) {
+            load_row<DM>(nodes + (int64_t)elems[(int64_t)e * NPE + a] * DM, X[a]);
+#pragma unroll
+            for (int i = 0; i < DM; ++i) U[a][i] = 0.0;
+            me[a] = me_in[(int64_t)e * NPE + a];
+        }
+        explicit_bound_element<NPE, DM>(X, U, nGP, dN, w, mat_kind, C, p0, p1, me, s_C, g, w2);
+        best = mass_scale_nan_to_inf(w2);
+        if (!measure) {
+            const double k = mass_scale_factor(w2, w2max, factor, tau, type);
+            fac[e] = k;
+            kbest = mass_scale_bad_to_inf(k);
+            scaled = k != 1.0 ? 1.0 : 0.0;
+        }
+    }
+    const int np = gridDim.x;
+    const double r = block_reduce<true>(best, sm);
+    if (threadIdx.x == 0) part[blockIdx.x] = r;
+    if (measure) return;
+    const double rk = block_reduce<true>(kbest, sm);
+    const double rs = block_reduce<false>(scaled, sm);
+    if (threadIdx.x == 0) {
+        part[np + blockIdx.x] = rk;
+        part[2 * np + blockIdx.x] = rs;
+    }
+}
+
+// the apply pass: me[e][a] *= fac[e] over the ne * npe contiguous shares; the thread of a = 0 also carries the element's
+// cumulative factor on (first: the first call on this lumped mass, cum is not read)
+__global__ void __launch_bounds__(XBS) k_mass_scale_apply(int64_t nshares, int32_t npe, const double* __restrict__ fac,
+                                                          bool first, double* __restrict__ me, double* __restrict__ cum) {
+    const int64_t i = (int64_t)blockIdx.x * XBS + threadIdx.x;
+    if (i >= nshares) return;
+    const int64_t e = i / npe;
+    const double k = fac[e];
+    me[i] *= k;
+    if (i == e * npe) cum[e] = first ? k : cum[e] * k;
+}
+
+// partial sums of the nodal masses, the pattern of k_explicit_energy: thread t of workgroup b takes the nodes
+// b * 256 + t + k * (workgroups * 256), k ascending
+__global__ void __launch_bounds__(XBS) k_mass_total(int32_t nn, const double* __restrict__ m, double* __restrict__ part) {
+    __shared__ double sm[XBS / 64];
+    double acc = 0.0;
+    for (int64_t a = (int64_t)blockIdx.x * XBS + threadIdx.x; a < nn; a += (int64_t)gridDim.x * XBS) acc += m[a];
+    const double r = block_reduce<false>(acc, sm);
+    if (threadIdx.x == 0) part[blockIdx.x] = r;
+}
+
 // ------------------------------------------------------------------------------- host launchers
 static int reduction_grid(int64_t items) {
     return (int)std::max<int64_t>(1, std::min<int64_t>((items + XBS - 1) / XBS, 1024));   // <= MAX_PARTIALS partials
@@ -421,6 +493,51 @@ int launch_explicit_bound_max(Ctx* c, const double* d_part, double* out) {
 
 int launch_explicit_clock(Ctx* c, const double* d_part, ExplicitClock* d_clk) {
     hipLaunchKernelGGL(k_explicit_clock, dim3(1), dim3(XBS), 0, c->stream, explicit_bound_partials(c), d_part, d_clk);
+    FEMCY_HIP(hipGetLastError());
+    return FEMCY_OK;
+}
+
+int launch_mass_total(Ctx* c, const double* d_m, double* out) {
+    const int g = reduction_grid(c->nn);
+    hipLaunchKernelGGL(k_mass_total, dim3(g), dim3(XBS), 0, c->stream, c->nn, d_m, c->d_part1);
+    hipLaunchKernelGGL((k_explicit_final<false>), dim3(1), dim3(XBS), 0, c->stream, g, c->d_part1, c->d_part2);
+    FEMCY_HIP(hipGetLastError());
+    return fetch_scalar(c, c->d_part2, out);
+}
+
+int launch_mass_scale_factors(Ctx* c, const double* d_me, double s_C, double w2max, double factor, double tau, int type,
+                              bool measure, double* d_fac, double* d_part, double* out) {
+    const int np = explicit_bound_partials(c);
+    size_t tm = timing_begin(c, T_GEOM);
+    const bool launched = dispatch_element(c->npe, c->dm, [&](auto npe, auto dm) {
+        hipLaunchKernelGGL((k_mass_scale_factors<npe(), dm()>), dim3(np), dim3(XBS), 0, c->stream, c->ne, c->nGP, c->d_nodes,
+                           c->d_elems, c->d_dN, c->d_w, c->mat_kind, c->d_C, c->mat_params[0], c->mat_params[1], d_me, s_C,
+                           w2max, factor, tau, type, measure, d_fac, d_part);
+    });
+    timing_end(c, tm);
+    if (!launched) {
+        set_error("no mass-scaling kernel instantiated for npe=%d dm=%d", c->npe, c->dm);
+        return FEMCY_ENOKERNEL;
+    }
+    double* res = c->d_part2;
+    hipLaunchKernelGGL((k_explicit_final<true>), dim3(1), dim3(XBS), 0, c->stream, np, d_part, res);
+    if (!measure) {
+        hipLaunchKernelGGL((k_explicit_final<true>), dim3(1), dim3(XBS), 0, c->stream, np, d_part + np, res + 1);
+        hipLaunchKernelGGL((k_explicit_final<false>), dim3(1), dim3(XBS), 0, c->stream, np, d_part + 2 * (size_t)np, res + 2);
+    }
+    FEMCY_HIP(hipGetLastError());
+    const int nres = measure ? 1 : 3;
+    FEMCY_HIP(hipMemcpyAsync(c->h_scalar, res, sizeof(double) * nres, hipMemcpyDeviceToHost, c->stream));
+    FEMCY_HIP(hipStreamSynchronize(c->stream));
+    for (int k = 0; k < nres; ++k) out[k] = c->h_scalar[k];
+    return FEMCY_OK;
+}
+
+int launch_mass_scale_apply(Ctx* c, const double* d_fac, bool first, double* d_me, double* d_cum, double* d_m) {
+    const int64_t nshares = (int64_t)c->ne * c->npe;
+    const unsigned grid = (unsigned)((nshares + XBS - 1) / XBS);
+    hipLaunchKernelGGL(k_mass_scale_apply, dim3(grid), dim3(XBS), 0, c->stream, nshares, c->npe, d_fac, first, d_me, d_cum);
+    launch_node_sum(c, d_me, d_m);
     FEMCY_HIP(hipGetLastError());
     return FEMCY_OK;
 }

@@ -67,6 +67,7 @@ struct LumpedMass {
     double rho = 0.0;        // the density it was created with: rho_0 of the bulk viscosity
     std::vector<double> m;   // [nn] HRZ-lumped nodal masses
     std::vector<double> me;  // [ne][npe] the element shares they were summed from (the element-by-element increment)
+    std::vector<double> scale;  // [ne] cumulative factors of femcy_lumped_mass_scale; empty before its first call: all 1
 };
 struct Explicit {
     std::vector<double> minv;   // [n] inverse mass per scalar DOF, 0 on the constrained DOFs
@@ -1327,6 +1328,64 @@ double block_reduce_sum(double (&x)[256]) {
     return r;
 }
 
+// the device's two sum reductions over n items (k_explicit_energy / k_mass_total, then k_explicit_final<false>): 256 strided
+// partial sums per workgroup, at most 1024 workgroups, then one workgroup; add(acc, i) folds item i into a thread's sum
+template <class Add>
+double device_order_sum(int64_t n, Add add) {
+    const int64_t g = std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 1024));
+    std::vector<double> part((size_t)g);
+#pragma omp parallel for schedule(static)
+    for (int64_t b = 0; b < g; ++b) {
+        double x[256];
+        for (int t = 0; t < 256; ++t) {
+            double acc = 0.0;
+            for (int64_t a = b * 256 + t; a < n; a += g * 256) acc = add(acc, a);
+            x[t] = acc;
+        }
+        part[(size_t)b] = block_reduce_sum(x);
+    }
+    double x[256];
+    for (int t = 0; t < 256; ++t) {
+        double acc = 0.0;
+        for (int64_t i = t; i < g; i += 256) acc += part[(size_t)i];
+        x[t] = acc;
+    }
+    return block_reduce_sum(x);
+}
+
+// the device's k_mass_scale_factors: fac[e] = k_e from omega_e^2 at u = 0 with the element's current shares
+// (csrc/element_math.hpp: explicit_bound_element, mass_scale_factor); -> max omega_e^2, max k_e (each with what is not a
+// usable number counted as infinity), the number of k_e != 1.  fac null: the measuring pass, max omega_e^2 alone
+template <int NPE, int DM>
+void mass_scale_factors(femcy_ctx* c, const double* me_all, double s_C, double w2max, double factor, double tau, int type,
+                        double* fac, double (&res)[3]) {
+    double best = 0.0, kbest = 0.0;
+    int64_t scaled = 0;
+#pragma omp parallel for schedule(static) reduction(max : best, kbest) reduction(+ : scaled)
+    for (int32_t e = 0; e < c->ne; ++e) {
+        double X[NPE][DM], U[NPE][DM], me[NPE], g, w2;
+        for (int a = 0; a < NPE; ++a) {
+            const int32_t nd = c->elems[(int64_t)e * NPE + a];
+            for (int i = 0; i < DM; ++i) {
+                X[a][i] = c->nodes[(int64_t)nd * DM + i];
+                U[a][i] = 0.0;
+            }
+            me[a] = me_all[(int64_t)e * NPE + a];
+        }
+        explicit_bound_element<NPE, DM>(X, U, c->nGP, c->dN.data(), c->w.data(), c->mat_kind, c->h_C, c->mat_params[0],
+                                        c->mat_params[1], me, s_C, g, w2);
+        best = std::fmax(best, mass_scale_nan_to_inf(w2));
+        if (!fac) continue;
+        const double k = mass_scale_factor(w2, w2max, factor, tau, type);
+        fac[e] = k;
+        kbest = std::fmax(kbest, mass_scale_bad_to_inf(k));
+        scaled += k != 1.0;
+    }
+    res[0] = best;
+    res[1] = kbest;
+    res[2] = (double)scaled;
+}
+
 // nsteps steps from a started state, as the device's explicit_steps runs them: the first drift, then per step the element
 // pass and the node pass.  A fixed run (clock null) takes dt and the load scale scale0 + k dscale from the caller; an
 // automatic one bounds the element frequencies and ticks its clock between the two passes, which then gives both.
@@ -1381,6 +1440,59 @@ int femcy_lumped_mass_get(femcy_ctx* ctx, int32_t id, double* out) {
     FEMCY_OBJECT_OR_FAIL(lm, c->lumped_masses, id, "lumped mass");
     FEMCY_REQUIRE(out, TEXT_NULL_OUTPUT);
     std::copy(lm.m.begin(), lm.m.end(), out);
+    return FEMCY_OK;
+}
+
+// the device's femcy_lumped_mass_scale: the total mass, the factors (FEMCY_MS_UNIFORM: the maximum first), and only once
+// omega_e^2 and every factor are finite and positive the shares, the node sums and the total again
+int femcy_lumped_mass_scale(femcy_ctx* ctx, int32_t lumped_id, double s_C, double factor, double dt, int32_t type,
+                            double* mass_before, double* mass_after, int64_t* n_scaled, double* factor_max) {
+    CTX_OR_FAIL(ctx);
+    READY_OR_FAIL();
+    FEMCY_TRY(check_lumped_mass_scale(c, lumped_id, s_C, factor, dt, type, mass_before, mass_after, n_scaled, factor_max));
+    LumpedMass& lm = c->lumped_masses[lumped_id];
+    const double sc = dt != 0.0 ? s_C : 1.0;      // without dt the estimate serves the test for broken elements alone
+    std::vector<double> fac((size_t)c->ne);
+    double res[3] = {0.0, 0.0, 0.0}, w2max = 0.0;
+    auto pass = [&](double* out) {
+        return dispatch_element(c->npe, c->dm, [&](auto npe, auto dm) {
+            mass_scale_factors<npe(), dm()>(c, lm.me.data(), sc, w2max, factor, dt, type, out, res);
+        });
+    };
+    const double m0 = device_order_sum(c->nn, [&](double acc, int64_t a) { return acc + lm.m[(size_t)a]; });
+    if (dt != 0.0 && type == FEMCY_MS_UNIFORM) {
+        if (!pass(nullptr)) return no_kernel(c, "mass-scaling");
+        w2max = res[0];
+    }
+    if (std::isfinite(w2max) && !pass(fac.data())) return no_kernel(c, "mass-scaling");
+    if (!std::isfinite(w2max) || !std::isfinite(res[0]) || !std::isfinite(res[1])) {
+        set_error("femcy_lumped_mass_scale: an element frequency or a factor is not finite and positive (max omega_e^2 = %g, "
+                  "max factor = %g): a broken element; the lumped mass is unchanged", res[0], res[1]);
+        return FEMCY_ENUMERIC;
+    }
+    if (lm.scale.empty()) lm.scale.assign((size_t)c->ne, 1.0);
+    const int npe = c->npe;
+#pragma omp parallel for schedule(static)
+    for (int32_t e = 0; e < c->ne; ++e) {
+        for (int a = 0; a < npe; ++a) lm.me[(size_t)e * npe + a] *= fac[(size_t)e];
+        lm.scale[(size_t)e] *= fac[(size_t)e];
+    }
+#pragma omp parallel for schedule(static)
+    for (int32_t a = 0; a < c->nn; ++a) node_sum(c, a, lm.me.data(), 1, &lm.m[a]);
+    *mass_before = m0;
+    *mass_after = device_order_sum(c->nn, [&](double acc, int64_t a) { return acc + lm.m[(size_t)a]; });
+    *n_scaled = (int64_t)res[2];
+    *factor_max = res[1];
+    return FEMCY_OK;
+}
+int femcy_lumped_mass_get_scaling(femcy_ctx* ctx, int32_t lumped_id, double* out) {
+    CTX_OR_FAIL(ctx);
+    FEMCY_OBJECT_OR_FAIL(lm, c->lumped_masses, lumped_id, "lumped mass");
+    FEMCY_REQUIRE(out, TEXT_NULL_OUTPUT);
+    if (lm.scale.empty())
+        std::fill(out, out + c->ne, 1.0);
+    else
+        std::copy(lm.scale.begin(), lm.scale.end(), out);
     return FEMCY_OK;
 }
 

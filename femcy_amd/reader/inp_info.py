@@ -33,7 +33,9 @@ under direct user control) -> procedure = "explicit", dynamic = {"direct_user_co
 time_incs whose increments are None until the driver has estimated one; `element by element` in place of `direct user
 control` -> dynamic_auto = True: the driver re-estimates the increment in every step.  `*Bulk Viscosity` (data `b1, b2`,
 defaults 0.06, 1.2) inside an explicit step -> bulk_viscosity = (b1, b2), None without the keyword; `*Damping, alpha=` in the
-`*Material` block -> damping_alpha (read_damping).  A deck with `*Static` has procedure = "static" and reads as before.
+`*Material` block -> damping_alpha (read_damping).  `*Fixed Mass Scaling[, factor=][, dt=][, type=]` inside an explicit step ->
+mass_scaling = {"factor", "dt", "type"}, None without the keyword (read_mass_scaling).  A deck with `*Static` has procedure =
+"static" and reads as before.
 """
 import sys
 from typing import Dict, List
@@ -141,6 +143,7 @@ class InpInfo(InpInfoBase):
         self.procedure, self.dynamic, self.amplitude = self.read_procedure(file)
         self.time_incs = self.read_time_inc(file)
         self.bulk_viscosity, self.damping_alpha = self.read_damping(file)
+        self.mass_scaling = self.read_mass_scaling(file)
         self.initial_velocity_info = self.read_initial_velocity(file)
 
     # ------------------------------------------------------------------ nodes and elements
@@ -575,6 +578,46 @@ class InpInfo(InpInfoBase):
                 raise ValueError("*Damping has not been supported outside a *Dynamic, explicit step: the implicit "
                                  "integrator is the undamped Newmark scheme")
         return bulk, alpha
+
+    def read_mass_scaling(self, fileName):
+        """`*Fixed Mass Scaling[, factor=f][, dt=tau][, type=uniform | below min | set equal dt]` inside a `*Dynamic, explicit`
+        step -> {"factor": f or None, "dt": tau or None, "type"}, None without the keyword.  The whole model is scaled once,
+        at the beginning of the step: every element's mass by f, and / or by what brings its estimated stable increment to tau
+        (`below min`, the default: only the elements below tau; `set equal dt`: all of them, which may lighten some;
+        `uniform`: one factor, the smallest increment becomes tau).  Refused: `elset=` (whole model only), `*Variable Mass
+        Scaling`, neither `factor` nor `dt`, values that are not positive, `type=` without `dt=`, an unknown type, and the
+        keyword in a deck whose procedure is not "explicit"."""
+        scaling = None
+        for line, block in _deck(fileName).keywords():
+            fields = [t.strip() for t in line.split(",")]
+            key = " ".join(fields[0].lower().split())
+            params = {t.split("=")[0].strip().lower(): t.split("=")[1].strip() for t in fields[1:] if "=" in t}
+            if key == "*variable mass scaling":
+                raise ValueError("*Variable Mass Scaling has not been supported: the mass is scaled once, at the beginning of "
+                                 "the step (*Fixed Mass Scaling)")
+            if key != "*fixed mass scaling":
+                continue
+            if "elset" in params:
+                raise ValueError("*Fixed Mass Scaling, elset={} has not been supported: the whole model is scaled".format(
+                    params["elset"]))
+            if "factor" not in params and "dt" not in params:
+                raise ValueError("*Fixed Mass Scaling needs factor=, dt= or both")
+            factor = float(params["factor"]) if "factor" in params else None
+            dt = float(params["dt"]) if "dt" in params else None
+            for name, val in (("factor", factor), ("dt", dt)):
+                if val is not None and not (val > 0.0 and np.isfinite(val)):
+                    raise ValueError("*Fixed Mass Scaling, {}={} is refused (it must be positive)".format(name, params[name]))
+            if "type" in params and dt is None:
+                raise ValueError("*Fixed Mass Scaling, type={} needs dt=: the type says how a target increment is "
+                                 "met".format(params["type"]))
+            kind = " ".join(params.get("type", "below min").lower().split())
+            if kind not in ("uniform", "below min", "set equal dt"):
+                raise ValueError("*Fixed Mass Scaling, type={} has not been supported (uniform, below min and set equal dt "
+                                 "are)".format(params["type"]))
+            scaling = {"factor": factor, "dt": dt, "type": kind}
+        if scaling is not None and self.procedure != "explicit":
+            raise ValueError("*Fixed Mass Scaling has not been supported outside a *Dynamic, explicit step")
+        return scaling
 
     def read_initial_velocity(self, fileName):
         """`*Initial Conditions, type=VELOCITY` data lines `nset-or-node-label, dof, value` -> [{"node_set", "dof",

@@ -50,7 +50,7 @@ def deck_view(inp) -> SimpleNamespace:
         expansion=opt("expansion"), temperature_info=opt("temperature_info"),
         initial_velocity_info=opt("initial_velocity_info") or [], dynamic=opt("dynamic"),
         dynamic_auto=bool(opt("dynamic_auto", False)), bulk_viscosity=opt("bulk_viscosity"),
-        damping_alpha=float(opt("damping_alpha", 0.0) or 0.0))
+        damping_alpha=float(opt("damping_alpha", 0.0) or 0.0), mass_scaling=opt("mass_scaling"))
 
 
 class LoadSchedule:
@@ -697,7 +697,11 @@ class System_of_equations:
         `*Bulk Viscosity` and `*Damping, alpha=` (`inp.bulk_viscosity`, `inp.damping_alpha`) go to the integrator once
         (`femcy_explicit_set_damping`, M_d from `dilatational_modulus`); the fixed increment estimated from the matrix is
         then 2 / omega x (sqrt(1 + xi^2) - xi) with xi = b1 + alpha / (2 omega), which `stable_dt` reports -- the quadratic
-        bulk term cannot be known in advance and is left to `scale factor`; `direct user control` is taken as given."""
+        bulk term cannot be known in advance and is left to `scale factor`; `direct user control` is taken as given.
+        `*Fixed Mass Scaling` (`inp.mass_scaling`) scales the element masses once, between the lumped mass and the integrator
+        (`femcy_lumped_mass_scale` with `material_stiffness()`); `mass_scaling` keeps {"mass0", "mass1", "scaled_elements",
+        "max_factor"} (None without the keyword).  Both increment estimates and the kinetic energy then see the scaled
+        masses.  The loads do not: body forces stay those of the deck's density, and so does rho_0 of the bulk viscosity."""
         deck = deck_view(inp)
         self._transient_gate(deck, "*Dynamic, explicit step", "lumped mass")
         if deck.temperature_info is not None:
@@ -709,6 +713,13 @@ class System_of_equations:
         self._external_force(loads, 1.0)                              # rhs = f at scale 1, once
         held = [self._dofset(bc["node_set"], bc["dof"]) for bc in loads.dirichletBCs]
         self.lumped_mass = ctx.lumped_mass(self.ELE, deck.density)
+        self.mass_scaling = None
+        if deck.mass_scaling is not None:                             # before the integrator: its inverse mass is derived once
+            ms = deck.mass_scaling
+            self.mass_scaling = ctx.lumped_mass_scale(self.lumped_mass, self.material_stiffness(), ms["factor"], ms["dt"],
+                                                      ms["type"])
+            self._say("fixed mass scaling: {scaled_elements} elements scaled, largest factor {max_factor}, total mass "
+                      "{mass0} -> {mass1}".format(**self.mass_scaling))
         self.explicit = ex = ctx.explicit(self.lumped_mass, held)
         bulk, alpha = deck.bulk_viscosity, deck.damping_alpha
         b1, b2 = bulk if bulk is not None else (0.0, 0.0)

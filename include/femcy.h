@@ -523,6 +523,31 @@ int femcy_explicit_auto_state(femcy_ctx* ctx, int32_t id, double* t, double* h_l
  * All four zero: the undamped launches and bits.  Refused with FEMCY_EINVAL, the context stays usable: an unknown id, a
  * value that is not finite or negative, M_d <= 0 while b1 or b2 is not zero, and once femcy_comm_init has run. */
 int femcy_explicit_set_damping(femcy_ctx* ctx, int32_t id, double alpha, double b1, double b2, double M_d);
+/* Fixed mass scaling (*Fixed Mass Scaling, whole model): the element shares m_a^e of a lumped mass are multiplied by one
+ * factor k_e per element, before an integrator is made from it, and the nodal masses are summed again.  omega_e^2 above is
+ * linear in 1 / m_a^e, so k_e divides it exactly and a target increment is met in closed form, in the project's own
+ * estimate.  With omega_e^2 the UNDAMPED estimate at u = 0 from the element's current shares and s_C, dt_e = 2 / omega_e:
+ *   factor = f alone                      k_e = f
+ *   dt = tau, FEMCY_MS_BELOW_MIN          k_e = max(1, omega_e^2 tau^2 / 4)        only elements with dt_e < tau grow
+ *   dt = tau, FEMCY_MS_SET_EQUAL_DT       k_e = omega_e^2 tau^2 / 4                every dt_e becomes tau; k_e < 1 lightens
+ *   dt = tau, FEMCY_MS_UNIFORM            k_e = max_e omega_e^2 tau^2 / 4          one factor, the smallest dt_e becomes tau
+ *   factor and dt                         factor first: omega_e^2 / f enters the dt rule, k_e is the product
+ * (0 stands for "not given"; type is ignored without dt).  A second call compounds.  Afterwards femcy_lumped_mass_get
+ * returns the scaled nodal masses, both increment estimates and the kinetic energy see them, and no stepping kernel changes.
+ * *mass_before / *mass_after: the sum of the nodal masses in a fixed order, *n_scaled: elements with k_e != 1, *factor_max:
+ * max_e k_e of this call.  femcy_lumped_mass_get_scaling: the cumulative k_e [ne], 1.0 before any call.
+ * DEVIATION from Abaqus: rho_0 of the bulk viscosity stays the density the lumped mass was created with (Abaqus uses the
+ * scaled density).  The lagged estimate xi_e = b1 + ... then overstates the damping fraction of a scaled element: the safe
+ * side.  Body forces are the caller's and are not scaled either, as in Abaqus.
+ * FEMCY_ENUMERIC, the lumped mass untouched: an omega_e^2 or a factor that is NaN, infinite or (the factor) not positive (a
+ * broken element).  Refused with FEMCY_EINVAL, the context stays usable: an unknown id, null outputs, factor and dt both 0,
+ * either negative or not finite, an unknown type, dt with s_C not finite and positive, a lumped mass that an integrator
+ * already refers to (scale before femcy_explicit_create: minv is derived once), and once femcy_comm_init has run. */
+enum femcy_mass_scaling { FEMCY_MS_BELOW_MIN = 0, FEMCY_MS_SET_EQUAL_DT = 1, FEMCY_MS_UNIFORM = 2 };
+int femcy_lumped_mass_scale(femcy_ctx* ctx, int32_t lumped_id, double s_C, double factor /*0: none*/, double dt /*0: none*/,
+                            int32_t type /*femcy_mass_scaling*/, double* mass_before, double* mass_after, int64_t* n_scaled,
+                            double* factor_max);
+int femcy_lumped_mass_get_scaling(femcy_ctx* ctx, int32_t lumped_id, double* out /*[ne]*/);
 /* compute_Ad (conjugateGradientSolver.py:53-58): vec[y] = K vec[x] */
 int femcy_spmv(femcy_ctx* ctx, int x_vec, int y_vec);
 /* ConjugateGradientSolver_rowMajor.re_init + solve (conjugateGradientSolver.py:32-51, 103-127):
