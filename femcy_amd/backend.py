@@ -49,6 +49,7 @@ OPT_NODE_ORDER = 14      # 0 = caller's numbering, 1 (default) = measured choice
 OPT_PCG_PERSIST = 11     # 1 (default) = persistent one-launch PCG (single rank, <= ~7e5 DOF, matrix <= Infinity Cache); 2 = any matrix size
 OPT_PCG_PERSIST_MULTI = 12   # 1 (default) = the persistent kernel across ranks once the mailboxes are exchanged and agreed
 OPT_PCG_SMALL = 10       # 1 (default) = one persistent launch per solve for systems that fit LDS
+TUNE_SMALL_REG_ROWS = 108    # small-system PCG: block rows per wave kept in registers (-1 default: a wave's share of the longest row; femcy.h)
 TUNE_PERSIST_VARIANT = 109   # persistent PCG variant bits (-1 default; femcy.h)
 TUNE_SKIP_OCCUPANCY_CHECK = 111
 TUNE_BARRIER_SPIN_LIMIT = 112

@@ -62,13 +62,14 @@ TUNE_SPMV_NT, TUNE_VEC_NT = 102, 103
 
 
 # ------------------------------------------------------------------------------------------------- the split, restated
-def layout(rowlen):
-    """-> (node_of [nslices * 64], -1 = padding; slice_len [nslices]) of build_pattern with the caller's numbering"""
+def layout(rowlen, sigma=SIGMA):
+    """-> (node_of [nslices * 64], -1 = padding; slice_len [nslices]) of build_pattern with the caller's numbering (sigma:
+    the sort window, FEMCY_OPT_SELL_SIGMA, a multiple of 64)"""
     nn = len(rowlen)
     ns = -(-nn // SLICE)
     node_of = -np.ones(ns * SLICE, dtype=np.int64)
-    for a0 in range(0, nn, SIGMA):
-        idx = np.arange(a0, min(nn, a0 + SIGMA))
+    for a0 in range(0, nn, sigma):
+        idx = np.arange(a0, min(nn, a0 + sigma))
         node_of[a0:a0 + len(idx)] = idx[np.argsort(-rowlen[idx], kind="stable")]
     L = np.where(node_of >= 0, rowlen[np.maximum(node_of, 0)], 0).reshape(ns, SLICE).max(axis=1)
     return node_of, L
@@ -282,12 +283,17 @@ class Case:
     """one row on one backend: the context with K assembled and constrained, the exported K, the restated split, the
     vectors and the long-double references (computed once)"""
 
+    mesh = staticmethod(build)                                     # (a further table may bring its own meshes)
+
     def __init__(self, row, backend):
         self.row, self.backend = row, backend
-        nodes, el, ELE, mat, cons = build(row)
+        nodes, el, ELE, mat, cons = self.mesh(row)
         self.dm = nodes.shape[1]
+        self.sigma = getattr(row, "sigma", SIGMA)                  # (a further table may narrow the sort window)
         ctx = self.ctx = be.Context(0, backend=backend)
         ctx.set_option(be.OPT_NODE_ORDER, 0)                       # the caller's numbering: what layout() restates
+        if self.sigma != SIGMA:
+            ctx.set_option(be.OPT_SELL_SIGMA, self.sigma)
         ctx.set_mesh(nodes, el)
         ctx.set_element(ELE)
         ctx.set_material(mat)
@@ -298,7 +304,7 @@ class Case:
         self.K.sort_indices()
         self.n, self.nn, self.cons = ctx.n, len(nodes), cons
         self.rowlen = np.diff(ctx.get_K_bsr().indptr)
-        self.node_of, self.L = layout(self.rowlen)
+        self.node_of, self.L = layout(self.rowlen, self.sigma)
         self.absK = None
         rng = np.random.default_rng(7)
         x0 = rng.standard_normal(self.n)
