@@ -224,7 +224,8 @@ FEMCY_HD void kblock_add<2>(const double* __restrict__ ga, const double* __restr
 //   neo-Hookean of neo_hookean.py:66-77 (sigma = 2 C1/J (b - I) + 2 D1 (J-1) I):
 //                                          c_ijkl = lambda' d_ij d_kl + mu' (d_ik d_jl + d_il d_jk),
 //                                          mu' = 2 C1/J - 2 D1 (J-1),  lambda' = 2 D1 (2J-1)
-// checked against central differences of femcy_internal_force (tests/test_gpu_tangent.py).
+// checked against central differences of femcy_internal_force (tests/test_gpu_tangent.py) and, entry by entry on every
+// element family and both branches, against a long-double complex-step derivative (tests/tangent_shapes.py).
 template <int DM>
 FEMCY_HD void kblock_consistent(const double* __restrict__ ga, const double* __restrict__ gb,
                                                   const double* __restrict__ Fp, const double* __restrict__ Sp,

@@ -699,7 +699,8 @@ int femcy_assemble_K(femcy_ctx* ctx, int u_vec) {
         du = c->d_vec[u_vec];
     }
     // the consistent tangent needs F and sigma of this state: the element pass then also evaluates the material
-    if (c->opt_tangent == 1) c->gp_lazy = false;
+    // (sigma is then no longer what femcy_compute_strain_stress(large = 0) left: femcy_thermal_stress must not correct it)
+    if (c->opt_tangent == 1) c->gp_lazy = c->post_small = false;
     int rc = launch_geom(c, du, c->opt_tangent == 1 ? (GEOM_DSDX | GEOM_F | GEOM_SIGMA) : GEOM_DSDX);
     if (rc) return rc;
     if ((rc = launch_assemble(c))) return rc;

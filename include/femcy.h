@@ -162,7 +162,15 @@ enum femcy_option {
                                    neo_hookean.py:62-64, 79-81) + geometric stiffness (grad N_a . sigma . grad N_b) I.
                                    An EXTENSION outside the parity runs: Newton iterates differ from the
                                    reference's (they converge quadratically).  Isotropic 3-D, plane-strain and
-                                   neo-Hookean materials; not available for plane stress. */
+                                   neo-Hookean materials; not available for plane stress.
+                                   What it leaves behind: with 1, femcy_assemble_K(u) evaluates the material at vec[u], so
+                                   afterwards FEMCY_GP_F and FEMCY_GP_SIGMA hold F and the Cauchy stress of the ASSEMBLED
+                                   state (u_vec = -1: I and 0) and an earlier force evaluation's F / sigma, pending or
+                                   read, are gone; with 0 the assembly leaves them those of the last force evaluation.
+                                   vec[f] of that evaluation is not touched either way, and the next
+                                   femcy_internal_force / femcy_residual_and_K makes F and sigma its own again,
+                                   whatever the option was in between: every call reads the option as it is then.
+                                   femcy_thermal_stress does not correct the stress such an assembly left. */
 
     /* ---- tuning and test knobs.  Not needed by a caller of the path; the tests and the tools under tools/ use them
      * to force code paths and to measure alternatives.  None of them changes results beyond summation order. */

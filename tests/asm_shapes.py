@@ -334,6 +334,40 @@ def _B(g):
 Ref = collections.namedtuple("Ref", "K A Arow A0 dsdx Adsdx vol Avol F AF sig Asig fe f Af")
 
 
+def reducer(lay, el, dt):
+    """-> reduce(v): element blocks v [ne, npe, npe, dm, dm] summed into the exported pattern (the order of lay.brow / lay.bcol)
+    by a sort and np.add.reduceat, ascending (e, la, lb) inside a block; reduce.slot: the block of every (e, la, lb)"""
+    dm, npe, nn = lay.dm, lay.npe, lay.nn
+    a = np.repeat(el, npe, axis=1).ravel().astype(np.int64)
+    b = np.tile(el, (1, npe)).ravel().astype(np.int64)
+    keys = lay.brow * nn + lay.bcol
+    slot = np.searchsorted(keys, a * nn + b)
+    order = np.argsort(slot, kind="stable")                      # ascending (e, la, lb) inside a block
+    starts = np.searchsorted(slot[order], np.arange(len(keys)))
+    have = lay.contributors > 0
+
+    def reduce(v):
+        out = np.zeros((len(keys), dm, dm), dt)
+        if len(order):
+            out[have] = np.add.reduceat(v.reshape(-1, dm, dm)[order], starts[have], axis=0)   # (blocks nobody names: no segment)
+        return out
+
+    reduce.slot = slot.reshape(el.shape[0], npe, npe)
+    return reduce
+
+
+def row_sums(lay, Amag):
+    """Amag with the diagonal blocks replaced by sum_(b != a) A_ab: what a diagonal taken from the row sum is made of"""
+    diag = lay.brow == lay.bcol
+    off = Amag.copy()
+    off[diag] = 0
+    Arow = Amag.copy()
+    rs = np.zeros((lay.nn,) + Amag.shape[1:], Amag.dtype)
+    np.add.at(rs, lay.brow, off)
+    Arow[diag] = rs
+    return Arow
+
+
 def reference(lay, nodes, el, ELE, mat, u, dt=LD, cubic=False, force=True):
     """everything in dtype dt.  K, A [nnzb, dm, dm] in the order of lay.brow / lay.bcol; Arow: A with the diagonal blocks
     replaced by sum_(b != a) A_ab; cubic: K from the geometric sum S, the constants applied once per block"""
@@ -364,20 +398,7 @@ def reference(lay, nodes, el, ELE, mat, u, dt=LD, cubic=False, force=True):
     mags = (np.einsum("egkai,egkbj,eg->eabij", aB, aCB, Avol)
             + np.einsum("egkai,egkbj,eg->eabij", gB, aCB, np.abs(vol))
             + np.einsum("egkai,egkbj,eg->eabij", aB, np.einsum("kl,eglbj->egkbj", aC, gB), np.abs(vol)))
-    a = np.repeat(el, npe, axis=1).ravel().astype(np.int64)
-    b = np.tile(el, (1, npe)).ravel().astype(np.int64)
-    keys = lay.brow * nn + lay.bcol
-    slot = np.searchsorted(keys, a * nn + b)
-    order = np.argsort(slot, kind="stable")                      # ascending (e, la, lb) inside a block
-    starts = np.searchsorted(slot[order], np.arange(len(keys)))
-    have = lay.contributors > 0
-
-    def reduce(v):
-        out = np.zeros((len(keys), dm, dm), dt)
-        if len(order):
-            out[have] = np.add.reduceat(v.reshape(-1, dm, dm)[order], starts[have], axis=0)   # (blocks nobody names: no segment)
-        return out
-
+    reduce = reducer(lay, el, dt)
     K, Amag = reduce(blocks), reduce(mags)
     A0 = reduce(np.einsum("egkai,egkbj,eg->eabij", aB, aCB, np.abs(vol)))      # the sum's own terms alone
     if cubic:
@@ -387,13 +408,7 @@ def reference(lay, nodes, el, ELE, mat, u, dt=LD, cubic=False, force=True):
         for i in range(3):
             Kc[:, i, i] = c11 * K[:, i, i] + c44 * (tr - K[:, i, i])
         K = Kc
-    diag = lay.brow == lay.bcol
-    off = Amag.copy()
-    off[diag] = 0
-    Arow = Amag.copy()
-    rs = np.zeros((nn, dm, dm), dt)
-    np.add.at(rs, lay.brow, off)
-    Arow[diag] = rs
+    Arow = row_sums(lay, Amag)
     F = AF = sig = Asig = fe = f = Af = None
     if force:
         U = u.reshape(nodes.shape).astype(dt)[el]
