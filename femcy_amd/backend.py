@@ -79,6 +79,7 @@ EXPORTS = [
     "femcy_explicit_advance", "femcy_explicit_kinetic_energy", "femcy_explicit_stable_dt",
     "femcy_explicit_element_bound", "femcy_explicit_auto_begin", "femcy_explicit_auto_advance", "femcy_explicit_auto_state",
     "femcy_explicit_set_damping", "femcy_lumped_mass_scale", "femcy_lumped_mass_get_scaling",
+    "femcy_amplitude_create", "femcy_explicit_set_motion",
     "femcy_loadset_create", "femcy_loadset_neumann", "femcy_loadset_neumann_add", "femcy_spmv", "femcy_pcg", "femcy_compute_strain_stress", "femcy_elastic_energy", "femcy_elastic_energy_small", "femcy_extrapolate",
     "femcy_get_K_ell", "femcy_get_K_bsr", "femcy_get_gp_field", "femcy_timing",
     "femcy_timing_reset", "femcy_comm_unique_id", "femcy_comm_local_id", "femcy_comm_init", "femcy_comm_info", "femcy_comm_set_neighbours",
@@ -103,6 +104,10 @@ FEMCY_ENOMEM = -6
 # femcy_lumped_mass_scale: the rule that turns a target increment into factors (*Fixed Mass Scaling, type=)
 MS_BELOW_MIN, MS_SET_EQUAL_DT, MS_UNIFORM = 0, 1, 2
 MS_TYPES = {"below min": MS_BELOW_MIN, "set equal dt": MS_SET_EQUAL_DT, "uniform": MS_UNIFORM}
+# femcy_amplitude_create: the kind of a curve (*Amplitude, definition=)
+AMP_TABULAR, AMP_SMOOTH_STEP = 0, 1
+AMP_KINDS = {"tabular": AMP_TABULAR, "smooth step": AMP_SMOOTH_STEP}
+AMP_MAX_POINTS = 16
 
 
 class DirectInfo(C.Structure):
@@ -193,6 +198,8 @@ def _bind(lib, kind):
         "femcy_explicit_set_damping": [p, i32, f64, f64, f64, f64],
         "femcy_lumped_mass_scale": [p, i32, f64, f64, f64, i32, C.POINTER(f64), C.POINTER(f64), C.POINTER(i64), C.POINTER(f64)],
         "femcy_lumped_mass_get_scaling": [p, i32, p],
+        "femcy_amplitude_create": [p, i32, i32, p, p, C.POINTER(i32)],
+        "femcy_explicit_set_motion": [p, i32, i32, p, p, p],
         "femcy_explicit_auto_state": [p, i32, C.POINTER(f64), C.POINTER(f64), C.POINTER(f64), C.POINTER(C.c_int64)],
         "femcy_loadset_create": [p, i32, i32, i32, p, p, p, p, p, i32, p, p, C.POINTER(i32)],
         "femcy_loadset_neumann": [p, i32, f64, p, cint],
@@ -637,6 +644,30 @@ class Context:
         """mass-proportional damping alpha and bulk viscosity (b1, b2, dilatational modulus M_d) of an integrator, from the
         next stepping call on; all zero restores the undamped launches and bits"""
         self._call("femcy_explicit_set_damping", int(ex), float(alpha), float(b1), float(b2), float(M_d))
+
+    def amplitude(self, definition: str, t, A) -> int:
+        """a curve A(t) in step time from 2 .. 16 points, t strictly increasing: "tabular" (piecewise linear) or
+        "smooth step" (quintic between the points, A' = A'' = 0 at each); clamped outside the table"""
+        kind = AMP_KINDS[str(definition).strip().lower()]
+        t, A = np.ascontiguousarray(t, dtype=np.float64), np.ascontiguousarray(A, dtype=np.float64)
+        if t.ndim != 1 or t.shape != A.shape:
+            raise ValueError("amplitude: t and A must be one-dimensional and of the same length")
+        out = C.c_int32()
+        self._call("femcy_amplitude_create", kind, int(t.size), _ptr(t), _ptr(A), C.byref(out))
+        return out.value
+
+    def explicit_set_motion(self, ex: int, dofsets=(), values=(), amplitudes=()):
+        """prescribed motion of an integrator, from its next explicit_start / explicit_auto_begin: the DOFs of held set
+        dofsets[k] follow u = values[k] A_k(t), v = values[k] A_k', a = values[k] A_k'' with A_k = amplitudes[k]; a later set
+        wins where two overlap.  No sets: the motion is removed and the integrator is launched as without it."""
+        ids = np.ascontiguousarray(list(dofsets), dtype=np.int32)
+        vals = np.ascontiguousarray(list(values), dtype=np.float64)
+        amps = np.ascontiguousarray(list(amplitudes), dtype=np.int32)
+        if not ids.size == vals.size == amps.size:
+            raise ValueError("explicit_set_motion: one value and one amplitude per DOF set")
+        some = ids.size > 0
+        self._call("femcy_explicit_set_motion", int(ex), int(ids.size), _ptr(ids) if some else None,
+                   _ptr(vals) if some else None, _ptr(amps) if some else None)
 
     def explicit_auto_state(self, ex: int):
         """-> (t, h_last, h_min, steps_done): the synchronising read-back of the device clock"""

@@ -385,6 +385,47 @@ int check_explicit_set_damping(const C* c, int32_t id, double alpha, double b1, 
     return FEMCY_OK;
 }
 
+// femcy_amplitude_create: a known kind, 2 .. FEMCY_AMP_MAX_POINTS finite points, t strictly increasing
+inline int check_amplitude_create(int32_t kind, int32_t npts, const double* t, const double* A, const int32_t* id_out) {
+    FEMCY_REQUIRE(id_out && t && A, "femcy_amplitude_create: null id_out, t or A");
+    FEMCY_REQUIRE(kind == FEMCY_AMP_TABULAR || kind == FEMCY_AMP_SMOOTH_STEP, "femcy_amplitude_create: unknown kind %d", (int)kind);
+    FEMCY_REQUIRE(npts >= 2 && npts <= FEMCY_AMP_MAX_POINTS, "femcy_amplitude_create: %d points, 2 .. %d are taken", (int)npts,
+                  FEMCY_AMP_MAX_POINTS);
+    for (int32_t k = 0; k < npts; ++k)
+        FEMCY_REQUIRE(std::isfinite(t[k]) && std::isfinite(A[k]), "femcy_amplitude_create: point %d is not finite", (int)k);
+    for (int32_t k = 1; k < npts; ++k)
+        FEMCY_REQUIRE(t[k] > t[k - 1], "femcy_amplitude_create: the times must be strictly increasing (point %d)", (int)k);
+    return FEMCY_OK;
+}
+
+// femcy_explicit_set_motion: known objects, finite values, only sets the integrator holds (explicits[id].held: the DOF-set
+// ids it was created with), at most FEMCY_MOTION_MAX_CURVES distinct curves
+template <class C>
+int check_explicit_set_motion(const C* c, int32_t id, int32_t nsets, const int32_t* dofset_ids, const double* values,
+                              const int32_t* amplitude_ids) {
+    FEMCY_TRY(check_object(c->explicits, id, "explicit integrator"));
+    FEMCY_REQUIRE(nsets >= 0 && (nsets == 0 || (dofset_ids && values && amplitude_ids)),
+                  "femcy_explicit_set_motion: null DOF-set, value or amplitude list");
+    int32_t curves[FEMCY_MOTION_MAX_CURVES], ncurves = 0;
+    for (int32_t k = 0; k < nsets; ++k) {
+        FEMCY_TRY(check_object(c->dofsets, dofset_ids[k], "DOF set"));
+        FEMCY_TRY(check_object(c->amplitudes, amplitude_ids[k], "amplitude"));
+        FEMCY_REQUIRE(std::isfinite(values[k]), "femcy_explicit_set_motion: value %d is not finite", (int)k);
+        bool held = false;
+        for (int32_t h : c->explicits[id].held) held = held || h == dofset_ids[k];
+        FEMCY_REQUIRE(held, "femcy_explicit_set_motion: DOF set %d is not one of the sets integrator %d holds "
+                      "(femcy_explicit_create); only held DOFs can be moved", (int)dofset_ids[k], (int)id);
+        int32_t j = 0;
+        while (j < ncurves && curves[j] != amplitude_ids[k]) ++j;
+        if (j == ncurves) {
+            FEMCY_REQUIRE(ncurves < FEMCY_MOTION_MAX_CURVES, "femcy_explicit_set_motion: more than %d distinct amplitudes",
+                          FEMCY_MOTION_MAX_CURVES);
+            curves[ncurves++] = amplitude_ids[k];
+        }
+    }
+    return FEMCY_OK;
+}
+
 template <class C>
 int check_explicit_start(const C* c, int32_t id, int rhs_vec, double scale) {
     FEMCY_TRY(check_explicit_rhs(c, "femcy_explicit_start", id, rhs_vec));

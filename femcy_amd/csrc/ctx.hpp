@@ -8,10 +8,9 @@
 #include <vector>
 #include "../../include/femcy.h"
 #include "api_checks.hpp"   // set_error, FEMCY_REQUIRE and what the entry points refuse
+#include "element_math.hpp" // ExplicitClock, Amplitude
 
 namespace femcy {
-
-struct ExplicitClock;   // element_math.hpp
 
 #define FEMCY_HIP(call)                                                                         \
     do {                                                                                        \
@@ -399,8 +398,21 @@ struct Ctx {
         double alpha = 0.0, b1 = 0.0, b2 = 0.0, Md = 0.0;      // femcy_explicit_set_damping; all 0: the undamped launches
         bool damped() const { return alpha != 0.0 || b1 != 0.0 || b2 != 0.0; }
         bool bulk() const { return b1 != 0.0 || b2 != 0.0; }
+        // prescribed motion (femcy_explicit_set_motion): the DOF-set ids the integrator holds, the compact list of moved
+        // DOFs (d_mdof, d_mval, d_mcurve [nmoved]), the per-DOF position in it or -1 (d_mslot [n]) and the curves (d_amp);
+        // nmoved = 0: no motion, the launches of an integrator that never had one
+        std::vector<int32_t> held;
+        DevBuf<int32_t> d_mslot, d_mdof, d_mcurve;
+        DevBuf<double> d_mval;
+        DevBuf<Amplitude> d_amp;
+        int32_t nmoved = 0;
+        // the clock of a fixed run: steps taken since femcy_explicit_start, and the (t_base, n_base, dt) of
+        // explicit_fixed_time (element_math.hpp)
+        int64_t n_done = 0, n_base = 0;
+        double t_base = 0.0, dt_prev = 0.0;
     };
     std::vector<Explicit> explicits;
+    std::vector<Amplitude> amplitudes;   // femcy_amplitude_create; dropped where integrators are
     int64_t K_serial = -1;            // pattern_serial of the last successful assembly: K holds a matrix when they agree
     bool post_small = false;         // sigma / mises hold femcy_compute_strain_stress(large = 0), not yet corrected
 
@@ -538,8 +550,20 @@ int launch_lumped_mass(Ctx* c, int32_t nq, const double* d_Nq, const double* d_d
                        double* d_me, double* d_m);
 int launch_explicit_minv(Ctx* c, const double* d_m, double* d_minv);
 int launch_explicit_drift(Ctx* c, const ExplicitClock* d_clk, double h);
+// mv (femcy_explicit_set_motion; null: none, today's instantiations with today's arguments): the tables of the moved DOFs
+// and, for a fixed step, the time t of the state being kicked and t_drift the drift reaches (an automatic run reads both
+// from the clock).  launch_explicit_place: u, v, a (what: MOVE_* of element_math.hpp) of the moved DOFs at t, or with d_clk
+// at the clock's t_next unless its h_next = 0.
+struct ExplicitMotion {
+    const int32_t *d_slot, *d_dof, *d_curve;
+    const double* d_val;
+    const Amplitude* d_amp;
+    int32_t nmoved;
+    double t, t_drift;
+};
 int launch_explicit_node(Ctx* c, const double* d_minv, const double* d_f, const ExplicitClock* d_clk, double scale, double h,
-                         int mode, double alpha = 0.0);
+                         int mode, double alpha = 0.0, const ExplicitMotion* mv = nullptr);
+int launch_explicit_place(Ctx* c, const ExplicitMotion& mv, const ExplicitClock* d_clk, double t, int what);
 int launch_explicit_energy(Ctx* c, const double* d_m, const double* d_v, double* out);   // 1/2 sum m v^2, fixed order
 // max over the rows i with minv_i != 0 of minv_i sum_j |K_ij| (Gershgorin bound on the spectrum of M_L^-1 K)
 int launch_rowabs_bound(Ctx* c, const double* d_minv, double* out);

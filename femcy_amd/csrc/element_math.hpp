@@ -1070,6 +1070,67 @@ FEMCY_HD bool explicit_step_clock(const ExplicitClock& k, int mode, ExplicitStep
     return true;
 }
 
+// Prescribed motion (*Boundary, amplitude=; femcy_amplitude_create, femcy_explicit_set_motion).  One curve: npts points
+// t[0] < t[1] < ... with the values A[], in step time.  amplitude() returns A(t), A'(t) and A''(t); a moved DOF with the
+// value g then has u = g A, v = g A', a = g A'' (explicit_moved).  Between two points, xi = (t - t_k) / (t_{k+1} - t_k):
+//   FEMCY_AMP_TABULAR      A = A_k + (A_{k+1} - A_k) xi,  A' the slope of [t_k, t_{k+1}) -- the right-hand one at a point --,
+//                          A'' = 0
+//   FEMCY_AMP_SMOOTH_STEP  A = A_k + (A_{k+1} - A_k) xi^3 (10 - 15 xi + 6 xi^2), and from the same polynomial
+//                          A'  = (A_{k+1} - A_k) / dt_k    30 xi^2 (1 - xi)^2
+//                          A'' = (A_{k+1} - A_k) / dt_k^2  60 xi (1 - xi)(1 - 2 xi):      both exactly 0 at every point
+// Outside the table both are clamped: (A_0, 0, 0) for t <= t_0 and (A_last, 0, 0), exactly, for t >= t_last.  The fused
+// multiply-adds are written out, so that the device kernels and the host backend round alike.
+struct Amplitude {
+    int32_t kind, npts;
+    double t[FEMCY_AMP_MAX_POINTS], A[FEMCY_AMP_MAX_POINTS];
+};
+FEMCY_HD void amplitude(const Amplitude& am, double t, double& A, double& dA, double& ddA) {
+    const int last = am.npts - 1;
+    dA = 0.0;
+    ddA = 0.0;
+    if (!(t > am.t[0])) {
+        A = am.A[0];
+        return;
+    }
+    if (t >= am.t[last]) {
+        A = am.A[last];
+        return;
+    }
+    int k = 0;
+    while (k + 1 < last && t >= am.t[k + 1]) ++k;
+    const double dt = am.t[k + 1] - am.t[k], rise = am.A[k + 1] - am.A[k];
+    const double xi = (t - am.t[k]) / dt, slope = rise / dt;
+    if (am.kind == FEMCY_AMP_TABULAR) {
+        A = fma(rise, xi, am.A[k]);
+        dA = slope;
+        return;
+    }
+    const double om = 1.0 - xi;
+    A = fma(rise, (xi * xi * xi) * fma(fma(6.0, xi, -15.0), xi, 10.0), am.A[k]);
+    dA = slope * (30.0 * (xi * xi) * (om * om));
+    ddA = (slope / dt) * (60.0 * xi * om * fma(-2.0, xi, 1.0));
+}
+// u, v and a of a moved DOF with the value g at time t: what k_explicit_place and the host backend store (what: a mask)
+enum { MOVE_U = 1, MOVE_V = 2, MOVE_A = 4 };
+FEMCY_HD void explicit_place(const Amplitude& am, double g, double t, int what, double& u, double& v, double& a) {
+    double A, dA, ddA;
+    amplitude(am, t, A, dA, ddA);
+    if (what & MOVE_U) u = g * A;
+    if (what & MOVE_V) v = g * dA;
+    if (what & MOVE_A) a = g * ddA;
+}
+// what the node pass does to a moved DOF instead of the kick (modes below, at ExplicitStep): a (and, but at the start, v) at
+// the time t of the state being kicked, then u at the time t_drift the drift reaches, by assignment
+FEMCY_HD void explicit_moved(const Amplitude& am, double g, double t, double t_drift, bool start, bool drift, double& u,
+                             double& v, double& a) {
+    explicit_place(am, g, t, start ? MOVE_A : MOVE_V | MOVE_A, u, v, a);
+    if (!start && drift) explicit_place(am, g, t_drift, MOVE_U, u, v, a);
+}
+// the clock of a fixed run: state n is at t_base + (n - n_base) dt, one rounding whichever call reaches it
+FEMCY_HD double explicit_fixed_time(double t_base, int64_t n_base, int64_t n, double dt) {
+    return fma((double)(n - n_base), dt, t_base);
+}
+
 // sum of 32 partial sums by the xor tree of half a wavefront, as lane 0 of k_nodal_force ends up with it: what the host
 // backend runs so that a node sum has the device's summation order
 inline double half_wave_tree(double (&p)[32]) {

@@ -11,6 +11,7 @@
 #include "element_dispatch.hpp"
 #include "element_math.hpp"
 #include "direct.hpp"
+#include "motion_tables.hpp"
 
 namespace femcy {
 
@@ -33,6 +34,7 @@ static void drop_objects(Ctx* c) {
     c->masses.clear();
     c->lumped_masses.clear();
     c->explicits.clear();
+    c->amplitudes.clear();
 }
 
 // Right-hand side of a stored load: apply(dst, add) writes this rank's share of it into dst (add: adds it) and is called
@@ -1177,6 +1179,7 @@ int femcy_explicit_create(femcy_ctx* ctx, int32_t lumped_id, int32_t ndofsets, c
     const Ctx::LumpedMass& lm = c->lumped_masses[lumped_id];
     Ctx::Explicit ex;
     ex.lumped = lumped_id;
+    ex.held.assign(dofset_ids, dofset_ids + ndofsets);
     if (ex.d_minv.alloc(sizeof(double) * (size_t)c->n) != hipSuccess) {
         set_error("out of device memory for the inverse mass of %lld DOF", (long long)c->n);
         return FEMCY_ENOMEM;
@@ -1214,16 +1217,70 @@ int femcy_explicit_set_damping(femcy_ctx* ctx, int32_t id, double alpha, double 
     return FEMCY_OK;
 }
 
+int femcy_amplitude_create(femcy_ctx* ctx, int32_t kind, int32_t npts, const double* t, const double* A, int32_t* id_out) {
+    CTX_OR_FAIL(ctx);
+    EXPLICIT_SINGLE_RANK_OR_FAIL("femcy_amplitude_create");
+    FEMCY_TRY(check_amplitude_create(kind, npts, t, A, id_out));
+    Amplitude am{};
+    am.kind = kind;
+    am.npts = npts;
+    std::copy(t, t + npts, am.t);
+    std::copy(A, A + npts, am.A);
+    c->amplitudes.push_back(am);
+    *id_out = (int32_t)c->amplitudes.size() - 1;
+    return FEMCY_OK;
+}
+
+// Set-up, synchronising: the DOF lists of the sets come back from the device, the tables are built on the host
+// (motion_tables.hpp) and replace the integrator's once nothing can still read the old ones.
+int femcy_explicit_set_motion(femcy_ctx* ctx, int32_t id, int32_t nsets, const int32_t* dofset_ids, const double* values,
+                              const int32_t* amplitude_ids) {
+    CTX_OR_FAIL(ctx);
+    EXPLICIT_SINGLE_RANK_OR_FAIL("femcy_explicit_set_motion");
+    FEMCY_TRY(check_explicit_set_motion(c, id, nsets, dofset_ids, values, amplitude_ids));
+    Ctx::Explicit& ex = c->explicits[id];
+    std::vector<std::vector<int32_t>> sets((size_t)nsets);
+    for (int32_t k = 0; k < nsets; ++k) {
+        const Ctx::DofSet& ds = c->dofsets[dofset_ids[k]];
+        sets[k].resize((size_t)ds.k);
+        if (ds.k) FEMCY_TRY(download(c, sets[k].data(), ds.d_dofs.get(), sizeof(int32_t) * (size_t)ds.k));
+    }
+    const MotionTables mt = motion_tables(c->n, sets, values, amplitude_ids, c->amplitudes);
+    FEMCY_HIP(hipStreamSynchronize(c->stream));
+    ex.nmoved = 0;
+    ex.d_mslot.reset(), ex.d_mdof.reset(), ex.d_mcurve.reset(), ex.d_mval.reset(), ex.d_amp.reset();
+    if (mt.dof.empty()) return FEMCY_OK;
+    int rc = dev_upload(ex.d_mslot, mt.slot);
+    if (!rc) rc = dev_upload(ex.d_mdof, mt.dof);
+    if (!rc) rc = dev_upload(ex.d_mcurve, mt.curve);
+    if (!rc) rc = dev_upload(ex.d_mval, mt.val);
+    if (!rc) rc = dev_upload(ex.d_amp, mt.amp);
+    if (rc) return rc;
+    ex.nmoved = (int32_t)mt.dof.size();
+    return FEMCY_OK;
+}
+
+// the motion tables of an integrator for the launchers, at the times t and t_drift of a fixed step
+static ExplicitMotion motion_of(const Ctx::Explicit& ex, double t, double t_drift) {
+    return {ex.d_mslot.get(), ex.d_mdof.get(), ex.d_mcurve.get(), ex.d_mval.get(), ex.d_amp.get(), ex.nmoved, t, t_drift};
+}
+
 int femcy_explicit_start(femcy_ctx* ctx, int32_t id, int rhs_vec, double scale) {
     CTX_OR_FAIL(ctx);
     READY_OR_FAIL();
     EXPLICIT_SINGLE_RANK_OR_FAIL("femcy_explicit_start");
     FEMCY_TRY(check_explicit_start(c, id, rhs_vec, scale));
-    const Ctx::Explicit& ex = c->explicits[id];
-    const GeomDamping gd = damping_of(c, ex, nullptr, 0.0, true);
-    int rc = force_pass(c, c->d_vec[FEMCY_VEC_DOF], ex.bulk() ? &gd : nullptr);
+    Ctx::Explicit& ex = c->explicits[id];
+    ex.n_done = ex.n_base = 0;                      // the clock of a fixed run: t = 0
+    ex.t_base = ex.dt_prev = 0.0;
+    const ExplicitMotion mv = motion_of(ex, 0.0, 0.0);
+    int rc = ex.nmoved ? launch_explicit_place(c, mv, nullptr, 0.0, MOVE_U | MOVE_V | MOVE_A) : FEMCY_OK;
     if (rc) return rc;
-    return launch_explicit_node(c, ex.d_minv.get(), c->d_vec[rhs_vec], nullptr, scale, 0.0, XN_START, ex.alpha);
+    const GeomDamping gd = damping_of(c, ex, nullptr, 0.0, true);
+    rc = force_pass(c, c->d_vec[FEMCY_VEC_DOF], ex.bulk() ? &gd : nullptr);
+    if (rc) return rc;
+    return launch_explicit_node(c, ex.d_minv.get(), c->d_vec[rhs_vec], nullptr, scale, 0.0, XN_START, ex.alpha,
+                                ex.nmoved ? &mv : nullptr);
 }
 
 // nsteps steps from a started state: the first drift, then per step the element pass and the node pass (kick, and the drift
@@ -1239,8 +1296,15 @@ static int explicit_steps(Ctx* c, const Ctx::Explicit& ex, ExplicitClock* clk, i
     // coefficient; with none of them set these are the launches of an undamped integrator
     const GeomDamping gd = damping_of(c, ex, clk, dt, false);
     const GeomDamping *gd_geom = ex.bulk() ? &gd : nullptr, *gd_bound = ex.damped() ? &gd : nullptr;
+    // motion (femcy_explicit_set_motion): a fixed run hands every launch the times of its own clock (time_of), an automatic
+    // one reads the device clock; without it these are the launches of an integrator that never had one
+    const bool moved = ex.nmoved != 0;
+    auto time_of = [&](int32_t k) { return explicit_fixed_time(ex.t_base, ex.n_base, ex.n_done + k, dt); };
+    ExplicitMotion mv = motion_of(ex, 0.0, 0.0);
     int rc = launch_explicit_drift(c, clk, dt);
+    if (!rc && moved) rc = launch_explicit_place(c, mv, clk, clk ? 0.0 : time_of(1), MOVE_U);
     for (int32_t k = 1; !rc && k <= nsteps; ++k) {
+        if (moved && !clk) mv.t = time_of(k), mv.t_drift = time_of(k + 1);
         // the element pass of force_pass without its per-call copy of u: the lazy state is set once, below
         if ((rc = launch_geom(c, u, GEOM_DSDX | GEOM_FE, gd_geom))) break;
         if (clk) {
@@ -1248,7 +1312,7 @@ static int explicit_steps(Ctx* c, const Ctx::Explicit& ex, ExplicitClock* clk, i
             if ((rc = launch_explicit_clock(c, ex.d_bpart.get(), clk))) break;
         }
         rc = launch_explicit_node(c, ex.d_minv.get(), c->d_vec[rhs_vec], clk, scale0 + k * dscale, dt,
-                                  k < nsteps ? XN_KICK_DRIFT : XN_KICK, ex.alpha);
+                                  k < nsteps ? XN_KICK_DRIFT : XN_KICK, ex.alpha, moved ? &mv : nullptr);
     }
     if (rc) return rc;
     // post-processing reads "the stress of the last force evaluation": that of the last state (the last step did not drift)
@@ -1263,7 +1327,15 @@ int femcy_explicit_advance(femcy_ctx* ctx, int32_t id, int rhs_vec, int32_t nste
     READY_OR_FAIL();
     EXPLICIT_SINGLE_RANK_OR_FAIL("femcy_explicit_advance");
     FEMCY_TRY(check_explicit_advance(c, id, rhs_vec, nsteps, dt, scale0, dscale));
-    return explicit_steps(c, c->explicits[id], nullptr, rhs_vec, nsteps, dt, scale0, dscale);
+    Ctx::Explicit& ex = c->explicits[id];
+    if (nsteps && dt != ex.dt_prev) {               // another increment: the clock counts on from the time it has reached
+        ex.t_base = explicit_fixed_time(ex.t_base, ex.n_base, ex.n_done, ex.dt_prev);
+        ex.n_base = ex.n_done;
+        ex.dt_prev = dt;
+    }
+    const int rc = explicit_steps(c, ex, nullptr, rhs_vec, nsteps, dt, scale0, dscale);
+    if (!rc) ex.n_done += nsteps;
+    return rc;
 }
 
 int femcy_explicit_kinetic_energy(femcy_ctx* ctx, int32_t id, int v_vec, double* out) {
@@ -1338,13 +1410,16 @@ int femcy_explicit_auto_begin(femcy_ctx* ctx, int32_t id, int rhs_vec, double s_
     clk.ramp = ramp ? 1 : 0;
     if ((rc = stage_h2d(c, exm.d_clock.get(), &clk, sizeof(clk)))) return rc;
     const double* u = c->d_vec[FEMCY_VEC_DOF];
+    const ExplicitMotion mv = motion_of(exm, 0.0, 0.0);                 // the clock is at t = 0 when the node pass reads it
+    if (exm.nmoved && (rc = launch_explicit_place(c, mv, nullptr, 0.0, MOVE_U | MOVE_V | MOVE_A))) return rc;
     const GeomDamping gd = damping_of(c, exm, nullptr, 0.0, true);      // v_{-1/2} := v_0, vec[ACC] is not read
     if ((rc = force_pass(c, u, exm.bulk() ? &gd : nullptr))) return rc;
     if ((rc = launch_explicit_bound(c, u, c->lumped_masses[exm.lumped].d_me.get(), s_C, exm.d_bpart.get(),
                                     exm.damped() ? &gd : nullptr)))
         return rc;
     if ((rc = launch_explicit_clock(c, exm.d_bpart.get(), exm.d_clock.get()))) return rc;   // t = 0, the first h
-    if ((rc = launch_explicit_node(c, exm.d_minv.get(), c->d_vec[rhs_vec], exm.d_clock.get(), 0.0, 0.0, XN_START, exm.alpha)))
+    if ((rc = launch_explicit_node(c, exm.d_minv.get(), c->d_vec[rhs_vec], exm.d_clock.get(), 0.0, 0.0, XN_START, exm.alpha,
+                                   exm.nmoved ? &mv : nullptr)))
         return rc;
     exm.auto_begun = true;
     exm.s_C = s_C;

@@ -54,19 +54,34 @@ __global__ void __launch_bounds__(XBS) k_explicit_minv(int64_t n, const double* 
 // requested before the gather and DM neighbouring lanes read and write DM contiguous doubles.  What mode and st say is with
 // ExplicitStep in element_math.hpp; the arithmetic is explicit_kick / explicit_drift there, the functions the first drift
 // below and the host backend call.
-template <int DM>
+// MOTION (empty, or one NodeMotion: an integrator with femcy_explicit_set_motion): a lane whose DOF is held (minv = 0) and
+// moved (slot >= 0) ignores the gathered force and stores explicit_moved of element_math.hpp instead -- a and v of its curve
+// at mo.t, the time of the state being kicked, and when drifting u at mo.t_drift by assignment.  Every other lane runs the
+// arithmetic below unchanged; without the argument the kernel has the arguments and the code it always had.
+struct NodeMotion {
+    const int32_t *slot, *curve;      // [n] position in the compact list or -1; [moved] curve of each list entry
+    const double* val;                // [moved] the value g
+    const Amplitude* amp;             // the curves
+    double t, t_drift;                // k_explicit_node_auto fills both from the clock
+};
+template <int DM, class... MOTION>
 __device__ __forceinline__ void explicit_node_pass(int32_t nn, const int32_t* __restrict__ ne_ptr,
                                                    const int32_t* __restrict__ ne_idx, const double* __restrict__ fe,
                                                    const double* __restrict__ f, const double* __restrict__ minv,
                                                    const ExplicitStep& st, int mode, double* __restrict__ u,
-                                                   double* __restrict__ v, double* __restrict__ acc_vec) {
+                                                   double* __restrict__ v, double* __restrict__ acc_vec,
+                                                   const MOTION&... motion) {
+    constexpr bool MOVE = sizeof...(MOTION) == 1;
+    static_assert(sizeof...(MOTION) <= 1, "at most one motion argument");
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int32_t a = (int32_t)(t >> 5);
     const int sub = (int)(t & 31);
     const bool mine = a < nn && sub < DM;
     const int64_t i = (int64_t)a * DM + sub;
     double fi = 0.0, mi = 0.0, ai = 0.0, vi = 0.0, ui = 0.0;
+    [[maybe_unused]] int32_t slot = -1;
     if (mine) {
+        if constexpr (MOVE) slot = (motion, ...).slot[i];
         fi = f[i];
         mi = minv[i];
         if (mode != XN_START) {
@@ -80,6 +95,17 @@ __device__ __forceinline__ void explicit_node_pass(int32_t nn, const int32_t* __
     double acc[DM];
     node_gather<DM>(a, sub, nn, ne_ptr, ne_idx, fe, acc);
     if (!mine) return;
+    if constexpr (MOVE) {
+        if (mi == 0.0 && slot >= 0) {
+            const NodeMotion& mo = (motion, ...);
+            explicit_moved(mo.amp[mo.curve[slot]], mo.val[slot], mo.t, mo.t_drift, mode == XN_START, st.drift, ui, vi, ai);
+            acc_vec[i] = ai;
+            if (mode == XN_START) return;
+            v[i] = vi;
+            if (st.drift) u[i] = ui;
+            return;
+        }
+    }
     const double fint = sub == 0 ? acc[0] : (sub == 1 ? acc[1] : acc[DM - 1]);
     if (st.alpha != 0.0)
         explicit_kick_damped(mi, st.s, fi, fint, st.hh, st.alpha, vi, ai);
@@ -92,28 +118,62 @@ __device__ __forceinline__ void explicit_node_pass(int32_t nn, const int32_t* __
 }
 
 // a fixed step: the host filled st (explicit_step_fixed)
-template <int DM>
+template <int DM, class... MOTION>
 __global__ void __launch_bounds__(XBS) k_explicit_node(int32_t nn, const int32_t* __restrict__ ne_ptr,
                                                        const int32_t* __restrict__ ne_idx,
                                                        const double* __restrict__ fe, const double* __restrict__ f,
                                                        const double* __restrict__ minv, ExplicitStep st, int mode,
                                                        double* __restrict__ u, double* __restrict__ v,
-                                                       double* __restrict__ acc_vec) {
-    explicit_node_pass<DM>(nn, ne_ptr, ne_idx, fe, f, minv, st, mode, u, v, acc_vec);
+                                                       double* __restrict__ acc_vec, MOTION... motion) {
+    explicit_node_pass<DM>(nn, ne_ptr, ne_idx, fe, f, minv, st, mode, u, v, acc_vec, motion...);
 }
 
 // a step of an automatic run: st from the device clock, which may say that nothing is written (explicit_step_clock)
-template <int DM>
+// with motion: the state being kicked is at the clock's t, the drift reaches its t_next; a no-op step writes no moved DOF
+// either
+template <int DM, class... MOTION>
 __global__ void __launch_bounds__(XBS) k_explicit_node_auto(int32_t nn, const int32_t* __restrict__ ne_ptr,
                                                             const int32_t* __restrict__ ne_idx,
                                                             const double* __restrict__ fe, const double* __restrict__ f,
                                                             const double* __restrict__ minv,
                                                             const ExplicitClock* __restrict__ clk, int mode,
                                                             double alpha, double* __restrict__ u,
-                                                            double* __restrict__ v, double* __restrict__ acc_vec) {
+                                                            double* __restrict__ v, double* __restrict__ acc_vec,
+                                                            MOTION... motion) {
     ExplicitStep st;
     if (!explicit_step_clock(*clk, mode, st, alpha)) return;
-    explicit_node_pass<DM>(nn, ne_ptr, ne_idx, fe, f, minv, st, mode, u, v, acc_vec);
+    if constexpr (sizeof...(MOTION) == 1) {
+        NodeMotion mo = (motion, ...);
+        mo.t = clk->t;
+        mo.t_drift = clk->t_next;
+        explicit_node_pass<DM>(nn, ne_ptr, ne_idx, fe, f, minv, st, mode, u, v, acc_vec, mo);
+    } else {
+        explicit_node_pass<DM>(nn, ne_ptr, ne_idx, fe, f, minv, st, mode, u, v, acc_vec);
+    }
+}
+
+// u, v and a (what: MOVE_U | MOVE_V | MOVE_A of element_math.hpp) of the moved DOFs at one time, one thread per entry of the
+// compact list: at the start of a run everything at t, before the element pass; after the first drift of a call u alone, at
+// the time that drift reached -- t, or with clk the clock's t_next, and nothing when its h_next = 0 (the drift wrote
+// nothing either).  Every DOF stands in the list once.
+__global__ void __launch_bounds__(XBS) k_explicit_place(int32_t nmoved, const int32_t* __restrict__ dof,
+                                                        const double* __restrict__ val, const int32_t* __restrict__ curve,
+                                                        const Amplitude* __restrict__ amp,
+                                                        const ExplicitClock* __restrict__ clk, double t, int what,
+                                                        double* __restrict__ u, double* __restrict__ v,
+                                                        double* __restrict__ a) {
+    const int32_t k = blockIdx.x * XBS + threadIdx.x;
+    if (k >= nmoved) return;
+    if (clk) {
+        if (clk->h_next == 0.0) return;
+        t = clk->t_next;
+    }
+    const int32_t i = dof[k];
+    double ui = 0.0, vi = 0.0, ai = 0.0;
+    explicit_place(amp[curve[k]], val[k], t, what, ui, vi, ai);
+    if (what & MOVE_U) u[i] = ui;
+    if (what & MOVE_V) v[i] = vi;
+    if (what & MOVE_A) a[i] = ai;
 }
 
 // the first drift of a call: u += h v + (h^2 / 2) a from memory, by the function the node pass applies to its registers
@@ -396,12 +456,21 @@ int launch_explicit_minv(Ctx* c, const double* d_m, double* d_minv) {
 }
 
 int launch_explicit_node(Ctx* c, const double* d_minv, const double* d_f, const ExplicitClock* d_clk, double scale, double h,
-                         int mode, double alpha) {
+                         int mode, double alpha, const ExplicitMotion* mv) {
     const unsigned grid = node_gather_grid(c->nn, XBS);
     double *u = c->d_vec[FEMCY_VEC_DOF], *v = c->d_vec[FEMCY_VEC_VEL], *a = c->d_vec[FEMCY_VEC_ACC];
     size_t tm = timing_begin(c, T_FORCE);
     dispatch_dm(c->dm, [&](auto dm) {
-        if (d_clk)
+        if (mv) {
+            const NodeMotion mo{mv->d_slot, mv->d_curve, mv->d_val, mv->d_amp, mv->t, mv->t_drift};
+            if (d_clk)
+                hipLaunchKernelGGL((k_explicit_node_auto<dm(), NodeMotion>), dim3(grid), dim3(XBS), 0, c->stream, c->nn,
+                                   c->d_ne_ptr, c->d_ne_idx, c->d_fe, d_f, d_minv, d_clk, mode, alpha, u, v, a, mo);
+            else
+                hipLaunchKernelGGL((k_explicit_node<dm(), NodeMotion>), dim3(grid), dim3(XBS), 0, c->stream, c->nn, c->d_ne_ptr,
+                                   c->d_ne_idx, c->d_fe, d_f, d_minv, explicit_step_fixed(scale, h, mode, alpha), mode, u, v, a,
+                                   mo);
+        } else if (d_clk)
             hipLaunchKernelGGL((k_explicit_node_auto<dm()>), dim3(grid), dim3(XBS), 0, c->stream, c->nn, c->d_ne_ptr,
                                c->d_ne_idx, c->d_fe, d_f, d_minv, d_clk, mode, alpha, u, v, a);
         else
@@ -409,6 +478,16 @@ int launch_explicit_node(Ctx* c, const double* d_minv, const double* d_f, const 
                                c->d_fe, d_f, d_minv, explicit_step_fixed(scale, h, mode, alpha), mode, u, v, a);
     });
     timing_end(c, tm);
+    FEMCY_HIP(hipGetLastError());
+    return FEMCY_OK;
+}
+
+int launch_explicit_place(Ctx* c, const ExplicitMotion& mv, const ExplicitClock* d_clk, double t, int what) {
+    if (mv.nmoved == 0) return FEMCY_OK;
+    const unsigned grid = (unsigned)((mv.nmoved + XBS - 1) / XBS);
+    hipLaunchKernelGGL(k_explicit_place, dim3(grid), dim3(XBS), 0, c->stream, mv.nmoved, mv.d_dof, mv.d_val, mv.d_curve,
+                       mv.d_amp, d_clk, t, what, c->d_vec[FEMCY_VEC_DOF].get(), c->d_vec[FEMCY_VEC_VEL].get(),
+                       c->d_vec[FEMCY_VEC_ACC].get());
     FEMCY_HIP(hipGetLastError());
     return FEMCY_OK;
 }

@@ -29,6 +29,7 @@
 #include "../csrc/band_order.hpp"
 #include "../csrc/element_dispatch.hpp"
 #include "../csrc/element_math.hpp"
+#include "../csrc/motion_tables.hpp"
 
 using namespace femcy;
 
@@ -77,6 +78,13 @@ struct Explicit {
     double alpha = 0.0, b1 = 0.0, b2 = 0.0, Md = 0.0;      // femcy_explicit_set_damping; all 0: undamped
     bool damped() const { return alpha != 0.0 || b1 != 0.0 || b2 != 0.0; }
     bool bulk() const { return b1 != 0.0 || b2 != 0.0; }
+    // femcy_explicit_set_motion: the DOF-set ids the integrator holds and the device's tables (csrc/motion_tables.hpp;
+    // motion.dof empty: no motion), then the clock of a fixed run (csrc/element_math.hpp: explicit_fixed_time)
+    std::vector<int32_t> held;
+    femcy::MotionTables motion;
+    bool moved() const { return !motion.dof.empty(); }
+    int64_t n_done = 0, n_base = 0;
+    double t_base = 0.0, dt_prev = 0.0;
 };
 // a damped element pass or bound (the device's GeomDamping): v, a (null: the start, v_{-1/2} := v_0) and hh = h / 2 of the
 // drift that led to the state
@@ -118,6 +126,7 @@ struct femcy_ctx {
     std::vector<Mass> masses;
     std::vector<LumpedMass> lumped_masses;
     std::vector<Explicit> explicits;
+    std::vector<femcy::Amplitude> amplitudes;   // femcy_amplitude_create; dropped where integrators are
     bool have_K = false;                  // K holds an assembled matrix of the current pattern (femcy_explicit_stable_dt)
     bool post_small = false;             // sigma / mises hold femcy_compute_strain_stress(large = 0), not yet corrected
     int opt_tangent = 0, opt_timing = 0;
@@ -464,6 +473,7 @@ int femcy_set_mesh(femcy_ctx* ctx, int32_t nn, int32_t dm, const double* nodes, 
     c->masses.clear();
     c->lumped_masses.clear();
     c->explicits.clear();
+    c->amplitudes.clear();
     c->have_K = false;
     c->post_small = false;
     c->nn = nn; c->dm = dm; c->ne = ne; c->npe = npe;
@@ -1250,8 +1260,13 @@ void lumped_mass(femcy_ctx* c, int32_t nq, const double* Nq, const double* dNq, 
 
 // the device's node pass (kernels_explicit.hip: explicit_node_pass) on the host: node sums of fe in the order of its gather,
 // then explicit_kick / explicit_drift; what mode and st say is with ExplicitStep in csrc/element_math.hpp
-void explicit_node(femcy_ctx* c, const Explicit& ex, const double* f, const ExplicitStep& st, int mode) {
+// With motion (t: the time of the state being kicked, t_drift: the time the drift reaches) a held and moved DOF takes
+// explicit_moved instead of the kick, as the device's motion policy does.
+void explicit_node(femcy_ctx* c, const Explicit& ex, const double* f, const ExplicitStep& st, int mode, double t = 0.0,
+                   double t_drift = 0.0) {
     const int dm = c->dm;
+    const MotionTables& mo = ex.motion;
+    const bool moved = ex.moved();
     double *u = c->vec[FEMCY_VEC_DOF].data(), *v = c->vec[FEMCY_VEC_VEL].data(), *acc = c->vec[FEMCY_VEC_ACC].data();
 #pragma omp parallel for schedule(static)
     for (int32_t a = 0; a < c->nn; ++a) {
@@ -1259,6 +1274,10 @@ void explicit_node(femcy_ctx* c, const Explicit& ex, const double* f, const Expl
         node_sum(c, a, c->fe.data(), dm, fint);
         for (int i = 0; i < dm; ++i) {
             const int64_t q = (int64_t)a * dm + i;
+            if (const int32_t s = moved ? mo.slot[q] : -1; s >= 0 && ex.minv[q] == 0.0) {
+                explicit_moved(mo.amp[mo.curve[s]], mo.val[s], t, t_drift, mode == XN_START, st.drift, u[q], v[q], acc[q]);
+                continue;
+            }
             // at the start vec[ACC] is not read; vec[VEL] only by the damped kick (v_{-1/2} := v_0)
             double vi = mode != XN_START || st.alpha != 0.0 ? v[q] : 0.0, ai = mode != XN_START ? acc[q] : 0.0;
             if (st.alpha != 0.0)
@@ -1386,6 +1405,16 @@ void mass_scale_factors(femcy_ctx* c, const double* me_all, double s_C, double w
     res[2] = (double)scaled;
 }
 
+// the device's k_explicit_place: u, v, a (what: MOVE_*) of the moved DOFs at time t
+void place_moved(femcy_ctx* c, const Explicit& ex, double t, int what) {
+    const MotionTables& mo = ex.motion;
+    double *u = c->vec[FEMCY_VEC_DOF].data(), *v = c->vec[FEMCY_VEC_VEL].data(), *a = c->vec[FEMCY_VEC_ACC].data();
+    for (size_t k = 0; k < mo.dof.size(); ++k) {
+        const int32_t i = mo.dof[k];
+        explicit_place(mo.amp[mo.curve[k]], mo.val[k], t, what, u[i], v[i], a[i]);
+    }
+}
+
 // nsteps steps from a started state, as the device's explicit_steps runs them: the first drift, then per step the element
 // pass and the node pass.  A fixed run (clock null) takes dt and the load scale scale0 + k dscale from the caller; an
 // automatic one bounds the element frequencies and ticks its clock between the two passes, which then gives both.
@@ -1394,10 +1423,12 @@ int explicit_steps(femcy_ctx* c, const Explicit& ex, ExplicitClock* clock, int r
     if (nsteps == 0) return FEMCY_OK;
     double* u = c->vec[FEMCY_VEC_DOF].data();
     const double *v = c->vec[FEMCY_VEC_VEL].data(), *a = c->vec[FEMCY_VEC_ACC].data();
+    auto time_of = [&](int32_t k) { return explicit_fixed_time(ex.t_base, ex.n_base, ex.n_done + k, dt); };
     if (const double h = clock ? clock->h_next : dt; h != 0.0) {
         const double h2h = 0.5 * h * h;
 #pragma omp parallel for schedule(static)
         for (int64_t i = 0; i < c->n; ++i) u[i] = explicit_drift(u[i], v[i], a[i], h, h2h);
+        place_moved(c, ex, clock ? clock->t_next : time_of(1), MOVE_U);      // a moved u is set, not integrated
     }
     for (int32_t k = 1; k <= nsteps; ++k) {
         const bool last = k == nsteps;      // F and sigma of the last state stay behind for post-processing
@@ -1415,7 +1446,8 @@ int explicit_steps(femcy_ctx* c, const Explicit& ex, ExplicitClock* clock, int r
         } else {
             st = explicit_step_fixed(scale0 + k * dscale, dt, mode, ex.alpha);
         }
-        explicit_node(c, ex, c->vec[rhs_vec].data(), st, mode);
+        explicit_node(c, ex, c->vec[rhs_vec].data(), st, mode, clock ? clock->t : time_of(k),
+                      clock ? clock->t_next : time_of(k + 1));
     }
     return FEMCY_OK;
 }
@@ -1502,6 +1534,7 @@ int femcy_explicit_create(femcy_ctx* ctx, int32_t lumped_id, int32_t ndofsets, c
     const LumpedMass& lm = c->lumped_masses[lumped_id];
     Explicit ex;
     ex.lumped = lumped_id;
+    ex.held.assign(dofset_ids, dofset_ids + ndofsets);
     ex.minv.resize((size_t)c->n);
     for (int64_t i = 0; i < c->n; ++i) ex.minv[i] = 1.0 / lm.m[i / c->dm];
     for (int32_t k = 0; k < ndofsets; ++k)
@@ -1515,7 +1548,10 @@ int femcy_explicit_start(femcy_ctx* ctx, int32_t id, int rhs_vec, double scale) 
     CTX_OR_FAIL(ctx);
     READY_OR_FAIL();
     FEMCY_TRY(check_explicit_start(c, id, rhs_vec, scale));
-    const Explicit& ex = c->explicits[id];
+    Explicit& ex = c->explicits[id];
+    ex.n_done = ex.n_base = 0;                      // the clock of a fixed run: t = 0
+    ex.t_base = ex.dt_prev = 0.0;
+    place_moved(c, ex, 0.0, MOVE_U | MOVE_V | MOVE_A);
     const HostDamping hd = damping_of(c, ex, 0.0, true);
     geom(c, c->vec[FEMCY_VEC_DOF].data(), GEOM_DSDX | GEOM_F | GEOM_SIGMA | GEOM_FE, ex.bulk() ? &hd : nullptr);
     explicit_node(c, ex, c->vec[rhs_vec].data(), explicit_step_fixed(scale, 0.0, XN_START, ex.alpha), XN_START);
@@ -1537,7 +1573,38 @@ int femcy_explicit_advance(femcy_ctx* ctx, int32_t id, int rhs_vec, int32_t nste
     CTX_OR_FAIL(ctx);
     READY_OR_FAIL();
     FEMCY_TRY(check_explicit_advance(c, id, rhs_vec, nsteps, dt, scale0, dscale));
-    return explicit_steps(c, c->explicits[id], nullptr, rhs_vec, nsteps, dt, scale0, dscale);
+    Explicit& ex = c->explicits[id];
+    if (nsteps && dt != ex.dt_prev) {               // another increment: the clock counts on from the time it has reached
+        ex.t_base = explicit_fixed_time(ex.t_base, ex.n_base, ex.n_done, ex.dt_prev);
+        ex.n_base = ex.n_done;
+        ex.dt_prev = dt;
+    }
+    const int rc = explicit_steps(c, ex, nullptr, rhs_vec, nsteps, dt, scale0, dscale);
+    if (!rc) ex.n_done += nsteps;
+    return rc;
+}
+
+int femcy_amplitude_create(femcy_ctx* ctx, int32_t kind, int32_t npts, const double* t, const double* A, int32_t* id_out) {
+    CTX_OR_FAIL(ctx);
+    FEMCY_TRY(check_amplitude_create(kind, npts, t, A, id_out));
+    Amplitude am{};
+    am.kind = kind;
+    am.npts = npts;
+    std::copy(t, t + npts, am.t);
+    std::copy(A, A + npts, am.A);
+    c->amplitudes.push_back(am);
+    *id_out = (int32_t)c->amplitudes.size() - 1;
+    return FEMCY_OK;
+}
+
+int femcy_explicit_set_motion(femcy_ctx* ctx, int32_t id, int32_t nsets, const int32_t* dofset_ids, const double* values,
+                              const int32_t* amplitude_ids) {
+    CTX_OR_FAIL(ctx);
+    FEMCY_TRY(check_explicit_set_motion(c, id, nsets, dofset_ids, values, amplitude_ids));
+    std::vector<std::vector<int32_t>> sets((size_t)nsets);
+    for (int32_t k = 0; k < nsets; ++k) sets[k] = c->dofsets[dofset_ids[k]].dofs;
+    c->explicits[id].motion = motion_tables(c->n, sets, values, amplitude_ids, c->amplitudes);
+    return FEMCY_OK;
 }
 
 int femcy_explicit_kinetic_energy(femcy_ctx* ctx, int32_t id, int v_vec, double* out) {
@@ -1617,6 +1684,7 @@ int femcy_explicit_auto_begin(femcy_ctx* ctx, int32_t id, int rhs_vec, double s_
     Explicit& exm = c->explicits[id];
     const double* u = c->vec[FEMCY_VEC_DOF].data();
     double w2 = 0.0;
+    place_moved(c, exm, 0.0, MOVE_U | MOVE_V | MOVE_A);
     const HostDamping hd = damping_of(c, exm, 0.0, true);      // v_{-1/2} := v_0, vec[ACC] is not read
     int rc = element_bound_any(c, exm, u, s_C, &w2, exm.damped() ? &hd : nullptr);
     if (rc) return rc;

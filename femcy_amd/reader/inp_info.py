@@ -135,6 +135,7 @@ class InpInfo(InpInfoBase):
         self.nodes, self.eSets = self.read_node_element(file)
         self.node_sets, self.ele_sets = self.read_set(file)
         self.face_sets = self.read_face_set(file)
+        self.amplitudes = self.read_amplitudes(file)
         self.dirichlet_bc_info, self.neumann_bc_info = self.get_boundary_condition(file)
         self.materials = self.read_material(file)
         self.density, self.body_force_info, self.cload_info = self.read_loads(file)
@@ -256,20 +257,66 @@ class InpInfo(InpInfoBase):
         return face_sets
 
     # ------------------------------------------------------------------ boundary conditions
+    def read_amplitudes(self, fileName):
+        """`*Amplitude, name=NAME[, definition=TABULAR|SMOOTH STEP]` -> {NAME: {"definition", "t", "A"}}, in step time.
+        The data are `t, A` pairs, up to four per line, over any number of lines; 2 to 16 points with increasing times.
+        A duplicate name, any other `definition=`, a point count outside that range, an odd number of values and times
+        that do not increase are refused."""
+        amplitudes = {}
+        for line, block in _deck(fileName).keywords():
+            fields = [t.strip() for t in line.split(",")]
+            if fields[0].lower() != "*amplitude":
+                continue
+            params = {t.split("=")[0].strip().lower(): t.split("=", 1)[1].strip() for t in fields[1:] if "=" in t}
+            name = params.get("name")
+            if not name:
+                raise ValueError("*Amplitude needs name=")
+            if name in amplitudes:
+                raise ValueError("*Amplitude, name={} is defined twice".format(name))
+            definition = " ".join(params.get("definition", "TABULAR").upper().split())
+            if definition not in ("TABULAR", "SMOOTH STEP"):
+                raise ValueError("*Amplitude, definition={} has not been supported (TABULAR and SMOOTH STEP are)".format(
+                    params["definition"]))
+            vals = _numbers(block, np.float64)
+            if vals.size % 2:
+                raise ValueError("*Amplitude, name={}: the data are `t, A` pairs, {} values were given".format(name, vals.size))
+            t, A = vals[0::2].copy(), vals[1::2].copy()
+            if not 2 <= t.size <= 16:
+                raise ValueError("*Amplitude, name={}: {} points are refused (2 to 16 are taken)".format(name, t.size))
+            if not np.all(np.isfinite(vals)) or not np.all(np.diff(t) > 0.0):
+                raise ValueError("*Amplitude, name={}: the times must be finite and increasing".format(name))
+            amplitudes[name] = {"definition": definition, "t": t, "A": A}
+        return amplitudes
+
     def get_boundary_condition(self, fileName):
         if not hasattr(self, "node_sets"):
             self.node_sets, self.ele_sets = self.read_set(fileName)
         if not hasattr(self, "face_sets"):
             self.face_sets = self.read_face_set(fileName)
+        if not hasattr(self, "amplitudes"):
+            self.amplitudes = self.read_amplitudes(fileName)
         dirichlet, neumann = [], []
         for line, block in _deck(fileName).keywords():
             if line[0:9] == "*Boundary":
-                user = "user" in line
+                # `*Boundary, amplitude=NAME` (prescribed motion, *Dynamic, explicit only: read_procedure): the entries gain
+                # the key "amplitude"; without the parameter the key is absent and the dictionaries are what they always were
+                fields = [t.strip() for t in line.split(",")[1:]]
+                named = [t.split("=", 1)[1].strip() for t in fields if t.split("=")[0].strip().lower() == "amplitude" and "=" in t]
+                if named:
+                    user = any(t.lower() == "user" for t in fields)
+                    if user:
+                        raise ValueError("*Boundary, amplitude={} together with `user` has not been supported".format(named[0]))
+                    if named[0] not in self.amplitudes:
+                        raise ValueError("*Boundary, amplitude={}: the deck has no *Amplitude of that name".format(named[0]))
+                else:
+                    user = "user" in line
                 for data_line in block:
                     if data_line:
                         f = data_line.split(",")
                         dirichlet.append({"node_set": self.node_sets[f[0]], "dof": int(f[1]) - 1,
                                           "val": float(f[3]) if len(f) >= 4 else 0., "user": user})
+                        if named:
+                            dirichlet[-1]["amplitude"] = named[0]
             elif line[0:7] == "*Dsload":
                 for data_line in block:
                     if not data_line:
@@ -480,8 +527,9 @@ class InpInfo(InpInfoBase):
         with t / T, as it always did) and to STEP under `*Dynamic` (loads in full from t = 0+).
         `*Dynamic, explicit[, direct user control][, scale factor=][, output_every=]` -> procedure "explicit" and dynamic =
         {"direct_user_control", "scale_factor", "output_every"}: central differences with a lumped mass (`solve_explicit`).
-        It refuses `beta=` / `gamma=` / `alpha=`, a deck without `*Density`, a non-zero `*Boundary` value and
-        `*Temperature`.  `element by element` on `*Dynamic, explicit` asks for the increment to be re-estimated from the
+        It refuses `beta=` / `gamma=` / `alpha=`, a deck without `*Density`, a non-zero `*Boundary` value that names no
+        `*Amplitude` (a jump is not a motion; with `amplitude=NAME` the entry is prescribed motion, and that parameter is
+        refused under `*Static` and `*Dynamic, direct`, where it is not built) and `*Temperature`.`element by element` on `*Dynamic, explicit` asks for the increment to be re-estimated from the
         current configuration in every step; it is refused together with `direct user control` and on any other
         `*Dynamic`.  The flag is kept beside the dictionary, as `self.dynamic_auto` (False for every other deck)."""
         procedure, dynamic, amplitude = "static", None, None
@@ -533,8 +581,14 @@ class InpInfo(InpInfoBase):
         if procedure in ("dynamic", "explicit"):
             if getattr(self, "density", None) is None:
                 raise ValueError("*Dynamic needs a *Density in the *Material block")
-            if any(bc["val"] != 0.0 for bc in self.dirichlet_bc_info):
+            if any(bc["val"] != 0.0 and "amplitude" not in bc for bc in self.dirichlet_bc_info):
                 raise ValueError("a non-zero *Boundary value in a *Dynamic step (prescribed motion) has not been supported")
+        if procedure != "explicit":
+            for bc in self.dirichlet_bc_info:
+                if "amplitude" in bc:
+                    raise ValueError("*Boundary, amplitude={} has not been supported in a *{} step: prescribed motion is "
+                                     "built for *Dynamic, explicit alone".format(
+                                         bc["amplitude"], "Static" if procedure == "static" else "Dynamic, direct"))
         if procedure == "explicit" and getattr(self, "temperature_info", None) is not None:
             raise ValueError("*Temperature in a *Dynamic, explicit step has not been supported: thermal loads are small "
                              "strain, an explicit step is not")

@@ -50,7 +50,8 @@ def deck_view(inp) -> SimpleNamespace:
         expansion=opt("expansion"), temperature_info=opt("temperature_info"),
         initial_velocity_info=opt("initial_velocity_info") or [], dynamic=opt("dynamic"),
         dynamic_auto=bool(opt("dynamic_auto", False)), bulk_viscosity=opt("bulk_viscosity"),
-        damping_alpha=float(opt("damping_alpha", 0.0) or 0.0), mass_scaling=opt("mass_scaling"))
+        damping_alpha=float(opt("damping_alpha", 0.0) or 0.0), mass_scaling=opt("mass_scaling"),
+        amplitudes=opt("amplitudes") or {})
 
 
 class LoadSchedule:
@@ -523,14 +524,49 @@ class System_of_equations:
                 self.dirichletBC_dof(bc["node_set"], bc["dof"], bc["val"], bc["user"], self.time1)
 
     # ------------------------------------------------------- shared by the transient drivers
-    def _transient_gate(self, deck, step: str, mass: str):
-        """what neither dynamic procedure takes; `step` and `mass` are the words in which the two name themselves"""
+    def _transient_gate(self, deck, step: str, mass: str, motion: bool = False):
+        """what neither dynamic procedure takes; `step` and `mass` are the words in which the two name themselves.  `motion`
+        (the explicit procedure): a `*Boundary` entry that names an `*Amplitude` is prescribed motion and passes; a non-zero
+        value without one is a jump, not a motion, and is refused everywhere."""
         if self.part is not None:
             raise ValueError("a {} on more than one rank has not been supported: the {} is single-rank".format(step, mass))
         if deck.density is None:
             raise ValueError("*Dynamic needs a *Density in the *Material block")
-        if any(bc["val"] != 0.0 for bc in deck.dirichlet_bc_info):
+        if any(bc["val"] != 0.0 and not (motion and "amplitude" in bc) for bc in deck.dirichlet_bc_info):
             raise ValueError("a non-zero *Boundary value in a *Dynamic step (prescribed motion) has not been supported")
+        for bc in deck.dirichlet_bc_info:
+            if "amplitude" in bc and not motion:
+                raise ValueError("*Boundary, amplitude={} has not been supported in a {}: prescribed motion is built for "
+                                 "*Dynamic, explicit alone".format(bc["amplitude"], step))
+            if "amplitude" in bc and bc["amplitude"] not in deck.amplitudes:
+                raise ValueError("*Boundary, amplitude={}: the deck has no *Amplitude of that name".format(bc["amplitude"]))
+
+    def _set_motion(self, deck, loads, ex, held):
+        """prescribed motion of an explicit step: the `*Boundary` entries that name an `*Amplitude` move as value x A(t), the
+        other held entries stay at rest.  One device curve per name that is used; `self.motion` lists the moved entries, in
+        the deck's order (empty: no call is made and the integrator is launched as it always was)."""
+        ctx = self.ctx
+        self.motion = [{"node_set": self._node_ids(bc["node_set"]), "dof": bc["dof"], "val": bc["val"],
+                        "amplitude": bc["amplitude"]} for bc in loads.dirichletBCs if "amplitude" in bc]
+        if not self.motion:
+            return
+        curves, sets = {}, [ds for ds, bc in zip(held, loads.dirichletBCs) if "amplitude" in bc]
+        for m in self.motion:
+            if m["amplitude"] not in curves:
+                a = deck.amplitudes[m["amplitude"]]
+                curves[m["amplitude"]] = ctx.amplitude(a["definition"], a["t"], a["A"])
+        ctx.explicit_set_motion(ex, sets, [m["val"] for m in self.motion], [curves[m["amplitude"]] for m in self.motion])
+
+    def _reaction(self, scale: float) -> list:
+        """per moved `*Boundary` entry, the force the body exerts on the boundary that moves it: the sum over the entry's DOFs
+        of scale x f - f_int at the current state, so that a bar pulled along +z answers with a negative number -- the
+        residual f_int - scale x f of those DOFs with the sign turned.  An internal-force evaluation and two vector calls;
+        the bulk-viscosity forces are not part of f_int and are not in it."""
+        ctx = self.ctx
+        ctx.internal_force(be.VEC_DOF, be.VEC_FORCE)
+        ctx.vec_axpy(be.VEC_RESIDUAL, be.VEC_FORCE, -scale, be.VEC_RHS)
+        r = ctx.download(be.VEC_RESIDUAL)
+        return [-float(r[m["node_set"] * self.dm + m["dof"]].sum()) for m in self.motion]
 
     def _external_force(self, loads: LoadSchedule, ratio: float):
         """rhs = `ratio` x the loads of a dynamic step, which reads rhs whatever the deck holds: zeroed here if it holds no load"""
@@ -701,9 +737,15 @@ class System_of_equations:
         `*Fixed Mass Scaling` (`inp.mass_scaling`) scales the element masses once, between the lumped mass and the integrator
         (`femcy_lumped_mass_scale` with `material_stiffness()`); `mass_scaling` keeps {"mass0", "mass1", "scaled_elements",
         "max_factor"} (None without the keyword).  Both increment estimates and the kinetic energy then see the scaled
-        masses.  The loads do not: body forces stay those of the deck's density, and so does rho_0 of the bulk viscosity."""
+        masses.  The loads do not: body forces stay those of the deck's density, and so does rho_0 of the bulk viscosity.
+        Prescribed motion: a `*Boundary, amplitude=NAME` entry moves its DOFs as value x A(t) with A the deck's `*Amplitude`
+        NAME in step time (`femcy_amplitude_create`, `femcy_explicit_set_motion`, right after the integrator is made); held
+        entries without an amplitude stay at rest, and a non-zero value without one is refused.  The integrator itself places
+        the moved DOFs at t = 0.  `self.motion` lists the moved entries, and only when there are any every record gains
+        "reaction": per moved entry the force the body exerts on its boundary, the sum over the entry's DOFs of s f - f_int at
+        the record's state, which opposes a pull (`_reaction`; the bulk-viscosity forces are not in it)."""
         deck = deck_view(inp)
-        self._transient_gate(deck, "*Dynamic, explicit step", "lumped mass")
+        self._transient_gate(deck, "*Dynamic, explicit step", "lumped mass", motion=True)
         if deck.temperature_info is not None:
             raise ValueError("*Temperature in a *Dynamic, explicit step has not been supported: thermal loads are small "
                              "strain, an explicit step is not")
@@ -721,6 +763,7 @@ class System_of_equations:
             self._say("fixed mass scaling: {scaled_elements} elements scaled, largest factor {max_factor}, total mass "
                       "{mass0} -> {mass1}".format(**self.mass_scaling))
         self.explicit = ex = ctx.explicit(self.lumped_mass, held)
+        self._set_motion(deck, loads, ex, held)
         bulk, alpha = deck.bulk_viscosity, deck.damping_alpha
         b1, b2 = bulk if bulk is not None else (0.0, 0.0)
         if bulk is not None or alpha != 0.0:
@@ -758,7 +801,8 @@ class System_of_equations:
             done += k
             self.time0, self.time1 = self.time1, max_time if done == nsteps else done * h
             self._displacements_are_finite("{} steps of dt = {}".format(done, h))
-            self._record(done, h, ctx.explicit_kinetic_energy(ex, be.VEC_VEL))
+            more = {"reaction": self._reaction(scale0 + done * dscale)} if self.motion else {}
+            self._record(done, h, ctx.explicit_kinetic_energy(ex, be.VEC_VEL), **more)
         self.dof_old.copy_from(self.dof)
 
     def material_stiffness(self):
@@ -803,7 +847,8 @@ class System_of_equations:
                 raise be.FemcyError("explicit step: the increment collapsed to 0 at t = {} of {} after {} steps (an unstable "
                                     "increment)".format(t, max_time, steps), status=be.FEMCY_ENUMERIC)
             done = steps
-            self._record(done, h_last, ctx.explicit_kinetic_energy(ex, be.VEC_VEL), dt_min=h_min)
+            more = {"reaction": self._reaction(loads.amplitude(t))} if self.motion else {}
+            self._record(done, h_last, ctx.explicit_kinetic_energy(ex, be.VEC_VEL), dt_min=h_min, **more)
         self.dof_old.copy_from(self.dof)
 
     def _residual(self, dirichletBCs):

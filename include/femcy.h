@@ -531,6 +531,38 @@ int femcy_explicit_auto_state(femcy_ctx* ctx, int32_t id, double* t, double* h_l
  * All four zero: the undamped launches and bits.  Refused with FEMCY_EINVAL, the context stays usable: an unknown id, a
  * value that is not finite or negative, M_d <= 0 while b1 or b2 is not zero, and once femcy_comm_init has run. */
 int femcy_explicit_set_damping(femcy_ctx* ctx, int32_t id, double alpha, double b1, double b2, double M_d);
+/* Prescribed motion (*Boundary, amplitude=NAME with *Amplitude): held DOFs that follow a curve in time instead of staying at
+ * rest.  femcy_amplitude_create: one curve A(t) in step time from npts points (2 .. FEMCY_AMP_MAX_POINTS), t strictly
+ * increasing.  Between two points, with xi = (t - t_k) / (t_{k+1} - t_k),
+ *   FEMCY_AMP_TABULAR      A = A_k + (A_{k+1} - A_k) xi,  A' the slope of [t_k, t_{k+1}) (the right-hand one at a point), A'' = 0
+ *   FEMCY_AMP_SMOOTH_STEP  A = A_k + (A_{k+1} - A_k) xi^3 (10 - 15 xi + 6 xi^2), A' and A'' from the same polynomial: both 0
+ *                          at every point
+ * and outside the table both are clamped: (A_0, 0, 0) for t <= t_0, (A_last, 0, 0) exactly for t >= t_last.
+ * femcy_explicit_set_motion: every DOF of DOF set dofset_ids[k] moves as
+ *   u = values[k] A_k(t),   v = values[k] A_k'(t),   a = values[k] A_k''(t),      A_k the curve amplitude_ids[k],
+ * whatever force it gathers.  Every set must be one of the sets the integrator was created with (minv = 0 there), at most 4
+ * distinct curves per integrator; where a DOF is in two sets, the later one wins.  Held sets that are not named stay at rest.
+ * It takes effect from the next femcy_explicit_start / _auto_begin: both first place u, v and a of the moved DOFs at t = 0,
+ * so that f_int(u_0) and the first increment estimate see the placed boundary.  In a step the node pass writes a and v of a
+ * moved DOF at the time of the state being kicked and, where it drifts, u at the time the drift reaches; the first drift of a
+ * call is followed by one small launch over the moved DOFs that does the same to u.  The step stays two launches.  The bulk
+ * viscosity reads these v and a like any other, v_{n+1/2} = values[k] (A' + (h / 2) A''); a moved DOF takes no alpha force.
+ * femcy_explicit_kinetic_energy counts the moved nodes with their mass; neither increment estimate changes.
+ * Time: an automatic run reads its device clock.  A fixed run keeps a clock of its own: femcy_explicit_start sets it to 0,
+ * step n is at t_base + (n - n_base) dt, and (t_base, n_base) is reset only when a call's dt differs from the previous
+ * call's -- so a run split into several femcy_explicit_advance calls of the same dt still gives the bits of one call.
+ * nsets = 0 removes the motion: the integrator is then launched exactly as without this call, the same bits.
+ * Amplitudes are dropped where integrators are.  Refused with FEMCY_EINVAL, the context stays usable: an unknown id (curve,
+ * integrator, DOF set), an unknown kind, npts outside 2 .. 16, t not strictly increasing, an entry or a value that is not
+ * finite, null arguments, a set that is not one of the integrator's held sets, more than 4 distinct curves, and either call
+ * once femcy_comm_init has run. */
+#define FEMCY_AMP_MAX_POINTS 16
+#define FEMCY_MOTION_MAX_CURVES 4
+enum femcy_amplitude_kind { FEMCY_AMP_TABULAR = 0, FEMCY_AMP_SMOOTH_STEP = 1 };
+int femcy_amplitude_create(femcy_ctx* ctx, int32_t kind, int32_t npts, const double* t /*[npts]*/, const double* A /*[npts]*/,
+                           int32_t* id_out);
+int femcy_explicit_set_motion(femcy_ctx* ctx, int32_t id, int32_t nsets, const int32_t* dofset_ids /*[nsets]*/,
+                              const double* values /*[nsets]*/, const int32_t* amplitude_ids /*[nsets]*/);
 /* Fixed mass scaling (*Fixed Mass Scaling, whole model): the element shares m_a^e of a lumped mass are multiplied by one
  * factor k_e per element, before an integrator is made from it, and the nodal masses are summed again.  omega_e^2 above is
  * linear in 1 / m_a^e, so k_e divides it exactly and a target increment is met in closed form, in the project's own
