@@ -79,7 +79,7 @@ EXPORTS = [
     "femcy_explicit_advance", "femcy_explicit_kinetic_energy", "femcy_explicit_stable_dt",
     "femcy_explicit_element_bound", "femcy_explicit_auto_begin", "femcy_explicit_auto_advance", "femcy_explicit_auto_state",
     "femcy_explicit_set_damping", "femcy_lumped_mass_scale", "femcy_lumped_mass_get_scaling",
-    "femcy_amplitude_create", "femcy_explicit_set_motion",
+    "femcy_amplitude_create", "femcy_explicit_set_motion", "femcy_explicit_energy_enable", "femcy_explicit_energy_get",
     "femcy_loadset_create", "femcy_loadset_neumann", "femcy_loadset_neumann_add", "femcy_spmv", "femcy_pcg", "femcy_compute_strain_stress", "femcy_elastic_energy", "femcy_elastic_energy_small", "femcy_extrapolate",
     "femcy_get_K_ell", "femcy_get_K_bsr", "femcy_get_gp_field", "femcy_timing",
     "femcy_timing_reset", "femcy_comm_unique_id", "femcy_comm_local_id", "femcy_comm_init", "femcy_comm_info", "femcy_comm_set_neighbours",
@@ -108,6 +108,8 @@ MS_TYPES = {"below min": MS_BELOW_MIN, "set equal dt": MS_SET_EQUAL_DT, "uniform
 AMP_TABULAR, AMP_SMOOTH_STEP = 0, 1
 AMP_KINDS = {"tabular": AMP_TABULAR, "smooth step": AMP_SMOOTH_STEP}
 AMP_MAX_POINTS = 16
+# femcy_explicit_energy_get: the four work sums of the energy balance (*Energy Output)
+EN_LOAD, EN_INTERNAL, EN_ALPHA, EN_BOUNDARY = 0, 1, 2, 3
 
 
 class DirectInfo(C.Structure):
@@ -200,6 +202,7 @@ def _bind(lib, kind):
         "femcy_lumped_mass_get_scaling": [p, i32, p],
         "femcy_amplitude_create": [p, i32, i32, p, p, C.POINTER(i32)],
         "femcy_explicit_set_motion": [p, i32, i32, p, p, p],
+        "femcy_explicit_energy_enable": [p, i32, i32], "femcy_explicit_energy_get": [p, i32, p],
         "femcy_explicit_auto_state": [p, i32, C.POINTER(f64), C.POINTER(f64), C.POINTER(f64), C.POINTER(C.c_int64)],
         "femcy_loadset_create": [p, i32, i32, i32, p, p, p, p, p, i32, p, p, C.POINTER(i32)],
         "femcy_loadset_neumann": [p, i32, f64, p, cint],
@@ -668,6 +671,18 @@ class Context:
         some = ids.size > 0
         self._call("femcy_explicit_set_motion", int(ex), int(ids.size), _ptr(ids) if some else None,
                    _ptr(vals) if some else None, _ptr(amps) if some else None)
+
+    def explicit_energy_enable(self, ex: int, on: bool = True):
+        """the energy balance of an integrator: on from its next explicit_start / explicit_auto_begin, which zero the four
+        work sums; the node pass of every step then adds to them on the device, with no launch added and the same u, v, a.
+        off: the launches of an integrator that never had it"""
+        self._call("femcy_explicit_energy_enable", int(ex), int(bool(on)))
+
+    def explicit_energy(self, ex: int) -> np.ndarray:
+        """-> [EN_LOAD, EN_INTERNAL, EN_ALPHA, EN_BOUNDARY]: the synchronising read-back of the work sums since the start"""
+        out = np.zeros(4, dtype=np.float64)
+        self._call("femcy_explicit_energy_get", int(ex), _ptr(out))
+        return out
 
     def explicit_auto_state(self, ex: int):
         """-> (t, h_last, h_min, steps_done): the synchronising read-back of the device clock"""

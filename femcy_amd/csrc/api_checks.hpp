@@ -426,6 +426,17 @@ int check_explicit_set_motion(const C* c, int32_t id, int32_t nsets, const int32
     return FEMCY_OK;
 }
 
+// femcy_explicit_energy_get: a known integrator whose balance has been running since a start (energy_on: set by
+// femcy_explicit_start / _auto_begin of an integrator with femcy_explicit_energy_enable(on != 0), cleared by on = 0)
+template <class C>
+int check_explicit_energy_get(const C* c, int32_t id, const double* out) {
+    FEMCY_TRY(check_object(c->explicits, id, "explicit integrator"));
+    FEMCY_REQUIRE(out, TEXT_NULL_OUTPUT);
+    FEMCY_REQUIRE(c->explicits[id].energy_on, "femcy_explicit_energy_get: the energy balance of integrator %d is not running "
+                  "(femcy_explicit_energy_enable, then femcy_explicit_start or femcy_explicit_auto_begin)", (int)id);
+    return FEMCY_OK;
+}
+
 template <class C>
 int check_explicit_start(const C* c, int32_t id, int rhs_vec, double scale) {
     FEMCY_TRY(check_explicit_rhs(c, "femcy_explicit_start", id, rhs_vec));

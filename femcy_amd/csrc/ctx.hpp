@@ -410,6 +410,11 @@ struct Ctx {
         // explicit_fixed_time (element_math.hpp)
         int64_t n_done = 0, n_base = 0;
         double t_base = 0.0, dt_prev = 0.0;
+        // the energy balance (femcy_explicit_energy_enable): asked for / running since a start; the forces of the last
+        // kicked state (d_efint, d_ealpha [n]) and one slot of EN_SLOT doubles per wavefront of the node-pass grid
+        // (explicit_energy_slots), all allocated by the first enable; off: the launches of an integrator that never had it
+        bool energy_want = false, energy_on = false;
+        DevBuf<double> d_efint, d_ealpha, d_eslot;
     };
     std::vector<Explicit> explicits;
     std::vector<Amplitude> amplitudes;   // femcy_amplitude_create; dropped where integrators are
@@ -561,8 +566,19 @@ struct ExplicitMotion {
     int32_t nmoved;
     double t, t_drift;
 };
+// en (femcy_explicit_energy_enable; null: none, today's instantiations with today's arguments): the energy variant of the
+// node pass, which also adds the step's four work addends into the wavefront's slot of d_slot [explicit_energy_slots(c)]
+// [EN_SLOT] and leaves the state's forces in d_fint / d_falpha [n]; d_m [nn] the lumped mass.  launch_explicit_energy_sum:
+// out[FEMCY_EN_*] = the slots summed in a fixed order, fetched (synchronises).
+constexpr int EN_SLOT = 8;      // the four sums, the load scale and the time of the last kicked state, padding to 64 B
+struct ExplicitEnergy {
+    const double* d_m;
+    double *d_fint, *d_falpha, *d_slot;
+};
+int explicit_energy_slots(const Ctx* c);
 int launch_explicit_node(Ctx* c, const double* d_minv, const double* d_f, const ExplicitClock* d_clk, double scale, double h,
-                         int mode, double alpha = 0.0, const ExplicitMotion* mv = nullptr);
+                         int mode, double alpha = 0.0, const ExplicitMotion* mv = nullptr, const ExplicitEnergy* en = nullptr);
+int launch_explicit_energy_sum(Ctx* c, const double* d_slot, double* out);
 int launch_explicit_place(Ctx* c, const ExplicitMotion& mv, const ExplicitClock* d_clk, double t, int what);
 int launch_explicit_energy(Ctx* c, const double* d_m, const double* d_v, double* out);   // 1/2 sum m v^2, fixed order
 // max over the rows i with minv_i != 0 of minv_i sum_j |K_ij| (Gershgorin bound on the spectrum of M_L^-1 K)

@@ -1131,6 +1131,42 @@ FEMCY_HD double explicit_fixed_time(double t_base, int64_t n_base, int64_t n, do
     return fma((double)(n - n_base), dt, t_base);
 }
 
+// Energy balance (*Energy Output; femcy_explicit_energy_enable / _get, where the definitions stand).  One scalar DOF's
+// addends w[FEMCY_EN_*] of the step that led to the state n being kicked, by the trapezoid rule 1/2 du (g_{n-1} + g_n) for
+// every force g; what the node pass of either backend calls with the numbers it holds anyway.  The forces of state n - 1
+// (fint_prev, ga_prev) and its load scale s_prev come from what the previous kick left behind.
+FEMCY_HD double energy_trapezoid(double du, double g_prev, double g) { return 0.5 * du * (g_prev + g); }
+// a DOF that is not moved: v and a are those of state n - 1 (at the start v_0 and 0), hh half the increment that led to
+// state n.  ga = alpha m v_{n-1/2}, the force explicit_kick_damped subtracts, for the next call; a held DOF (minv = 0)
+// has du = 0 and takes no alpha force.  start: only ga.
+FEMCY_HD void explicit_energy_free(double minv, double m, double s_prev, double s, double f, double fint_prev, double fint,
+                                   double ga_prev, double alpha, double v, double a, double hh, bool start, double (&w)[4],
+                                   double& ga) {
+    w[0] = w[1] = w[2] = w[3] = 0.0;
+    ga = 0.0;
+    if (minv == 0.0) return;
+    const double vh = explicit_vhalf(v, a, hh);
+    if (alpha != 0.0) ga = alpha * m * vh;
+    if (start) return;
+    const double du = (2.0 * hh) * vh;
+    w[FEMCY_EN_LOAD] = energy_trapezoid(du, s_prev * f, s * f);
+    w[FEMCY_EN_INTERNAL] = energy_trapezoid(du, fint_prev, fint);
+    w[FEMCY_EN_ALPHA] = energy_trapezoid(du, ga_prev, ga);
+}
+// a moved DOF: du is the curve's own difference between the two states, a_prev and a its accelerations there, and the
+// support applies R = m a + fint - s f
+FEMCY_HD void explicit_energy_moved(const Amplitude& am, double g, double t_prev, double t, double m, double s_prev, double s,
+                                    double f, double fint_prev, double fint, double a_prev, double a, double (&w)[4]) {
+    double u0 = 0.0, u1 = 0.0, unused = 0.0;
+    explicit_place(am, g, t_prev, MOVE_U, u0, unused, unused);
+    explicit_place(am, g, t, MOVE_U, u1, unused, unused);
+    const double du = u1 - u0;
+    w[FEMCY_EN_LOAD] = energy_trapezoid(du, s_prev * f, s * f);
+    w[FEMCY_EN_INTERNAL] = energy_trapezoid(du, fint_prev, fint);
+    w[FEMCY_EN_ALPHA] = 0.0;
+    w[FEMCY_EN_BOUNDARY] = energy_trapezoid(du, m * a_prev + fint_prev - s_prev * f, m * a + fint - s * f);
+}
+
 // sum of 32 partial sums by the xor tree of half a wavefront, as lane 0 of k_nodal_force ends up with it: what the host
 // backend runs so that a node sum has the device's summation order
 inline double half_wave_tree(double (&p)[32]) {

@@ -1265,6 +1265,38 @@ static ExplicitMotion motion_of(const Ctx::Explicit& ex, double t, double t_drif
     return {ex.d_mslot.get(), ex.d_mdof.get(), ex.d_mcurve.get(), ex.d_mval.get(), ex.d_amp.get(), ex.nmoved, t, t_drift};
 }
 
+// the energy balance of an integrator for the launchers (femcy_explicit_energy_enable)
+static ExplicitEnergy energy_of(const Ctx* c, const Ctx::Explicit& ex) {
+    return {c->lumped_masses[ex.lumped].d_m.get(), ex.d_efint.get(), ex.d_ealpha.get(), ex.d_eslot.get()};
+}
+
+int femcy_explicit_energy_enable(femcy_ctx* ctx, int32_t id, int32_t on) {
+    CTX_OR_FAIL(ctx);
+    EXPLICIT_SINGLE_RANK_OR_FAIL("femcy_explicit_energy_enable");
+    FEMCY_TRY(check_object(c->explicits, id, "explicit integrator"));
+    Ctx::Explicit& ex = c->explicits[id];
+    if (!on) {
+        ex.energy_want = ex.energy_on = false;
+        return FEMCY_OK;
+    }
+    const size_t nslot = (size_t)explicit_energy_slots(c) * EN_SLOT;
+    if ((!ex.d_efint.get() && ex.d_efint.alloc(sizeof(double) * (size_t)c->n) != hipSuccess) ||
+        (!ex.d_ealpha.get() && ex.d_ealpha.alloc(sizeof(double) * (size_t)c->n) != hipSuccess) ||
+        (!ex.d_eslot.get() && ex.d_eslot.alloc(sizeof(double) * nslot) != hipSuccess)) {
+        set_error("out of device memory for the energy balance of %lld DOF", (long long)c->n);
+        return FEMCY_ENOMEM;
+    }
+    ex.energy_want = true;
+    return FEMCY_OK;
+}
+
+int femcy_explicit_energy_get(femcy_ctx* ctx, int32_t id, double* out) {
+    CTX_OR_FAIL(ctx);
+    EXPLICIT_SINGLE_RANK_OR_FAIL("femcy_explicit_energy_get");
+    FEMCY_TRY(check_explicit_energy_get(c, id, out));
+    return launch_explicit_energy_sum(c, c->explicits[id].d_eslot.get(), out);
+}
+
 int femcy_explicit_start(femcy_ctx* ctx, int32_t id, int rhs_vec, double scale) {
     CTX_OR_FAIL(ctx);
     READY_OR_FAIL();
@@ -1279,8 +1311,10 @@ int femcy_explicit_start(femcy_ctx* ctx, int32_t id, int rhs_vec, double scale) 
     const GeomDamping gd = damping_of(c, ex, nullptr, 0.0, true);
     rc = force_pass(c, c->d_vec[FEMCY_VEC_DOF], ex.bulk() ? &gd : nullptr);
     if (rc) return rc;
+    ex.energy_on = ex.energy_want;                  // the start zeroes the sums and records the forces of state 0
+    const ExplicitEnergy en = energy_of(c, ex);
     return launch_explicit_node(c, ex.d_minv.get(), c->d_vec[rhs_vec], nullptr, scale, 0.0, XN_START, ex.alpha,
-                                ex.nmoved ? &mv : nullptr);
+                                ex.nmoved ? &mv : nullptr, ex.energy_on ? &en : nullptr);
 }
 
 // nsteps steps from a started state: the first drift, then per step the element pass and the node pass (kick, and the drift
@@ -1301,6 +1335,8 @@ static int explicit_steps(Ctx* c, const Ctx::Explicit& ex, ExplicitClock* clk, i
     const bool moved = ex.nmoved != 0;
     auto time_of = [&](int32_t k) { return explicit_fixed_time(ex.t_base, ex.n_base, ex.n_done + k, dt); };
     ExplicitMotion mv = motion_of(ex, 0.0, 0.0);
+    // energy balance (femcy_explicit_energy_enable): the energy variant of the node pass, the same number of launches
+    const ExplicitEnergy en = energy_of(c, ex);
     int rc = launch_explicit_drift(c, clk, dt);
     if (!rc && moved) rc = launch_explicit_place(c, mv, clk, clk ? 0.0 : time_of(1), MOVE_U);
     for (int32_t k = 1; !rc && k <= nsteps; ++k) {
@@ -1312,7 +1348,8 @@ static int explicit_steps(Ctx* c, const Ctx::Explicit& ex, ExplicitClock* clk, i
             if ((rc = launch_explicit_clock(c, ex.d_bpart.get(), clk))) break;
         }
         rc = launch_explicit_node(c, ex.d_minv.get(), c->d_vec[rhs_vec], clk, scale0 + k * dscale, dt,
-                                  k < nsteps ? XN_KICK_DRIFT : XN_KICK, ex.alpha, moved ? &mv : nullptr);
+                                  k < nsteps ? XN_KICK_DRIFT : XN_KICK, ex.alpha, moved ? &mv : nullptr,
+                                  ex.energy_on ? &en : nullptr);
     }
     if (rc) return rc;
     // post-processing reads "the stress of the last force evaluation": that of the last state (the last step did not drift)
@@ -1418,8 +1455,10 @@ int femcy_explicit_auto_begin(femcy_ctx* ctx, int32_t id, int rhs_vec, double s_
                                     exm.damped() ? &gd : nullptr)))
         return rc;
     if ((rc = launch_explicit_clock(c, exm.d_bpart.get(), exm.d_clock.get()))) return rc;   // t = 0, the first h
+    exm.energy_on = exm.energy_want;                                    // as femcy_explicit_start
+    const ExplicitEnergy en = energy_of(c, exm);
     if ((rc = launch_explicit_node(c, exm.d_minv.get(), c->d_vec[rhs_vec], exm.d_clock.get(), 0.0, 0.0, XN_START, exm.alpha,
-                                   exm.nmoved ? &mv : nullptr)))
+                                   exm.nmoved ? &mv : nullptr, exm.energy_on ? &en : nullptr)))
         return rc;
     exm.auto_begun = true;
     exm.s_C = s_C;

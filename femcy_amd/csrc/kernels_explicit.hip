@@ -17,6 +17,7 @@
 #include "element_math.hpp"
 #include "load_row.hpp"
 #include "node_gather.hpp"
+#include "wave_reduce.hpp"
 
 namespace femcy {
 
@@ -152,6 +153,174 @@ __global__ void __launch_bounds__(XBS) k_explicit_node_auto(int32_t nn, const in
     }
 }
 
+// ---------------------------------------------------------------------- node pass with the energy balance
+// The node pass above plus the work addends of the step that led to the state being kicked (femcy.h at
+// femcy_explicit_energy_enable; the arithmetic is explicit_energy_free / _moved of element_math.hpp): a variant of its own,
+// so that the pass above keeps its arguments and its code.  u, v and a go through the same functions in the same order: the
+// same bits.  The lanes of a DOF hold what the addends need in registers -- f, minv, v and a of the previous state, the
+// gathered force -- and read three more numbers: the node's mass and the two forces of the previous state (NodeEnergy::
+// fint, falpha), which they then replace by this state's.
+// Sums: a wavefront covers two nodes, so its addends stand in the lanes 0 .. DM-1 and 32 .. 32+DM-1 and every other lane
+// holds 0.  Two quad swaps on the DPP network sum each quad, lane 0's and lane 32's results are read as scalars and added:
+// a fixed order, no LDS, no barrier, no atomics.  Lane 0 adds the four sums to the wavefront's own slot (EN_SLOT doubles,
+// one 64-byte line), which nobody else touches; the grid is the same in every step of a run, and launch_explicit_energy_sum
+// adds the slots up.  The slot also carries the load scale and the time of the last kicked state from one kick to the
+// next (every lane reads them, lane 0 writes them): a split run needs nothing from the host.  No lane leaves before the
+// sums, a >= nn included.  At XN_START the slot is zeroed and only the forces of state 0 are recorded.  hh = 0 in a kick
+// (nothing led to the state): nothing is added.
+struct NodeEnergy {
+    const double* m;                  // [nn] the lumped mass
+    double *fint, *falpha;            // [n] the gathered force and the alpha force of the last kicked state
+    double* slot;                     // [wavefronts of the grid][EN_SLOT]
+};
+enum { EN_S = 4, EN_T = 5 };          // where a slot keeps the load scale and the time of the last kicked state
+__device__ __forceinline__ double energy_wave_sum(double x) {
+    x += dpp_move<0xB1, 0xf>(x);      // quad_perm [1,0,3,2]
+    x += dpp_move<0x4E, 0xf>(x);      // quad_perm [2,3,0,1]: lanes 0 and 32 hold their quad's sum
+    const double lo = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), 0),
+                                       __builtin_amdgcn_readlane(__double2loint(x), 0));
+    const double hi = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), 32),
+                                       __builtin_amdgcn_readlane(__double2loint(x), 32));
+    return lo + hi;
+}
+template <int DM, class... MOTION>
+__device__ __forceinline__ void explicit_node_pass_energy(int32_t nn, const int32_t* __restrict__ ne_ptr,
+                                                          const int32_t* __restrict__ ne_idx,
+                                                          const double* __restrict__ fe, const double* __restrict__ f,
+                                                          const double* __restrict__ minv, const ExplicitStep& st, int mode,
+                                                          double* __restrict__ u, double* __restrict__ v,
+                                                          double* __restrict__ acc_vec, const NodeEnergy& en,
+                                                          const MOTION&... motion) {
+    constexpr bool MOVE = sizeof...(MOTION) == 1;
+    static_assert(sizeof...(MOTION) <= 1, "at most one motion argument");
+    static_assert(DM <= 4 && XBS % 64 == 0, "a node's addends must stand in one quad, a wavefront in one workgroup");
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int32_t a = (int32_t)(t >> 5);
+    const int sub = (int)(t & 31);
+    const bool mine = a < nn && sub < DM;
+    const bool start = mode == XN_START;
+    const int64_t i = (int64_t)a * DM + sub;
+    double* my_slot = en.slot + (t >> 6) * EN_SLOT;
+    double fi = 0.0, mi = 0.0, ai = 0.0, vi = 0.0, ui = 0.0, ma = 0.0, fp = 0.0, gp = 0.0, s_prev = 0.0;
+    [[maybe_unused]] double t_prev = 0.0;
+    [[maybe_unused]] int32_t slot = -1;
+    if (!start) {
+        s_prev = my_slot[EN_S];
+        if constexpr (MOVE) t_prev = my_slot[EN_T];
+    }
+    if (mine) {
+        if constexpr (MOVE) slot = (motion, ...).slot[i];
+        fi = f[i];
+        mi = minv[i];
+        ma = en.m[a];
+        if (!start) {
+            ai = acc_vec[i];
+            vi = v[i];
+            fp = en.fint[i];
+            gp = en.falpha[i];
+        } else if (st.alpha != 0.0) {
+            vi = v[i];                                  // v_{-1/2} := v_0; vec[ACC] is not read at the start
+        }
+        if (st.drift) ui = u[i];
+    }
+    double acc[DM];
+    node_gather<DM>(a, sub, nn, ne_ptr, ne_idx, fe, acc);
+    double w[4] = {0.0, 0.0, 0.0, 0.0};
+    [[maybe_unused]] double t_now = 0.0;
+    if constexpr (MOVE) t_now = (motion, ...).t;
+    if (mine) {
+        const double fint = sub == 0 ? acc[0] : (sub == 1 ? acc[1] : acc[DM - 1]);
+        const bool count = !start && st.hh != 0.0;
+        bool moved = false;
+        if constexpr (MOVE) moved = mi == 0.0 && slot >= 0;
+        if constexpr (MOVE) {
+            if (moved) {
+                const NodeMotion& mo = (motion, ...);
+                const Amplitude& am = mo.amp[mo.curve[slot]];
+                const double a_prev = ai;
+                explicit_moved(am, mo.val[slot], mo.t, mo.t_drift, start, st.drift, ui, vi, ai);
+                if (count) explicit_energy_moved(am, mo.val[slot], t_prev, mo.t, ma, s_prev, st.s, fi, fp, fint, a_prev, ai, w);
+                en.fint[i] = fint;
+                en.falpha[i] = 0.0;
+                acc_vec[i] = ai;
+                if (!start) {
+                    v[i] = vi;
+                    if (st.drift) u[i] = ui;
+                }
+            }
+        }
+        if (!moved) {
+            double ga;
+            explicit_energy_free(mi, ma, s_prev, st.s, fi, fp, fint, gp, st.alpha, vi, ai, st.hh, !count, w, ga);
+            en.fint[i] = fint;
+            en.falpha[i] = ga;
+            if (st.alpha != 0.0)
+                explicit_kick_damped(mi, st.s, fi, fint, st.hh, st.alpha, vi, ai);
+            else
+                explicit_kick(mi, st.s, fi, fint, st.hh, vi, ai);
+            acc_vec[i] = ai;
+            if (!start) {
+                v[i] = vi;
+                if (st.drift) u[i] = explicit_drift(ui, vi, ai, st.h, st.h2h);
+            }
+        }
+    }
+    if (start) {
+        if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) my_slot[k] = 0.0;
+            my_slot[EN_S] = st.s;
+            my_slot[EN_T] = t_now;
+        }
+        return;
+    }
+    if (st.hh != 0.0) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) w[k] = energy_wave_sum(w[k]);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (st.hh != 0.0) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) my_slot[k] += w[k];
+        }
+        my_slot[EN_S] = st.s;
+        my_slot[EN_T] = t_now;
+    }
+}
+
+template <int DM, class... MOTION>
+__global__ void __launch_bounds__(XBS) k_explicit_node_energy(int32_t nn, const int32_t* __restrict__ ne_ptr,
+                                                              const int32_t* __restrict__ ne_idx,
+                                                              const double* __restrict__ fe, const double* __restrict__ f,
+                                                              const double* __restrict__ minv, ExplicitStep st, int mode,
+                                                              double* __restrict__ u, double* __restrict__ v,
+                                                              double* __restrict__ acc_vec, NodeEnergy en, MOTION... motion) {
+    explicit_node_pass_energy<DM>(nn, ne_ptr, ne_idx, fe, f, minv, st, mode, u, v, acc_vec, en, motion...);
+}
+
+// a step that does nothing (explicit_step_clock false) returns before anything is read: no slot, no force is written
+template <int DM, class... MOTION>
+__global__ void __launch_bounds__(XBS) k_explicit_node_auto_energy(int32_t nn, const int32_t* __restrict__ ne_ptr,
+                                                                   const int32_t* __restrict__ ne_idx,
+                                                                   const double* __restrict__ fe,
+                                                                   const double* __restrict__ f,
+                                                                   const double* __restrict__ minv,
+                                                                   const ExplicitClock* __restrict__ clk, int mode,
+                                                                   double alpha, double* __restrict__ u,
+                                                                   double* __restrict__ v, double* __restrict__ acc_vec,
+                                                                   NodeEnergy en, MOTION... motion) {
+    ExplicitStep st;
+    if (!explicit_step_clock(*clk, mode, st, alpha)) return;
+    if constexpr (sizeof...(MOTION) == 1) {
+        NodeMotion mo = (motion, ...);
+        mo.t = clk->t;
+        mo.t_drift = clk->t_next;
+        explicit_node_pass_energy<DM>(nn, ne_ptr, ne_idx, fe, f, minv, st, mode, u, v, acc_vec, en, mo);
+    } else {
+        explicit_node_pass_energy<DM>(nn, ne_ptr, ne_idx, fe, f, minv, st, mode, u, v, acc_vec, en);
+    }
+}
+
 // u, v and a (what: MOVE_U | MOVE_V | MOVE_A of element_math.hpp) of the moved DOFs at one time, one thread per entry of the
 // compact list: at the start of a run everything at t, before the element pass; after the first drift of a call u alone, at
 // the time that drift reached -- t, or with clk the clock's t_next, and nothing when its h_next = 0 (the drift wrote
@@ -242,6 +411,17 @@ __global__ void __launch_bounds__(XBS) k_explicit_final(int np, const double* __
     __shared__ double sm[XBS / 64];
     const double r = reduce_partials<MAX>(np, part, sm);
     if (threadIdx.x == 0) *out = r;
+}
+
+// the read-back of the energy balance: workgroup k = 0 .. 3 sums the k-th double of the nslots slots of the node pass, thread
+// t the slots t, t + 256, ... in ascending order, then the same tree
+__global__ void __launch_bounds__(XBS) k_explicit_energy_sum(int nslots, const double* __restrict__ slot,
+                                                             double* __restrict__ out) {
+    __shared__ double sm[XBS / 64];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < nslots; i += XBS) acc += slot[(int64_t)i * EN_SLOT + blockIdx.x];
+    const double r = block_reduce<false>(acc, sm);
+    if (threadIdx.x == 0) out[blockIdx.x] = r;
 }
 
 // Gershgorin pass over the SELL storage: one lane per stored row position p = slice * 64 + lane (node_of[p] < 0: padding),
@@ -455,11 +635,53 @@ int launch_explicit_minv(Ctx* c, const double* d_m, double* d_minv) {
     return FEMCY_OK;
 }
 
+int explicit_energy_slots(const Ctx* c) { return (int)node_gather_grid(c->nn, XBS) * (XBS / 64); }
+
+// the energy variants of the four node-pass launches below, on the same grid
+static void launch_explicit_node_energy(Ctx* c, unsigned grid, const double* d_minv, const double* d_f,
+                                        const ExplicitClock* d_clk, double scale, double h, int mode, double alpha,
+                                        const ExplicitMotion* mv, const ExplicitEnergy& e) {
+    double *u = c->d_vec[FEMCY_VEC_DOF], *v = c->d_vec[FEMCY_VEC_VEL], *a = c->d_vec[FEMCY_VEC_ACC];
+    const NodeEnergy en{e.d_m, e.d_fint, e.d_falpha, e.d_slot};
+    dispatch_dm(c->dm, [&](auto dm) {
+        if (mv) {
+            const NodeMotion mo{mv->d_slot, mv->d_curve, mv->d_val, mv->d_amp, mv->t, mv->t_drift};
+            if (d_clk)
+                hipLaunchKernelGGL((k_explicit_node_auto_energy<dm(), NodeMotion>), dim3(grid), dim3(XBS), 0, c->stream, c->nn,
+                                   c->d_ne_ptr, c->d_ne_idx, c->d_fe, d_f, d_minv, d_clk, mode, alpha, u, v, a, en, mo);
+            else
+                hipLaunchKernelGGL((k_explicit_node_energy<dm(), NodeMotion>), dim3(grid), dim3(XBS), 0, c->stream, c->nn,
+                                   c->d_ne_ptr, c->d_ne_idx, c->d_fe, d_f, d_minv, explicit_step_fixed(scale, h, mode, alpha),
+                                   mode, u, v, a, en, mo);
+        } else if (d_clk)
+            hipLaunchKernelGGL((k_explicit_node_auto_energy<dm()>), dim3(grid), dim3(XBS), 0, c->stream, c->nn, c->d_ne_ptr,
+                               c->d_ne_idx, c->d_fe, d_f, d_minv, d_clk, mode, alpha, u, v, a, en);
+        else
+            hipLaunchKernelGGL((k_explicit_node_energy<dm()>), dim3(grid), dim3(XBS), 0, c->stream, c->nn, c->d_ne_ptr,
+                               c->d_ne_idx, c->d_fe, d_f, d_minv, explicit_step_fixed(scale, h, mode, alpha), mode, u, v, a, en);
+    });
+}
+
+int launch_explicit_energy_sum(Ctx* c, const double* d_slot, double* out) {
+    hipLaunchKernelGGL(k_explicit_energy_sum, dim3(4), dim3(XBS), 0, c->stream, explicit_energy_slots(c), d_slot, c->d_part2);
+    FEMCY_HIP(hipGetLastError());
+    FEMCY_HIP(hipMemcpyAsync(c->h_scalar, c->d_part2, sizeof(double) * 4, hipMemcpyDeviceToHost, c->stream));
+    FEMCY_HIP(hipStreamSynchronize(c->stream));
+    for (int k = 0; k < 4; ++k) out[k] = c->h_scalar[k];
+    return FEMCY_OK;
+}
+
 int launch_explicit_node(Ctx* c, const double* d_minv, const double* d_f, const ExplicitClock* d_clk, double scale, double h,
-                         int mode, double alpha, const ExplicitMotion* mv) {
+                         int mode, double alpha, const ExplicitMotion* mv, const ExplicitEnergy* en) {
     const unsigned grid = node_gather_grid(c->nn, XBS);
     double *u = c->d_vec[FEMCY_VEC_DOF], *v = c->d_vec[FEMCY_VEC_VEL], *a = c->d_vec[FEMCY_VEC_ACC];
     size_t tm = timing_begin(c, T_FORCE);
+    if (en) {
+        launch_explicit_node_energy(c, grid, d_minv, d_f, d_clk, scale, h, mode, alpha, mv, *en);
+        timing_end(c, tm);
+        FEMCY_HIP(hipGetLastError());
+        return FEMCY_OK;
+    }
     dispatch_dm(c->dm, [&](auto dm) {
         if (mv) {
             const NodeMotion mo{mv->d_slot, mv->d_curve, mv->d_val, mv->d_amp, mv->t, mv->t_drift};

@@ -85,6 +85,11 @@ struct Explicit {
     bool moved() const { return !motion.dof.empty(); }
     int64_t n_done = 0, n_base = 0;
     double t_base = 0.0, dt_prev = 0.0;
+    // femcy_explicit_energy_enable: asked for / running since a start; the four sums, the forces [n] of the last kicked
+    // state with its load scale and time, and per-node scratch [nn][4] of one step's addends
+    bool energy_want = false, energy_on = false;
+    double en[4] = {0.0, 0.0, 0.0, 0.0}, en_s = 0.0, en_t = 0.0;
+    std::vector<double> efint, ealpha, ew;
 };
 // a damped element pass or bound (the device's GeomDamping): v, a (null: the start, v_{-1/2} := v_0) and hh = h / 2 of the
 // drift that led to the state
@@ -1262,24 +1267,47 @@ void lumped_mass(femcy_ctx* c, int32_t nq, const double* Nq, const double* dNq, 
 // then explicit_kick / explicit_drift; what mode and st say is with ExplicitStep in csrc/element_math.hpp
 // With motion (t: the time of the state being kicked, t_drift: the time the drift reaches) a held and moved DOF takes
 // explicit_moved instead of the kick, as the device's motion policy does.
-void explicit_node(femcy_ctx* c, const Explicit& ex, const double* f, const ExplicitStep& st, int mode, double t = 0.0,
+// With the energy balance running (ex.energy_on) every DOF's addends of the step that led to the state (csrc/element_math.hpp:
+// explicit_energy_free / _moved, the device's functions) go to the node's row of ex.ew and are then added to the four sums
+// node by node: one order, whatever the number of threads.  The forces of the state stay in ex.efint / ex.ealpha.
+void explicit_node(femcy_ctx* c, Explicit& ex, const double* f, const ExplicitStep& st, int mode, double t = 0.0,
                    double t_drift = 0.0) {
     const int dm = c->dm;
     const MotionTables& mo = ex.motion;
-    const bool moved = ex.moved();
+    const bool moved = ex.moved(), energy = ex.energy_on, start = mode == XN_START, count = !start && st.hh != 0.0;
+    const double* mass = c->lumped_masses[ex.lumped].m.data();
     double *u = c->vec[FEMCY_VEC_DOF].data(), *v = c->vec[FEMCY_VEC_VEL].data(), *acc = c->vec[FEMCY_VEC_ACC].data();
 #pragma omp parallel for schedule(static)
     for (int32_t a = 0; a < c->nn; ++a) {
-        double fint[3];
+        double fint[3], wn[4] = {0.0, 0.0, 0.0, 0.0};
         node_sum(c, a, c->fe.data(), dm, fint);
         for (int i = 0; i < dm; ++i) {
             const int64_t q = (int64_t)a * dm + i;
             if (const int32_t s = moved ? mo.slot[q] : -1; s >= 0 && ex.minv[q] == 0.0) {
+                const double a_prev = acc[q];
                 explicit_moved(mo.amp[mo.curve[s]], mo.val[s], t, t_drift, mode == XN_START, st.drift, u[q], v[q], acc[q]);
+                if (energy) {
+                    if (count) {
+                        double w[4];
+                        explicit_energy_moved(mo.amp[mo.curve[s]], mo.val[s], ex.en_t, t, mass[a], ex.en_s, st.s, f[q],
+                                              ex.efint[q], fint[i], a_prev, acc[q], w);
+                        for (int k = 0; k < 4; ++k) wn[k] += w[k];
+                    }
+                    ex.efint[q] = fint[i];
+                    ex.ealpha[q] = 0.0;
+                }
                 continue;
             }
             // at the start vec[ACC] is not read; vec[VEL] only by the damped kick (v_{-1/2} := v_0)
             double vi = mode != XN_START || st.alpha != 0.0 ? v[q] : 0.0, ai = mode != XN_START ? acc[q] : 0.0;
+            if (energy) {
+                double w[4], ga;
+                explicit_energy_free(ex.minv[q], mass[a], ex.en_s, st.s, f[q], ex.efint[q], fint[i], ex.ealpha[q], st.alpha, vi,
+                                     ai, st.hh, !count, w, ga);
+                for (int k = 0; k < 4; ++k) wn[k] += w[k];
+                ex.efint[q] = fint[i];
+                ex.ealpha[q] = ga;
+            }
             if (st.alpha != 0.0)
                 explicit_kick_damped(ex.minv[q], st.s, f[q], fint[i], st.hh, st.alpha, vi, ai);
             else
@@ -1289,7 +1317,19 @@ void explicit_node(femcy_ctx* c, const Explicit& ex, const double* f, const Expl
             v[q] = vi;
             if (st.drift) u[q] = explicit_drift(u[q], vi, ai, st.h, st.h2h);
         }
+        if (energy && count)
+            for (int k = 0; k < 4; ++k) ex.ew[(size_t)a * 4 + k] = wn[k];
     }
+    if (!energy) return;
+    if (start) std::fill(ex.en, ex.en + 4, 0.0);
+    if (count) {
+        double step[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int32_t a = 0; a < c->nn; ++a)
+            for (int k = 0; k < 4; ++k) step[k] += ex.ew[(size_t)a * 4 + k];
+        for (int k = 0; k < 4; ++k) ex.en[k] += step[k];
+    }
+    ex.en_s = st.s;
+    ex.en_t = t;
 }
 
 // max_e omega_e^2 at u (csrc/element_math.hpp: explicit_bound_element); a NaN counts as infinity
@@ -1418,7 +1458,7 @@ void place_moved(femcy_ctx* c, const Explicit& ex, double t, int what) {
 // nsteps steps from a started state, as the device's explicit_steps runs them: the first drift, then per step the element
 // pass and the node pass.  A fixed run (clock null) takes dt and the load scale scale0 + k dscale from the caller; an
 // automatic one bounds the element frequencies and ticks its clock between the two passes, which then gives both.
-int explicit_steps(femcy_ctx* c, const Explicit& ex, ExplicitClock* clock, int rhs_vec, int32_t nsteps, double dt,
+int explicit_steps(femcy_ctx* c, Explicit& ex, ExplicitClock* clock, int rhs_vec, int32_t nsteps, double dt,
                    double scale0, double dscale) {
     if (nsteps == 0) return FEMCY_OK;
     double* u = c->vec[FEMCY_VEC_DOF].data();
@@ -1554,6 +1594,7 @@ int femcy_explicit_start(femcy_ctx* ctx, int32_t id, int rhs_vec, double scale) 
     place_moved(c, ex, 0.0, MOVE_U | MOVE_V | MOVE_A);
     const HostDamping hd = damping_of(c, ex, 0.0, true);
     geom(c, c->vec[FEMCY_VEC_DOF].data(), GEOM_DSDX | GEOM_F | GEOM_SIGMA | GEOM_FE, ex.bulk() ? &hd : nullptr);
+    ex.energy_on = ex.energy_want;                  // the start zeroes the sums and records the forces of state 0
     explicit_node(c, ex, c->vec[rhs_vec].data(), explicit_step_fixed(scale, 0.0, XN_START, ex.alpha), XN_START);
     return FEMCY_OK;
 }
@@ -1604,6 +1645,30 @@ int femcy_explicit_set_motion(femcy_ctx* ctx, int32_t id, int32_t nsets, const i
     std::vector<std::vector<int32_t>> sets((size_t)nsets);
     for (int32_t k = 0; k < nsets; ++k) sets[k] = c->dofsets[dofset_ids[k]].dofs;
     c->explicits[id].motion = motion_tables(c->n, sets, values, amplitude_ids, c->amplitudes);
+    return FEMCY_OK;
+}
+
+int femcy_explicit_energy_enable(femcy_ctx* ctx, int32_t id, int32_t on) {
+    CTX_OR_FAIL(ctx);
+    FEMCY_TRY(check_object(c->explicits, id, "explicit integrator"));
+    Explicit& ex = c->explicits[id];
+    ex.energy_want = on != 0;
+    if (!on) {
+        ex.energy_on = false;
+        return FEMCY_OK;
+    }
+    if (ex.efint.empty()) {                         // a running balance keeps what it holds
+        ex.efint.assign((size_t)c->n, 0.0);
+        ex.ealpha.assign((size_t)c->n, 0.0);
+        ex.ew.assign((size_t)c->nn * 4, 0.0);
+    }
+    return FEMCY_OK;
+}
+
+int femcy_explicit_energy_get(femcy_ctx* ctx, int32_t id, double* out) {
+    CTX_OR_FAIL(ctx);
+    FEMCY_TRY(check_explicit_energy_get(c, id, out));
+    std::copy(c->explicits[id].en, c->explicits[id].en + 4, out);
     return FEMCY_OK;
 }
 
@@ -1698,6 +1763,7 @@ int femcy_explicit_auto_begin(femcy_ctx* ctx, int32_t id, int rhs_vec, double s_
     explicit_clock_tick(exm.clock, w2);                        // t = 0, the first h
     ExplicitStep st;
     explicit_step_clock(exm.clock, XN_START, st, exm.alpha);   // always something to do at the start
+    exm.energy_on = exm.energy_want;                           // as femcy_explicit_start
     explicit_node(c, exm, c->vec[rhs_vec].data(), st, XN_START);
     exm.auto_begun = true;
     return FEMCY_OK;

@@ -36,6 +36,14 @@ def run(fileName: str, device: int = 0, verbose: bool = True, tangent: str = "re
     time1 = time.time()
     print(f"\033[40;33;1m system.dof = \n{system.dof.to_numpy()}, "
           f"time for finite element computing is {time1 - time0} s \033[0m")
+    if getattr(inp, "energy_output", False):      # *Energy Output: the balance of every record, and how well it closed
+        e0 = system.initial_energy["energy_total"]
+        for rec in system.increments:
+            print(" t = {time1:.6e}: kinetic {kinetic:.6e}, internal work {internal_work:.6e}, external work "
+                  "{external_work:.6e} (boundary {boundary_work:.6e}), viscous dissipation {viscous_dissipation:.6e}, "
+                  "total {energy_total:.6e}".format(**rec))
+        drift = max(abs(rec["energy_total"] - e0) for rec in system.increments)
+        print(f" energy balance: largest |energy_total - energy_total(0)| = {drift:.6e} (energy_total(0) = {e0:.6e})")
     system.get_elasEng()
     print(f"total elastic energy is {system.elsEng}"
           + (" (of the total strain: the thermal strain is not taken out)" if system._thermal is not None else ""))

@@ -34,8 +34,9 @@ time_incs whose increments are None until the driver has estimated one; `element
 control` -> dynamic_auto = True: the driver re-estimates the increment in every step.  `*Bulk Viscosity` (data `b1, b2`,
 defaults 0.06, 1.2) inside an explicit step -> bulk_viscosity = (b1, b2), None without the keyword; `*Damping, alpha=` in the
 `*Material` block -> damping_alpha (read_damping).  `*Fixed Mass Scaling[, factor=][, dt=][, type=]` inside an explicit step ->
-mass_scaling = {"factor", "dt", "type"}, None without the keyword (read_mass_scaling).  A deck with `*Static` has procedure =
-"static" and reads as before.
+mass_scaling = {"factor", "dt", "type"}, None without the keyword (read_mass_scaling).  `*Energy Output` inside an explicit
+step, alone or under `*Output, history` -> energy_output = True, False without the keyword (read_energy_output).  A deck with
+`*Static` has procedure = "static" and reads as before.
 """
 import sys
 from typing import Dict, List
@@ -145,6 +146,7 @@ class InpInfo(InpInfoBase):
         self.time_incs = self.read_time_inc(file)
         self.bulk_viscosity, self.damping_alpha = self.read_damping(file)
         self.mass_scaling = self.read_mass_scaling(file)
+        self.energy_output = self.read_energy_output(file)
         self.initial_velocity_info = self.read_initial_velocity(file)
 
     # ------------------------------------------------------------------ nodes and elements
@@ -632,6 +634,26 @@ class InpInfo(InpInfoBase):
                 raise ValueError("*Damping has not been supported outside a *Dynamic, explicit step: the implicit "
                                  "integrator is the undamped Newmark scheme")
         return bulk, alpha
+
+    def read_energy_output(self, fileName):
+        """`*Energy Output` inside a `*Dynamic, explicit` step, alone or under `*Output, history` -> True, False without the
+        keyword.  The driver then keeps an energy balance of the run and adds it to every record.  Optional data lines name
+        variables out of ALLKE, ALLSE, ALLIE, ALLWK, ALLVD and ETOTAL; the whole balance is recorded whichever are named.
+        Refused: any other variable, by name, and the keyword in a deck whose procedure is not "explicit"."""
+        known = ("ALLKE", "ALLSE", "ALLIE", "ALLWK", "ALLVD", "ETOTAL")
+        asked = False
+        for line, block in _deck(fileName).keywords():
+            if " ".join(line.split(",")[0].lower().split()) != "*energy output":
+                continue
+            asked = True
+            for row in block:
+                for name in (t.strip() for t in row.split(",")):
+                    if name and name.upper() not in known:
+                        raise ValueError("*Energy Output: the variable {} has not been supported ({} are)".format(
+                            name, ", ".join(known)))
+        if asked and self.procedure != "explicit":
+            raise ValueError("*Energy Output has not been supported outside a *Dynamic, explicit step")
+        return asked
 
     def read_mass_scaling(self, fileName):
         """`*Fixed Mass Scaling[, factor=f][, dt=tau][, type=uniform | below min | set equal dt]` inside a `*Dynamic, explicit`

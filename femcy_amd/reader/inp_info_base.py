@@ -26,7 +26,9 @@ class InpInfoBase:
                   # dynamic_auto: `element by element` on *Dynamic, explicit (bool; kept beside the dictionary)
                   "procedure", "dynamic", "amplitude", "initial_velocity_info", "dynamic_auto",
                   # damping of an explicit step: *Bulk Viscosity as (b1, b2) or None, *Damping, alpha= (0.0 without it)
-                  "bulk_viscosity", "damping_alpha")
+                  "bulk_viscosity", "damping_alpha",
+                  # *Energy Output inside an explicit step (bool): the driver keeps an energy balance of the run
+                  "energy_output")
 
     def __init_subclass__(cls, **kwargs):
         super().__init_subclass__(**kwargs)

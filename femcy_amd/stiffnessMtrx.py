@@ -51,7 +51,7 @@ def deck_view(inp) -> SimpleNamespace:
         initial_velocity_info=opt("initial_velocity_info") or [], dynamic=opt("dynamic"),
         dynamic_auto=bool(opt("dynamic_auto", False)), bulk_viscosity=opt("bulk_viscosity"),
         damping_alpha=float(opt("damping_alpha", 0.0) or 0.0), mass_scaling=opt("mass_scaling"),
-        amplitudes=opt("amplitudes") or {})
+        amplitudes=opt("amplitudes") or {}, energy_output=bool(opt("energy_output", False)))
 
 
 class LoadSchedule:
@@ -588,7 +588,20 @@ class System_of_equations:
         self.time0 = self.time1 = 0.0
 
     def _energies(self, kinetic: float) -> dict:
-        return {"kinetic": kinetic, "strain_energy": self.get_elasEng()}
+        out = {"kinetic": kinetic, "strain_energy": self.get_elasEng()}
+        bal = getattr(self, "_energy_balance", None)
+        if bal is not None:                                           # *Energy Output in an explicit step
+            w = self.ctx.explicit_energy(bal["ex"])                   # the work sums since t = 0, one synchronising read-back
+            if bal["strain0"] is None:
+                bal["strain0"] = out["strain_energy"]
+            load, internal, alpha, boundary = (float(x) for x in w)
+            external = load + boundary
+            # derived on the host: the material is hyperelastic, so what the internal forces did beyond the stored strain
+            # energy is the share of the bulk viscosity
+            bulk = internal - (out["strain_energy"] - bal["strain0"])
+            out.update(external_work=external, boundary_work=boundary, internal_work=internal,
+                       viscous_dissipation=alpha + bulk, energy_total=kinetic + internal + alpha - external)
+        return out
 
     def _record(self, kinc: int, dt: float, kinetic: float, **more):
         """the entry of `increments` after a step, or a batch of steps, that ended at `time1`"""
@@ -605,6 +618,7 @@ class System_of_equations:
         """multiple time increments with automatic cut-back (reference :647-711).  A `*Dynamic` step goes to
         `solve_dynamic`; a deck without it makes the calls it always made."""
         self._linear_energy = False      # get_elasEng: the reference's energy, unless solve_dynamic says otherwise
+        self._energy_balance = None      # set by solve_explicit for a deck with *Energy Output
         deck = deck_view(inp)
         if deck.procedure == "dynamic":
             return self.solve_dynamic(inp)
@@ -743,7 +757,13 @@ class System_of_equations:
         entries without an amplitude stay at rest, and a non-zero value without one is refused.  The integrator itself places
         the moved DOFs at t = 0.  `self.motion` lists the moved entries, and only when there are any every record gains
         "reaction": per moved entry the force the body exerts on its boundary, the sum over the entry's DOFs of s f - f_int at
-        the record's state, which opposes a pull (`_reaction`; the bulk-viscosity forces are not in it)."""
+        the record's state, which opposes a pull (`_reaction`; the bulk-viscosity forces are not in it).
+        `*Energy Output` (`inp.energy_output`): the integrator keeps an energy balance on the device
+        (`femcy_explicit_energy_enable`, with the definitions), and every record and `initial_energy` gain "external_work"
+        (loads + moved boundary), "boundary_work", "internal_work", "viscous_dissipation" -- the alpha work plus internal_work
+        - (strain_energy - strain_energy at t = 0), the bulk-viscosity share, DERIVED on the host because the material is
+        hyperelastic -- and "energy_total" = kinetic + internal_work + alpha work - external_work, which a stable run
+        keeps near its initial value.  Without the keyword the records, the launches and the bits are unchanged."""
         deck = deck_view(inp)
         self._transient_gate(deck, "*Dynamic, explicit step", "lumped mass", motion=True)
         if deck.temperature_info is not None:
@@ -768,6 +788,10 @@ class System_of_equations:
         b1, b2 = bulk if bulk is not None else (0.0, 0.0)
         if bulk is not None or alpha != 0.0:
             ctx.explicit_set_damping(ex, alpha, b1, b2, self.dilatational_modulus() if bulk is not None else 0.0)
+        self._energy_balance = None
+        if deck.energy_output:                                        # before the start, which zeroes the work sums
+            ctx.explicit_energy_enable(ex, True)
+            self._energy_balance = {"ex": ex, "strain0": None}
         if deck.dynamic_auto:
             return self._solve_explicit_auto(deck, loads, ex)
         if deck.dynamic["direct_user_control"]:

@@ -563,6 +563,31 @@ int femcy_amplitude_create(femcy_ctx* ctx, int32_t kind, int32_t npts, const dou
                            int32_t* id_out);
 int femcy_explicit_set_motion(femcy_ctx* ctx, int32_t id, int32_t nsets, const int32_t* dofset_ids /*[nsets]*/,
                               const double* values /*[nsets]*/, const int32_t* amplitude_ids /*[nsets]*/);
+/* Energy balance of an explicit run (*Energy Output): four work integrals, accumulated inside the node pass of every step
+ * and kept on the device (the steps run in batches with no host synchronisation and leave only the last state).  State k has
+ * the load scale s_k; du_k = u_{k+1} - u_k is h_k v_{k+1/2} on a free DOF (v_{k+1/2} = fma(h_k / 2, a_k, v_k), h_k the
+ * increment of the drift the step applied), the curve's own difference values[.] (A(t_{k+1}) - A(t_k)) on a moved DOF and 0
+ * on a held one.  The work of a force g is the trapezoid sum W_g = sum_k 1/2 du_k . (g_k + g_{k+1}) over the scalar DOFs:
+ *   FEMCY_EN_LOAD      g_k = s_k f                              free and moved DOFs
+ *   FEMCY_EN_INTERNAL  g_k = the node sum of fe at state k      the stress force plus the bulk-viscosity force, as the node
+ *                                                               pass gathers it
+ *   FEMCY_EN_ALPHA     g_k = alpha m v_{k-1/2}                  free DOFs: the force the damped kick subtracts, v_{-1/2} := v_0
+ *   FEMCY_EN_BOUNDARY  g_k = R_k = m a_k + f_int,k - s_k f      moved DOFs only: what the support applies, the inertia of the
+ *                                                               moved node included; m from the lumped mass
+ * For a fixed increment h the update gives, on the free DOFs and in exact arithmetic,
+ *   [KE - (h^2 / 8) a.M a]_N - [KE - (h^2 / 8) a.M a]_0 = W_LOAD - W_INTERNAL - W_ALPHA.
+ * femcy_explicit_energy_enable: on != 0 takes effect from the next femcy_explicit_start / _auto_begin, which zero the four
+ * sums and record the forces of state 0; every kick then adds the step that led to its state and records the forces of that
+ * state (two vectors [n], allocated here), so a run split into several calls gives the bits of one call.  No launch is
+ * added, no atomics: every wavefront of the node pass owns one slot and adds its partial sum in a fixed order; a step of an
+ * automatic run that does nothing adds and writes nothing.  u, v and a are bit for bit those of a run without it.  on = 0:
+ * the launches of an integrator that never had it, from the next stepping call.
+ * femcy_explicit_energy_get: the one synchronising read-back, out[FEMCY_EN_*], the slots summed in a fixed order.
+ * Refused with FEMCY_EINVAL, the context stays usable: an unknown id, a null output, _get while the balance is off or before
+ * a start, and either call once femcy_comm_init has run. */
+enum femcy_energy_term { FEMCY_EN_LOAD = 0, FEMCY_EN_INTERNAL = 1, FEMCY_EN_ALPHA = 2, FEMCY_EN_BOUNDARY = 3 };
+int femcy_explicit_energy_enable(femcy_ctx* ctx, int32_t id, int32_t on);
+int femcy_explicit_energy_get(femcy_ctx* ctx, int32_t id, double* out /*[4]*/);
 /* Fixed mass scaling (*Fixed Mass Scaling, whole model): the element shares m_a^e of a lumped mass are multiplied by one
  * factor k_e per element, before an integrator is made from it, and the nodal masses are summed again.  omega_e^2 above is
  * linear in 1 / m_a^e, so k_e divides it exactly and a target increment is met in closed form, in the project's own
