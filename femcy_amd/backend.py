@@ -80,6 +80,7 @@ EXPORTS = [
     "femcy_explicit_element_bound", "femcy_explicit_auto_begin", "femcy_explicit_auto_advance", "femcy_explicit_auto_state",
     "femcy_explicit_set_damping", "femcy_lumped_mass_scale", "femcy_lumped_mass_get_scaling",
     "femcy_amplitude_create", "femcy_explicit_set_motion", "femcy_explicit_energy_enable", "femcy_explicit_energy_get",
+    "femcy_explicit_set_wall", "femcy_explicit_wall_get",
     "femcy_loadset_create", "femcy_loadset_neumann", "femcy_loadset_neumann_add", "femcy_spmv", "femcy_pcg", "femcy_compute_strain_stress", "femcy_elastic_energy", "femcy_elastic_energy_small", "femcy_extrapolate",
     "femcy_get_K_ell", "femcy_get_K_bsr", "femcy_get_gp_field", "femcy_timing",
     "femcy_timing_reset", "femcy_comm_unique_id", "femcy_comm_local_id", "femcy_comm_init", "femcy_comm_info", "femcy_comm_set_neighbours",
@@ -108,6 +109,8 @@ MS_TYPES = {"below min": MS_BELOW_MIN, "set equal dt": MS_SET_EQUAL_DT, "uniform
 AMP_TABULAR, AMP_SMOOTH_STEP = 0, 1
 AMP_KINDS = {"tabular": AMP_TABULAR, "smooth step": AMP_SMOOTH_STEP}
 AMP_MAX_POINTS = 16
+# femcy_explicit_set_wall: the most walls an integrator takes
+WALL_MAX = 4
 # femcy_explicit_energy_get: the four work sums of the energy balance (*Energy Output)
 EN_LOAD, EN_INTERNAL, EN_ALPHA, EN_BOUNDARY = 0, 1, 2, 3
 
@@ -203,6 +206,7 @@ def _bind(lib, kind):
         "femcy_amplitude_create": [p, i32, i32, p, p, C.POINTER(i32)],
         "femcy_explicit_set_motion": [p, i32, i32, p, p, p],
         "femcy_explicit_energy_enable": [p, i32, i32], "femcy_explicit_energy_get": [p, i32, p],
+        "femcy_explicit_set_wall": [p, i32, i32, p, p, p], "femcy_explicit_wall_get": [p, i32, i32, p],
         "femcy_explicit_auto_state": [p, i32, C.POINTER(f64), C.POINTER(f64), C.POINTER(f64), C.POINTER(C.c_int64)],
         "femcy_loadset_create": [p, i32, i32, i32, p, p, p, p, p, i32, p, p, C.POINTER(i32)],
         "femcy_loadset_neumann": [p, i32, f64, p, cint],
@@ -682,6 +686,27 @@ class Context:
         """-> [EN_LOAD, EN_INTERNAL, EN_ALPHA, EN_BOUNDARY]: the synchronising read-back of the work sums since the start"""
         out = np.zeros(4, dtype=np.float64)
         self._call("femcy_explicit_energy_get", int(ex), _ptr(out))
+        return out
+
+    def explicit_set_wall(self, ex: int, points=(), normals=(), kappas=()):
+        """frictionless planar rigid walls of an integrator (*Rigid Wall), from its next explicit_start /
+        explicit_auto_begin: wall k passes through points[k] with the normal normals[k] into the free half space (normalised
+        by the library) and the penalty kappas[k] in 1/s^2; a node with the gap g < 0 takes the acceleration -kappa g n on
+        its free DOFs.  At most WALL_MAX walls; none: the launches of an integrator that never had one"""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1)
+        nrm = np.ascontiguousarray(normals, dtype=np.float64).reshape(-1)
+        kap = np.ascontiguousarray(kappas, dtype=np.float64).reshape(-1)
+        if pts.size != kap.size * self.dm or nrm.size != kap.size * self.dm:
+            raise ValueError("explicit_set_wall: one point and one normal of dm entries and one kappa per wall")
+        some = kap.size > 0
+        self._call("femcy_explicit_set_wall", int(ex), int(kap.size), _ptr(pts) if some else None,
+                   _ptr(nrm) if some else None, _ptr(kap) if some else None)
+
+    def explicit_wall_get(self, ex: int, wall: int = 0) -> np.ndarray:
+        """-> [normal force, potential E_w, nodes with g < 0, largest penetration] of one wall at vec[DOF]: a synchronising
+        read-back, reduced in a fixed order"""
+        out = np.zeros(4, dtype=np.float64)
+        self._call("femcy_explicit_wall_get", int(ex), int(wall), _ptr(out))
         return out
 
     def explicit_auto_state(self, ex: int):

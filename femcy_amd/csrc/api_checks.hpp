@@ -437,6 +437,53 @@ int check_explicit_energy_get(const C* c, int32_t id, const double* out) {
     return FEMCY_OK;
 }
 
+// femcy_explicit_set_wall: a known integrator, 0 .. FEMCY_WALL_MAX walls of finite entries, a normal that has a length, a
+// positive penalty.  What both libraries then run on: the unit normal, d = n . point and kappa of every wall in `out` (W:
+// ExplicitWalls of element_math.hpp), with the fused multiply-adds written out so that both round alike.  out is written
+// only when everything holds.
+template <class C, class W>
+int check_explicit_set_wall(const C* c, int32_t id, int32_t nwalls, const double* point, const double* normal,
+                            const double* kappa, W& out) {
+    FEMCY_TRY(check_object(c->explicits, id, "explicit integrator"));
+    FEMCY_REQUIRE(nwalls >= 0 && nwalls <= FEMCY_WALL_MAX, "femcy_explicit_set_wall: %d walls, 0 .. %d are taken", (int)nwalls,
+                  FEMCY_WALL_MAX);
+    FEMCY_REQUIRE(nwalls == 0 || (point && normal && kappa), "femcy_explicit_set_wall: null point, normal or kappa");
+    W w{};
+    w.n = nwalls;
+    for (int32_t k = 0; k < nwalls; ++k) {
+        double len2 = 0.0;
+        for (int j = 0; j < c->dm; ++j) {
+            const double pj = point[k * c->dm + j], nj = normal[k * c->dm + j];
+            FEMCY_REQUIRE(std::isfinite(pj) && std::isfinite(nj), "femcy_explicit_set_wall: wall %d has an entry that is not finite",
+                          (int)k);
+            len2 = std::fma(nj, nj, len2);
+        }
+        const double len = std::sqrt(len2);
+        FEMCY_REQUIRE(positive_finite(len), "femcy_explicit_set_wall: the normal of wall %d has no length", (int)k);
+        FEMCY_REQUIRE(positive_finite(kappa[k]), "femcy_explicit_set_wall: the penalty of wall %d must be finite and positive",
+                      (int)k);
+        double d = 0.0;
+        for (int j = 0; j < c->dm; ++j) {
+            w.nrm[k][j] = normal[k * c->dm + j] / len;
+            d = std::fma(w.nrm[k][j], point[k * c->dm + j], d);
+        }
+        w.d[k] = d;
+        w.kappa[k] = kappa[k];
+    }
+    out = w;
+    return FEMCY_OK;
+}
+
+// femcy_explicit_wall_get: a known integrator, one of the walls it has
+template <class C>
+int check_explicit_wall_get(const C* c, int32_t id, int32_t wall, const double* out) {
+    FEMCY_TRY(check_object(c->explicits, id, "explicit integrator"));
+    FEMCY_REQUIRE(out, TEXT_NULL_OUTPUT);
+    FEMCY_REQUIRE(wall >= 0 && wall < c->explicits[id].walls.n, "femcy_explicit_wall_get: wall %d of integrator %d, which has %d "
+                  "(femcy_explicit_set_wall)", (int)wall, (int)id, (int)c->explicits[id].walls.n);
+    return FEMCY_OK;
+}
+
 template <class C>
 int check_explicit_start(const C* c, int32_t id, int rhs_vec, double scale) {
     FEMCY_TRY(check_explicit_rhs(c, "femcy_explicit_start", id, rhs_vec));

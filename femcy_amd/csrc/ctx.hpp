@@ -415,6 +415,14 @@ struct Ctx {
         // (explicit_energy_slots), all allocated by the first enable; off: the launches of an integrator that never had it
         bool energy_want = false, energy_on = false;
         DevBuf<double> d_efint, d_ealpha, d_eslot;
+        // rigid walls (femcy_explicit_set_wall): they travel in the kernel arguments; walls.n = 0: none, the launches of an
+        // integrator that never had one.  wall_kappa: the sum of their penalties, what the element bound adds
+        ExplicitWalls walls{};
+        double wall_kappa() const {
+            double k = 0.0;
+            for (int32_t w = 0; w < walls.n; ++w) k += walls.kappa[w];
+            return k;
+        }
     };
     std::vector<Explicit> explicits;
     std::vector<Amplitude> amplitudes;   // femcy_amplitude_create; dropped where integrators are
@@ -576,8 +584,13 @@ struct ExplicitEnergy {
     double *d_fint, *d_falpha, *d_slot;
 };
 int explicit_energy_slots(const Ctx* c);
+// wl (femcy_explicit_set_wall; null: none, today's instantiations with today's arguments): the wall variant of either node
+// pass, which also reads the node coordinates and u in every mode and adds wall_accel (element_math.hpp) to the kick.
+// launch_explicit_wall_get: out[0..4) of femcy_explicit_wall_get for wall k from vec[DOF], fetched (synchronises).
 int launch_explicit_node(Ctx* c, const double* d_minv, const double* d_f, const ExplicitClock* d_clk, double scale, double h,
-                         int mode, double alpha = 0.0, const ExplicitMotion* mv = nullptr, const ExplicitEnergy* en = nullptr);
+                         int mode, double alpha = 0.0, const ExplicitMotion* mv = nullptr, const ExplicitEnergy* en = nullptr,
+                         const ExplicitWalls* wl = nullptr);
+int launch_explicit_wall_get(Ctx* c, const ExplicitWalls& wl, int k, const double* d_m, const double* d_minv, double* out);
 int launch_explicit_energy_sum(Ctx* c, const double* d_slot, double* out);
 int launch_explicit_place(Ctx* c, const ExplicitMotion& mv, const ExplicitClock* d_clk, double t, int what);
 int launch_explicit_energy(Ctx* c, const double* d_m, const double* d_v, double* out);   // 1/2 sum m v^2, fixed order
@@ -587,9 +600,10 @@ int launch_rowabs_bound(Ctx* c, const double* d_minv, double* out);
 // [explicit_bound_partials(c)], recomputed from the mesh.  _bound_max: their maximum, fetched (synchronises).  _clock: their
 // maximum + one tick of the device clock.  All but _bound_max only enqueue.
 int explicit_bound_partials(const Ctx* c);
-// gd: omega_eff,e^2 with the damping of gd at v_{n+1/2}, formed as the element pass forms it
+// gd: omega_eff,e^2 with the damping of gd at v_{n+1/2}, formed as the element pass forms it; kappa: the sum of the wall
+// penalties, added to omega_e^2 before that (0: none)
 int launch_explicit_bound(Ctx* c, const double* d_u, const double* d_me, double s_C, double* d_part,
-                          const GeomDamping* gd = nullptr);
+                          const GeomDamping* gd = nullptr, double kappa = 0.0);
 int launch_explicit_bound_max(Ctx* c, const double* d_part, double* out);
 int launch_explicit_clock(Ctx* c, const double* d_part, ExplicitClock* d_clk);
 // fixed mass scaling (femcy_lumped_mass_scale).  launch_mass_total: the sum of d_m [nn] in a fixed order, fetched.

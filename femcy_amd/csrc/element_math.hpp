@@ -833,6 +833,61 @@ FEMCY_HD void explicit_kick_damped(double minv, double s, double f, double fint,
     a = an;
 }
 
+// Frictionless planar rigid walls (*Rigid Wall; femcy_explicit_set_wall, where the law stands).  Wall k: the unit normal
+// nrm[k] into the free half space, d[k] = nrm[k] . point and the penalty kappa[k] in 1/s^2, all formed once on the host
+// (api_checks.hpp: check_explicit_set_wall).  The gap of a node at x = X + u (one rounding per component) is the fma chain
+//   g = fma(n[DM-1], x[DM-1], ... fma(n[0], x[0], -d)),
+// and wall_accel adds the wall's share to the acceleration of component i of a node inside it, walls in ascending order:
+//   g < 0:  a = fma(-kappa g, n_i, a)        i.e. a_i += -kappa min(g, 0) n_i; a wall that is not reached adds nothing at all
+struct ExplicitWalls {
+    int32_t n;
+    double nrm[FEMCY_WALL_MAX][3], d[FEMCY_WALL_MAX], kappa[FEMCY_WALL_MAX];
+};
+template <int DM>
+FEMCY_HD double wall_gap(const ExplicitWalls& w, int k, const double (&x)[DM]) {
+    double g = fma(w.nrm[k][0], x[0], -w.d[k]);
+#pragma unroll
+    for (int j = 1; j < DM; ++j) g = fma(w.nrm[k][j], x[j], g);
+    return g;
+}
+template <int DM>
+FEMCY_HD double wall_accel(const ExplicitWalls& w, const double (&x)[DM], int i, double a) {
+    for (int k = 0; k < w.n; ++k) {
+        const double g = wall_gap<DM>(w, k, x);
+        const double ni = i == 0 ? w.nrm[k][0] : (i == 1 ? w.nrm[k][1] : w.nrm[k][DM - 1]);
+        if (g < 0.0) a = fma(-w.kappa[k] * g, ni, a);
+    }
+    return a;
+}
+// the kick of a DOF of an integrator with walls: explicit_kick / explicit_kick_damped (alpha = 0: the former's arithmetic)
+// with the wall term after minv (s f - f_int) and before the alpha term, on a free DOF only
+template <int DM>
+FEMCY_HD void explicit_kick_wall(double minv, double s, double f, double fint, double hh, double alpha, const ExplicitWalls& w,
+                                 const double (&x)[DM], int i, double& v, double& a) {
+    const double vh = explicit_vhalf(v, a, hh);
+    double an = minv * fma(s, f, -fint);
+    if (minv != 0.0) {
+        an = wall_accel<DM>(w, x, i, an);
+        if (alpha != 0.0) an = fma(-alpha, vh, an);
+    }
+    v = fma(hh, a + an, v);
+    a = an;
+}
+// what femcy_explicit_wall_get sums of one node for wall k: its mass m, whether any of its DOFs is free; t[0] the normal
+// force kappa m p, t[1] the potential 1/2 kappa m p^2 (both 0 on a node that is held in every DOF), t[2] 1 if g < 0,
+// t[3] the penetration p = max(-g, 0)
+template <int DM>
+FEMCY_HD void wall_node_terms(const ExplicitWalls& w, int k, const double (&x)[DM], double m, bool any_free, double (&t)[4]) {
+    const double g = wall_gap<DM>(w, k, x);
+    const double p = fmax(-g, 0.0);
+    const double km = any_free ? w.kappa[k] * m : 0.0;
+    const double fn = km * p;
+    t[0] = fn;
+    t[1] = (0.5 * fn) * p;
+    t[2] = g < 0.0 ? 1.0 : 0.0;
+    t[3] = p;
+}
+
 // Bulk viscosity at one Gauss point of the stiffness rule, on the CURRENT configuration.  With G_a = grad_x N_a (formed from
 // dNg and inv = J_x^-1 as the element pass forms them) and vh the element's rows of v_{n+1/2}:
 //   rate = sum_a vh_a . G_a        (the dm-dimensional divergence; plane stress: in the plane only)
@@ -910,11 +965,17 @@ FEMCY_HD void explicit_bound_point(const double* __restrict__ G, double v, const
 // the critical fraction of the lagged damping forces in the element's highest mode (bulk_rate_point, bulk_xi_point).  An
 // element with omega_e = 0 and alpha != 0 gives xi_e = inf and omega_eff,e^2 = NaN, which the callers count as an infinite
 // frequency: no increment, the safe side.
+// kappa (the sum of the penalties of the integrator's rigid walls, 0: none): added to omega_e^2 BEFORE the damping factor.
+// On a node in contact wall k adds kappa_k m_a n n^T to the stiffness; in the M-inner product that is kappa_k n n^T on the
+// node's block, positive semi-definite with the largest eigenvalue kappa_k (|n| = 1), so by Weyl's inequality
+// lambda_max(M^-1 (K + K_w)) <= lambda_max(M^-1 K) + sum_k kappa_k: omega_c^2 <= omega^2 + kappa.  Any element may touch a
+// wall, so every element takes the whole sum: the safe side.
 template <int NPE, int DM, bool DAMP>
 FEMCY_HD void explicit_bound_element_impl(const double (&X)[NPE][DM], const double (&U)[NPE][DM], const double* vh,
                                           const ExplicitDamping* d, int32_t nGP, const double* __restrict__ dN,
                                           const double* __restrict__ w, int kind, const double* __restrict__ C, double p0,
-                                          double p1, const double (&me)[NPE], double s_C, double& g, double& w2) {
+                                          double p1, const double (&me)[NPE], double s_C, double& g, double& w2,
+                                          double kappa) {
     double rme[NPE];
     double xq = 0.0;
 #pragma unroll
@@ -969,6 +1030,7 @@ FEMCY_HD void explicit_bound_element_impl(const double (&X)[NPE][DM], const doub
             }
         }
     }
+    if (kappa != 0.0) w2 += kappa;
     if constexpr (DAMP) {
         const double om = sqrt(w2);
         const double xi = (d->alpha != 0.0 ? d->alpha / (2.0 * om) : 0.0) + d->b1 + d->b2 * d->b2 * xq;
@@ -980,15 +1042,16 @@ template <int NPE, int DM>
 FEMCY_HD void explicit_bound_element(const double (&X)[NPE][DM], const double (&U)[NPE][DM], int32_t nGP,
                                      const double* __restrict__ dN, const double* __restrict__ w, int kind,
                                      const double* __restrict__ C, double p0, double p1, const double (&me)[NPE], double s_C,
-                                     double& g, double& w2) {
-    explicit_bound_element_impl<NPE, DM, false>(X, U, nullptr, nullptr, nGP, dN, w, kind, C, p0, p1, me, s_C, g, w2);
+                                     double& g, double& w2, double kappa = 0.0) {
+    explicit_bound_element_impl<NPE, DM, false>(X, U, nullptr, nullptr, nGP, dN, w, kind, C, p0, p1, me, s_C, g, w2, kappa);
 }
 template <int NPE, int DM>
 FEMCY_HD void explicit_bound_element_damped(const double (&X)[NPE][DM], const double (&U)[NPE][DM], const double (&vh)[NPE][DM],
                                             const ExplicitDamping& d, int32_t nGP, const double* __restrict__ dN,
                                             const double* __restrict__ w, int kind, const double* __restrict__ C, double p0,
-                                            double p1, const double (&me)[NPE], double s_C, double& g, double& w2) {
-    explicit_bound_element_impl<NPE, DM, true>(X, U, &vh[0][0], &d, nGP, dN, w, kind, C, p0, p1, me, s_C, g, w2);
+                                            double p1, const double (&me)[NPE], double s_C, double& g, double& w2,
+                                            double kappa = 0.0) {
+    explicit_bound_element_impl<NPE, DM, true>(X, U, &vh[0][0], &d, nGP, dN, w, kind, C, p0, p1, me, s_C, g, w2, kappa);
 }
 
 // Fixed mass scaling (femcy_lumped_mass_scale): the factor k_e of one element from w2 = its undamped omega_e^2 at u = 0 with

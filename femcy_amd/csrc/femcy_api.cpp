@@ -1297,6 +1297,24 @@ int femcy_explicit_energy_get(femcy_ctx* ctx, int32_t id, double* out) {
     return launch_explicit_energy_sum(c, c->explicits[id].d_eslot.get(), out);
 }
 
+int femcy_explicit_set_wall(femcy_ctx* ctx, int32_t id, int32_t nwalls, const double* point, const double* normal,
+                            const double* kappa) {
+    CTX_OR_FAIL(ctx);
+    EXPLICIT_SINGLE_RANK_OR_FAIL("femcy_explicit_set_wall");
+    ExplicitWalls w{};
+    FEMCY_TRY(check_explicit_set_wall(c, id, nwalls, point, normal, kappa, w));
+    c->explicits[id].walls = w;                     // they travel in the kernel arguments: nothing on the device to replace
+    return FEMCY_OK;
+}
+
+int femcy_explicit_wall_get(femcy_ctx* ctx, int32_t id, int32_t wall, double* out) {
+    CTX_OR_FAIL(ctx);
+    EXPLICIT_SINGLE_RANK_OR_FAIL("femcy_explicit_wall_get");
+    FEMCY_TRY(check_explicit_wall_get(c, id, wall, out));
+    const Ctx::Explicit& ex = c->explicits[id];
+    return launch_explicit_wall_get(c, ex.walls, wall, c->lumped_masses[ex.lumped].d_m.get(), ex.d_minv.get(), out);
+}
+
 int femcy_explicit_start(femcy_ctx* ctx, int32_t id, int rhs_vec, double scale) {
     CTX_OR_FAIL(ctx);
     READY_OR_FAIL();
@@ -1314,7 +1332,7 @@ int femcy_explicit_start(femcy_ctx* ctx, int32_t id, int rhs_vec, double scale) 
     ex.energy_on = ex.energy_want;                  // the start zeroes the sums and records the forces of state 0
     const ExplicitEnergy en = energy_of(c, ex);
     return launch_explicit_node(c, ex.d_minv.get(), c->d_vec[rhs_vec], nullptr, scale, 0.0, XN_START, ex.alpha,
-                                ex.nmoved ? &mv : nullptr, ex.energy_on ? &en : nullptr);
+                                ex.nmoved ? &mv : nullptr, ex.energy_on ? &en : nullptr, ex.walls.n ? &ex.walls : nullptr);
 }
 
 // nsteps steps from a started state: the first drift, then per step the element pass and the node pass (kick, and the drift
@@ -1344,12 +1362,12 @@ static int explicit_steps(Ctx* c, const Ctx::Explicit& ex, ExplicitClock* clk, i
         // the element pass of force_pass without its per-call copy of u: the lazy state is set once, below
         if ((rc = launch_geom(c, u, GEOM_DSDX | GEOM_FE, gd_geom))) break;
         if (clk) {
-            if ((rc = launch_explicit_bound(c, u, me, ex.s_C, ex.d_bpart.get(), gd_bound))) break;
+            if ((rc = launch_explicit_bound(c, u, me, ex.s_C, ex.d_bpart.get(), gd_bound, ex.wall_kappa()))) break;
             if ((rc = launch_explicit_clock(c, ex.d_bpart.get(), clk))) break;
         }
         rc = launch_explicit_node(c, ex.d_minv.get(), c->d_vec[rhs_vec], clk, scale0 + k * dscale, dt,
                                   k < nsteps ? XN_KICK_DRIFT : XN_KICK, ex.alpha, moved ? &mv : nullptr,
-                                  ex.energy_on ? &en : nullptr);
+                                  ex.energy_on ? &en : nullptr, ex.walls.n ? &ex.walls : nullptr);
     }
     if (rc) return rc;
     // post-processing reads "the stress of the last force evaluation": that of the last state (the last step did not drift)
@@ -1422,7 +1440,7 @@ int femcy_explicit_element_bound(femcy_ctx* ctx, int32_t id, int u_vec, double s
     if (rc) return rc;
     const GeomDamping gd = damping_of(c, exm, nullptr, 0.0, true);      // v_{1/2} := vec[VEL]
     rc = launch_explicit_bound(c, c->d_vec[u_vec], c->lumped_masses[exm.lumped].d_me.get(), s_C, exm.d_bpart.get(),
-                               exm.damped() ? &gd : nullptr);
+                               exm.damped() ? &gd : nullptr, exm.wall_kappa());
     if (rc) return rc;
     double w2 = 0.0;
     if ((rc = launch_explicit_bound_max(c, exm.d_bpart.get(), &w2))) return rc;
@@ -1452,13 +1470,14 @@ int femcy_explicit_auto_begin(femcy_ctx* ctx, int32_t id, int rhs_vec, double s_
     const GeomDamping gd = damping_of(c, exm, nullptr, 0.0, true);      // v_{-1/2} := v_0, vec[ACC] is not read
     if ((rc = force_pass(c, u, exm.bulk() ? &gd : nullptr))) return rc;
     if ((rc = launch_explicit_bound(c, u, c->lumped_masses[exm.lumped].d_me.get(), s_C, exm.d_bpart.get(),
-                                    exm.damped() ? &gd : nullptr)))
+                                    exm.damped() ? &gd : nullptr, exm.wall_kappa())))
         return rc;
     if ((rc = launch_explicit_clock(c, exm.d_bpart.get(), exm.d_clock.get()))) return rc;   // t = 0, the first h
     exm.energy_on = exm.energy_want;                                    // as femcy_explicit_start
     const ExplicitEnergy en = energy_of(c, exm);
     if ((rc = launch_explicit_node(c, exm.d_minv.get(), c->d_vec[rhs_vec], exm.d_clock.get(), 0.0, 0.0, XN_START, exm.alpha,
-                                   exm.nmoved ? &mv : nullptr, exm.energy_on ? &en : nullptr)))
+                                   exm.nmoved ? &mv : nullptr, exm.energy_on ? &en : nullptr,
+                                   exm.walls.n ? &exm.walls : nullptr)))
         return rc;
     exm.auto_begun = true;
     exm.s_C = s_C;

@@ -12,6 +12,7 @@
 // viscosity, the node pass subtracts alpha v_{n+1/2} (explicit_kick_damped) and the bound kernel returns omega_eff.
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 #include "ctx.hpp"
 #include "element_dispatch.hpp"
 #include "element_math.hpp"
@@ -65,6 +66,37 @@ struct NodeMotion {
     const Amplitude* amp;             // the curves
     double t, t_drift;                // k_explicit_node_auto fills both from the clock
 };
+// WALL (empty, or one NodeWall after the motion if there is one: an integrator with femcy_explicit_set_wall): a lane also
+// reads X[i] and, in every mode, u[i]; once the gather has reconverged the wavefront -- before any lane leaves -- the DM
+// lanes of a node hand x = X + u round inside their quad on the DPP network (quad_perm broadcasts of the quad's lanes
+// 0 .. DM-1, which are all `mine` or all not; a lane that is not reads back the 0 it put in and uses nothing of it), and
+// every lane evaluates the gap and its own component by wall_accel of element_math.hpp inside explicit_kick_wall.  A moved
+// lane takes no wall force, but its u has entered x.  Without the argument a kernel has the arguments and the code it has
+// with the motion alone.
+struct NodeWall {
+    const double* X;                  // [n] the node coordinates
+    ExplicitWalls w;
+};
+template <class T, class... A>
+constexpr bool has_opt = (std::is_same_v<T, A> || ...);
+template <class T, class A, class... R>
+__device__ __forceinline__ const T& opt_arg(const A& a, const R&... r) {
+    if constexpr (std::is_same_v<T, A>)
+        return a;
+    else
+        return opt_arg<T>(r...);
+}
+template <class... OPT>
+constexpr bool opt_known = ((std::is_same_v<NodeMotion, OPT> || std::is_same_v<NodeWall, OPT>) && ...) && sizeof...(OPT) <= 2 &&
+                           (sizeof...(OPT) < 2 || (has_opt<NodeMotion, OPT...> && has_opt<NodeWall, OPT...>));
+// x[j] of the lane's node from the quad's lane j; all 64 lanes active
+template <int DM>
+__device__ __forceinline__ void quad_gather(double xi, double (&x)[DM]) {
+    static_assert(DM <= 3, "a node's components must stand in the first lanes of one quad");
+    x[0] = dpp_move<0x00, 0xf>(xi);   // quad_perm [0,0,0,0]
+    x[1] = dpp_move<0x55, 0xf>(xi);   // quad_perm [1,1,1,1]
+    if constexpr (DM == 3) x[2] = dpp_move<0xAA, 0xf>(xi);   // quad_perm [2,2,2,2]
+}
 template <int DM, class... MOTION>
 __device__ __forceinline__ void explicit_node_pass(int32_t nn, const int32_t* __restrict__ ne_ptr,
                                                    const int32_t* __restrict__ ne_idx, const double* __restrict__ fe,
@@ -72,17 +104,18 @@ __device__ __forceinline__ void explicit_node_pass(int32_t nn, const int32_t* __
                                                    const ExplicitStep& st, int mode, double* __restrict__ u,
                                                    double* __restrict__ v, double* __restrict__ acc_vec,
                                                    const MOTION&... motion) {
-    constexpr bool MOVE = sizeof...(MOTION) == 1;
-    static_assert(sizeof...(MOTION) <= 1, "at most one motion argument");
+    constexpr bool MOVE = has_opt<NodeMotion, MOTION...>, WALL = has_opt<NodeWall, MOTION...>;
+    static_assert(opt_known<MOTION...>, "at most one motion and one wall argument");
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int32_t a = (int32_t)(t >> 5);
     const int sub = (int)(t & 31);
     const bool mine = a < nn && sub < DM;
     const int64_t i = (int64_t)a * DM + sub;
     double fi = 0.0, mi = 0.0, ai = 0.0, vi = 0.0, ui = 0.0;
+    [[maybe_unused]] double xi = 0.0;
     [[maybe_unused]] int32_t slot = -1;
     if (mine) {
-        if constexpr (MOVE) slot = (motion, ...).slot[i];
+        if constexpr (MOVE) slot = opt_arg<NodeMotion>(motion...).slot[i];
         fi = f[i];
         mi = minv[i];
         if (mode != XN_START) {
@@ -91,14 +124,17 @@ __device__ __forceinline__ void explicit_node_pass(int32_t nn, const int32_t* __
         } else if (st.alpha != 0.0) {
             vi = v[i];                                  // v_{-1/2} := v_0; vec[ACC] is not read at the start
         }
-        if (st.drift) ui = u[i];
+        if (WALL || st.drift) ui = u[i];
+        if constexpr (WALL) xi = opt_arg<NodeWall>(motion...).X[i] + ui;
     }
     double acc[DM];
     node_gather<DM>(a, sub, nn, ne_ptr, ne_idx, fe, acc);
+    [[maybe_unused]] double x[DM];
+    if constexpr (WALL) quad_gather<DM>(xi, x);
     if (!mine) return;
     if constexpr (MOVE) {
         if (mi == 0.0 && slot >= 0) {
-            const NodeMotion& mo = (motion, ...);
+            const NodeMotion& mo = opt_arg<NodeMotion>(motion...);
             explicit_moved(mo.amp[mo.curve[slot]], mo.val[slot], mo.t, mo.t_drift, mode == XN_START, st.drift, ui, vi, ai);
             acc_vec[i] = ai;
             if (mode == XN_START) return;
@@ -108,7 +144,9 @@ __device__ __forceinline__ void explicit_node_pass(int32_t nn, const int32_t* __
         }
     }
     const double fint = sub == 0 ? acc[0] : (sub == 1 ? acc[1] : acc[DM - 1]);
-    if (st.alpha != 0.0)
+    if constexpr (WALL)
+        explicit_kick_wall<DM>(mi, st.s, fi, fint, st.hh, st.alpha, opt_arg<NodeWall>(motion...).w, x, sub, vi, ai);
+    else if (st.alpha != 0.0)
         explicit_kick_damped(mi, st.s, fi, fint, st.hh, st.alpha, vi, ai);
     else
         explicit_kick(mi, st.s, fi, fint, st.hh, vi, ai);
@@ -143,13 +181,16 @@ __global__ void __launch_bounds__(XBS) k_explicit_node_auto(int32_t nn, const in
                                                             MOTION... motion) {
     ExplicitStep st;
     if (!explicit_step_clock(*clk, mode, st, alpha)) return;
-    if constexpr (sizeof...(MOTION) == 1) {
-        NodeMotion mo = (motion, ...);
+    if constexpr (has_opt<NodeMotion, MOTION...>) {
+        NodeMotion mo = opt_arg<NodeMotion>(motion...);
         mo.t = clk->t;
         mo.t_drift = clk->t_next;
-        explicit_node_pass<DM>(nn, ne_ptr, ne_idx, fe, f, minv, st, mode, u, v, acc_vec, mo);
+        if constexpr (has_opt<NodeWall, MOTION...>)
+            explicit_node_pass<DM>(nn, ne_ptr, ne_idx, fe, f, minv, st, mode, u, v, acc_vec, mo, opt_arg<NodeWall>(motion...));
+        else
+            explicit_node_pass<DM>(nn, ne_ptr, ne_idx, fe, f, minv, st, mode, u, v, acc_vec, mo);
     } else {
-        explicit_node_pass<DM>(nn, ne_ptr, ne_idx, fe, f, minv, st, mode, u, v, acc_vec);
+        explicit_node_pass<DM>(nn, ne_ptr, ne_idx, fe, f, minv, st, mode, u, v, acc_vec, motion...);
     }
 }
 
@@ -191,8 +232,8 @@ __device__ __forceinline__ void explicit_node_pass_energy(int32_t nn, const int3
                                                           double* __restrict__ u, double* __restrict__ v,
                                                           double* __restrict__ acc_vec, const NodeEnergy& en,
                                                           const MOTION&... motion) {
-    constexpr bool MOVE = sizeof...(MOTION) == 1;
-    static_assert(sizeof...(MOTION) <= 1, "at most one motion argument");
+    constexpr bool MOVE = has_opt<NodeMotion, MOTION...>, WALL = has_opt<NodeWall, MOTION...>;
+    static_assert(opt_known<MOTION...>, "at most one motion and one wall argument");
     static_assert(DM <= 4 && XBS % 64 == 0, "a node's addends must stand in one quad, a wavefront in one workgroup");
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int32_t a = (int32_t)(t >> 5);
@@ -202,14 +243,14 @@ __device__ __forceinline__ void explicit_node_pass_energy(int32_t nn, const int3
     const int64_t i = (int64_t)a * DM + sub;
     double* my_slot = en.slot + (t >> 6) * EN_SLOT;
     double fi = 0.0, mi = 0.0, ai = 0.0, vi = 0.0, ui = 0.0, ma = 0.0, fp = 0.0, gp = 0.0, s_prev = 0.0;
-    [[maybe_unused]] double t_prev = 0.0;
+    [[maybe_unused]] double t_prev = 0.0, xi = 0.0;
     [[maybe_unused]] int32_t slot = -1;
     if (!start) {
         s_prev = my_slot[EN_S];
         if constexpr (MOVE) t_prev = my_slot[EN_T];
     }
     if (mine) {
-        if constexpr (MOVE) slot = (motion, ...).slot[i];
+        if constexpr (MOVE) slot = opt_arg<NodeMotion>(motion...).slot[i];
         fi = f[i];
         mi = minv[i];
         ma = en.m[a];
@@ -221,13 +262,16 @@ __device__ __forceinline__ void explicit_node_pass_energy(int32_t nn, const int3
         } else if (st.alpha != 0.0) {
             vi = v[i];                                  // v_{-1/2} := v_0; vec[ACC] is not read at the start
         }
-        if (st.drift) ui = u[i];
+        if (WALL || st.drift) ui = u[i];
+        if constexpr (WALL) xi = opt_arg<NodeWall>(motion...).X[i] + ui;
     }
     double acc[DM];
     node_gather<DM>(a, sub, nn, ne_ptr, ne_idx, fe, acc);
+    [[maybe_unused]] double x[DM];
+    if constexpr (WALL) quad_gather<DM>(xi, x);
     double w[4] = {0.0, 0.0, 0.0, 0.0};
     [[maybe_unused]] double t_now = 0.0;
-    if constexpr (MOVE) t_now = (motion, ...).t;
+    if constexpr (MOVE) t_now = opt_arg<NodeMotion>(motion...).t;
     if (mine) {
         const double fint = sub == 0 ? acc[0] : (sub == 1 ? acc[1] : acc[DM - 1]);
         const bool count = !start && st.hh != 0.0;
@@ -235,7 +279,7 @@ __device__ __forceinline__ void explicit_node_pass_energy(int32_t nn, const int3
         if constexpr (MOVE) moved = mi == 0.0 && slot >= 0;
         if constexpr (MOVE) {
             if (moved) {
-                const NodeMotion& mo = (motion, ...);
+                const NodeMotion& mo = opt_arg<NodeMotion>(motion...);
                 const Amplitude& am = mo.amp[mo.curve[slot]];
                 const double a_prev = ai;
                 explicit_moved(am, mo.val[slot], mo.t, mo.t_drift, start, st.drift, ui, vi, ai);
@@ -254,7 +298,9 @@ __device__ __forceinline__ void explicit_node_pass_energy(int32_t nn, const int3
             explicit_energy_free(mi, ma, s_prev, st.s, fi, fp, fint, gp, st.alpha, vi, ai, st.hh, !count, w, ga);
             en.fint[i] = fint;
             en.falpha[i] = ga;
-            if (st.alpha != 0.0)
+            if constexpr (WALL)
+                explicit_kick_wall<DM>(mi, st.s, fi, fint, st.hh, st.alpha, opt_arg<NodeWall>(motion...).w, x, sub, vi, ai);
+            else if (st.alpha != 0.0)
                 explicit_kick_damped(mi, st.s, fi, fint, st.hh, st.alpha, vi, ai);
             else
                 explicit_kick(mi, st.s, fi, fint, st.hh, vi, ai);
@@ -311,13 +357,16 @@ __global__ void __launch_bounds__(XBS) k_explicit_node_auto_energy(int32_t nn, c
                                                                    NodeEnergy en, MOTION... motion) {
     ExplicitStep st;
     if (!explicit_step_clock(*clk, mode, st, alpha)) return;
-    if constexpr (sizeof...(MOTION) == 1) {
-        NodeMotion mo = (motion, ...);
+    if constexpr (has_opt<NodeMotion, MOTION...>) {
+        NodeMotion mo = opt_arg<NodeMotion>(motion...);
         mo.t = clk->t;
         mo.t_drift = clk->t_next;
-        explicit_node_pass_energy<DM>(nn, ne_ptr, ne_idx, fe, f, minv, st, mode, u, v, acc_vec, en, mo);
+        if constexpr (has_opt<NodeWall, MOTION...>)
+            explicit_node_pass_energy<DM>(nn, ne_ptr, ne_idx, fe, f, minv, st, mode, u, v, acc_vec, en, mo, opt_arg<NodeWall>(motion...));
+        else
+            explicit_node_pass_energy<DM>(nn, ne_ptr, ne_idx, fe, f, minv, st, mode, u, v, acc_vec, en, mo);
     } else {
-        explicit_node_pass_energy<DM>(nn, ne_ptr, ne_idx, fe, f, minv, st, mode, u, v, acc_vec, en);
+        explicit_node_pass_energy<DM>(nn, ne_ptr, ne_idx, fe, f, minv, st, mode, u, v, acc_vec, en, motion...);
     }
 }
 
@@ -424,6 +473,38 @@ __global__ void __launch_bounds__(XBS) k_explicit_energy_sum(int nslots, const d
     if (threadIdx.x == 0) out[blockIdx.x] = r;
 }
 
+// the read-back of a rigid wall (femcy_explicit_wall_get): partials of the four terms of wall_node_terms (element_math.hpp)
+// over the nodes in the pattern of k_explicit_energy -- thread t of workgroup b takes the nodes b * 256 + t + k *
+// (workgroups * 256), k ascending -- into part[j * gridDim.x + b]: three sums and one maximum, then k_explicit_final
+template <int DM>
+__global__ void __launch_bounds__(XBS) k_explicit_wall(int32_t nn, const double* __restrict__ X, const double* __restrict__ u,
+                                                       const double* __restrict__ m, const double* __restrict__ minv,
+                                                       ExplicitWalls wl, int k, double* __restrict__ part) {
+    __shared__ double sm[XBS / 64];
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int64_t a = (int64_t)blockIdx.x * XBS + threadIdx.x; a < nn; a += (int64_t)gridDim.x * XBS) {
+        double x[DM], t[4];
+        bool any_free = false;
+#pragma unroll
+        for (int c = 0; c < DM; ++c) {
+            x[c] = X[a * DM + c] + u[a * DM + c];
+            any_free = any_free || minv[a * DM + c] != 0.0;
+        }
+        wall_node_terms<DM>(wl, k, x, m[a], any_free, t);
+        acc[0] += t[0];
+        acc[1] += t[1];
+        acc[2] += t[2];
+        acc[3] = fmax(acc[3], t[3]);
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const double r = block_reduce<false>(acc[j], sm);
+        if (threadIdx.x == 0) part[j * gridDim.x + blockIdx.x] = r;
+    }
+    const double r = block_reduce<true>(acc[3], sm);
+    if (threadIdx.x == 0) part[3 * gridDim.x + blockIdx.x] = r;
+}
+
 // Gershgorin pass over the SELL storage: one lane per stored row position p = slice * 64 + lane (node_of[p] < 0: padding),
 // the node's blocks j = 0 .. rowlen - 1 in storage order, the DM entries of each of its DM scalar rows through kv_index in
 // ascending column order; a scalar row counts with sum_j |K_ij| minv_i unless minv_i = 0 (constrained).  A NaN counts as
@@ -469,7 +550,9 @@ __global__ void __launch_bounds__(XBS) k_rowabs_bound(int64_t npos, const int32_
 // counts as infinity, as in k_rowabs_bound, so that a broken element gives no increment.
 // DAMPING (empty, or one BoundDamping: an integrator with damping set): omega_eff,e^2 of explicit_bound_element_damped, with
 // v_{n+1/2} gathered and formed as the damped element pass does it -- hh from the host or, with clk, half of the clock's
-// h_next, read before k_explicit_clock ticks.  Without it the kernel has the arguments and the code it always had.
+// h_next, read before k_explicit_clock ticks.  Without it the kernel has the code it always had.  kappa: the sum of the
+// penalties of the integrator's rigid walls, added to omega_e^2 before the damping factor; an argument the kernel always
+// takes, 0 without walls, when nothing is added and the bits are those of a kernel without it.
 struct BoundDamping {
     const double *vel, *accv;
     ExplicitDamping d;
@@ -481,7 +564,7 @@ __global__ void __launch_bounds__(XBS) k_explicit_bound(int32_t ne, int32_t nGP,
                                                         const double* __restrict__ u, const int32_t* __restrict__ elems,
                                                         const double* __restrict__ dN, const double* __restrict__ w,
                                                         int mat_kind, const double* __restrict__ C, double p0, double p1,
-                                                        const double* __restrict__ me_in, double s_C,
+                                                        const double* __restrict__ me_in, double s_C, double kappa,
                                                         double* __restrict__ part, DAMPING... damping) {
     constexpr bool DAMP = sizeof...(DAMPING) == 1;
     static_assert(sizeof...(DAMPING) <= 1, "at most one damping argument");
@@ -510,9 +593,10 @@ __global__ void __launch_bounds__(XBS) k_explicit_bound(int32_t ne, int32_t nGP,
             }
         }
         if constexpr (DAMP)
-            explicit_bound_element_damped<NPE, DM>(X, U, Vh, (damping, ...).d, nGP, dN, w, mat_kind, C, p0, p1, me, s_C, g, w2);
+            explicit_bound_element_damped<NPE, DM>(X, U, Vh, (damping, ...).d, nGP, dN, w, mat_kind, C, p0, p1, me, s_C, g, w2,
+                                                   kappa);
         else
-            explicit_bound_element<NPE, DM>(X, U, nGP, dN, w, mat_kind, C, p0, p1, me, s_C, g, w2);
+            explicit_bound_element<NPE, DM>(X, U, nGP, dN, w, mat_kind, C, p0, p1, me, s_C, g, w2, kappa);
         best = w2 != w2 ? INFINITY : w2;
     }
     const double r = block_reduce<true>(best, sm);
@@ -640,11 +724,30 @@ int explicit_energy_slots(const Ctx* c) { return (int)node_gather_grid(c->nn, XB
 // the energy variants of the four node-pass launches below, on the same grid
 static void launch_explicit_node_energy(Ctx* c, unsigned grid, const double* d_minv, const double* d_f,
                                         const ExplicitClock* d_clk, double scale, double h, int mode, double alpha,
-                                        const ExplicitMotion* mv, const ExplicitEnergy& e) {
+                                        const ExplicitMotion* mv, const ExplicitEnergy& e, const ExplicitWalls* wl) {
     double *u = c->d_vec[FEMCY_VEC_DOF], *v = c->d_vec[FEMCY_VEC_VEL], *a = c->d_vec[FEMCY_VEC_ACC];
     const NodeEnergy en{e.d_m, e.d_fint, e.d_falpha, e.d_slot};
     dispatch_dm(c->dm, [&](auto dm) {
-        if (mv) {
+        if (wl) {
+            const NodeWall nw{c->d_nodes.get(), *wl};
+            if (mv) {
+                const NodeMotion mo{mv->d_slot, mv->d_curve, mv->d_val, mv->d_amp, mv->t, mv->t_drift};
+                if (d_clk)
+                    hipLaunchKernelGGL((k_explicit_node_auto_energy<dm(), NodeMotion, NodeWall>), dim3(grid), dim3(XBS), 0,
+                                       c->stream, c->nn, c->d_ne_ptr, c->d_ne_idx, c->d_fe, d_f, d_minv, d_clk, mode, alpha, u, v,
+                                       a, en, mo, nw);
+                else
+                    hipLaunchKernelGGL((k_explicit_node_energy<dm(), NodeMotion, NodeWall>), dim3(grid), dim3(XBS), 0, c->stream,
+                                       c->nn, c->d_ne_ptr, c->d_ne_idx, c->d_fe, d_f, d_minv,
+                                       explicit_step_fixed(scale, h, mode, alpha), mode, u, v, a, en, mo, nw);
+            } else if (d_clk)
+                hipLaunchKernelGGL((k_explicit_node_auto_energy<dm(), NodeWall>), dim3(grid), dim3(XBS), 0, c->stream, c->nn,
+                                   c->d_ne_ptr, c->d_ne_idx, c->d_fe, d_f, d_minv, d_clk, mode, alpha, u, v, a, en, nw);
+            else
+                hipLaunchKernelGGL((k_explicit_node_energy<dm(), NodeWall>), dim3(grid), dim3(XBS), 0, c->stream, c->nn,
+                                   c->d_ne_ptr, c->d_ne_idx, c->d_fe, d_f, d_minv, explicit_step_fixed(scale, h, mode, alpha),
+                                   mode, u, v, a, en, nw);
+        } else if (mv) {
             const NodeMotion mo{mv->d_slot, mv->d_curve, mv->d_val, mv->d_amp, mv->t, mv->t_drift};
             if (d_clk)
                 hipLaunchKernelGGL((k_explicit_node_auto_energy<dm(), NodeMotion>), dim3(grid), dim3(XBS), 0, c->stream, c->nn,
@@ -672,18 +775,36 @@ int launch_explicit_energy_sum(Ctx* c, const double* d_slot, double* out) {
 }
 
 int launch_explicit_node(Ctx* c, const double* d_minv, const double* d_f, const ExplicitClock* d_clk, double scale, double h,
-                         int mode, double alpha, const ExplicitMotion* mv, const ExplicitEnergy* en) {
+                         int mode, double alpha, const ExplicitMotion* mv, const ExplicitEnergy* en, const ExplicitWalls* wl) {
     const unsigned grid = node_gather_grid(c->nn, XBS);
     double *u = c->d_vec[FEMCY_VEC_DOF], *v = c->d_vec[FEMCY_VEC_VEL], *a = c->d_vec[FEMCY_VEC_ACC];
     size_t tm = timing_begin(c, T_FORCE);
     if (en) {
-        launch_explicit_node_energy(c, grid, d_minv, d_f, d_clk, scale, h, mode, alpha, mv, *en);
+        launch_explicit_node_energy(c, grid, d_minv, d_f, d_clk, scale, h, mode, alpha, mv, *en, wl);
         timing_end(c, tm);
         FEMCY_HIP(hipGetLastError());
         return FEMCY_OK;
     }
     dispatch_dm(c->dm, [&](auto dm) {
-        if (mv) {
+        if (wl) {
+            const NodeWall nw{c->d_nodes.get(), *wl};
+            if (mv) {
+                const NodeMotion mo{mv->d_slot, mv->d_curve, mv->d_val, mv->d_amp, mv->t, mv->t_drift};
+                if (d_clk)
+                    hipLaunchKernelGGL((k_explicit_node_auto<dm(), NodeMotion, NodeWall>), dim3(grid), dim3(XBS), 0, c->stream,
+                                       c->nn, c->d_ne_ptr, c->d_ne_idx, c->d_fe, d_f, d_minv, d_clk, mode, alpha, u, v, a, mo, nw);
+                else
+                    hipLaunchKernelGGL((k_explicit_node<dm(), NodeMotion, NodeWall>), dim3(grid), dim3(XBS), 0, c->stream, c->nn,
+                                       c->d_ne_ptr, c->d_ne_idx, c->d_fe, d_f, d_minv,
+                                       explicit_step_fixed(scale, h, mode, alpha), mode, u, v, a, mo, nw);
+            } else if (d_clk)
+                hipLaunchKernelGGL((k_explicit_node_auto<dm(), NodeWall>), dim3(grid), dim3(XBS), 0, c->stream, c->nn,
+                                   c->d_ne_ptr, c->d_ne_idx, c->d_fe, d_f, d_minv, d_clk, mode, alpha, u, v, a, nw);
+            else
+                hipLaunchKernelGGL((k_explicit_node<dm(), NodeWall>), dim3(grid), dim3(XBS), 0, c->stream, c->nn, c->d_ne_ptr,
+                                   c->d_ne_idx, c->d_fe, d_f, d_minv, explicit_step_fixed(scale, h, mode, alpha), mode, u, v, a,
+                                   nw);
+        } else if (mv) {
             const NodeMotion mo{mv->d_slot, mv->d_curve, mv->d_val, mv->d_amp, mv->t, mv->t_drift};
             if (d_clk)
                 hipLaunchKernelGGL((k_explicit_node_auto<dm(), NodeMotion>), dim3(grid), dim3(XBS), 0, c->stream, c->nn,
@@ -747,6 +868,23 @@ int launch_explicit_energy(Ctx* c, const double* d_m, const double* d_v, double*
     return rc;
 }
 
+int launch_explicit_wall_get(Ctx* c, const ExplicitWalls& wl, int k, const double* d_m, const double* d_minv, double* out) {
+    const int g = reduction_grid(c->nn);        // 4 g <= MAX_PARTIALS partials
+    dispatch_dm(c->dm, [&](auto dm) {
+        hipLaunchKernelGGL((k_explicit_wall<dm()>), dim3(g), dim3(XBS), 0, c->stream, c->nn, c->d_nodes.get(),
+                           c->d_vec[FEMCY_VEC_DOF].get(), d_m, d_minv, wl, k, c->d_part1);
+    });
+    double* res = c->d_part2;
+    for (int j = 0; j < 3; ++j)
+        hipLaunchKernelGGL((k_explicit_final<false>), dim3(1), dim3(XBS), 0, c->stream, g, c->d_part1.get() + (size_t)j * g, res + j);
+    hipLaunchKernelGGL((k_explicit_final<true>), dim3(1), dim3(XBS), 0, c->stream, g, c->d_part1.get() + 3 * (size_t)g, res + 3);
+    FEMCY_HIP(hipGetLastError());
+    FEMCY_HIP(hipMemcpyAsync(c->h_scalar, res, sizeof(double) * 4, hipMemcpyDeviceToHost, c->stream));
+    FEMCY_HIP(hipStreamSynchronize(c->stream));
+    for (int j = 0; j < 4; ++j) out[j] = c->h_scalar[j];
+    return FEMCY_OK;
+}
+
 int launch_rowabs_bound(Ctx* c, const double* d_minv, double* out) {
     const int64_t npos = (int64_t)c->nslices * SLICE;
     const int g = reduction_grid(npos);
@@ -761,20 +899,21 @@ int launch_rowabs_bound(Ctx* c, const double* d_minv, double* out) {
 
 int explicit_bound_partials(const Ctx* c) { return (c->ne + XBS - 1) / XBS; }
 
-int launch_explicit_bound(Ctx* c, const double* d_u, const double* d_me, double s_C, double* d_part, const GeomDamping* gd) {
+int launch_explicit_bound(Ctx* c, const double* d_u, const double* d_me, double s_C, double* d_part, const GeomDamping* gd,
+                          double kappa) {
     const int grid = explicit_bound_partials(c);
     size_t tm = timing_begin(c, T_GEOM);
     const bool launched = dispatch_element(c->npe, c->dm, [&](auto npe, auto dm) {
         if (gd)
             hipLaunchKernelGGL((k_explicit_bound<npe(), dm(), BoundDamping>), dim3(grid), dim3(XBS), 0, c->stream, c->ne,
                                c->nGP, c->d_nodes, d_u, c->d_elems, c->d_dN, c->d_w, c->mat_kind, c->d_C, c->mat_params[0],
-                               c->mat_params[1], d_me, s_C, d_part,
+                               c->mat_params[1], d_me, s_C, kappa, d_part,
                                BoundDamping{gd->d_v, gd->d_a, {gd->alpha, gd->b1, gd->b2, gd->Md, gd->rho0}, 0.5 * gd->h,
                                             gd->d_clk});
         else
             hipLaunchKernelGGL((k_explicit_bound<npe(), dm()>), dim3(grid), dim3(XBS), 0, c->stream, c->ne, c->nGP, c->d_nodes, d_u,
                            c->d_elems, c->d_dN, c->d_w, c->mat_kind, c->d_C, c->mat_params[0], c->mat_params[1], d_me, s_C,
-                           d_part);
+                           kappa, d_part);
     });
     timing_end(c, tm);
     if (!launched) {

@@ -90,6 +90,13 @@ struct Explicit {
     bool energy_want = false, energy_on = false;
     double en[4] = {0.0, 0.0, 0.0, 0.0}, en_s = 0.0, en_t = 0.0;
     std::vector<double> efint, ealpha, ew;
+    // femcy_explicit_set_wall (csrc/element_math.hpp: ExplicitWalls; walls.n = 0: none) and the sum of the penalties
+    femcy::ExplicitWalls walls{};
+    double wall_kappa() const {
+        double k = 0.0;
+        for (int32_t w = 0; w < walls.n; ++w) k += walls.kappa[w];
+        return k;
+    }
 };
 // a damped element pass or bound (the device's GeomDamping): v, a (null: the start, v_{-1/2} := v_0) and hh = h / 2 of the
 // drift that led to the state
@@ -1270,9 +1277,12 @@ void lumped_mass(femcy_ctx* c, int32_t nq, const double* Nq, const double* dNq, 
 // With the energy balance running (ex.energy_on) every DOF's addends of the step that led to the state (csrc/element_math.hpp:
 // explicit_energy_free / _moved, the device's functions) go to the node's row of ex.ew and are then added to the four sums
 // node by node: one order, whatever the number of threads.  The forces of the state stay in ex.efint / ex.ealpha.
+// With rigid walls (ex.walls.n) the kick is explicit_kick_wall at x = X + u of the node, u before any of its DOFs drifts.
+template <int DM>
 void explicit_node(femcy_ctx* c, Explicit& ex, const double* f, const ExplicitStep& st, int mode, double t = 0.0,
                    double t_drift = 0.0) {
-    const int dm = c->dm;
+    const int dm = DM;
+    const bool wall = ex.walls.n != 0;
     const MotionTables& mo = ex.motion;
     const bool moved = ex.moved(), energy = ex.energy_on, start = mode == XN_START, count = !start && st.hh != 0.0;
     const double* mass = c->lumped_masses[ex.lumped].m.data();
@@ -1281,6 +1291,8 @@ void explicit_node(femcy_ctx* c, Explicit& ex, const double* f, const ExplicitSt
     for (int32_t a = 0; a < c->nn; ++a) {
         double fint[3], wn[4] = {0.0, 0.0, 0.0, 0.0};
         node_sum(c, a, c->fe.data(), dm, fint);
+        double x[DM];
+        for (int i = 0; i < dm; ++i) x[i] = c->nodes[(int64_t)a * dm + i] + u[(int64_t)a * dm + i];
         for (int i = 0; i < dm; ++i) {
             const int64_t q = (int64_t)a * dm + i;
             if (const int32_t s = moved ? mo.slot[q] : -1; s >= 0 && ex.minv[q] == 0.0) {
@@ -1308,7 +1320,9 @@ void explicit_node(femcy_ctx* c, Explicit& ex, const double* f, const ExplicitSt
                 ex.efint[q] = fint[i];
                 ex.ealpha[q] = ga;
             }
-            if (st.alpha != 0.0)
+            if (wall)
+                explicit_kick_wall<DM>(ex.minv[q], st.s, f[q], fint[i], st.hh, st.alpha, ex.walls, x, i, vi, ai);
+            else if (st.alpha != 0.0)
                 explicit_kick_damped(ex.minv[q], st.s, f[q], fint[i], st.hh, st.alpha, vi, ai);
             else
                 explicit_kick(ex.minv[q], st.s, f[q], fint[i], st.hh, vi, ai);
@@ -1331,10 +1345,18 @@ void explicit_node(femcy_ctx* c, Explicit& ex, const double* f, const ExplicitSt
     ex.en_s = st.s;
     ex.en_t = t;
 }
+void explicit_node_any(femcy_ctx* c, Explicit& ex, const double* f, const ExplicitStep& st, int mode, double t = 0.0,
+                       double t_drift = 0.0) {
+    if (c->dm == 2)
+        explicit_node<2>(c, ex, f, st, mode, t, t_drift);
+    else
+        explicit_node<3>(c, ex, f, st, mode, t, t_drift);
+}
 
 // max_e omega_e^2 at u (csrc/element_math.hpp: explicit_bound_element); a NaN counts as infinity
 template <int NPE, int DM>
-void element_bound(femcy_ctx* c, const double* u, const double* me_all, double s_C, const HostDamping* hd, double& out) {
+void element_bound(femcy_ctx* c, const double* u, const double* me_all, double s_C, const HostDamping* hd, double kappa,
+                   double& out) {
     double best = 0.0;
 #pragma omp parallel for schedule(static) reduction(max : best)
     for (int32_t e = 0; e < c->ne; ++e) {
@@ -1353,10 +1375,10 @@ void element_bound(femcy_ctx* c, const double* u, const double* me_all, double s
         }
         if (hd)
             explicit_bound_element_damped<NPE, DM>(X, U, Vh, hd->d, c->nGP, c->dN.data(), c->w.data(), c->mat_kind, c->h_C,
-                                                   c->mat_params[0], c->mat_params[1], me, s_C, g, w2);
+                                                   c->mat_params[0], c->mat_params[1], me, s_C, g, w2, kappa);
         else
             explicit_bound_element<NPE, DM>(X, U, c->nGP, c->dN.data(), c->w.data(), c->mat_kind, c->h_C, c->mat_params[0],
-                                            c->mat_params[1], me, s_C, g, w2);
+                                            c->mat_params[1], me, s_C, g, w2, kappa);
         if (w2 != w2) w2 = INFINITY;
         best = std::fmax(best, w2);
     }
@@ -1369,7 +1391,8 @@ HostDamping damping_of(const femcy_ctx* c, const Explicit& ex, double h, bool st
 }
 int element_bound_any(femcy_ctx* c, const Explicit& ex, const double* u, double s_C, double* w2, const HostDamping* hd = nullptr) {
     const double* me = c->lumped_masses[ex.lumped].me.data();
-    if (!dispatch_element(c->npe, c->dm, [&](auto npe, auto dm) { element_bound<npe(), dm()>(c, u, me, s_C, hd, *w2); }))
+    if (!dispatch_element(c->npe, c->dm,
+                          [&](auto npe, auto dm) { element_bound<npe(), dm()>(c, u, me, s_C, hd, ex.wall_kappa(), *w2); }))
         return no_kernel(c, "element-bound");
     return FEMCY_OK;
 }
@@ -1486,7 +1509,7 @@ int explicit_steps(femcy_ctx* c, Explicit& ex, ExplicitClock* clock, int rhs_vec
         } else {
             st = explicit_step_fixed(scale0 + k * dscale, dt, mode, ex.alpha);
         }
-        explicit_node(c, ex, c->vec[rhs_vec].data(), st, mode, clock ? clock->t : time_of(k),
+        explicit_node_any(c, ex, c->vec[rhs_vec].data(), st, mode, clock ? clock->t : time_of(k),
                       clock ? clock->t_next : time_of(k + 1));
     }
     return FEMCY_OK;
@@ -1595,7 +1618,7 @@ int femcy_explicit_start(femcy_ctx* ctx, int32_t id, int rhs_vec, double scale) 
     const HostDamping hd = damping_of(c, ex, 0.0, true);
     geom(c, c->vec[FEMCY_VEC_DOF].data(), GEOM_DSDX | GEOM_F | GEOM_SIGMA | GEOM_FE, ex.bulk() ? &hd : nullptr);
     ex.energy_on = ex.energy_want;                  // the start zeroes the sums and records the forces of state 0
-    explicit_node(c, ex, c->vec[rhs_vec].data(), explicit_step_fixed(scale, 0.0, XN_START, ex.alpha), XN_START);
+    explicit_node_any(c, ex, c->vec[rhs_vec].data(), explicit_step_fixed(scale, 0.0, XN_START, ex.alpha), XN_START);
     return FEMCY_OK;
 }
 
@@ -1669,6 +1692,51 @@ int femcy_explicit_energy_get(femcy_ctx* ctx, int32_t id, double* out) {
     CTX_OR_FAIL(ctx);
     FEMCY_TRY(check_explicit_energy_get(c, id, out));
     std::copy(c->explicits[id].en, c->explicits[id].en + 4, out);
+    return FEMCY_OK;
+}
+
+int femcy_explicit_set_wall(femcy_ctx* ctx, int32_t id, int32_t nwalls, const double* point, const double* normal,
+                            const double* kappa) {
+    CTX_OR_FAIL(ctx);
+    ExplicitWalls w{};
+    FEMCY_TRY(check_explicit_set_wall(c, id, nwalls, point, normal, kappa, w));
+    c->explicits[id].walls = w;
+    return FEMCY_OK;
+}
+
+}  // extern "C"
+namespace {
+// the device's k_explicit_wall and its four final reductions: the terms of wall_node_terms in the order of device_order_sum,
+// the maximum as it is
+template <int DM>
+void wall_get(const femcy_ctx* c, const Explicit& ex, int k, double* out) {
+    const double* m = c->lumped_masses[ex.lumped].m.data();
+    const double* u = c->vec[FEMCY_VEC_DOF].data();
+    auto term = [&](int64_t a, int j) {
+        double x[DM], t[4];
+        bool any_free = false;
+        for (int i = 0; i < DM; ++i) {
+            x[i] = c->nodes[a * DM + i] + u[a * DM + i];
+            any_free = any_free || ex.minv[a * DM + i] != 0.0;
+        }
+        wall_node_terms<DM>(ex.walls, k, x, m[a], any_free, t);
+        return t[j];
+    };
+    for (int j = 0; j < 3; ++j) out[j] = device_order_sum(c->nn, [&](double acc, int64_t a) { return acc + term(a, j); });
+    double p = 0.0;
+    for (int64_t a = 0; a < c->nn; ++a) p = std::fmax(p, term(a, 3));
+    out[3] = p;
+}
+}  // namespace
+extern "C" {
+
+int femcy_explicit_wall_get(femcy_ctx* ctx, int32_t id, int32_t wall, double* out) {
+    CTX_OR_FAIL(ctx);
+    FEMCY_TRY(check_explicit_wall_get(c, id, wall, out));
+    if (c->dm == 2)
+        wall_get<2>(c, c->explicits[id], wall, out);
+    else
+        wall_get<3>(c, c->explicits[id], wall, out);
     return FEMCY_OK;
 }
 
@@ -1764,7 +1832,7 @@ int femcy_explicit_auto_begin(femcy_ctx* ctx, int32_t id, int rhs_vec, double s_
     ExplicitStep st;
     explicit_step_clock(exm.clock, XN_START, st, exm.alpha);   // always something to do at the start
     exm.energy_on = exm.energy_want;                           // as femcy_explicit_start
-    explicit_node(c, exm, c->vec[rhs_vec].data(), st, XN_START);
+    explicit_node_any(c, exm, c->vec[rhs_vec].data(), st, XN_START);
     exm.auto_begun = true;
     return FEMCY_OK;
 }

@@ -41,7 +41,8 @@ def run(fileName: str, device: int = 0, verbose: bool = True, tangent: str = "re
         for rec in system.increments:
             print(" t = {time1:.6e}: kinetic {kinetic:.6e}, internal work {internal_work:.6e}, external work "
                   "{external_work:.6e} (boundary {boundary_work:.6e}), viscous dissipation {viscous_dissipation:.6e}, "
-                  "total {energy_total:.6e}".format(**rec))
+                  "total {energy_total:.6e}".format(**rec)
+                  + (", of which contact {:.6e}".format(rec["contact_energy"]) if "contact_energy" in rec else ""))
         drift = max(abs(rec["energy_total"] - e0) for rec in system.increments)
         print(f" energy balance: largest |energy_total - energy_total(0)| = {drift:.6e} (energy_total(0) = {e0:.6e})")
     system.get_elasEng()

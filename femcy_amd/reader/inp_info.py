@@ -35,8 +35,10 @@ control` -> dynamic_auto = True: the driver re-estimates the increment in every 
 defaults 0.06, 1.2) inside an explicit step -> bulk_viscosity = (b1, b2), None without the keyword; `*Damping, alpha=` in the
 `*Material` block -> damping_alpha (read_damping).  `*Fixed Mass Scaling[, factor=][, dt=][, type=]` inside an explicit step ->
 mass_scaling = {"factor", "dt", "type"}, None without the keyword (read_mass_scaling).  `*Energy Output` inside an explicit
-step, alone or under `*Output, history` -> energy_output = True, False without the keyword (read_energy_output).  A deck with
-`*Static` has procedure = "static" and reads as before.
+step, alone or under `*Output, history` -> energy_output = True, False without the keyword (read_energy_output).  `*Rigid Wall[, penalty=kappa]` inside an
+explicit step, data `x0, y0[, z0], nx, ny[, nz]` -> rigid_walls = [{"point", "normal", "penalty"}] (read_rigid_walls): an
+EXTENSION keyword, Abaqus has none for a planar rigid wall.  A deck with `*Static` has procedure = "static" and reads as
+before.
 """
 import sys
 from typing import Dict, List
@@ -147,6 +149,7 @@ class InpInfo(InpInfoBase):
         self.bulk_viscosity, self.damping_alpha = self.read_damping(file)
         self.mass_scaling = self.read_mass_scaling(file)
         self.energy_output = self.read_energy_output(file)
+        self.rigid_walls = self.read_rigid_walls(file)
         self.initial_velocity_info = self.read_initial_velocity(file)
 
     # ------------------------------------------------------------------ nodes and elements
@@ -654,6 +657,43 @@ class InpInfo(InpInfoBase):
         if asked and self.procedure != "explicit":
             raise ValueError("*Energy Output has not been supported outside a *Dynamic, explicit step")
         return asked
+
+    def read_rigid_walls(self, fileName):
+        """`*Rigid Wall[, penalty=kappa]` inside a `*Dynamic, explicit` step, data lines `x0, y0[, z0], nx, ny[, nz]` ->
+        [{"point", "normal", "penalty"}], one entry per data line of every keyword, [] without it.  A frictionless planar
+        rigid wall through the point with the normal pointing into the free half space; a node behind it is pushed back by
+        the penalty force kappa m (depth) along the normal (`femcy_explicit_set_wall`).  `penalty` is kappa in 1/s^2, None
+        without the parameter: the driver then takes 0.1 omega^2 of its first frequency estimate.
+        This is an EXTENSION keyword in the spirit of LS-DYNA's planar rigid wall: Abaqus has no single keyword for it (it
+        needs an analytical rigid surface, a reference node, a contact pair and a surface interaction).
+        Refused: more than 4 walls, the wrong number of fields for the mesh dimension, a zero normal, `penalty <= 0`, and the
+        keyword in a deck whose procedure is not "explicit"."""
+        dm = int(self.ELE.dm)
+        walls = []
+        for line, block in _deck(fileName).keywords():
+            fields = [t.strip() for t in line.split(",")]
+            if " ".join(fields[0].lower().split()) != "*rigid wall":
+                continue
+            params = {t.split("=")[0].strip().lower(): t.split("=")[1].strip() for t in fields[1:] if "=" in t}
+            penalty = float(params["penalty"]) if "penalty" in params else None
+            if penalty is not None and not (penalty > 0.0 and np.isfinite(penalty)):
+                raise ValueError("*Rigid Wall, penalty={} is refused (it must be positive)".format(params["penalty"]))
+            for d in block:
+                if not d.strip():
+                    continue
+                cols = [t for t in (t.strip() for t in d.rstrip().rstrip(",").split(","))]
+                if len(cols) != 2 * dm or not all(cols):
+                    raise ValueError("*Rigid Wall data line needs {} fields on a {}-D mesh (a point and a normal): {}".format(
+                        2 * dm, dm, ", ".join(cols)))
+                vals = np.array([float(t) for t in cols])
+                if not np.all(np.isfinite(vals)) or not np.linalg.norm(vals[dm:]) > 0.0:
+                    raise ValueError("*Rigid Wall: the normal {} is refused (it must have a length)".format(", ".join(cols[dm:])))
+                walls.append({"point": vals[:dm].copy(), "normal": vals[dm:].copy(), "penalty": penalty})
+        if len(walls) > 4:
+            raise ValueError("*Rigid Wall: {} walls have not been supported (at most 4)".format(len(walls)))
+        if walls and self.procedure != "explicit":
+            raise ValueError("*Rigid Wall has not been supported outside a *Dynamic, explicit step")
+        return walls
 
     def read_mass_scaling(self, fileName):
         """`*Fixed Mass Scaling[, factor=f][, dt=tau][, type=uniform | below min | set equal dt]` inside a `*Dynamic, explicit`

@@ -51,7 +51,8 @@ def deck_view(inp) -> SimpleNamespace:
         initial_velocity_info=opt("initial_velocity_info") or [], dynamic=opt("dynamic"),
         dynamic_auto=bool(opt("dynamic_auto", False)), bulk_viscosity=opt("bulk_viscosity"),
         damping_alpha=float(opt("damping_alpha", 0.0) or 0.0), mass_scaling=opt("mass_scaling"),
-        amplitudes=opt("amplitudes") or {}, energy_output=bool(opt("energy_output", False)))
+        amplitudes=opt("amplitudes") or {}, energy_output=bool(opt("energy_output", False)),
+        rigid_walls=opt("rigid_walls") or [])
 
 
 class LoadSchedule:
@@ -601,7 +602,27 @@ class System_of_equations:
             bulk = internal - (out["strain_energy"] - bal["strain0"])
             out.update(external_work=external, boundary_work=boundary, internal_work=internal,
                        viscous_dissipation=alpha + bulk, energy_total=kinetic + internal + alpha - external)
+        walls = getattr(self, "walls", None)
+        if walls:                                                     # *Rigid Wall: one synchronising read-back per wall
+            got = [self.ctx.explicit_wall_get(self.explicit, k) for k in range(len(walls))]
+            out["wall"] = [{"force": float(g[0]), "energy": float(g[1]), "nodes": int(g[2]), "penetration": float(g[3])}
+                           for g in got]
+            if bal is not None:                                       # the walls are conservative: their potential counts
+                out["contact_energy"] = float(sum(g[1] for g in got))
+                out["energy_total"] += out["contact_energy"]
         return out
+
+    def _set_walls(self, deck, ex, omega_ref: float):
+        """`*Rigid Wall` (`deck.rigid_walls`) -> `femcy_explicit_set_wall`, before the start.  A wall without `penalty=` takes
+        kappa = 0.1 omega_ref^2 with omega_ref the first frequency estimate of the run.  `self.walls` keeps {"point", "normal",
+        "penalty"} per wall as set, `self.wall_kappa` the sum of the penalties (0.0 without walls)."""
+        self.walls = [{"point": np.asarray(w["point"], dtype=np.float64), "normal": np.asarray(w["normal"], dtype=np.float64),
+                       "penalty": float(w["penalty"]) if w["penalty"] is not None else 0.1 * (omega_ref * omega_ref)}
+                      for w in deck.rigid_walls]
+        self.wall_kappa = float(sum(w["penalty"] for w in self.walls))
+        if self.walls:
+            self.ctx.explicit_set_wall(ex, [w["point"] for w in self.walls], [w["normal"] for w in self.walls],
+                                       [w["penalty"] for w in self.walls])
 
     def _record(self, kinc: int, dt: float, kinetic: float, **more):
         """the entry of `increments` after a step, or a batch of steps, that ended at `time1`"""
@@ -763,7 +784,16 @@ class System_of_equations:
         (loads + moved boundary), "boundary_work", "internal_work", "viscous_dissipation" -- the alpha work plus internal_work
         - (strain_energy - strain_energy at t = 0), the bulk-viscosity share, DERIVED on the host because the material is
         hyperelastic -- and "energy_total" = kinetic + internal_work + alpha work - external_work, which a stable run
-        keeps near its initial value.  Without the keyword the records, the launches and the bits are unchanged."""
+        keeps near its initial value.  Without the keyword the records, the launches and the bits are unchanged.
+        `*Rigid Wall` (`inp.rigid_walls`, an extension keyword): frictionless planar rigid walls with a mass-proportional
+        penalty (`femcy_explicit_set_wall`, with the law), set before the start.  A wall without `penalty=` takes kappa =
+        0.1 omega_ref^2, omega_ref being the first estimate the run has: `omega_bound` of the matrix on the fixed path, the
+        element bound at u_0 taken before the walls are set on the element-by-element path, 2 / dt under `direct user
+        control`.  With kappa the sum of the penalties the fixed path uses omega_c = sqrt(omega_bound^2 + kappa) wherever it
+        used omega_bound (`omega_contact`; the lagged-damping factor too), the element-by-element estimate adds kappa itself.
+        Every record and `initial_energy` gain "wall": per wall {"force", "energy", "nodes", "penetration"}
+        (`femcy_explicit_wall_get`); with `*Energy Output` also "contact_energy", the sum of the walls' potentials, which
+        "energy_total" then includes.  Without the keyword the records, the launches and the bits are unchanged."""
         deck = deck_view(inp)
         self._transient_gate(deck, "*Dynamic, explicit step", "lumped mass", motion=True)
         if deck.temperature_info is not None:
@@ -792,18 +822,25 @@ class System_of_equations:
         if deck.energy_output:                                        # before the start, which zeroes the work sums
             ctx.explicit_energy_enable(ex, True)
             self._energy_balance = {"ex": ex, "strain0": None}
+        self.walls, self.wall_kappa = [], 0.0
         if deck.dynamic_auto:
             return self._solve_explicit_auto(deck, loads, ex)
         if deck.dynamic["direct_user_control"]:
             dt = deck.time_incs["ini_inc"]
+            self._set_walls(deck, ex, 2.0 / dt)
         else:
             ctx.assemble_K(-1)                                        # the matrix of the undeformed mesh, for the estimate only
             self.stats["assemblies"] += 1
             self.stable_dt, self.omega_bound = ctx.explicit_stable_dt(ex)
+            self._set_walls(deck, ex, self.omega_bound)
+            omega = self.omega_bound
+            if self.walls:                                            # omega_c^2 <= omega^2 + kappa (femcy_explicit_set_wall)
+                self.omega_contact = omega = float(np.sqrt(self.omega_bound * self.omega_bound + self.wall_kappa))
+                self.stable_dt = 2.0 / omega
             if bulk is not None or alpha != 0.0:
                 # lagged damping of critical fraction xi: h <= (2 / omega)(sqrt(1 + xi^2) - xi); the quadratic bulk term is
                 # not known in advance and left to `scale factor`
-                xi = b1 + alpha / (2.0 * self.omega_bound)
+                xi = b1 + alpha / (2.0 * omega)
                 self.stable_dt *= np.sqrt(1.0 + xi * xi) - xi
             dt = deck.dynamic["scale_factor"] * self.stable_dt
         if not (np.isfinite(dt) and dt > 0.0):
@@ -851,6 +888,9 @@ class System_of_equations:
         s_C, sf, batch = self.material_stiffness(), deck.dynamic["scale_factor"], deck.dynamic["output_every"]
         self._initial_state(deck, loads.dirichletBCs)
         self.omega_bound = ctx.explicit_element_bound(ex, s_C, be.VEC_DOF)
+        if deck.rigid_walls:                                          # the reference frequency is taken before the walls are
+            self._set_walls(deck, ex, self.omega_bound)               # set; the estimate with them is the run's first
+            self.omega_bound = ctx.explicit_element_bound(ex, s_C, be.VEC_DOF)
         self.stable_dt = 2.0 / self.omega_bound if self.omega_bound > 0.0 else np.inf
         if not np.isfinite(self.omega_bound):
             raise be.FemcyError("explicit step: no usable increment (omega = {})".format(self.omega_bound),

@@ -588,6 +588,46 @@ int femcy_explicit_set_motion(femcy_ctx* ctx, int32_t id, int32_t nsets, const i
 enum femcy_energy_term { FEMCY_EN_LOAD = 0, FEMCY_EN_INTERNAL = 1, FEMCY_EN_ALPHA = 2, FEMCY_EN_BOUNDARY = 3 };
 int femcy_explicit_energy_enable(femcy_ctx* ctx, int32_t id, int32_t on);
 int femcy_explicit_energy_get(femcy_ctx* ctx, int32_t id, double* out /*[4]*/);
+/* Frictionless planar rigid walls (*Rigid Wall: an extension keyword in the spirit of LS-DYNA's planar rigid wall; Abaqus
+ * needs an analytical rigid surface, a reference node, a contact pair and a surface interaction for the same thing).  Wall w
+ * is a point p, a normal n into the free half space and a penalty kappa_w in 1/s^2; n is normalised and d = n . p formed
+ * once on the host, by code both backends share.  At most FEMCY_WALL_MAX walls per integrator.  For node a at
+ * x = X_a + u_a (one rounding per component) the gap is formed in exactly this order,
+ *   g = fma(n[dm-1], x[dm-1], ... fma(n[0], x[0], -d)),
+ * and the wall adds to the acceleration of every FREE scalar DOF i of the node (minv != 0)
+ *   a_i += -kappa_w min(g, 0) n_i,          evaluated as  g < 0: a_i = fma(-kappa_w g, n_i, a_i)
+ * -- the force -kappa_w m_a min(g, 0) n divided by the node's mass -- walls in ascending index order, after
+ * minv (s f - f_int) and before the alpha term.  A wall that a node has not reached adds nothing at all, bit for bit.  Held
+ * DOFs take no wall force and stay at rest; moved DOFs ignore it as they ignore every other force, but their u enters g.
+ * The wall acts at femcy_explicit_start / _auto_begin as well: a_0 of a mesh that starts inside a wall contains it.  The
+ * step stays two launches: the node pass reads X and u of its DOF and the lanes of a node exchange x inside their quad.
+ * The wall is conservative, with the potential
+ *   E_w = 1/2 kappa_w sum_a m_a min(g_a, 0)^2       (the lumped mass, scaled if it was scaled; nodes with a free DOF only),
+ * so the energy balance needs no new accumulator: the wall force enters the kick but none of the four sums,
+ * FEMCY_EN_INTERNAL keeps meaning the gathered fe, and the fixed-increment identity above becomes
+ *   [KE + sum_w E_w - (h^2 / 8) a.M a]_N - [...]_0 = W_LOAD - W_INTERNAL - W_ALPHA      (all DOFs of contacting nodes free),
+ * with E_w read from the state by femcy_explicit_wall_get.
+ * Stable increment: write kappa = sum_w kappa_w.  On a contacting node wall w adds kappa_w m_a n n^T to the stiffness; in
+ * the M-inner product that is kappa_w n n^T, positive semi-definite with largest eigenvalue kappa_w, so by Weyl's inequality
+ * omega_c^2 <= omega^2 + kappa.  The element-by-element estimate (femcy_explicit_element_bound and the clock of an automatic
+ * run) adds kappa to every element's omega_e^2 BEFORE the damping factor -- any element may touch a wall --; a caller of
+ * femcy_explicit_stable_dt, which is unchanged, uses omega_c = sqrt(omega_bound^2 + kappa).
+ * femcy_explicit_set_wall is meant to be called before femcy_explicit_start / _auto_begin, which put the wall force into
+ * a_0.  The walls are kept in the integrator and travel in the kernel arguments, so a call between two stepping calls is
+ * taken at once: the next kick and the next increment estimate see the new walls, while a of the current state still
+ * holds the old ones.  nwalls = 0 removes the walls: the node pass is then launched exactly as without this call, the same
+ * kernels with the same arguments, and the bound kernel -- which since the walls always takes the sum of the penalties as
+ * one more argument -- gets 0 and adds nothing: the same bits.
+ * femcy_explicit_wall_get: a synchronising read-back from vec[DOF], one pass over the nodes and a fixed-order reduction, no
+ * atomics: out[0] = sum_a kappa_w m_a max(-g_a, 0), the normal force on the wall; out[1] = E_w; out[2] = the number of nodes
+ * with g < 0; out[3] = max_a max(-g_a, 0).  out[0] and out[1] count the nodes with at least one free DOF.
+ * Refused with FEMCY_EINVAL, the context stays usable: an unknown id, nwalls outside 0 .. FEMCY_WALL_MAX, null arguments, an
+ * entry that is not finite, a normal of length 0, kappa <= 0, a wall index out of range or _get with no walls set, and
+ * either call once femcy_comm_init has run.  Walls are dropped where integrators are. */
+#define FEMCY_WALL_MAX 4
+int femcy_explicit_set_wall(femcy_ctx* ctx, int32_t id, int32_t nwalls, const double* point /*[nwalls][dm]*/,
+                            const double* normal /*[nwalls][dm]*/, const double* kappa /*[nwalls]*/);
+int femcy_explicit_wall_get(femcy_ctx* ctx, int32_t id, int32_t wall, double* out /*[4]*/);
 /* Fixed mass scaling (*Fixed Mass Scaling, whole model): the element shares m_a^e of a lumped mass are multiplied by one
  * factor k_e per element, before an integrator is made from it, and the nodal masses are summed again.  omega_e^2 above is
  * linear in 1 / m_a^e, so k_e divides it exactly and a target increment is met in closed form, in the project's own
